@@ -2,7 +2,9 @@
 """Headline benchmark: utterances/sec (4 s, 16 kHz, 2-speaker rows) of one pBSRNN training
 step -- forward, SI-SDR, backward, per-tensor clip, Adam -- on N MI355X.
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2                       # the headline line alone
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full                # + kernel times, rooflines, MFMA census, CPU baseline
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR    # + the last step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -209,6 +211,33 @@ def _sha16(path):
     return hashlib.sha256(open(path, "rb").read()).hexdigest()[:16]
 
 
+DUMP_PARAM_SAMPLE = 2048                               # elements per parameter tensor written by --dump-outputs
+DUMP_EST_ROWS = 128                                    # rows of the separated waveforms written by --dump-outputs
+
+
+def dump_outputs(out_dir, model, loss, est):
+    """--dump-outputs: what a caller of the timed step holds after the last one, as float32 .npy files (~10 MB at the
+    default 32 rows, never more than 40 MB):
+      est.npy    the separated waveforms of its forward, [R, T] (the first DUMP_EST_ROWS rows);
+      loss.npy   its SI-SDR loss in dB, a scalar;
+      params.npy the parameters its Adam step left, min(numel, DUMP_PARAM_SAMPLE) elements of every tensor in
+                 named_parameters() order at positions drawn by a generator seeded with 0 (the whole set is 87 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(0)
+    parts = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_PARAM_SAMPLE:
+                idx = torch.randperm(flat.numel(), generator=g)[:DUMP_PARAM_SAMPLE].sort().values
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu())
+        arrays = {"est": est[:DUMP_EST_ROWS].float().cpu(), "loss": loss.detach().float().cpu(), "params": torch.cat(parts)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -224,13 +253,18 @@ def main():
     ap.add_argument("--joint", action="store_true",
                     help="the shipped confs/bsrnn.yaml variant: speaker encoder (wespeaker ResNet34 on 80-d fbank, "
                          "398 frames) trained jointly instead of fixed 256-d embeddings; not the headline line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beyond the headline: per-class kernel times (HIP events on every profiled "
+                         "launch of the timed steps), roofline objects, MFMA census, allocator figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy: the separated "
+                         "waveforms, the loss and a fixed sample of every updated parameter (rank 0)")
     args = ap.parse_args()
 
     if args.cpu_only:
         print(json.dumps(cpu_baseline(kind=args.cpu_baseline, threads=args.cpu_threads)), flush=True)
         return
     from wesep_amd import dev
-    from wesep_amd import _lib as L
     from wesep_amd.models import get_model
     from wesep_amd.optim import FusedClipAdam
     from wesep_amd.parallel import all_ranks, all_ranks_tensor_spread, barrier, comm_info, init_distributed, max_over_ranks, rank_seed, wrap_ddp
@@ -273,7 +307,7 @@ def main():
         opt.zero_grad()
         loss.backward()
         opt.step()
-        return loss
+        return loss, est.detach()
 
     # WESEP_MAIN_PRIORITY (experiment): run the step on a stream of that HIP priority instead of the default stream
     main_pr = os.environ.get("WESEP_MAIN_PRIORITY")
@@ -283,19 +317,21 @@ def main():
             step(i)
         torch.cuda.synchronize()
         barrier()
-        dev.prof_enable(True)
-        dev.alg_reset(True)                  # algorithmic bytes / flops of every timed launch, per class (dev._alg)
+        if args.full:
+            dev.prof_enable(True)
+            dev.alg_reset(True)              # algorithmic bytes / flops of every timed launch, per class (dev._alg)
+            allocs0 = torch.cuda.memory_stats().get("num_device_alloc", 0)
         torch.cuda.synchronize()
-        allocs0 = torch.cuda.memory_stats().get("num_device_alloc", 0)
         t0 = time.perf_counter()
         for i in range(args.steps):
-            loss = step(args.warmup + i)
+            loss, est = step(args.warmup + i)
         torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
-    dev.prof_enable(False)
-    alg = {k: list(v) for k, v in (dev.ALG or {}).items()}
-    dev.alg_reset(False)
+    if args.full:
+        dev.prof_enable(False)
+        alg = {k: list(v) for k, v in (dev.ALG or {}).items()}
+        dev.alg_reset(False)
     per_rank_ms = all_ranks(elapsed / args.steps * 1e3, d)       # rank-ordered, for the SCALE record
     # outside the timed region: do all replicas hold the same parameters?  (Data parallelism keeps them bit-identical;
     # a disturbed all-reduce -- profiles/r02_kernel_race.md -- would not.)  Checksum of every parameter, max - min over ranks.
@@ -305,6 +341,63 @@ def main():
     elapsed = max_over_ranks(elapsed, d)
     final_loss = float(loss.item())
 
+    census = mfma_terms_census()
+    gfmt = dev.gates_fmt()
+    from wesep_amd.functional import pair_rfmt
+    F_pair_rfmt = pair_rfmt(gfmt)
+    tv, bv = census["terms_per_product"]["time"], census["terms_per_product"]["band"]
+    band2 = bv["bptt"] <= 2 and bv["recur_fwd"] <= 2
+    f8 = [n for n, v in (("band forward", bv["recur_fwd"]), ("band BPTT", bv["bptt"]), ("time-view forward", tv["recur_fwd"]),
+                         ("pair BPTT", tv["bptt"]), ("d(xn)", tv["d_xn"])) if v == 1.5]
+    arith = (("bf16x3 (x-projections, projections, d(hcat), BN / mask GEMMs) + fp16x2 (recurrent products of all four "
+              "recurrence kernels, d(xn))" if band2 else
+              "bf16x3 (band-view recurrences, x-projections, projections, d(hcat), BN / mask GEMMs) + fp16x2 (recurrent "
+              "products of the time-view cluster forward and pair BPTT, d(xn))") +
+             " + fp16x1 (LSTM weight gradients); 2-byte saved gates / d(gates); fp32 accumulate"
+             + ("; BPTT kernels: W_hh as fp16 hi + block-scaled FP8 lo" if F_pair_rfmt >= 2 else "")
+             + (f"; the lo term of the recurrent product on the block-scaled FP8 MFMA (fp8x0.5: {', '.join(f8)})" if f8 else ""))
+    if rank == 0:
+        ms_per_step = elapsed / args.steps * 1e3
+        out = {
+            "metric": "utterances/sec (4 s, 16 kHz, 2-spk) fwd+bwd, pBSRNN",
+            "value": world * R * args.steps / elapsed, "unit": "utterances/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": ("bf16x3+fp16x2+fp16x1 split products" + (" (+fp8 lo terms)" if f8 else "") + ", fp32 accumulate")
+            if census["mean_terms_step"] < 2.99 else "bf16x3",
+            "data": "synthetic",
+            "config": {"workload": "pBSRNN FiLM multi-fuse, 6 repeats, feature_dim 128, " +
+                                   ("jointly trained wespeaker ResNet34 speaker encoder on [R, 398, 80] fbank"
+                                    if args.joint else "fixed 256-d embeddings") +
+                                   "; fwd + SI-SDR + bwd + per-tensor clip + Adam-L2; " + arith,
+                       "rows_per_gpu": R, "global_rows": world * R, "samples_per_row": T,
+                       "parallelism": f"dp{world}", "final_loss_dB": final_loss},
+        }
+        if args.full:
+            out.update(full_figures(R, args.steps, elapsed, alg, census, allocs0))
+        out["per_rank_ms_per_step"] = per_rank_ms
+        out["replicas_in_sync"] = bool(spread == 0.0)
+        out["replica_checksum_spread"] = spread
+        out["comm"] = comm_info()
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(kind=args.cpu_baseline, threads=args.cpu_threads)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, model, loss, est)
+        print(json.dumps(out), flush=True)
+    barrier()
+    # a scaling record of replicas that drifted apart, or of fewer ranks than asked for, is not a measurement
+    if comm_info()["world_size"] != args.gpus or spread != 0.0:
+        sys.stderr.write(f"bench.py: world_size {comm_info()['world_size']} (asked for {args.gpus}), replica checksum "
+                         f"spread {spread}: FAILED\n")
+        sys.exit(3)
+
+
+def full_figures(R, steps, elapsed, alg, census, allocs0):
+    """--full: the figures of the line beyond the headline -- per-class kernel time of the timed steps (HIP events
+    on every profiled launch, enabled only under --full), each class against both roofs, the whole step against SURVEY
+    8d's algorithmic work, the MFMA census and the caching allocator.  Rank 0, after the timed steps."""
+    from wesep_amd import dev
+    from wesep_amd import _lib as L
     # dominant kernels: the two BLSTM recurrences (HIP events on the launch stream, see runtime.hip)
     K, Tf = 32, 1 + T // 128
     P = R * K * Tf
@@ -384,7 +477,7 @@ def main():
         if not pr["launches"] or not al or not al[2]:
             continue
         sec_c = pr["ms_total"] * 1e-3
-        ent = {"stream": cls_stream[name], "ms_per_step": pr["ms_total"] / args.steps, "launches_per_step": pr["launches"] / args.steps,
+        ent = {"stream": cls_stream[name], "ms_per_step": pr["ms_total"] / steps, "launches_per_step": pr["launches"] / steps,
                "ms_per_launch": pr["ms_avg"], "timed_launches": pr["launches"], "counted_launches": al[2],
                "alg_bytes_per_launch": al[0] / al[2], "alg_gbs": al[0] / sec_c / 1e9, "frac_hbm": al[0] / sec_c / 1e9 / HBM_PEAK_GBS,
                "alg_tflops": al[1] / sec_c / 1e12, "frac_mfma_algorithmic": al[1] / sec_c / 1e12 / BF16_MFMA_PEAK_TFLOPS}
@@ -396,122 +489,82 @@ def main():
             if n_:
                 ent["traffic_per_launch"] = sum(v["hbm_bytes_per_launch_corrected"] * v["launches"] for v in hit) / n_
                 ent["traffic_gb_per_step"] = sum(v["hbm_bytes_per_launch_corrected"] * v["launches"] for v in hit) / 2 / 1e9
-                ent["traffic_over_algorithmic"] = ent["traffic_gb_per_step"] * 1e9 / (al[0] / args.steps)
+                ent["traffic_over_algorithmic"] = ent["traffic_gb_per_step"] * 1e9 / (al[0] / steps)
         by_class[name] = ent
     crit = max((k for k in by_class if k != "gemm_tn"), key=lambda k: by_class[k]["ms_per_step"], default=None)
     largest = max(by_class, key=lambda k: by_class[k]["ms_per_step"], default=None)
 
-    census = mfma_terms_census()
-    from wesep_amd.functional import pair_rfmt
-    F_pair_rfmt = pair_rfmt(gfmt)
     tv, bv = census["terms_per_product"]["time"], census["terms_per_product"]["band"]
     dom_terms = 0.5 * ((tv["bptt"] + bv["bptt"]) if dom == "lstm_bwd" else (tv["recur_fwd"] + bv["recur_fwd"]))
-    band2 = bv["bptt"] <= 2 and bv["recur_fwd"] <= 2
-    f8 = [n for n, v in (("band forward", bv["recur_fwd"]), ("band BPTT", bv["bptt"]), ("time-view forward", tv["recur_fwd"]),
-                         ("pair BPTT", tv["bptt"]), ("d(xn)", tv["d_xn"])) if v == 1.5]
-    arith = (("bf16x3 (x-projections, projections, d(hcat), BN / mask GEMMs) + fp16x2 (recurrent products of all four "
-              "recurrence kernels, d(xn))" if band2 else
-              "bf16x3 (band-view recurrences, x-projections, projections, d(hcat), BN / mask GEMMs) + fp16x2 (recurrent "
-              "products of the time-view cluster forward and pair BPTT, d(xn))") +
-             " + fp16x1 (LSTM weight gradients); 2-byte saved gates / d(gates); fp32 accumulate"
-             + ("; BPTT kernels: W_hh as fp16 hi + block-scaled FP8 lo" if F_pair_rfmt >= 2 else "")
-             + (f"; the lo term of the recurrent product on the block-scaled FP8 MFMA (fp8x0.5: {', '.join(f8)})" if f8 else ""))
-    if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        out = {
-            "metric": "utterances/sec (4 s, 16 kHz, 2-spk) fwd+bwd, pBSRNN",
-            "value": world * R * args.steps / elapsed, "unit": "utterances/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": ("bf16x3+fp16x2+fp16x1 split products" + (" (+fp8 lo terms)" if f8 else "") + ", fp32 accumulate")
-            if census["mean_terms_step"] < 2.99 else "bf16x3",
-            "data": "synthetic",
-            "config": {"workload": "pBSRNN FiLM multi-fuse, 6 repeats, feature_dim 128, " +
-                                   ("jointly trained wespeaker ResNet34 speaker encoder on [R, 398, 80] fbank"
-                                    if args.joint else "fixed 256-d embeddings") +
-                                   "; fwd + SI-SDR + bwd + per-tensor clip + Adam-L2; " + arith,
-                       "rows_per_gpu": R, "global_rows": world * R, "samples_per_row": T,
-                       "parallelism": f"dp{world}", "final_loss_dB": final_loss},
-            # the recurrence kernels are bound by memory paths (HBM activations + the per-step L2 weight
-            # stream), not by the matrix cores: HBM is the roof they are priced against
-            "roofline": {"bound": "hbm", "kernel": dom + " recurrence kernels, launch average over the time view (" +
-                                   ("lstm_fwd_cluster_kernel" if dom == "lstm_fwd" else
-                                    ("lstm_bwd_pair_kernel" if os.environ.get("WESEP_LSTM_PAIR_BWD", "1") != "0"
-                                     else "lstm_bwd_s16_kernel")) +
-                                   ") and the band view (" + dom + "_bf16_kernel<BLK>)",
-                         "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
-                         "traffic": traffic, "bytes_per_launch": bytes_per_launch,
-                         "bytes_per_cell": cell_bytes[dom],
-                         "gates_format": {L.GATES_F32: "f32", L.GATES_H2: "h2b (unorm16 gates, bf16 d(gates))",
-                                          L.GATES_H2S: "h2s (unorm16 gates, split-pair d(gates))",
-                                          L.GATES_H2F: "h2 (unorm16 gates, scaled-fp16 d(gates))"}[gfmt],
-                         # the same launches priced at round 3's 40 B per cell (fp32 gates, split-pair d(gates)), for
-                         # comparison with the earlier rounds' lines: bytes that no longer move are not achieved bandwidth
-                         "frac_at_round3_bytes": 40.0 * P * 2 * L.LSTM_H / sec / 1e9 / HBM_PEAK_GBS,
-                         "ms_per_launch": prof[dom]["ms_avg"],
-                         # MFMAs executed per product in THIS class: the launch average over the time view (pair BPTT /
-                         # cluster forward) and the band view (three-term streaming kernels)
-                         "mfma": {"alg_tflops": tfl, "terms_per_product": dom_terms, "executed_tflops": dom_terms * tfl,
-                                  "peak_tflops": BF16_MFMA_PEAK_TFLOPS,
-                                  "frac_executed": dom_terms * tfl / BF16_MFMA_PEAK_TFLOPS,
-                                  "frac_algorithmic": tfl / BF16_MFMA_PEAK_TFLOPS,
-                                  "busy_frac_pmc": mfma_busy}},
-            "kernel_ms_per_step": {k: v["ms_total"] / args.steps for k, v in prof.items()},
-        }
-        # counters cannot be collected inside this run: say which run they come from (commit + bench.py hash at
-        # collection time, written by tools/pmc_summary.py), next to this run's own bench.py hash
-        out["roofline"]["counters_from"] = pmc_src
-        out["roofline_by_class"] = by_class
-        out["critical_path_largest"] = crit
-        out["largest_any_stream"] = largest
-        out["bench_py_sha16"] = _sha16(os.path.abspath(__file__))
-        # whole step against SURVEY 8d's algorithmic work (per row, 4 s, fwd+bwd): 1.017 TFLOP fp32-equivalent
-        # (x3 executed as split-bf16) and the layer-fused minimum of 2.26 GB of fp32 traffic
-        sec_step = elapsed / args.steps
-        alg_flops, alg_bytes = 1.017e12 * R, 2.26e9 * R
-        mt = census["mean_terms_step"]
-        t_mfma = mt * alg_flops / (BF16_MFMA_PEAK_TFLOPS * 1e12)
-        t_hbm = alg_bytes / (HBM_PEAK_GBS * 1e9)
-        out["mfma_terms"] = census
-        out["step_roofline"] = {
-            "alg_flops_per_step": alg_flops, "alg_bytes_per_step": alg_bytes,
-            "alg_tflops": alg_flops / sec_step / 1e12, "mean_mfma_terms_per_product": mt,
-            "executed_tflops": mt * alg_flops / sec_step / 1e12,
-            "frac_mfma_executed": t_mfma / sec_step, "alg_gbs": alg_bytes / sec_step / 1e9,
-            "frac_hbm_alg": t_hbm / sec_step, "bound": "mfma" if t_mfma >= t_hbm else "hbm",
-            "frac": max(alg_flops / (BF16_MFMA_PEAK_TFLOPS * 1e12), t_hbm) / sec_step,
-            "frac_mfma_algorithmic": alg_flops / (BF16_MFMA_PEAK_TFLOPS * 1e12) / sec_step,
-            # counted HBM bytes of the whole step (committed PMC passes of the same command) over SURVEY 8d's layer-fused
-            # minimum: how much of the step's traffic the algorithm does not ask for
-            "counter_gb_per_step": counter_gb_step,
-            "traffic_over_algorithmic": (counter_gb_step * 1e9 / alg_bytes) if counter_gb_step else None,
-            "note": "per GPU; `frac` = `frac_mfma_algorithmic`: every fp32-equivalent product counted ONCE against the dense "
-                    "bf16 / fp16 MFMA peak (2.5 PFLOP/s) -- the defensible step figure.  `frac_mfma_executed` counts the MFMA "
-                    "instructions the kernels really issue per product (`mfma_terms`: 1, 2 or 3 by GEMM class, FLOP-weighted "
-                    "mean over the step), not a flat 3"}
-        # caching-allocator figures of rank 0 after the timed steps: `reserved` next to `peak_allocated` says that the host's
-        # run-ahead cost no memory (profiles/r06_run_ahead.md: 265 GB reserved for 72.6 GB allocated before the step fence and the
-        # held side-stream operands); `device_allocs_in_timed_steps` = hipMalloc calls inside the timed region
-        ms1 = torch.cuda.memory_stats()
-        out["memory"] = {"peak_allocated_GB": ms1.get("allocated_bytes.all.peak", 0) / 1e9,
-                         "reserved_GB": ms1.get("reserved_bytes.all.current", 0) / 1e9,
-                         "device_allocs_in_timed_steps": ms1.get("num_device_alloc", 0) - allocs0,
-                         "alloc_retries": ms1.get("num_alloc_retries", 0),
-                         "host_run_ahead_steps": int(os.environ.get("WESEP_RUN_AHEAD", "1")),
-                         "side_stream_operands": "held by the carrier" if os.environ.get("WESEP_WGRAD_HOLD", "1") != "0" else "record_stream"}
-        out["per_rank_ms_per_step"] = per_rank_ms
-        out["replicas_in_sync"] = bool(spread == 0.0)
-        out["replica_checksum_spread"] = spread
-        out["comm"] = comm_info()
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(kind=args.cpu_baseline, threads=args.cpu_threads)
-        print(json.dumps(out), flush=True)
-    barrier()
-    # a scaling record of replicas that drifted apart, or of fewer ranks than asked for, is not a measurement
-    if comm_info()["world_size"] != args.gpus or spread != 0.0:
-        sys.stderr.write(f"bench.py: world_size {comm_info()['world_size']} (asked for {args.gpus}), replica checksum "
-                         f"spread {spread}: FAILED\n")
-        sys.exit(3)
+    out = {
+        # the recurrence kernels are bound by memory paths (HBM activations + the per-step L2 weight
+        # stream), not by the matrix cores: HBM is the roof they are priced against
+        "roofline": {"bound": "hbm", "kernel": dom + " recurrence kernels, launch average over the time view (" +
+                               ("lstm_fwd_cluster_kernel" if dom == "lstm_fwd" else
+                                ("lstm_bwd_pair_kernel" if os.environ.get("WESEP_LSTM_PAIR_BWD", "1") != "0"
+                                 else "lstm_bwd_s16_kernel")) +
+                               ") and the band view (" + dom + "_bf16_kernel<BLK>)",
+                     "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
+                     "traffic": traffic, "bytes_per_launch": bytes_per_launch,
+                     "bytes_per_cell": cell_bytes[dom],
+                     "gates_format": {L.GATES_F32: "f32", L.GATES_H2: "h2b (unorm16 gates, bf16 d(gates))",
+                                      L.GATES_H2S: "h2s (unorm16 gates, split-pair d(gates))",
+                                      L.GATES_H2F: "h2 (unorm16 gates, scaled-fp16 d(gates))"}[gfmt],
+                     # the same launches priced at round 3's 40 B per cell (fp32 gates, split-pair d(gates)), for
+                     # comparison with the earlier rounds' lines: bytes that no longer move are not achieved bandwidth
+                     "frac_at_round3_bytes": 40.0 * P * 2 * L.LSTM_H / sec / 1e9 / HBM_PEAK_GBS,
+                     "ms_per_launch": prof[dom]["ms_avg"],
+                     # MFMAs executed per product in THIS class: the launch average over the time view (pair BPTT /
+                     # cluster forward) and the band view (three-term streaming kernels)
+                     "mfma": {"alg_tflops": tfl, "terms_per_product": dom_terms, "executed_tflops": dom_terms * tfl,
+                              "peak_tflops": BF16_MFMA_PEAK_TFLOPS,
+                              "frac_executed": dom_terms * tfl / BF16_MFMA_PEAK_TFLOPS,
+                              "frac_algorithmic": tfl / BF16_MFMA_PEAK_TFLOPS,
+                              "busy_frac_pmc": mfma_busy}},
+        "kernel_ms_per_step": {k: v["ms_total"] / steps for k, v in prof.items()},
+    }
+    # counters cannot be collected inside this run: say which run they come from (commit + bench.py hash at
+    # collection time, written by tools/pmc_summary.py), next to this run's own bench.py hash
+    out["roofline"]["counters_from"] = pmc_src
+    out["roofline_by_class"] = by_class
+    out["critical_path_largest"] = crit
+    out["largest_any_stream"] = largest
+    out["bench_py_sha16"] = _sha16(os.path.abspath(__file__))
+    # whole step against SURVEY 8d's algorithmic work (per row, 4 s, fwd+bwd): 1.017 TFLOP fp32-equivalent
+    # (x3 executed as split-bf16) and the layer-fused minimum of 2.26 GB of fp32 traffic
+    sec_step = elapsed / steps
+    alg_flops, alg_bytes = 1.017e12 * R, 2.26e9 * R
+    mt = census["mean_terms_step"]
+    t_mfma = mt * alg_flops / (BF16_MFMA_PEAK_TFLOPS * 1e12)
+    t_hbm = alg_bytes / (HBM_PEAK_GBS * 1e9)
+    out["mfma_terms"] = census
+    out["step_roofline"] = {
+        "alg_flops_per_step": alg_flops, "alg_bytes_per_step": alg_bytes,
+        "alg_tflops": alg_flops / sec_step / 1e12, "mean_mfma_terms_per_product": mt,
+        "executed_tflops": mt * alg_flops / sec_step / 1e12,
+        "frac_mfma_executed": t_mfma / sec_step, "alg_gbs": alg_bytes / sec_step / 1e9,
+        "frac_hbm_alg": t_hbm / sec_step, "bound": "mfma" if t_mfma >= t_hbm else "hbm",
+        "frac": max(alg_flops / (BF16_MFMA_PEAK_TFLOPS * 1e12), t_hbm) / sec_step,
+        "frac_mfma_algorithmic": alg_flops / (BF16_MFMA_PEAK_TFLOPS * 1e12) / sec_step,
+        # counted HBM bytes of the whole step (committed PMC passes of the same command) over SURVEY 8d's layer-fused
+        # minimum: how much of the step's traffic the algorithm does not ask for
+        "counter_gb_per_step": counter_gb_step,
+        "traffic_over_algorithmic": (counter_gb_step * 1e9 / alg_bytes) if counter_gb_step else None,
+        "note": "per GPU; `frac` = `frac_mfma_algorithmic`: every fp32-equivalent product counted ONCE against the dense "
+                "bf16 / fp16 MFMA peak (2.5 PFLOP/s) -- the defensible step figure.  `frac_mfma_executed` counts the MFMA "
+                "instructions the kernels really issue per product (`mfma_terms`: 1, 2 or 3 by GEMM class, FLOP-weighted "
+                "mean over the step), not a flat 3"}
+    # caching-allocator figures of rank 0 after the timed steps: `reserved` next to `peak_allocated` says that the host's
+    # run-ahead cost no memory (profiles/r06_run_ahead.md: 265 GB reserved for 72.6 GB allocated before the step fence and the
+    # held side-stream operands); `device_allocs_in_timed_steps` = hipMalloc calls inside the timed region
+    ms1 = torch.cuda.memory_stats()
+    out["memory"] = {"peak_allocated_GB": ms1.get("allocated_bytes.all.peak", 0) / 1e9,
+                     "reserved_GB": ms1.get("reserved_bytes.all.current", 0) / 1e9,
+                     "device_allocs_in_timed_steps": ms1.get("num_device_alloc", 0) - allocs0,
+                     "alloc_retries": ms1.get("num_alloc_retries", 0),
+                     "host_run_ahead_steps": int(os.environ.get("WESEP_RUN_AHEAD", "1")),
+                     "side_stream_operands": "held by the carrier" if os.environ.get("WESEP_WGRAD_HOLD", "1") != "0" else "record_stream"}
+    return out
 
 
 if __name__ == "__main__":

@@ -10,7 +10,9 @@ step has to TRACK this fp32 loss curve step by step and arrive at the same param
     python -m oracle.make_trajectory            # ~3 minutes on 8 cores -> tests/golden/bsrnn_trajectory_r4_t16000_s60.npz
 
 Fixture: losses [60]; lr [60]; per parameter tensor 256 sampled elements (indices from a generator seeded with the
-tensor's name) of the INITIAL and the FINAL value, and the L2 norm of the whole update.
+tensor's name) of the INITIAL and the FINAL value, and the L2 norm of the whole update.  On disk the per-tensor arrays
+are concatenated in `names` order (`pack`; one zip entry per array would cost more than the data); `load` returns them
+keyed as `run` made them: "idx/<name>", "init/<name>", "final/<name>", "updnorm/<name>".
 """
 import os
 import sys
@@ -71,9 +73,32 @@ def run(log=print):
     return out
 
 
+def pack(res):
+    """run()'s dict -> a few concatenated arrays (the fixture as stored)."""
+    names = [k[len("idx/"):] for k in res if k.startswith("idx/")]
+    return {"losses": res["losses"], "lr": res["lr"], "names": np.asarray(names),
+            "sizes": np.asarray([res["idx/" + k].size for k in names], np.int64),
+            "idx": np.concatenate([res["idx/" + k] for k in names]),
+            "init": np.concatenate([res["init/" + k] for k in names]),
+            "final": np.concatenate([res["final/" + k] for k in names]),
+            "updnorm": np.asarray([res["updnorm/" + k] for k in names], np.float64)}
+
+
+def load(path):
+    """The stored fixture -> the dict run() returned."""
+    g = np.load(path)
+    out = {"losses": g["losses"], "lr": g["lr"]}
+    offs = np.concatenate([[0], np.cumsum(g["sizes"])])
+    for i, k in enumerate(g["names"].tolist()):
+        for part in ("idx", "init", "final"):
+            out[f"{part}/{k}"] = g[part][offs[i]:offs[i + 1]]
+        out["updnorm/" + k] = g["updnorm"][i]
+    return out
+
+
 if __name__ == "__main__":
     torch.set_num_threads(os.cpu_count())
     res = run()
     path = os.path.join(ROOT, "tests", "golden", NAME + ".npz")
-    np.savez_compressed(path, **res)
+    np.savez_compressed(path, **pack(res))
     print("wrote", path, os.path.getsize(path), "bytes")

@@ -290,7 +290,7 @@ def test_training_trajectory_tracks_the_fp32_oracle(golden_dir, monkeypatch):
     from oracle import bsrnn_oracle as O
     from oracle import make_trajectory as MT
     d = _cuda()
-    g = np.load(os.path.join(golden_dir, MT.NAME + ".npz"))
+    g = MT.load(os.path.join(golden_dir, MT.NAME + ".npz"))
     batches = MT.batches()
     runs = {}
     for name, env in (("bf16x3", {}), ("f32", {"WESEP_RESRNN": "plain", "WESEP_GEMM": "f32", "WESEP_LSTM": "f32"})):
