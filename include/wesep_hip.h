@@ -769,6 +769,28 @@ int ws_astp_fwd(const float* x, const float* logits, int R, int T, int C, float 
                 void* stream);
 int ws_astp_bwd(const float* x, const float* logits, const float* out, const float* aux, const float* dout, int R, int T,
                 int C, float floor_, float* dx, float* dlogits, void* stream);
+/* MHASTP / MQMHASTP (wespeaker multi-head / multi-query multi-head attentive statistics pooling; csrc/mhastp.hip) on
+ * channels-last x [R][F][T][C]: Q queries x H heads, head h = channels [h*C/H, (h+1)*C/H) x all F rows, d_model
+ * dm = C/H*F, upstream feature index c*F + f.  layers 2: logits = W2 tanh(W1 x + b1) + b2 (W1 [64][dm], W2 [ds][64]);
+ * layers 1: logits = W1 x + b1 (W1 [ds][dm]); ds = 1 (one logit row per head) or dm (one per feature).
+ * pack = Q*H blocks of ws_mhastp_sizes(..., block_floats) floats, block (q, h) at (q*H + h): W1 with columns in the
+ * order f*(C/H) + c, b1, then (layers 2) W2, b2 as they are; ws_mhastp_pack writes one block.
+ * fwd: out [R][Q][H][2][dm] = (mean, sqrt(max(var, 1e-7))) per head in upstream order; aux [R][Q][H][4][dm] = (max logit,
+ * sum exp, mean, var), features in the kernel order f*(C/H) + c, for ws_mhastp_bwd.  One launch for any T.
+ * bwd: dx [R][F][T][C] (written, not accumulated).  dpack NULL: no weight gradients (one launch).  Otherwise work =
+ * ws_mhastp_sizes(..., work_floats) floats, slab = nsplit * Q*H*block floats (unused when nsplit == 1) and
+ * dpack gets the weight gradients in the pack layout but with W1's columns in the upstream order c*F + f, i.e.
+ * every block is (dW1, db1, dW2, db2) as the parameters are shaped (two more launches, deterministic: no atomics). */
+/* block_floats: one (query, head) block of the pack; work_floats: the backward's workspace (either pointer may be NULL) */
+int ws_mhastp_sizes(int R, int T, int Q, int H, int layers, int ds, int d_model, long long* block_floats,
+                    long long* work_floats);
+int ws_mhastp_pack(const float* w1, const float* b1, const float* w2, const float* b2, int F, int Ch, int layers, int ds,
+                   float* blk, void* stream);
+int ws_mhastp_fwd(const float* x, const float* pack, int R, int F, int T, int C, int Q, int H, int layers, int ds,
+                  float* out, float* aux, void* stream);
+int ws_mhastp_bwd(const float* x, const float* pack, const float* aux, const float* dout, int R, int F, int T, int C,
+                  int Q, int H, int layers, int ds, float* dx, float* work, float* slab, int nsplit, float* dpack,
+                  void* stream);
 /* y = act(x + rb[row / rows_per_r]) on [rows][C] (act 1 tanh, 3 sigmoid; rb NULL or [rows / rows_per_r][C]) and
  * dx = dy * act'(y) from the saved output: ECAPA's attention bottleneck (tanh) and SE gate (sigmoid).            */
 int ws_rowbias_act_fwd(const float* x, const float* rb, long long rows, int C, int rows_per_r, int act, float* y,

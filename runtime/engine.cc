@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
@@ -232,6 +233,10 @@ struct ws_engine {
   // ECAPA-TDNN speaker encoder (spk_kind 1; wesep_amd/models/ecapa_tdnn.py)
   int spk_kind = 0, spk_channels = 512, spk_glob = 0, spk_emb_bn = 0;
   int spk_bottleneck = 0, spk_two_emb = 0;        // wespeaker ResNet50 / 101 / 152 blocks; seg_1 -> ReLU -> BN -> seg_2
+  // ResNet pooling (meta spk_pool: 0 TSTP, 1 MHASTP, 2 MQMHASTP): queries x heads of attentive statistics, the weights
+  // of every (query, head) in one pack (include/wesep_hip.h, ws_mhastp_fwd)
+  int spk_pool = 0, pool_q = 1, pool_h = 1, pool_layers = 2, pool_ds = 1;
+  float* pool_pack = nullptr;
   float* seg_bn_st = nullptr;
   TdnnPrep tdnn1;
   std::vector<SeRes2Prep> se_blocks;
@@ -531,6 +536,50 @@ float* bn_eval_stats(ws_engine* e, const std::string& bn, int c);
 int prep_campplus(ws_engine* e);
 int campplus_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb);
 
+// MHASTP / MQMHASTP (models/resnet.py): the pool's tensors, packed per (query, head) as ws_mhastp_fwd reads them --
+// W1 with its columns in the kernel order f*(C/H) + c, then b1, W2, b2 (csrc/mhastp.hip, ws_mhastp_pack)
+int prep_resnet_pool(ws_engine* e, int in_dim, int C) {
+  if (e->spk_pool == 0) return WS_OK;
+  const int Q = e->pool_q, H = e->pool_h, L = e->pool_layers, Fp = in_dim / C;
+  if (e->spk_pool < 0 || e->spk_pool > 2 || Q < 1 || (e->spk_pool == 1 && Q != 1) || H < 1 || C % H || (L != 1 && L != 2)) {
+    set_err("engine: ResNet pooling %d (%d queries, %d heads, %d layers) has no launch plan", e->spk_pool, Q, H, L);
+    return WS_ERR_INVALID;
+  }
+  const int Ch = C / H, dm = Ch * Fp, ds = e->pool_ds, n1 = L == 2 ? 64 : ds;
+  if (ds != 1 && ds != dm) {
+    set_err("engine: MHASTP d_s %d (1 or d_model %d)", ds, dm);
+    return WS_ERR_INVALID;
+  }
+  long long block_floats = 0;
+  if (ws_mhastp_sizes(0, 0, 0, 0, L, ds, dm, &block_floats, nullptr) != WS_OK) return WS_ERR_INVALID;
+  const size_t P1 = static_cast<size_t>(block_floats);
+  std::vector<float> pack(P1 * Q * H);
+  for (int q = 0; q < Q; ++q)
+    for (int h = 0; h < H; ++h) {
+      const std::string b = std::string("spk_model.pool.") + (e->spk_pool == 2 ? "n_query." + std::to_string(q) + "." : "") +
+                            "heads_att_trans." + std::to_string(h) + ".att_";
+      if (!require(e, b + "0.weight", {n1, dm, 1}) || !require(e, b + "0.bias", {n1})) return WS_ERR_INVALID;
+      if (L == 2 && (!require(e, b + "1.weight", {ds, 64, 1}) || !require(e, b + "1.bias", {ds}))) return WS_ERR_INVALID;
+      float* blk = pack.data() + P1 * (size_t(q) * H + h);
+      const float* w1 = e->host(b + "0.weight");
+      for (int u = 0; u < n1; ++u)
+        for (int f = 0; f < Fp; ++f)
+          for (int c = 0; c < Ch; ++c) blk[size_t(u) * dm + f * Ch + c] = w1[size_t(u) * dm + c * Fp + f];
+      const float* b1 = e->host(b + "0.bias");
+      std::copy(b1, b1 + n1, blk + size_t(n1) * dm);
+      if (L == 2) {
+        const float* w2 = e->host(b + "1.weight");
+        const float* b2 = e->host(b + "1.bias");
+        float* o2 = blk + size_t(n1) * dm + n1;
+        std::copy(w2, w2 + size_t(ds) * 64, o2);
+        std::copy(b2, b2 + ds, o2 + size_t(ds) * 64);
+      }
+    }
+  e->pool_pack = upload(e, e->persist, pack.data(), pack.size());
+  WS_PTR(e->pool_pack);
+  return WS_OK;
+}
+
 int prep_resnet(ws_engine* e) {
   const int m = 32, ex = e->spk_bottleneck ? 4 : 1;
   const std::string p = "spk_model.";
@@ -560,7 +609,10 @@ int prep_resnet(ws_engine* e) {
     }
   }
   const int stats_dim = (e->feat_dim / 8) * m * 8 * ex;
-  if (!require(e, p + "seg_1.weight", {e->E, 2 * stats_dim}) || !require(e, p + "seg_1.bias", {e->E})) return WS_ERR_INVALID;
+  int rc_pool = prep_resnet_pool(e, stats_dim, 8 * m * ex);
+  if (rc_pool != WS_OK) return rc_pool;
+  const int pooled = e->spk_pool ? e->pool_q * 2 * stats_dim : 2 * stats_dim;
+  if (!require(e, p + "seg_1.weight", {e->E, pooled}) || !require(e, p + "seg_1.bias", {e->E})) return WS_ERR_INVALID;
   const float s0 = 0.f, s1 = 1.f;
   e->slope0 = upload(e, e->persist, &s0, 1);
   e->slope1 = upload(e, e->persist, &s1, 1);
@@ -896,6 +948,11 @@ int read_speaker_meta(ws_engine* e) {
   e->spk_emb_bn = static_cast<int>(meta_or(e, "spk_emb_bn", 0));
   e->spk_bottleneck = static_cast<int>(meta_or(e, "spk_bottleneck", 0));
   e->spk_two_emb = static_cast<int>(meta_or(e, "spk_two_emb", 0));
+  e->spk_pool = static_cast<int>(meta_or(e, "spk_pool", 0));
+  e->pool_q = static_cast<int>(meta_or(e, "spk_pool_queries", 1));
+  e->pool_h = static_cast<int>(meta_or(e, "spk_pool_heads", 1));
+  e->pool_layers = static_cast<int>(meta_or(e, "spk_pool_layers", 2));
+  e->pool_ds = static_cast<int>(meta_or(e, "spk_pool_ds", 1));
   if (e->spk_kind < 0 || e->spk_kind > 2) {
     set_err("engine: speaker encoder kind %d is not built (0 ResNet, 1 ECAPA-TDNN, 2 CAM++)", e->spk_kind);
     return WS_ERR_INVALID;
@@ -928,6 +985,11 @@ int prepare(ws_engine* e) {
   e->spk_emb_bn = static_cast<int>(meta_or(e, "spk_emb_bn", 0));
   e->spk_bottleneck = static_cast<int>(meta_or(e, "spk_bottleneck", 0));
   e->spk_two_emb = static_cast<int>(meta_or(e, "spk_two_emb", 0));
+  e->spk_pool = static_cast<int>(meta_or(e, "spk_pool", 0));
+  e->pool_q = static_cast<int>(meta_or(e, "spk_pool_queries", 1));
+  e->pool_h = static_cast<int>(meta_or(e, "spk_pool_heads", 1));
+  e->pool_layers = static_cast<int>(meta_or(e, "spk_pool_layers", 2));
+  e->pool_ds = static_cast<int>(meta_or(e, "spk_pool_ds", 1));
   if (e->spk_kind < 0 || e->spk_kind > 2) {
     set_err("engine: speaker encoder kind %d is not built (0 ResNet, 1 ECAPA-TDNN, 2 CAM++)", e->spk_kind);
     return WS_ERR_INVALID;
@@ -1320,18 +1382,27 @@ int resnet_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
     }
     H = H2, W = W2;
   }
-  float* stats = a.alloc(size_t(R) * 2 * C * H);
+  const int pooled = e->spk_pool ? e->pool_q * 2 * C * H : 2 * C * H;
+  float* stats = a.alloc(size_t(R) * pooled);
   WS_PTR(stats);
-  WS_RUN(e, ws_tstp_fwd(bufs[cur], R, H, W, C, kTstpEps, stats, s));
+  if (e->spk_pool) {          // MHASTP / MQMHASTP: one launch, straight from the [R][F'][T'][C] activation
+    const int dm = C / e->pool_h * H;
+    float* aux = a.alloc(size_t(R) * e->pool_q * e->pool_h * 4 * dm);
+    WS_PTR(aux);
+    WS_RUN(e, ws_mhastp_fwd(bufs[cur], e->pool_pack, R, H, W, C, e->pool_q, e->pool_h, e->pool_layers, e->pool_ds, stats,
+                            aux, s));
+  } else {
+    WS_RUN(e, ws_tstp_fwd(bufs[cur], R, H, W, C, kTstpEps, stats, s));
+  }
   const std::string p = "spk_model.";
   if (!e->spk_two_emb) {
-    rc = linear(e, stats, R, 2 * C * H, e->dev(p + "seg_1.weight"), 2 * C * H, e->E, e->dev(p + "seg_1.bias"), 0, emb);
+    rc = linear(e, stats, R, pooled, e->dev(p + "seg_1.weight"), pooled, e->E, e->dev(p + "seg_1.bias"), 0, emb);
   } else {
     float* t = a.alloc(size_t(R) * e->E);
     float* u = a.alloc(size_t(R) * e->E);
     float* v = a.alloc(size_t(R) * e->E);
     WS_PTR(t && u && v);
-    if ((rc = linear(e, stats, R, 2 * C * H, e->dev(p + "seg_1.weight"), 2 * C * H, e->E, e->dev(p + "seg_1.bias"), 2, t)) != WS_OK)
+    if ((rc = linear(e, stats, R, pooled, e->dev(p + "seg_1.weight"), pooled, e->E, e->dev(p + "seg_1.bias"), 2, t)) != WS_OK)
       return rc;
     WS_RUN(e, ws_bn_prelu_fwd(t, e->seg_bn_st, e->id_one, e->id_zero, nullptr, e->slope1, R, e->E, u, v, s));
     rc = linear(e, v, R, e->E, e->dev(p + "seg_2.weight"), e->E, e->E, e->dev(p + "seg_2.bias"), 0, emb);

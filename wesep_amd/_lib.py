@@ -237,6 +237,10 @@ _SIGS = {
     "ws_conv_wgrad": (_i, [C.POINTER(ConvWgradArgs), _p]),
     "ws_astp_fwd": (_i, [_p, _p, _i, _i, _i, C.c_float, _p, _p, _p]),
     "ws_astp_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, C.c_float, _p, _p, _p]),
+    "ws_mhastp_sizes": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "ws_mhastp_pack": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "ws_mhastp_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ws_mhastp_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "ws_rowbias_act_fwd": (_i, [_p, _p, _ll, _i, _i, _i, _p, _p]),
     "ws_act_bwd": (_i, [_p, _p, _ll, _i, _p, _p]),
     "ws_seg_sums": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),

@@ -18,6 +18,7 @@ import torch
 
 FUSE = {"concat": 0, "additive": 1, "multiply": 2, "FiLM": 3}
 SKIP_PREFIXES = ("pred_linear.",)
+SPK_POOL = {"TSTP": 0, "MHASTP": 1, "MQMHASTP": 2}     # meta spk_pool: the ResNet pooling layer (absent: TSTP)
 
 
 def engine_meta(model):
@@ -43,12 +44,17 @@ def speaker_meta(model, meta):
                         spk_glob=int(spk.pool.linear1.in_channels == 3 * spk.pool.linear2.out_channels),
                         spk_emb_bn=int(isinstance(getattr(spk, "bn2", None), torch.nn.BatchNorm1d)))
         elif hasattr(spk, "seg_1") and type(spk.layer1[0]).__name__ in ("BasicBlock", "Bottleneck") and \
-                getattr(spk, "pooling_func", "TSTP") == "TSTP":
+                getattr(spk, "pooling_func", "TSTP") in SPK_POOL:
             ex = 4 if type(spk.layer1[0]).__name__ == "Bottleneck" else 1
             meta.update(spk_kind=0, spk_bottleneck=int(ex == 4), spk_two_emb=int(bool(getattr(spk, "two_emb_layer", False))))
             for i, layer in enumerate((spk.layer1, spk.layer2, spk.layer3, spk.layer4)):
                 meta[f"spk_blocks{i}"] = len(layer)
-            meta["feat_dim"] = int(spk.seg_1.weight.shape[1] // (2 * 32 * 8 * ex)) * 8
+            meta["feat_dim"] = int(spk.feat_dim)
+            pool = getattr(spk, "pooling_func", "TSTP")
+            if pool != "TSTP":        # MHASTP / MQMHASTP: the attention geometry of the pool (models/resnet.py)
+                queries = list(spk.pool.n_query) if pool == "MQMHASTP" else [spk.pool]
+                meta.update(spk_pool=SPK_POOL[pool], spk_pool_queries=len(queries), spk_pool_heads=queries[0].head_num,
+                            spk_pool_layers=queries[0].layer_num, spk_pool_ds=queries[0].d_s)
         elif type(spk).__name__ == "CAMPPlus":            # wespeaker CAM++ (round 5: spk_kind 2; the constructor's defaults)
             xv = spk.xvector
             layers = [len(getattr(xv, f"block{i}")) for i in (1, 2, 3)]
@@ -60,8 +66,8 @@ def speaker_meta(model, meta):
             meta.update(spk_kind=2, feat_dim=spk.feat_dim)
         else:
             raise NotImplementedError(f"export_engine: speaker encoder {type(spk).__name__} (a ResNet with a pooling layer "
-                                      "other than TSTP) has no launch plan in the native runtime; the wespeaker ResNets "
-                                      "with TSTP, ECAPA-TDNN and CAM++ do")
+                                      "other than TSTP, MHASTP or MQMHASTP) has no launch plan in the native runtime; the "
+                                      "wespeaker ResNets with those, ECAPA-TDNN and CAM++ do")
     return meta
 
 

@@ -1345,6 +1345,52 @@ def tstp_bwd(x, stats, dstats, R: int, F: int, T: int, Cc: int, dx):
     _call("ws_tstp_bwd", _p(x), _p(stats), _p(dstats), R, F, T, Cc, _p(dx))
 
 
+def mhastp_sizes(R: int, T: int, Q: int, H: int, layers: int, ds: int, dm: int):
+    """(floats of one (query, head) block of the MHASTP weight pack, floats of the backward's workspace)."""
+    blk, work = C.c_longlong(0), C.c_longlong(0)
+    if L.lib().ws_mhastp_sizes(R, T, Q, H, layers, ds, dm, C.byref(blk), C.byref(work)) != L.WS_OK:   # host only
+        raise L.WesepHipError(L.lib().ws_last_error().decode("utf-8", "replace"))
+    return blk.value, work.value
+
+
+def mhastp_block_floats(layers: int, ds: int, dm: int) -> int:
+    return mhastp_sizes(0, 0, 0, 0, layers, ds, dm)[0]
+
+
+def mhastp_pack(w1, b1, w2, b2, F: int, Ch: int, layers: int, ds: int, blk):
+    """One (query, head) block of the pack: W1 with columns in the kernel order f*Ch + c, then b1, W2, b2."""
+    for n, t in (("w1", w1), ("b1", b1), ("blk", blk)):
+        _chk(t, n)
+    _call("ws_mhastp_pack", _p(w1), _p(b1), _p(w2), _p(b2), F, Ch, layers, ds, _p(blk))
+
+
+def mhastp_fwd(x, pack, R: int, F: int, T: int, Cc: int, Q: int, H: int, layers: int, ds: int, out, aux):
+    for n, t in (("x", x), ("pack", pack), ("out", out), ("aux", aux)):
+        _chk(t, n)
+    _call("ws_mhastp_fwd", _p(x), _p(pack), R, F, T, Cc, Q, H, layers, ds, _p(out), _p(aux))
+
+
+def mhastp_nsplit(R: int, T: int) -> int:
+    """Row splits of the MHASTP weight gradients: a few hundred rows each, at most 4 slabs to reduce."""
+    return max(1, min(4, (R * T) // 256))
+
+
+def mhastp_bwd(x, pack, aux, dout, R: int, F: int, T: int, Cc: int, Q: int, H: int, layers: int, ds: int, dx,
+               dpack=None):
+    """dx (and, with dpack, the weight gradients in the pack layout): one launch, or three with dpack."""
+    for n, t in (("x", x), ("pack", pack), ("aux", aux), ("dout", dout), ("dx", dx)):
+        _chk(t, n)
+    work = slab = None
+    nsplit = 0
+    if dpack is not None:
+        nsplit = mhastp_nsplit(R, T)
+        work = torch.empty(mhastp_sizes(R, T, Q, H, layers, ds, Cc // H * F)[1], device=x.device, dtype=torch.float32)
+        if nsplit > 1:
+            slab = torch.empty(nsplit * dpack.numel(), device=x.device, dtype=torch.float32)
+    _call("ws_mhastp_bwd", _p(x), _p(pack), _p(aux), _p(dout), R, F, T, Cc, Q, H, layers, ds, _p(dx), _p(work),
+          _p(slab), nsplit, _p(dpack))
+
+
 ASTP_FLOOR = 1e-7
 
 

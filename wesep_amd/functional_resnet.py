@@ -117,3 +117,60 @@ class TstpFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dev.tstp_bwd(x, stats, dstats.contiguous(), R, Fq, T, Cc, dx)
         return dx, None
+
+
+class MhastpFn(torch.autograd.Function):
+    """MHASTP / MQMHASTP pooling (models/resnet.py) of x [R*F*T, C] -> [R, Q*H*2*dm]: per query and head, mean || std
+    under the head's attention (csrc/mhastp.hip).  geo = (R, F, T, Q, H, layers, ds); params = per query, per head:
+    att_0.weight, att_0.bias (, att_1.weight, att_1.bias); cache: the pooling module's PackCache, which keeps the weight
+    pack (W1's columns in the kernel order) for one weight version."""
+
+    @staticmethod
+    def forward(ctx, x, geo, cache, *params):
+        _need_cuda(x, "MHASTP pooling")
+        R, Fq, T, Q, Hh, layers, ds = geo
+        x = x.contiguous()
+        Cc = x.shape[1]
+        Ch = Cc // Hh
+        dm = Ch * Fq
+        P1 = dev.mhastp_block_floats(layers, ds, dm)
+        sig = cache.begin(params)
+        pack = cache.get(sig, "mhastp", lambda: _mhastp_pack(params, Q * Hh, layers, ds, Fq, Ch, P1, x.device))
+        out = _empty(x.device, R, Q * Hh * 2 * dm)
+        aux = _empty(x.device, R * Q * Hh * 4, dm)
+        dev.mhastp_fwd(x, pack, R, Fq, T, Cc, Q, Hh, layers, ds, out, aux)
+        ctx.save_for_backward(x, pack, aux)
+        ctx.geo = (R, Fq, T, Cc, Q, Hh, layers, ds, Ch, dm, P1)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, pack, aux = ctx.saved_tensors
+        R, Fq, T, Cc, Q, Hh, layers, ds, Ch, dm, P1 = ctx.geo
+        wgrad = any(ctx.needs_input_grad[3:])
+        dx = torch.empty_like(x)
+        dpack = torch.empty(Q * Hh * P1, device=x.device, dtype=torch.float32) if wgrad else None
+        dev.mhastp_bwd(x, pack, aux, dout.contiguous(), R, Fq, T, Cc, Q, Hh, layers, ds, dx, dpack)
+        if not wgrad:
+            return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
+        n1 = 64 if layers == 2 else ds
+        grads = []
+        for qh in range(Q * Hh):
+            blk = dpack[qh * P1:(qh + 1) * P1]
+            grads.append(blk[:n1 * dm].view(n1, dm, 1))          # views of dpack: no copies
+            grads.append(blk[n1 * dm:n1 * dm + n1])
+            if layers == 2:
+                off2 = n1 * dm + n1
+                grads.append(blk[off2:off2 + 64 * ds].view(ds, 64, 1))
+                grads.append(blk[off2 + 64 * ds:])
+        return (dx, None, None) + tuple(grads)
+
+
+def _mhastp_pack(params, nqh, layers, ds, Fq, Ch, P1, device):
+    pack = torch.empty(nqh * P1, device=device, dtype=torch.float32)
+    per = len(params) // nqh
+    for qh in range(nqh):
+        p = [t.detach().contiguous() for t in params[qh * per:(qh + 1) * per]]
+        w2, b2 = (p[2], p[3]) if layers == 2 else (None, None)
+        dev.mhastp_pack(p[0], p[1], w2, b2, Fq, Ch, layers, ds, pack[qh * P1:(qh + 1) * P1])
+    return pack

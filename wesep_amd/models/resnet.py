@@ -2,12 +2,13 @@
 `wespeaker.models.resnet.ResNet` (BasicBlock variants: ResNet18 / ResNet34), so `spk_model_init` checkpoints load.
 The package itself is a third-party dependency absent from the reference tree: parity is against the restatement in
 oracle/resnet_oracle.py and is UNPINNED.  nn.Conv2d / nn.BatchNorm2d / nn.Linear objects are parameter
-containers only; forward is a chain of C-ABI launches (wesep_amd/functional_resnet.py)."""
+containers only; forward is a chain of C-ABI launches (wesep_amd/functional_resnet.py).  Pooling: TSTP / TAP / TSDP,
+ASTP, and wespeaker's MHASTP / MQMHASTP (restated in tests/pooling_ref.py; one launch each way, csrc/mhastp.hip)."""
 import torch
 import torch.nn as nn
 
 from .. import functional_resnet as FR
-from ..functional import LinearFn
+from ..functional import LinearFn, PackCache
 
 
 class TSTP(nn.Module):
@@ -35,15 +36,105 @@ class TSDP(TSTP):
         return self.in_dim
 
 
+MHASTP_LDS_FLOATS = 16384 - 64        # csrc/mhastp.hip: one frame of the head (x, dx, attention rows) per 64 KiB of LDS
+
+
+class MHASTP(nn.Module):
+    """wespeaker `pooling_layers.MHASTP` (multi-head attentive statistics pooling): the [R, C*F', T'] view splits into
+    head_num heads of d_model = in_dim / head_num features; per head alpha = softmax_T(att(chunk)) with att = Conv1d(d_model,
+    64, 1) - Tanh - Conv1d(64, d_s, 1) (layer_num 2) or Conv1d(d_model, d_s, 1) (layer_num 1), d_s = d_model if d_s > 1
+    else 1; out = cat over heads of (mean || sqrt(clamp(var, 1e-7))).  Module tree and names as upstream
+    (heads_att_trans.{h}.att_{i}); forward is one HIP launch (functional_resnet.MhastpFn)."""
+
+    def __init__(self, in_dim, layer_num=2, head_num=2, d_s=1, bottleneck_dim=64, **kwargs):
+        super().__init__()
+        assert in_dim % head_num == 0, (in_dim, head_num)
+        if layer_num not in (1, 2):
+            raise NotImplementedError(f"MHASTP layer_num {layer_num}: the HIP kernels are built for 1 and 2")
+        if layer_num == 2 and bottleneck_dim != 64:
+            raise NotImplementedError(f"MHASTP bottleneck_dim {bottleneck_dim}: the HIP kernels are built for 64")
+        self.in_dim, self.head_num, self.layer_num = in_dim, head_num, layer_num
+        d_model = in_dim // head_num
+        self.d_model = d_model
+        self.d_s = d_model if d_s > 1 else 1
+        dims = [bottleneck_dim] * (layer_num + 1)
+        dims[0], dims[-1] = d_model, self.d_s
+        heads = []
+        for _ in range(head_num):
+            att = nn.Sequential()
+            for i in range(layer_num - 1):
+                att.add_module(f"att_{i}", nn.Conv1d(dims[i], dims[i + 1], 1, 1))
+                att.add_module(f"tanh{i}", nn.Tanh())
+            att.add_module(f"att_{layer_num - 1}", nn.Conv1d(dims[layer_num - 1], dims[layer_num], 1, 1))
+            heads.append(att)
+        self.heads_att_trans = nn.ModuleList(heads)
+        self.cache = PackCache()
+
+    def get_out_dim(self):
+        return 2 * self.in_dim
+
+    def att_params(self):
+        out = []
+        for att in self.heads_att_trans:
+            for i in range(self.layer_num):
+                conv = getattr(att, f"att_{i}")
+                out += [conv.weight, conv.bias]
+        return out
+
+    def check_channels(self, C):
+        """The kernels' geometry: a head is a channel range of the [R, F', T', C] activation (C*F' = in_dim)."""
+        if C % self.head_num:
+            raise NotImplementedError(f"MHASTP head_num {self.head_num} does not divide the {C} channels: a head must be "
+                                      "a channel range of the ResNet's activation")
+        n1 = 64 if self.layer_num == 2 else self.d_s
+        if 2 * self.d_model + n1 + (self.d_s if self.layer_num == 2 else 0) > MHASTP_LDS_FLOATS:
+            raise NotImplementedError(f"MHASTP d_model {self.d_model}: one frame of a head exceeds the kernels' LDS "
+                                      "tile; use more heads")
+
+    def run(self, y, R, Fq, T):
+        """y [R*F'*T', C] (the last block's channels-last output) -> [R, 2 * in_dim]."""
+        return _mhastp_run([self], self.cache, y, R, Fq, T)
+
+
+class MQMHASTP(nn.Module):
+    """wespeaker `pooling_layers.MQMHASTP`: query_num independent MHASTP layers (n_query.{q}) on the same input,
+    concatenated; one HIP launch serves all queries (each (row, head) chunk is staged once)."""
+
+    def __init__(self, in_dim, layer_num=2, query_num=2, head_num=8, d_s=2, bottleneck_dim=64, **kwargs):
+        super().__init__()
+        self.in_dim, self.query_num = in_dim, query_num
+        self.n_query = nn.ModuleList([MHASTP(in_dim, layer_num=layer_num, head_num=head_num, d_s=d_s,
+                                             bottleneck_dim=bottleneck_dim) for _ in range(query_num)])
+        self.cache = PackCache()
+
+    def get_out_dim(self):
+        return self.query_num * 2 * self.in_dim
+
+    def check_channels(self, C):
+        self.n_query[0].check_channels(C)
+
+    def run(self, y, R, Fq, T):
+        return _mhastp_run(list(self.n_query), self.cache, y, R, Fq, T)
+
+
+def _mhastp_run(queries, cache, y, R, Fq, T):
+    q0 = queries[0]
+    params = [p for q in queries for p in q.att_params()]
+    return FR.MhastpFn.apply(y, (R, Fq, T, len(queries), q0.head_num, q0.layer_num, q0.d_s), cache, *params)
+
+
 def _pooling_layer(name, in_dim):
-    """wespeaker.models.pooling_layers by name: TSTP / TAP / TSDP (one statistics kernel) and ASTP (attentive statistics,
-    the ECAPA-TDNN module of models/ecapa_tdnn.py on the [R, C * F', T] view)."""
+    """wespeaker.models.pooling_layers by name: TSTP / TAP / TSDP (one statistics kernel), ASTP (attentive statistics,
+    the ECAPA-TDNN module of models/ecapa_tdnn.py on the [R, C * F', T] view), MHASTP and MQMHASTP (csrc/mhastp.hip) --
+    each with the constructor defaults wespeaker's ResNet builds it with (`in_dim` only)."""
     if name in ("TSTP", "TAP", "TSDP"):
         return {"TSTP": TSTP, "TAP": TAP, "TSDP": TSDP}[name](in_dim=in_dim)
     if name == "ASTP":
         from .ecapa_tdnn import ASTP
         return ASTP(in_dim=in_dim)
-    raise NotImplementedError(f"pooling_func {name!r}: TSTP, TAP, TSDP and ASTP are built (not MHASTP / MQMHASTP)")
+    if name in ("MHASTP", "MQMHASTP"):
+        return {"MHASTP": MHASTP, "MQMHASTP": MQMHASTP}[name](in_dim=in_dim)
+    raise NotImplementedError(f"pooling_func {name!r}: TSTP, TAP, TSDP, ASTP, MHASTP and MQMHASTP are built")
 
 
 class BasicBlock(nn.Module):
@@ -105,6 +196,8 @@ class ResNet(nn.Module):
         self.layer3 = self._make_layer(block, m_channels * 4, num_blocks[2], stride=2)
         self.layer4 = self._make_layer(block, m_channels * 8, num_blocks[3], stride=2)
         self.pool = _pooling_layer(pooling_func, self.stats_dim * block.expansion)
+        if pooling_func in ("MHASTP", "MQMHASTP"):
+            self.pool.check_channels(m_channels * 8 * block.expansion)
         self.pool_out_dim = self.pool.get_out_dim()
         self.seg_1 = nn.Linear(self.pool_out_dim, embed_dim)
         if two_emb_layer:
@@ -150,6 +243,8 @@ class ResNet(nn.Module):
             Cc = y.shape[1]
             frames = y.view(R, H, W, Cc).permute(0, 2, 3, 1).reshape(R * W, Cc * H)
             stats = self.pool.run(frames, R, W)
+        elif self.pooling_func in ("MHASTP", "MQMHASTP"):      # straight from the [R, F', T', C] layout
+            stats = self.pool.run(y, R, H, W)
         else:
             stats = FR.TstpFn.apply(y, (R, H, W))                               # mean || std, each [C * F']
             half = stats.shape[1] // 2
