@@ -791,6 +791,18 @@ int ws_mhastp_fwd(const float* x, const float* pack, int R, int F, int T, int C,
 int ws_mhastp_bwd(const float* x, const float* pack, const float* aux, const float* dout, int R, int F, int T, int C,
                   int Q, int H, int layers, int ds, float* dx, float* work, float* slab, int nsplit, float* dpack,
                   void* stream);
+/* The same pooling on a grid split over T (the 1-D speaker encoders, which pool at the full frame rate: ECAPA-TDNN,
+ * CAM++).  ws_mhastp_split_sizes: tsplit, the T splits that cover about two workgroups per CU (cus) over the R*H
+ * (row, head) pairs, and part_floats = tsplit*R*Q*H*4*d_model, the forward's workspace.  fwd_split: workgroup (r*H + h, s)
+ * keeps the online-softmax state of frames [s*ceil(T/tsplit), ...) in part, then one merge launch combines the splits in
+ * ascending order and writes out and aux exactly as ws_mhastp_fwd lays them out (two launches, no atomics).
+ * bwd_split: ws_mhastp_bwd with its dx launch on the (R*H, tsplit) grid; the weight gradients are unchanged.        */
+int ws_mhastp_split_sizes(int R, int F, int T, int C, int Q, int H, int cus, int* tsplit, long long* part_floats);
+int ws_mhastp_fwd_split(const float* x, const float* pack, int R, int F, int T, int C, int Q, int H, int layers, int ds,
+                        int tsplit, float* part, float* out, float* aux, void* stream);
+int ws_mhastp_bwd_split(const float* x, const float* pack, const float* aux, const float* dout, int R, int F, int T,
+                        int C, int Q, int H, int layers, int ds, int tsplit, float* dx, float* work, float* slab,
+                        int nsplit, float* dpack, void* stream);
 /* y = act(x + rb[row / rows_per_r]) on [rows][C] (act 1 tanh, 3 sigmoid; rb NULL or [rows / rows_per_r][C]) and
  * dx = dy * act'(y) from the saved output: ECAPA's attention bottleneck (tanh) and SE gate (sigmoid).            */
 int ws_rowbias_act_fwd(const float* x, const float* rb, long long rows, int C, int rows_per_r, int act, float* y,

@@ -49,6 +49,8 @@ constexpr float kGnEps = 1.1920928955078125e-07f;   // torch.finfo(float32).eps,
 constexpr float kBnEps = 1e-5f;
 constexpr float kTstpEps = 1e-7f;
 constexpr float kAstpFloor = 1e-7f;
+// meta spk_pool codes (wesep_amd/bin/export_engine.py SPK_POOL)
+constexpr int kPoolTSTP = 0, kPoolMHASTP = 1, kPoolMQMHASTP = 2, kPoolASTP = 3, kPoolTAP = 4, kPoolTSDP = 5;
 
 struct Tensor {
   std::vector<int64_t> dims;
@@ -233,8 +235,9 @@ struct ws_engine {
   // ECAPA-TDNN speaker encoder (spk_kind 1; wesep_amd/models/ecapa_tdnn.py)
   int spk_kind = 0, spk_channels = 512, spk_glob = 0, spk_emb_bn = 0;
   int spk_bottleneck = 0, spk_two_emb = 0;        // wespeaker ResNet50 / 101 / 152 blocks; seg_1 -> ReLU -> BN -> seg_2
-  // ResNet pooling (meta spk_pool: 0 TSTP, 1 MHASTP, 2 MQMHASTP): queries x heads of attentive statistics, the weights
-  // of every (query, head) in one pack (include/wesep_hip.h, ws_mhastp_fwd)
+  // speaker pooling (meta spk_pool: 0 TSTP, 1 MHASTP, 2 MQMHASTP, 3 ASTP, 4 TAP, 5 TSDP; absent: ASTP for ECAPA-TDNN,
+  // TSTP otherwise).  MHASTP / MQMHASTP: queries x heads of attentive statistics, the weights of every (query, head) in
+  // one pack (include/wesep_hip.h, ws_mhastp_fwd; the 1-D encoders launch ws_mhastp_fwd_split)
   int spk_pool = 0, pool_q = 1, pool_h = 1, pool_layers = 2, pool_ds = 1;
   float* pool_pack = nullptr;
   float* seg_bn_st = nullptr;
@@ -542,7 +545,7 @@ int prep_resnet_pool(ws_engine* e, int in_dim, int C) {
   if (e->spk_pool == 0) return WS_OK;
   const int Q = e->pool_q, H = e->pool_h, L = e->pool_layers, Fp = in_dim / C;
   if (e->spk_pool < 0 || e->spk_pool > 2 || Q < 1 || (e->spk_pool == 1 && Q != 1) || H < 1 || C % H || (L != 1 && L != 2)) {
-    set_err("engine: ResNet pooling %d (%d queries, %d heads, %d layers) has no launch plan", e->spk_pool, Q, H, L);
+    set_err("engine: speaker pooling %d (%d queries, %d heads, %d layers) has no launch plan", e->spk_pool, Q, H, L);
     return WS_ERR_INVALID;
   }
   const int Ch = C / H, dm = Ch * Fp, ds = e->pool_ds, n1 = L == 2 ? 64 : ds;
@@ -578,6 +581,36 @@ int prep_resnet_pool(ws_engine* e, int in_dim, int C) {
   e->pool_pack = upload(e, e->persist, pack.data(), pack.size());
   WS_PTR(e->pool_pack);
   return WS_OK;
+}
+
+// width of the pooled statistics of a 1-D encoder's pooling layer over P channels
+int pool_width(const ws_engine* e, int P) {
+  if (e->spk_pool == kPoolTAP || e->spk_pool == kPoolTSDP) return P;
+  if (e->spk_pool == kPoolMHASTP || e->spk_pool == kPoolMQMHASTP) return e->pool_q * 2 * P;
+  return 2 * P;
+}
+
+// the pooling layer of a 1-D encoder over P channels: its tensors under `prefix` checked, MHASTP's weights packed
+int prep_pool_1d(ws_engine* e, const std::string& prefix, int P, int glob) {
+  const int B = 128;
+  switch (e->spk_pool) {
+    case kPoolTSTP:
+    case kPoolTAP:
+    case kPoolTSDP:
+      return WS_OK;
+    case kPoolASTP:
+      if (!require(e, prefix + "linear1.weight", {B, glob ? 3 * P : P, 1}) || !require(e, prefix + "linear1.bias", {B}) ||
+          !require(e, prefix + "linear2.weight", {P, B, 1}) || !require(e, prefix + "linear2.bias", {P}))
+        return WS_ERR_INVALID;
+      return WS_OK;
+    case kPoolMHASTP:
+    case kPoolMQMHASTP:
+      return prep_resnet_pool(e, P, P);
+    default:
+      set_err("engine: speaker pooling %d has no launch plan (0 TSTP, 1 MHASTP, 2 MQMHASTP, 3 ASTP, 4 TAP, 5 TSDP)",
+              e->spk_pool);
+      return WS_ERR_INVALID;
+  }
 }
 
 int prep_resnet(ws_engine* e) {
@@ -702,14 +735,14 @@ int prep_ecapa(ws_engine* e) {
       return WS_ERR_INVALID;
     e->se_blocks.push_back(b);
   }
+  if ((rc = prep_pool_1d(e, p + "pool.", P, e->spk_glob)) != WS_OK) return rc;
+  const int D = pool_width(e, P);
   if (!require(e, p + "conv.weight", {P, 3 * C, 1}) || !require(e, p + "conv.bias", {P}) ||
-      !require(e, p + "pool.linear1.weight", {B, e->spk_glob ? 3 * P : P, 1}) || !require(e, p + "pool.linear1.bias", {B}) ||
-      !require(e, p + "pool.linear2.weight", {P, B, 1}) || !require(e, p + "pool.linear2.bias", {P}) ||
-      !require(e, p + "bn.weight", {2 * P}) || !require(e, p + "bn.bias", {2 * P}) ||
-      !require(e, p + "bn.running_mean", {2 * P}) || !require(e, p + "bn.running_var", {2 * P}) ||
-      !require(e, p + "linear.weight", {e->E, 2 * P}) || !require(e, p + "linear.bias", {e->E}))
+      !require(e, p + "bn.weight", {D}) || !require(e, p + "bn.bias", {D}) ||
+      !require(e, p + "bn.running_mean", {D}) || !require(e, p + "bn.running_var", {D}) ||
+      !require(e, p + "linear.weight", {e->E, D}) || !require(e, p + "linear.bias", {e->E}))
     return WS_ERR_INVALID;
-  e->pool_bn_st = bn_eval_stats(e, p + "bn", 2 * P);
+  e->pool_bn_st = bn_eval_stats(e, p + "bn", D);
   WS_PTR(e->pool_bn_st);
   if (e->spk_emb_bn) {
     if (!require(e, p + "bn2.weight", {e->E}) || !require(e, p + "bn2.bias", {e->E}) ||
@@ -844,7 +877,8 @@ int prep_campplus(ws_engine* e) {
     return WS_ERR_INVALID;
   }
   if ((rc = cam_bn_prep(e, x + "out_nonlinear.batchnorm", ch, true, &e->cam_out_bn)) != WS_OK) return rc;
-  if (!require(e, x + "dense.linear.weight", {e->E, 2 * ch, 1})) return WS_ERR_INVALID;
+  if ((rc = prep_pool_1d(e, p + "pool.", ch, 0)) != WS_OK) return rc;
+  if (!require(e, x + "dense.linear.weight", {e->E, pool_width(e, ch), 1})) return WS_ERR_INVALID;
   if ((rc = cam_bn_prep(e, x + "dense.nonlinear.batchnorm", e->E, false, &e->cam_dense_bn)) != WS_OK) return rc;
   return WS_OK;
 }
@@ -948,7 +982,7 @@ int read_speaker_meta(ws_engine* e) {
   e->spk_emb_bn = static_cast<int>(meta_or(e, "spk_emb_bn", 0));
   e->spk_bottleneck = static_cast<int>(meta_or(e, "spk_bottleneck", 0));
   e->spk_two_emb = static_cast<int>(meta_or(e, "spk_two_emb", 0));
-  e->spk_pool = static_cast<int>(meta_or(e, "spk_pool", 0));
+  e->spk_pool = static_cast<int>(meta_or(e, "spk_pool", e->spk_kind == 1 ? kPoolASTP : kPoolTSTP));
   e->pool_q = static_cast<int>(meta_or(e, "spk_pool_queries", 1));
   e->pool_h = static_cast<int>(meta_or(e, "spk_pool_heads", 1));
   e->pool_layers = static_cast<int>(meta_or(e, "spk_pool_layers", 2));
@@ -985,7 +1019,7 @@ int prepare(ws_engine* e) {
   e->spk_emb_bn = static_cast<int>(meta_or(e, "spk_emb_bn", 0));
   e->spk_bottleneck = static_cast<int>(meta_or(e, "spk_bottleneck", 0));
   e->spk_two_emb = static_cast<int>(meta_or(e, "spk_two_emb", 0));
-  e->spk_pool = static_cast<int>(meta_or(e, "spk_pool", 0));
+  e->spk_pool = static_cast<int>(meta_or(e, "spk_pool", e->spk_kind == 1 ? kPoolASTP : kPoolTSTP));
   e->pool_q = static_cast<int>(meta_or(e, "spk_pool_queries", 1));
   e->pool_h = static_cast<int>(meta_or(e, "spk_pool_heads", 1));
   e->pool_layers = static_cast<int>(meta_or(e, "spk_pool_layers", 2));
@@ -1526,9 +1560,77 @@ int se_res2_block(ws_engine* e, const SeRes2Prep& b, const float* x, int R, int 
   return WS_OK;
 }
 
+// pooling layer of a 1-D speaker encoder (ECAPA-TDNN, CAM++; F' = 1): h [R*T][P] -> pooled [R][pool_width(e, P)]
+// (models/resnet.py run_pool).  TSTP / TAP / TSDP: the TSTP statistics or one half of them; ASTP: the attention MLP, then
+// ws_astp_fwd; MHASTP / MQMHASTP: ws_mhastp_fwd_split (two launches).  Tensors under `prefix` (".../pool.").
+int pool_1d(ws_engine* e, const std::string& prefix, const float* h, int R, int T, int P, int glob, float* pooled) {
+  const int B = 128;
+  const long long M = (long long)R * T;
+  void* s = e->stream;
+  Arena& a = e->work;
+  const Arena::Mark mk = a.mark();
+  int rc;
+  switch (e->spk_pool) {
+    case kPoolTSTP:
+      WS_RUN(e, ws_tstp_fwd(h, R, 1, T, P, kTstpEps, pooled, s));
+      break;
+    case kPoolTAP:
+    case kPoolTSDP: {         // mean || std, keep one half
+      float* st = a.alloc(size_t(R) * 2 * P);
+      WS_PTR(st);
+      WS_RUN(e, ws_tstp_fwd(h, R, 1, T, P, kTstpEps, st, s));
+      if ((rc = copy_cols(e, pooled, P, st + (e->spk_pool == kPoolTSDP ? P : 0), 2 * P, P, R)) != WS_OK) return rc;
+      break;
+    }
+    case kPoolASTP: {
+      // attentive statistics pooling (models/ecapa_tdnn.py ASTP); global context: cat(x, mean, std) W1^T =
+      // x Wx^T + (mean Wm^T + std Ws^T + b1), the context a per-utterance bias of the bottleneck
+      float* att = a.alloc(size_t(M) * B);
+      float* logits = a.alloc(size_t(M) * P);
+      float* aux = a.alloc(size_t(R) * 4 * P);
+      WS_PTR(att && logits && aux);
+      const float* W1 = e->dev(prefix + "linear1.weight");
+      const float* rowbias = nullptr;
+      if (glob) {
+        float* ctx = a.alloc(size_t(R) * 2 * P);
+        float* rb = a.alloc(size_t(R) * B);
+        WS_PTR(ctx && rb);
+        WS_RUN(e, ws_tstp_fwd(h, R, 1, T, P, kTstpEps, ctx, s));
+        if ((rc = linear(e, ctx, R, 2 * P, W1 + P, 3 * P, B, e->dev(prefix + "linear1.bias"), 0, rb)) != WS_OK) return rc;
+        if ((rc = linear(e, h, static_cast<int>(M), P, W1, 3 * P, B, nullptr, 0, att)) != WS_OK) return rc;
+        rowbias = rb;
+      } else {
+        if ((rc = linear(e, h, static_cast<int>(M), P, W1, P, B, e->dev(prefix + "linear1.bias"), 0, att)) != WS_OK) return rc;
+      }
+      WS_RUN(e, ws_rowbias_act_fwd(att, rowbias, M, B, T, 1, att, s));
+      if ((rc = linear(e, att, static_cast<int>(M), B, e->dev(prefix + "linear2.weight"), B, P, e->dev(prefix + "linear2.bias"),
+                       0, logits)) != WS_OK)
+        return rc;
+      WS_RUN(e, ws_astp_fwd(h, logits, R, T, P, kAstpFloor, pooled, aux, s));
+      break;
+    }
+    default: {                // MHASTP / MQMHASTP on the grid split over T
+      const int Q = e->pool_q, H = e->pool_h, dm = P / H;
+      int tsplit = 1;
+      long long part_floats = 0;
+      if (ws_mhastp_split_sizes(R, 1, T, P, Q, H, e->cu_count > 0 ? e->cu_count : 256, &tsplit, &part_floats) != WS_OK) {
+        set_err("engine: %s", ws_last_error());        // host only: no launch
+        return WS_ERR_INVALID;
+      }
+      float* part = a.alloc(static_cast<size_t>(part_floats));
+      float* aux = a.alloc(size_t(R) * Q * H * 4 * dm);
+      WS_PTR(part && aux);
+      WS_RUN(e, ws_mhastp_fwd_split(h, e->pool_pack, R, 1, T, P, Q, H, e->pool_layers, e->pool_ds, tsplit, part, pooled,
+                                    aux, s));
+    }
+  }
+  a.release(mk);
+  return WS_OK;
+}
+
 // fbank [R][Te][F] (device) -> embedding [R][E]   (wespeaker ECAPA-TDNN, eval mode; models/ecapa_tdnn.py:135-160)
 int ecapa_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
-  const int C = e->spk_channels, P = 1536, B = 128, T = Te;
+  const int C = e->spk_channels, P = 1536, T = Te;
   const long long M = (long long)R * T;
   const std::string p = "spk_model.";
   void* s = e->stream;
@@ -1545,47 +1647,26 @@ int ecapa_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
     if ((rc = copy_cols(e, cat + size_t(li) * C, 3 * C, nxt, C, C, M)) != WS_OK) return rc;
     std::swap(cur, nxt);
   }
+  const int D = pool_width(e, P);
   float* h = a.alloc(size_t(M) * P);           // relu(conv1x1(cat)): the pooled sequence
-  float* att = a.alloc(size_t(M) * B);
-  float* logits = a.alloc(size_t(M) * P);
-  float* pooled = a.alloc(size_t(R) * 2 * P);
-  float* aux = a.alloc(size_t(R) * 4 * P);
-  float* normed = a.alloc(size_t(R) * 2 * P);
-  float* u = a.alloc(size_t(R) * 2 * P);
-  WS_PTR(h && att && logits && pooled && aux && normed && u);
+  float* pooled = a.alloc(size_t(R) * D);
+  float* normed = a.alloc(size_t(R) * D);
+  float* u = a.alloc(size_t(R) * D);
+  WS_PTR(h && pooled && normed && u);
   if ((rc = linear(e, cat, static_cast<int>(M), 3 * C, e->dev(p + "conv.weight"), 3 * C, P, e->dev(p + "conv.bias"), 2, h)) != WS_OK)
     return rc;
-  // attentive statistics pooling (models/ecapa_tdnn.py:96-123); global context: cat(x, mean, std) W1^T =
-  // x Wx^T + (mean Wm^T + std Ws^T + b1), the context a per-utterance bias of the bottleneck
-  const float* W1 = e->dev(p + "pool.linear1.weight");
-  const float* rowbias = nullptr;
-  if (e->spk_glob) {
-    float* ctx = a.alloc(size_t(R) * 2 * P);
-    float* rb = a.alloc(size_t(R) * B);
-    WS_PTR(ctx && rb);
-    WS_RUN(e, ws_tstp_fwd(h, R, 1, T, P, kTstpEps, ctx, s));
-    if ((rc = linear(e, ctx, R, 2 * P, W1 + P, 3 * P, B, e->dev(p + "pool.linear1.bias"), 0, rb)) != WS_OK) return rc;
-    if ((rc = linear(e, h, static_cast<int>(M), P, W1, 3 * P, B, nullptr, 0, att)) != WS_OK) return rc;
-    rowbias = rb;
-  } else {
-    if ((rc = linear(e, h, static_cast<int>(M), P, W1, P, B, e->dev(p + "pool.linear1.bias"), 0, att)) != WS_OK) return rc;
-  }
-  WS_RUN(e, ws_rowbias_act_fwd(att, rowbias, M, B, T, 1, att, s));
-  if ((rc = linear(e, att, static_cast<int>(M), B, e->dev(p + "pool.linear2.weight"), B, P, e->dev(p + "pool.linear2.bias"), 0,
-                   logits)) != WS_OK)
-    return rc;
-  WS_RUN(e, ws_astp_fwd(h, logits, R, T, P, kAstpFloor, pooled, aux, s));
+  if ((rc = pool_1d(e, p + "pool.", h, R, T, P, e->spk_glob, pooled)) != WS_OK) return rc;
   WS_RUN(e, ws_bn_prelu_fwd(pooled, e->pool_bn_st, e->dev(p + "bn.weight"), e->dev(p + "bn.bias"), nullptr, e->slope1, R,
-                            2 * P, u, normed, s));
+                            D, u, normed, s));
   if (e->spk_emb_bn) {
     float* raw = a.alloc(size_t(R) * e->E);
     float* u2 = a.alloc(size_t(R) * e->E);
     WS_PTR(raw && u2);
-    if ((rc = linear(e, normed, R, 2 * P, e->dev(p + "linear.weight"), 2 * P, e->E, e->dev(p + "linear.bias"), 0, raw)) != WS_OK)
+    if ((rc = linear(e, normed, R, D, e->dev(p + "linear.weight"), D, e->E, e->dev(p + "linear.bias"), 0, raw)) != WS_OK)
       return rc;
     WS_RUN(e, ws_bn_prelu_fwd(raw, e->emb_bn_st, e->dev(p + "bn2.weight"), e->dev(p + "bn2.bias"), nullptr, e->slope1, R, e->E,
                               u2, emb, s));
-  } else if ((rc = linear(e, normed, R, 2 * P, e->dev(p + "linear.weight"), 2 * P, e->E, e->dev(p + "linear.bias"), 0, emb)) !=
+  } else if ((rc = linear(e, normed, R, D, e->dev(p + "linear.weight"), D, e->E, e->dev(p + "linear.bias"), 0, emb)) !=
              WS_OK) {
     return rc;
   }
@@ -1764,14 +1845,15 @@ int campplus_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) 
     if ((rc = cam_lin(e, tin, ld, M, static_cast<int>(ld), t.w, t.cout, nullptr, tout)) != WS_OK) return rc;
     y = tout, ch = t.cout;
   }
+  const int D = pool_width(e, ch);
   float* yo = a.alloc(size_t(M) * ch);
-  float* stats = a.alloc(size_t(R) * 2 * ch);
+  float* stats = a.alloc(size_t(R) * D);
   float* raw = a.alloc(size_t(R) * e->E);
   float* u2 = a.alloc(size_t(R) * e->E);
   WS_PTR(yo && stats && raw && u2);
   if ((rc = cam_bn_act(e, e->cam_out_bn, y, M, true, scratch, yo)) != WS_OK) return rc;
-  WS_RUN(e, ws_tstp_fwd(yo, R, 1, T, ch, kTstpEps, stats, s));
-  if ((rc = cam_lin(e, stats, 2 * ch, R, 2 * ch, e->dev("spk_model.xvector.dense.linear.weight"), e->E, nullptr, raw)) != WS_OK)
+  if ((rc = pool_1d(e, "spk_model.pool.", yo, R, T, ch, 0, stats)) != WS_OK) return rc;
+  if ((rc = cam_lin(e, stats, D, R, D, e->dev("spk_model.xvector.dense.linear.weight"), e->E, nullptr, raw)) != WS_OK)
     return rc;
   if ((rc = cam_bn_act(e, e->cam_dense_bn, raw, R, false, u2, emb)) != WS_OK) return rc;
   a.release(mk);
@@ -3515,6 +3597,7 @@ extern "C" long long ws_engine_info(const ws_engine* e, const char* key) {
   if (k == "cluster_fallbacks") return e->cluster_fallbacks;
   if (k == "nband") return e->K;
   if (k == "arch") return e->arch;
+  if (k == "spk_pool" && (e->arch == 0 || e->arch == 2)) return e->spk_pool;   // meta, or the encoder's default
   auto it = e->meta.find(k);
   return it == e->meta.end() ? -1 : it->second;
 }

@@ -241,6 +241,9 @@ _SIGS = {
     "ws_mhastp_pack": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ws_mhastp_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "ws_mhastp_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
+    "ws_mhastp_split_sizes": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "ws_mhastp_fwd_split": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "ws_mhastp_bwd_split": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "ws_rowbias_act_fwd": (_i, [_p, _p, _ll, _i, _i, _i, _p, _p]),
     "ws_act_bwd": (_i, [_p, _p, _ll, _i, _p, _p]),
     "ws_seg_sums": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),

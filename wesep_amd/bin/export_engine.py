@@ -18,7 +18,20 @@ import torch
 
 FUSE = {"concat": 0, "additive": 1, "multiply": 2, "FiLM": 3}
 SKIP_PREFIXES = ("pred_linear.",)
-SPK_POOL = {"TSTP": 0, "MHASTP": 1, "MQMHASTP": 2}     # meta spk_pool: the ResNet pooling layer (absent: TSTP)
+# meta spk_pool: the speaker encoder's pooling layer (absent: ASTP for ECAPA-TDNN, TSTP otherwise); the ResNets' plan
+# has the first three
+SPK_POOL = {"TSTP": 0, "MHASTP": 1, "MQMHASTP": 2, "ASTP": 3, "TAP": 4, "TSDP": 5}
+RESNET_POOLS = ("TSTP", "MHASTP", "MQMHASTP")
+
+
+def pool_meta(spk, pool):
+    """spk_pool and (MHASTP / MQMHASTP) the attention geometry of the pool (models/resnet.py)."""
+    meta = {"spk_pool": SPK_POOL[pool]}
+    if pool in ("MHASTP", "MQMHASTP"):
+        queries = list(spk.pool.n_query) if pool == "MQMHASTP" else [spk.pool]
+        meta.update(spk_pool_queries=len(queries), spk_pool_heads=queries[0].head_num,
+                    spk_pool_layers=queries[0].layer_num, spk_pool_ds=queries[0].d_s)
+    return meta
 
 
 def engine_meta(model):
@@ -40,11 +53,13 @@ def speaker_meta(model, meta):
         meta["spk_feat"] = int(bool(model.spk_feat))      # False: the in-model front-end's buffers are exported too
         spk = model.spk_model
         if type(spk).__name__ == "ECAPA_TDNN":            # wespeaker ECAPA-TDNN (the published bsrnn_ecapa_vox1 model)
+            pool = getattr(spk, "pooling_func", "ASTP")
             meta.update(spk_kind=1, spk_channels=spk.layer1.conv.out_channels, feat_dim=spk.layer1.conv.in_channels,
-                        spk_glob=int(spk.pool.linear1.in_channels == 3 * spk.pool.linear2.out_channels),
+                        spk_glob=int(pool == "ASTP" and spk.pool.linear1.in_channels == 3 * spk.pool.linear2.out_channels),
                         spk_emb_bn=int(isinstance(getattr(spk, "bn2", None), torch.nn.BatchNorm1d)))
+            meta.update(pool_meta(spk, pool))
         elif hasattr(spk, "seg_1") and type(spk.layer1[0]).__name__ in ("BasicBlock", "Bottleneck") and \
-                getattr(spk, "pooling_func", "TSTP") in SPK_POOL:
+                getattr(spk, "pooling_func", "TSTP") in RESNET_POOLS:
             ex = 4 if type(spk.layer1[0]).__name__ == "Bottleneck" else 1
             meta.update(spk_kind=0, spk_bottleneck=int(ex == 4), spk_two_emb=int(bool(getattr(spk, "two_emb_layer", False))))
             for i, layer in enumerate((spk.layer1, spk.layer2, spk.layer3, spk.layer4)):
@@ -52,9 +67,7 @@ def speaker_meta(model, meta):
             meta["feat_dim"] = int(spk.feat_dim)
             pool = getattr(spk, "pooling_func", "TSTP")
             if pool != "TSTP":        # MHASTP / MQMHASTP: the attention geometry of the pool (models/resnet.py)
-                queries = list(spk.pool.n_query) if pool == "MQMHASTP" else [spk.pool]
-                meta.update(spk_pool=SPK_POOL[pool], spk_pool_queries=len(queries), spk_pool_heads=queries[0].head_num,
-                            spk_pool_layers=queries[0].layer_num, spk_pool_ds=queries[0].d_s)
+                meta.update(pool_meta(spk, pool))
         elif type(spk).__name__ == "CAMPPlus":            # wespeaker CAM++ (round 5: spk_kind 2; the constructor's defaults)
             xv = spk.xvector
             layers = [len(getattr(xv, f"block{i}")) for i in (1, 2, 3)]
@@ -64,6 +77,7 @@ def speaker_meta(model, meta):
                 raise NotImplementedError("export_engine: CAM++ with a non-default backbone (growth_rate 32, bn_size 4, "
                                           "init_channels 128, 'batchnorm-relu') has no launch plan in the native runtime")
             meta.update(spk_kind=2, feat_dim=spk.feat_dim)
+            meta.update(pool_meta(spk, getattr(spk, "pooling_func", "TSTP")))
         else:
             raise NotImplementedError(f"export_engine: speaker encoder {type(spk).__name__} (a ResNet with a pooling layer "
                                       "other than TSTP, MHASTP or MQMHASTP) has no launch plan in the native runtime; the "

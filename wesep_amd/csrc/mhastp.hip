@@ -32,6 +32,7 @@ constexpr float MH_FLOOR = 1e-7f;     // var.clamp(min=1e-7)
 struct MhGeom {
   int R, F, T, C, Q, H, layers, ds;
   int Ch, dm, n1, P1, off2, TT;
+  int tchunk;                         // frames per T split (T: one split, the per-(row, head) grid)
 };
 
 __host__ __device__ inline int mh_n1(int layers, int ds) { return layers == 2 ? 64 : ds; }
@@ -113,17 +114,22 @@ __device__ void mh_stage_x(const MhGeom& g, const float* __restrict__ x, int r, 
   }
 }
 
-__global__ __launch_bounds__(MH_THREADS) void mhastp_fwd_kernel(const float* __restrict__ x,
-                                                                const float* __restrict__ pack, MhGeom g,
-                                                                float* __restrict__ out, float* __restrict__ aux) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int r = blockIdx.x / g.H, h = blockIdx.x % g.H, dm = g.dm, TT = g.TT;
+// Online-softmax statistics of frames [t_lo, t_hi) of row r, head h, for every query, into acc (layout of aux:
+// [R][Q][H][4][dm] = running max, sum exp, sum e x, sum e x^2).  An empty range leaves (-inf, 0, 0, 0).
+__device__ void mh_fwd_range(const MhGeom& g, const float* __restrict__ x, const float* __restrict__ pack, int r, int h,
+                             int t_lo, int t_hi, float* __restrict__ acc, float* lds) {
+  const int dm = g.dm, TT = g.TT;
   float* xs = lds;
   float* hs = xs + TT * dm;
   float* ls = hs + TT * g.n1;
   const float* lg = g.layers == 2 ? ls : hs;
-  for (int t0 = 0; t0 < g.T; t0 += TT) {
-    const int nt = min(TT, g.T - t0);
+  if (t_lo >= t_hi)
+    for (int q = 0; q < g.Q; ++q) {
+      float* a = acc + (((long long)r * g.Q + q) * g.H + h) * 4 * dm;
+      for (int k = threadIdx.x; k < dm; k += MH_THREADS) a[k] = -INFINITY, a[dm + k] = 0.f, a[2 * dm + k] = 0.f, a[3 * dm + k] = 0.f;
+    }
+  for (int t0 = t_lo; t0 < t_hi; t0 += TT) {
+    const int nt = min(TT, t_hi - t0);
     __syncthreads();
     mh_stage_x(g, x, r, h, t0, nt, xs);
     __syncthreads();
@@ -135,11 +141,11 @@ __global__ __launch_bounds__(MH_THREADS) void mhastp_fwd_kernel(const float* __r
         mh_stage2(g, blk, hs, ls, nt);
         __syncthreads();
       }
-      float* a = aux + (((long long)r * g.Q + q) * g.H + h) * 4 * dm;
+      float* a = acc + (((long long)r * g.Q + q) * g.H + h) * 4 * dm;
       for (int k = threadIdx.x; k < dm; k += MH_THREADS) {       // this thread owns feature k in every tile
         const int row = g.ds == 1 ? 0 : mh_native(g, k);
-        float m = t0 == 0 ? -INFINITY : a[k];
-        float s = t0 == 0 ? 0.f : a[dm + k], sx = t0 == 0 ? 0.f : a[2 * dm + k], sxx = t0 == 0 ? 0.f : a[3 * dm + k];
+        float m = t0 == t_lo ? -INFINITY : a[k];
+        float s = t0 == t_lo ? 0.f : a[dm + k], sx = t0 == t_lo ? 0.f : a[2 * dm + k], sxx = t0 == t_lo ? 0.f : a[3 * dm + k];
         float mt = m;
         for (int tt = 0; tt < nt; ++tt) mt = fmaxf(mt, lg[tt * g.ds + row]);
         const float sc = expf(m - mt);
@@ -155,21 +161,73 @@ __global__ __launch_bounds__(MH_THREADS) void mhastp_fwd_kernel(const float* __r
       __syncthreads();
     }
   }
+}
+
+// (max logit, sum exp, sum e x, sum e x^2) of one (r, q, h) -> aux (max logit, sum exp, mean, raw var) and out
+// (mean || sqrt(max(var, floor)), native order)
+__device__ __forceinline__ void mh_finish(const MhGeom& g, int r, int q, int h, int k, float m, float s, float sx,
+                                          float sxx, float* __restrict__ out, float* __restrict__ aux) {
+  const int dm = g.dm;
+  float* a = aux + (((long long)r * g.Q + q) * g.H + h) * 4 * dm;
+  float* o = out + (long long)r * g.Q * g.H * 2 * dm + (long long)(q * g.H + h) * 2 * dm;
+  const float mean = sx / s, var = sxx / s - mean * mean;
+  a[k] = m, a[dm + k] = s, a[2 * dm + k] = mean, a[3 * dm + k] = var;
+  const int nk = mh_native(g, k);
+  o[nk] = mean;
+  o[dm + nk] = sqrtf(fmaxf(var, MH_FLOOR));
+}
+
+__global__ __launch_bounds__(MH_THREADS) void mhastp_fwd_kernel(const float* __restrict__ x,
+                                                                const float* __restrict__ pack, MhGeom g,
+                                                                float* __restrict__ out, float* __restrict__ aux) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int r = blockIdx.x / g.H, h = blockIdx.x % g.H, dm = g.dm;
+  mh_fwd_range(g, x, pack, r, h, 0, g.T, aux, lds);
   // aux becomes (max logit, sum exp, mean, raw var); std = sqrt(max(var, floor)) goes to out
   for (int q = 0; q < g.Q; ++q) {
-    float* a = aux + (((long long)r * g.Q + q) * g.H + h) * 4 * dm;
-    float* o = out + (long long)r * g.Q * g.H * 2 * dm + (long long)(q * g.H + h) * 2 * dm;
-    for (int k = threadIdx.x; k < dm; k += MH_THREADS) {
-      const float s = a[dm + k], mean = a[2 * dm + k] / s, var = a[3 * dm + k] / s - mean * mean;
-      a[2 * dm + k] = mean, a[3 * dm + k] = var;
-      const int nk = mh_native(g, k);
-      o[nk] = mean;
-      o[dm + nk] = sqrtf(fmaxf(var, MH_FLOOR));
-    }
+    const float* a = aux + (((long long)r * g.Q + q) * g.H + h) * 4 * dm;
+    for (int k = threadIdx.x; k < dm; k += MH_THREADS)
+      mh_finish(g, r, q, h, k, a[k], a[dm + k], a[2 * dm + k], a[3 * dm + k], out, aux);
   }
 }
 
-// Backward of one (r, h) for all queries.  work (NULL: no weight gradients) = dz [M][Q*H][n1], then (layers 2)
+// Split over T: workgroup (r*H + h, s) takes frames [s*tchunk, min(T, (s+1)*tchunk)) and leaves its partial state in
+// part[s] (each [R][Q][H][4][dm], the layout of aux).
+__global__ __launch_bounds__(MH_THREADS) void mhastp_fwd_part_kernel(const float* __restrict__ x,
+                                                                     const float* __restrict__ pack, MhGeom g,
+                                                                     float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int r = blockIdx.x / g.H, h = blockIdx.x % g.H, s = blockIdx.y;
+  const int t_lo = min(g.T, s * g.tchunk), t_hi = min(g.T, t_lo + g.tchunk);
+  mh_fwd_range(g, x, pack, r, h, t_lo, t_hi, part + (long long)s * g.R * g.Q * g.H * 4 * g.dm, lds);
+}
+
+// Merge of the nsplit partial states of one (r, q, h) per workgroup, splits in ascending order (the same bits every run)
+__global__ __launch_bounds__(MH_THREADS) void mhastp_merge_kernel(const float* __restrict__ part, MhGeom g, int nsplit,
+                                                                  float* __restrict__ out, float* __restrict__ aux) {
+  const int h = blockIdx.x % g.H, q = (blockIdx.x / g.H) % g.Q, r = blockIdx.x / (g.H * g.Q), dm = g.dm;
+  const long long stride = (long long)g.R * g.Q * g.H * 4 * dm;
+  const float* p0 = part + (((long long)r * g.Q + q) * g.H + h) * 4 * dm;
+  for (int k = threadIdx.x; k < dm; k += MH_THREADS) {
+    float m = -INFINITY;
+    for (int s = 0; s < nsplit; ++s) m = fmaxf(m, p0[s * stride + k]);
+    float se = 0.f, sx = 0.f, sxx = 0.f;
+    for (int s = 0; s < nsplit; ++s) {
+      const float* p = p0 + s * stride;
+      if (p[dm + k] == 0.f) continue;                 // an empty split (max -inf)
+      const float sc = expf(p[k] - m);
+      se = fmaf(p[dm + k], sc, se);
+      sx = fmaf(p[2 * dm + k], sc, sx);
+      sxx = fmaf(p[3 * dm + k], sc, sxx);
+    }
+    mh_finish(g, r, q, h, k, m, se, sx, sxx, out, aux);
+  }
+}
+
+// Backward of one (r, h) for all queries, frames [y*tchunk, min(T, (y+1)*tchunk)) of split y = blockIdx.y.  Every
+// tile is independent given aux: with g_t = dmean x_t + dvar (x_t^2 - 2 mean x_t), the softmax's cross-frame term is
+// sum_t alpha_t g_t = dmean mean + dvar (E[x^2] - 2 mean^2) = dmean mean + dvar (var - mean^2), so a T split needs no
+// pass over the other frames.  work (NULL: no weight gradients) = dz [M][Q*H][n1], then (layers 2)
 // h [M][Q*H][64] and d(logit) [M][Q*H][ds], M = R*T, row m = r*T + t.
 __global__ __launch_bounds__(MH_THREADS) void mhastp_bwd_kernel(const float* __restrict__ x,
                                                                 const float* __restrict__ pack,
@@ -189,8 +247,9 @@ __global__ __launch_bounds__(MH_THREADS) void mhastp_bwd_kernel(const float* __r
   float* wh = work ? work + M * QH * g.n1 : nullptr;
   float* wl = work ? wh + M * QH * 64 : nullptr;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int t0 = 0; t0 < g.T; t0 += TT) {
-    const int nt = min(TT, g.T - t0);
+  const int t_lo = min(g.T, (int)blockIdx.y * g.tchunk), t_hi = min(g.T, t_lo + g.tchunk);
+  for (int t0 = t_lo; t0 < t_hi; t0 += TT) {
+    const int nt = min(TT, t_hi - t0);
     __syncthreads();
     mh_stage_x(g, x, r, h, t0, nt, xs);
     for (int i = threadIdx.x; i < nt * dm; i += MH_THREADS) dxs[i] = 0.f;
@@ -403,6 +462,7 @@ bool mh_geom(int R, int F, int T, int C, int Q, int H, int layers, int ds, bool 
   const int per_tt = (bwd ? 2 : 1) * g->dm + g->n1 + (layers == 2 ? ds : 0);
   const int fixed = bwd ? 4 * MH_TT : 0;
   g->TT = min(MH_TT, (MH_LDS_FLOATS - fixed) / per_tt);
+  g->tchunk = T;
   return g->TT >= 1;
 }
 
@@ -451,21 +511,28 @@ extern "C" int ws_mhastp_fwd(const float* x, const float* pack, int R, int F, in
   return ws_check_launch("ws_mhastp_fwd");
 }
 
-extern "C" int ws_mhastp_bwd(const float* x, const float* pack, const float* aux, const float* dout, int R, int F,
-                             int T, int C, int Q, int H, int layers, int ds, float* dx, float* work, float* slab,
-                             int nsplit, float* dpack, void* stream) {
+namespace {
+
+// the backward behind ws_mhastp_bwd (tsplit 1) and ws_mhastp_bwd_split: dx over a (R*H, tsplit) grid, then the weight
+// gradients from the workspace as before
+int mh_bwd(const char* who, const float* x, const float* pack, const float* aux, const float* dout, int R, int F, int T,
+           int C, int Q, int H, int layers, int ds, int tsplit, float* dx, float* work, float* slab, int nsplit,
+           float* dpack, void* stream) {
   MhGeom g{};
-  WS_REQUIRE(x && pack && aux && dout && dx, "ws_mhastp_bwd: null pointer");
+  WS_REQUIRE(x && pack && aux && dout && dx, "%s: null pointer", who);
   WS_REQUIRE(mh_geom(R, F, T, C, Q, H, layers, ds, true, &g),
-             "ws_mhastp_bwd: unsupported geometry (R %d F %d T %d C %d Q %d H %d layers %d ds %d)", R, F, T, C, Q, H,
-             layers, ds);
+             "%s: unsupported geometry (R %d F %d T %d C %d Q %d H %d layers %d ds %d)", who, R, F, T, C, Q, H, layers,
+             ds);
+  WS_REQUIRE(tsplit >= 1 && tsplit <= T && tsplit <= 65535, "%s: %d T splits for %d frames", who, tsplit, T);
+  WS_REQUIRE((long long)R * H < (1LL << 31), "%s: grid too large", who);
   const bool wgrad = dpack != nullptr;
   WS_REQUIRE(!wgrad || (work && nsplit > 0 && (nsplit == 1 || slab)),
-             "ws_mhastp_bwd: weight gradients need work, nsplit > 0 and (nsplit > 1) a slab");
+             "%s: weight gradients need work, nsplit > 0 and (nsplit > 1) a slab", who);
+  g.tchunk = (T + tsplit - 1) / tsplit;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(mhastp_bwd_kernel, dim3(R * H), dim3(MH_THREADS), mh_lds_bytes(g, true), s, x, pack, aux, dout, g,
-                     dx, wgrad ? work : nullptr);
-  int rc = ws_check_launch("ws_mhastp_bwd");
+  hipLaunchKernelGGL(mhastp_bwd_kernel, dim3(R * H, tsplit), dim3(MH_THREADS), mh_lds_bytes(g, true), s, x, pack, aux,
+                     dout, g, dx, wgrad ? work : nullptr);
+  int rc = ws_check_launch(who);
   if (rc != WS_OK || !wgrad) return rc;
   const long long M = (long long)R * T;
   const int rps = (int)((M + nsplit - 1) / nsplit);
@@ -477,4 +544,60 @@ extern "C" int ws_mhastp_bwd(const float* x, const float* pack, const float* aux
   if ((rc = ws_check_launch("ws_mhastp_bwd(wgrad)")) != WS_OK || nsplit == 1) return rc;
   const long long P = (long long)Q * H * g.P1;
   return ws_reduce_slabs(slab, nsplit, P, P, dpack, 0, 0, stream);
+}
+
+// T splits of the split grid: about two workgroups per CU over the R*H (row, head) pairs, at least MH_TT frames each
+int mh_tsplit(int R, int T, int H, int cus) {
+  const long long rh = (long long)R * H, want = 2LL * (cus > 0 ? cus : 1);
+  const int tiles = (T + MH_TT - 1) / MH_TT;
+  long long n = (want + rh - 1) / rh;
+  if (n > tiles) n = tiles;
+  if (n < 1) n = 1;
+  const int per = (int)((tiles + n - 1) / n);           // tiles per split; no split is left empty
+  return (tiles + per - 1) / per;
+}
+
+}  // namespace
+
+extern "C" int ws_mhastp_bwd(const float* x, const float* pack, const float* aux, const float* dout, int R, int F,
+                             int T, int C, int Q, int H, int layers, int ds, float* dx, float* work, float* slab,
+                             int nsplit, float* dpack, void* stream) {
+  return mh_bwd("ws_mhastp_bwd", x, pack, aux, dout, R, F, T, C, Q, H, layers, ds, 1, dx, work, slab, nsplit, dpack,
+                stream);
+}
+
+extern "C" int ws_mhastp_split_sizes(int R, int F, int T, int C, int Q, int H, int cus, int* tsplit,
+                                     long long* part_floats) {
+  WS_REQUIRE(R > 0 && F > 0 && T > 0 && C > 0 && Q > 0 && H > 0 && C % H == 0 && cus > 0 && tsplit,
+             "ws_mhastp_split_sizes: bad args (R %d F %d T %d C %d Q %d H %d cus %d)", R, F, T, C, Q, H, cus);
+  *tsplit = mh_tsplit(R, T, H, cus);
+  if (part_floats) *part_floats = (long long)*tsplit * R * Q * H * 4 * (C / H) * F;
+  return WS_OK;
+}
+
+extern "C" int ws_mhastp_fwd_split(const float* x, const float* pack, int R, int F, int T, int C, int Q, int H,
+                                   int layers, int ds, int tsplit, float* part, float* out, float* aux, void* stream) {
+  MhGeom g{};
+  WS_REQUIRE(x && pack && part && out && aux, "ws_mhastp_fwd_split: null pointer");
+  WS_REQUIRE(mh_geom(R, F, T, C, Q, H, layers, ds, false, &g),
+             "ws_mhastp_fwd_split: unsupported geometry (R %d F %d T %d C %d Q %d H %d layers %d ds %d): H must divide "
+             "C, layers 1 or 2, ds 1 or C/H*F, one frame of the head within the LDS budget",
+             R, F, T, C, Q, H, layers, ds);
+  WS_REQUIRE(tsplit >= 1 && tsplit <= T && tsplit <= 65535, "ws_mhastp_fwd_split: %d T splits for %d frames", tsplit, T);
+  WS_REQUIRE((long long)R * Q * H < (1LL << 31), "ws_mhastp_fwd_split: grid too large");
+  g.tchunk = (T + tsplit - 1) / tsplit;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(mhastp_fwd_part_kernel, dim3(R * H, tsplit), dim3(MH_THREADS), mh_lds_bytes(g, false), s, x, pack,
+                     g, part);
+  int rc = ws_check_launch("ws_mhastp_fwd_split");
+  if (rc != WS_OK) return rc;
+  hipLaunchKernelGGL(mhastp_merge_kernel, dim3(R * Q * H), dim3(MH_THREADS), 0, s, part, g, tsplit, out, aux);
+  return ws_check_launch("ws_mhastp_fwd_split(merge)");
+}
+
+extern "C" int ws_mhastp_bwd_split(const float* x, const float* pack, const float* aux, const float* dout, int R,
+                                   int F, int T, int C, int Q, int H, int layers, int ds, int tsplit, float* dx,
+                                   float* work, float* slab, int nsplit, float* dpack, void* stream) {
+  return mh_bwd("ws_mhastp_bwd_split", x, pack, aux, dout, R, F, T, C, Q, H, layers, ds, tsplit, dx, work, slab, nsplit,
+                dpack, stream);
 }

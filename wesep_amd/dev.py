@@ -1391,6 +1391,46 @@ def mhastp_bwd(x, pack, aux, dout, R: int, F: int, T: int, Cc: int, Q: int, H: i
           _p(slab), nsplit, _p(dpack))
 
 
+def mhastp_split_sizes(R: int, F: int, T: int, Cc: int, Q: int, H: int, cus: int):
+    """(T splits of the split grid for `cus` CUs, floats of the split forward's workspace)."""
+    n, part = C.c_int(0), C.c_longlong(0)
+    if L.lib().ws_mhastp_split_sizes(R, F, T, Cc, Q, H, cus, C.byref(n), C.byref(part)) != L.WS_OK:   # host only
+        raise L.WesepHipError(L.lib().ws_last_error().decode("utf-8", "replace"))
+    return n.value, part.value
+
+
+def mhastp_fwd_split(x, pack, R: int, F: int, T: int, Cc: int, Q: int, H: int, layers: int, ds: int, out, aux,
+                     tsplit=None):
+    """MHASTP forward on the (R*H, tsplit) grid plus the merge; tsplit None: sized for this device's CUs."""
+    for n, t in (("x", x), ("pack", pack), ("out", out), ("aux", aux)):
+        _chk(t, n)
+    n, part = mhastp_split_sizes(R, F, T, Cc, Q, H, cu_count(x.device))
+    if tsplit is not None:
+        n, part = tsplit, part // n * tsplit
+    work = torch.empty(part, device=x.device, dtype=torch.float32)
+    _call("ws_mhastp_fwd_split", _p(x), _p(pack), R, F, T, Cc, Q, H, layers, ds, n, _p(work), _p(out), _p(aux))
+    return n
+
+
+def mhastp_bwd_split(x, pack, aux, dout, R: int, F: int, T: int, Cc: int, Q: int, H: int, layers: int, ds: int, dx,
+                     dpack=None, tsplit=None):
+    """mhastp_bwd with the dx launch split over T (tsplit None: sized for this device's CUs)."""
+    for n, t in (("x", x), ("pack", pack), ("aux", aux), ("dout", dout), ("dx", dx)):
+        _chk(t, n)
+    if tsplit is None:
+        tsplit = mhastp_split_sizes(R, F, T, Cc, Q, H, cu_count(x.device))[0]
+    work = slab = None
+    nsplit = 0
+    if dpack is not None:
+        nsplit = mhastp_nsplit(R, T)
+        work = torch.empty(mhastp_sizes(R, T, Q, H, layers, ds, Cc // H * F)[1], device=x.device, dtype=torch.float32)
+        if nsplit > 1:
+            slab = torch.empty(nsplit * dpack.numel(), device=x.device, dtype=torch.float32)
+    _call("ws_mhastp_bwd_split", _p(x), _p(pack), _p(aux), _p(dout), R, F, T, Cc, Q, H, layers, ds, tsplit, _p(dx),
+          _p(work), _p(slab), nsplit, _p(dpack))
+    return tsplit
+
+
 ASTP_FLOOR = 1e-7
 
 

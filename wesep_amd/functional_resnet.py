@@ -121,14 +121,16 @@ class TstpFn(torch.autograd.Function):
 
 class MhastpFn(torch.autograd.Function):
     """MHASTP / MQMHASTP pooling (models/resnet.py) of x [R*F*T, C] -> [R, Q*H*2*dm]: per query and head, mean || std
-    under the head's attention (csrc/mhastp.hip).  geo = (R, F, T, Q, H, layers, ds); params = per query, per head:
+    under the head's attention (csrc/mhastp.hip).  geo = (R, F, T, Q, H, layers, ds[, split]) -- split True: the grid
+    split over T (ws_mhastp_fwd_split / _bwd_split; the 1-D encoders); params = per query, per head:
     att_0.weight, att_0.bias (, att_1.weight, att_1.bias); cache: the pooling module's PackCache, which keeps the weight
     pack (W1's columns in the kernel order) for one weight version."""
 
     @staticmethod
     def forward(ctx, x, geo, cache, *params):
         _need_cuda(x, "MHASTP pooling")
-        R, Fq, T, Q, Hh, layers, ds = geo
+        R, Fq, T, Q, Hh, layers, ds = geo[:7]
+        split = len(geo) > 7 and bool(geo[7])
         x = x.contiguous()
         Cc = x.shape[1]
         Ch = Cc // Hh
@@ -138,9 +140,13 @@ class MhastpFn(torch.autograd.Function):
         pack = cache.get(sig, "mhastp", lambda: _mhastp_pack(params, Q * Hh, layers, ds, Fq, Ch, P1, x.device))
         out = _empty(x.device, R, Q * Hh * 2 * dm)
         aux = _empty(x.device, R * Q * Hh * 4, dm)
-        dev.mhastp_fwd(x, pack, R, Fq, T, Cc, Q, Hh, layers, ds, out, aux)
+        if split:
+            dev.mhastp_fwd_split(x, pack, R, Fq, T, Cc, Q, Hh, layers, ds, out, aux)
+        else:
+            dev.mhastp_fwd(x, pack, R, Fq, T, Cc, Q, Hh, layers, ds, out, aux)
         ctx.save_for_backward(x, pack, aux)
         ctx.geo = (R, Fq, T, Cc, Q, Hh, layers, ds, Ch, dm, P1)
+        ctx.split = split
         return out
 
     @staticmethod
@@ -150,7 +156,8 @@ class MhastpFn(torch.autograd.Function):
         wgrad = any(ctx.needs_input_grad[3:])
         dx = torch.empty_like(x)
         dpack = torch.empty(Q * Hh * P1, device=x.device, dtype=torch.float32) if wgrad else None
-        dev.mhastp_bwd(x, pack, aux, dout.contiguous(), R, Fq, T, Cc, Q, Hh, layers, ds, dx, dpack)
+        bwd = dev.mhastp_bwd_split if ctx.split else dev.mhastp_bwd
+        bwd(x, pack, aux, dout.contiguous(), R, Fq, T, Cc, Q, Hh, layers, ds, dx, dpack)
         if not wgrad:
             return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
         n1 = 64 if layers == 2 else ds

@@ -1,6 +1,7 @@
 """wespeaker CAM++ speaker encoder (`CAMPPlus`) on MI355X: module tree and `state_dict` keys of
 `wespeaker.models.campplus.CAMPPlus` (FCM convolutional head, D-TDNN backbone of three CAM-dense-TDNN blocks with
-context-aware masking, TSTP pooling, dense embedding layer), so that `spk_model_init` checkpoints load by name and
+context-aware masking, TSTP pooling by default or any of wespeaker's TAP / TSDP / ASTP / MHASTP / MQMHASTP, dense
+embedding layer), so that `spk_model_init` checkpoints load by name and
 `BSRNN(spk_model="CAMPPlus", ...)` trains jointly (recipe alternative: examples/librimix/tse/v2/confs/bsrnn.yaml:66-74;
 call site wesep/models/bsrnn.py:217,352-356).  wespeaker is a third-party dependency absent from the reference tree: the
 architecture is restated from its published definition (Wang et al. 2023) and parity is against
@@ -211,11 +212,9 @@ class CAMPPlus(nn.Module):
     def __init__(self, feat_dim=80, embed_dim=512, pooling_func="TSTP", growth_rate=32, bn_size=4, init_channels=128,
                  config_str="batchnorm-relu", memory_efficient=True):
         super().__init__()
-        if pooling_func != "TSTP":
-            raise NotImplementedError(f"CAM++ pooling_func {pooling_func!r}: TSTP (the upstream default) is built")
         if feat_dim % 8:
             raise NotImplementedError("CAM++: feat_dim must be a multiple of 8 (three mel-axis strides of 2)")
-        from .resnet import TSTP
+        from .resnet import _pooling_layer
         self.head = FCM(feat_dim=feat_dim)
         channels = self.head.out_channels
         self.xvector = nn.Sequential(OrderedDict([
@@ -232,9 +231,12 @@ class CAMPPlus(nn.Module):
                                     TransitLayer(channels, channels // 2, bias=False, config_str=config_str))
             channels //= 2
         self.xvector.add_module("out_nonlinear", get_nonlinear(config_str, channels))
-        self.pool = TSTP(in_dim=channels)
+        self.pooling_func = pooling_func
+        self.pool = _pooling_layer(pooling_func, channels)
+        if pooling_func in ("MHASTP", "MQMHASTP"):
+            self.pool.check_channels(channels)
         self.pool_out_dim = self.pool.get_out_dim()
-        self.xvector.add_module("stats", self.pool)
+        self.xvector.add_module("stats", self.pool)         # one object under two names: its tensors under both prefixes
         self.xvector.add_module("dense", DenseLayer(self.pool_out_dim, embed_dim, config_str="batchnorm_"))
         self.feat_dim, self.embed_dim = feat_dim, embed_dim
         for m in self.modules():
@@ -258,5 +260,6 @@ class CAMPPlus(nn.Module):
             y = getattr(xv, "block%d" % i).run(y, R, T, tr)
             y = getattr(xv, "transit%d" % i).run(y, R, T, tr)
         y = _nonlinear(y, xv.out_nonlinear, tr)
-        stats = FR.TstpFn.apply(y, (R, 1, T))                                 # [R, 2C] mean || sqrt(var + 1e-7)
+        from .resnet import run_pool
+        stats = run_pool(self.pool, self.pooling_func, y, R, T)               # TSTP: [R, 2C] mean || sqrt(var + 1e-7)
         return xv.dense.run(stats, tr)

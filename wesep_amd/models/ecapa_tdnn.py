@@ -1,6 +1,7 @@
 """wespeaker ECAPA-TDNN speaker encoder on MI355X: module tree and `state_dict` keys
-of `wespeaker.models.ecapa_tdnn.ECAPA_TDNN` (ECAPA_TDNN_c512 / _c1024 and their global-context "GLOB" variants with
-ASTP pooling), so that `spk_model_init` checkpoints and the speaker half of the reference's published
+of `wespeaker.models.ecapa_tdnn.ECAPA_TDNN` (ECAPA_TDNN_c512 / _c1024 and their global-context "GLOB" variants; ASTP
+pooling by default, or any of wespeaker's TSTP / TAP / TSDP / MHASTP / MQMHASTP, models/resnet.py), so that
+`spk_model_init` checkpoints and the speaker half of the reference's published
 `bsrnn_ecapa_vox1` model (wesep/cli/hub.py:86-95; recipe alternative examples/librimix/tse/v2/confs/bsrnn.yaml:66-71)
 load by name.  wespeaker is a third-party dependency absent from the reference tree: the architecture is restated
 from its published definition (Desplanques et al. 2020: Conv1d-ReLU-BN layers, three SE-Res2Blocks of scale 8 with
@@ -126,8 +127,7 @@ class ECAPA_TDNN(nn.Module):
     def __init__(self, channels=512, feat_dim=80, embed_dim=192, pooling_func="ASTP", global_context_att=False,
                  emb_bn=False):
         super().__init__()
-        if pooling_func != "ASTP":
-            raise NotImplementedError(f"ECAPA-TDNN pooling_func {pooling_func!r}: ASTP (the recipe's) is built")
+        from .resnet import _pooling_layer
         self.layer1 = Conv1dReluBn(feat_dim, channels, kernel_size=5, padding=2)
         self.layer2 = SE_Res2Block(channels, kernel_size=3, stride=1, padding=2, dilation=2, scale=8)
         self.layer3 = SE_Res2Block(channels, kernel_size=3, stride=1, padding=3, dilation=3, scale=8)
@@ -135,7 +135,10 @@ class ECAPA_TDNN(nn.Module):
         cat_channels = channels * 3
         out_channels = 512 * 3
         self.conv = nn.Conv1d(cat_channels, out_channels, kernel_size=1)
-        self.pool = ASTP(in_dim=out_channels, global_context_att=global_context_att)
+        self.pooling_func = pooling_func
+        self.pool = _pooling_layer(pooling_func, out_channels, global_context_att=global_context_att)
+        if pooling_func in ("MHASTP", "MQMHASTP"):
+            self.pool.check_channels(out_channels)
         self.pool_out_dim = self.pool.get_out_dim()
         self.bn = nn.BatchNorm1d(self.pool_out_dim)
         self.linear = nn.Linear(self.pool_out_dim, embed_dim)
@@ -159,7 +162,8 @@ class ECAPA_TDNN(nn.Module):
         out4 = self.layer4.run(out3, R, T)
         cat = torch.cat([out2, out3, out4], 1)
         h = FE.LinearReluFn.apply(cat, self.conv.weight.view(self.conv.weight.shape[0], -1), self.conv.bias)
-        stats = self.pool.run(h, R, T)
+        from .resnet import run_pool
+        stats = run_pool(self.pool, self.pooling_func, h, R, T)
         if tr:
             self.bn.num_batches_tracked += 1
         stats = FE.BatchNormRowsFn.apply(stats, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var, tr)

@@ -85,15 +85,16 @@ class MHASTP(nn.Module):
         """The kernels' geometry: a head is a channel range of the [R, F', T', C] activation (C*F' = in_dim)."""
         if C % self.head_num:
             raise NotImplementedError(f"MHASTP head_num {self.head_num} does not divide the {C} channels: a head must be "
-                                      "a channel range of the ResNet's activation")
+                                      "a channel range of the encoder's activation")
         n1 = 64 if self.layer_num == 2 else self.d_s
         if 2 * self.d_model + n1 + (self.d_s if self.layer_num == 2 else 0) > MHASTP_LDS_FLOATS:
             raise NotImplementedError(f"MHASTP d_model {self.d_model}: one frame of a head exceeds the kernels' LDS "
                                       "tile; use more heads")
 
-    def run(self, y, R, Fq, T):
-        """y [R*F'*T', C] (the last block's channels-last output) -> [R, 2 * in_dim]."""
-        return _mhastp_run([self], self.cache, y, R, Fq, T)
+    def run(self, y, R, Fq, T, split=False):
+        """y [R*F'*T', C] (the last block's channels-last output) -> [R, 2 * in_dim].  split: the grid split over T
+        (the 1-D encoders, F' = 1, which pool at the full frame rate)."""
+        return _mhastp_run([self], self.cache, y, R, Fq, T, split)
 
 
 class MQMHASTP(nn.Module):
@@ -113,28 +114,49 @@ class MQMHASTP(nn.Module):
     def check_channels(self, C):
         self.n_query[0].check_channels(C)
 
-    def run(self, y, R, Fq, T):
-        return _mhastp_run(list(self.n_query), self.cache, y, R, Fq, T)
+    def run(self, y, R, Fq, T, split=False):
+        return _mhastp_run(list(self.n_query), self.cache, y, R, Fq, T, split)
 
 
-def _mhastp_run(queries, cache, y, R, Fq, T):
+def _mhastp_run(queries, cache, y, R, Fq, T, split=False):
     q0 = queries[0]
     params = [p for q in queries for p in q.att_params()]
-    return FR.MhastpFn.apply(y, (R, Fq, T, len(queries), q0.head_num, q0.layer_num, q0.d_s), cache, *params)
+    geo = (R, Fq, T, len(queries), q0.head_num, q0.layer_num, q0.d_s) + ((True,) if split else ())
+    return FR.MhastpFn.apply(y, geo, cache, *params)
 
 
-def _pooling_layer(name, in_dim):
+POOLING_FUNCS = ("TSTP", "TAP", "TSDP", "ASTP", "MHASTP", "MQMHASTP")
+
+
+def _pooling_layer(name, in_dim, **kwargs):
     """wespeaker.models.pooling_layers by name: TSTP / TAP / TSDP (one statistics kernel), ASTP (attentive statistics,
     the ECAPA-TDNN module of models/ecapa_tdnn.py on the [R, C * F', T] view), MHASTP and MQMHASTP (csrc/mhastp.hip) --
-    each with the constructor defaults wespeaker's ResNet builds it with (`in_dim` only)."""
+    each with the constructor defaults wespeaker builds it with (`in_dim` only); kwargs (ECAPA-TDNN's
+    global_context_att) go to every class, and only ASTP uses them."""
     if name in ("TSTP", "TAP", "TSDP"):
-        return {"TSTP": TSTP, "TAP": TAP, "TSDP": TSDP}[name](in_dim=in_dim)
+        return {"TSTP": TSTP, "TAP": TAP, "TSDP": TSDP}[name](in_dim=in_dim, **kwargs)
     if name == "ASTP":
         from .ecapa_tdnn import ASTP
-        return ASTP(in_dim=in_dim)
+        return ASTP(in_dim=in_dim, **kwargs)
     if name in ("MHASTP", "MQMHASTP"):
-        return {"MHASTP": MHASTP, "MQMHASTP": MQMHASTP}[name](in_dim=in_dim)
+        return {"MHASTP": MHASTP, "MQMHASTP": MQMHASTP}[name](in_dim=in_dim, **kwargs)
     raise NotImplementedError(f"pooling_func {name!r}: TSTP, TAP, TSDP, ASTP, MHASTP and MQMHASTP are built")
+
+
+def run_pool(pool, name, y, R, T):
+    """A pooling layer of _pooling_layer on the channels-last frames y [R*T, C] of a 1-D encoder (F' = 1) ->
+    [R, pool.get_out_dim()]; MHASTP / MQMHASTP on the grid split over T."""
+    if name == "ASTP":
+        return pool.run(y, R, T)
+    if name in ("MHASTP", "MQMHASTP"):
+        return pool.run(y, R, 1, T, split=True)
+    stats = FR.TstpFn.apply(y, (R, 1, T))                                   # mean || sqrt(var + 1e-7), each [C]
+    half = stats.shape[1] // 2
+    if name == "TAP":
+        return stats[:, :half].contiguous()
+    if name == "TSDP":
+        return stats[:, half:].contiguous()
+    return stats
 
 
 class BasicBlock(nn.Module):
