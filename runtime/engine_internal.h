@@ -1,0 +1,381 @@
+// engine_internal.h -- private header of libwesep_engine.so (include/wesep_engine.h is the public C ABI).
+//
+// The runtime is one translation unit per part:
+//   engine.cc        weight container, arena helpers, shared launch helpers, load dispatch by meta "arch", the C ABI
+//   speaker.cc       speaker stage: kaldi fbank / MelSpectrogram front-ends, ResNet / ECAPA-TDNN / CAM++ encoders,
+//                    their pooling layer, SpeakerTransform
+//   bsrnn_plan.cc    pBSRNN (arch 0)
+//   tasnet_plan.cc   Conv-TasNet / SpEx+ (arch 1)
+//   dpccn_plan.cc    DPCCN (arch 2)
+//   gridnet_plan.cc  TF-GridNet (arch 3)
+// Everything here lives in namespace wsrt and is built with -fvisibility=hidden: the library exports the C ABI only
+// (WS_ENGINE_API).  Host code only: no kernels in the runtime.
+#ifndef WESEP_ENGINE_INTERNAL_H_
+#define WESEP_ENGINE_INTERNAL_H_
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <initializer_list>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../include/wesep_engine.h"
+#include "../include/wesep_hip.h"
+
+#define WS_ENGINE_API extern "C" __attribute__((visibility("default")))
+
+namespace wsrt {
+
+constexpr int kN = 128;                 // feature_dim
+constexpr int kH = 256;                 // LSTM hidden size
+constexpr int kG4 = 4 * kH;             // gate rows per direction
+constexpr int kNBin = 257;              // n_fft / 2 + 1
+constexpr int kHop = 128;
+constexpr int kBig = 1 << 30;           // row divisor meaning "never wraps"
+constexpr int kDpBins = 257;            // DPCCN: n_fft / 2 + 1
+constexpr float kGnEps = 1.1920928955078125e-07f;   // torch.finfo(float32).eps, bsrnn.py:23
+constexpr float kBnEps = 1e-5f;
+constexpr float kLnEps = 1e-5f;
+
+struct Tensor {
+  std::vector<int64_t> dims;
+  size_t off = 0;   // floats into the weight blob
+  size_t n = 0;
+};
+
+void set_err(const char* fmt, ...);
+
+// ---- device memory: chunked bump allocator with stack discipline --------------------------------------------
+struct Arena {
+  struct Chunk {
+    char* base;
+    size_t cap;
+  };
+  std::vector<Chunk> chunks;
+  size_t cur = 0, top = 0;      // current chunk and offset inside it
+  size_t live_bytes = 0, peak_bytes = 0;
+  bool dry = false;
+  bool poison = getenv("WS_ENGINE_POISON") != nullptr;
+
+  struct Mark {
+    size_t cur, top, live;
+  };
+
+  static size_t round_up(size_t b) { return (b + 255) & ~size_t(255); }
+
+  bool add_chunk(size_t bytes) {
+    Chunk c{nullptr, bytes};
+    if (dry) {
+      c.base = static_cast<char*>(malloc(bytes));
+    } else if (hipMalloc(reinterpret_cast<void**>(&c.base), bytes) != hipSuccess) {
+      c.base = nullptr;
+    }
+    if (!c.base) return false;
+    chunks.push_back(c);
+    return true;
+  }
+
+  float* alloc(size_t nfloats) {
+    const size_t bytes = round_up(nfloats * 4 + 4);
+    while (true) {
+      if (cur < chunks.size() && top + bytes <= chunks[cur].cap) break;
+      if (cur + 1 < chunks.size()) {           // move on to the next existing chunk
+        ++cur;
+        top = 0;
+        continue;
+      }
+      const size_t want = bytes > (size_t(256) << 20) ? bytes : (size_t(256) << 20);
+      if (!add_chunk(want)) {
+        set_err("engine: device allocation of %zu bytes failed", want);
+        return nullptr;
+      }
+      cur = chunks.size() - 1;
+      top = 0;
+    }
+    float* p = reinterpret_cast<float*>(chunks[cur].base + top);
+    // WS_ENGINE_POISON=1 (tests): every allocation starts as NaN (0xFF bytes), so a launch plan that reads memory no
+    // kernel has written shows up as NaN output instead of depending on what the arena held before (device-wide
+    // syncs around it: the engine's stream is non-blocking).
+    if (poison && !dry) {
+      (void)hipDeviceSynchronize();
+      (void)hipMemset(p, 0xFF, bytes);
+      (void)hipDeviceSynchronize();
+    }
+    top += bytes;
+    live_bytes += bytes;
+    if (live_bytes > peak_bytes) peak_bytes = live_bytes;
+    return p;
+  }
+
+  Mark mark() const { return Mark{cur, top, live_bytes}; }
+  void release(const Mark& m) {
+    cur = m.cur;
+    top = m.top;
+    live_bytes = m.live;
+  }
+  void reset() {
+    cur = 0;
+    top = 0;
+    live_bytes = 0;
+  }
+  // after a forward that had to add chunks: one chunk of the peak size for the next call
+  void consolidate() {
+    if (chunks.size() <= 1 || live_bytes != 0) return;
+    const size_t want = round_up(peak_bytes + (size_t(16) << 20));
+    free_all();
+    add_chunk(want);
+  }
+  void free_all() {
+    for (auto& c : chunks) {
+      if (dry)
+        free(c.base);
+      else
+        (void)hipFree(c.base);
+    }
+    chunks.clear();
+    reset();
+  }
+};
+
+struct RnnPrep {            // one ResRNN (bsrnn.py:26-46) or TF-GridNet BLSTM, everything the forward needs, device pointers
+  const float *norm_w, *norm_b, *whf, *whr, *proj_b;
+  float *bcat, *wih_pack, *proj_pack, *fpack, *pack16, *pack32;
+};
+
+// ---- speaker encoder, its front-end and pooling layer (speaker.cc) ----
+struct ConvPrep {           // conv (bias-free) + BatchNorm(eval) (+ ReLU) of the speaker encoder
+  int cin, cout, k, stride, ldp;
+  int sw = 0;               // stride along W when it differs from `stride` (CAM++'s FCM head strides the mel axis only); 0: same
+  bool relu;
+  const float *gamma, *beta;
+  float *w2, *st;           // [cout][ldp] in im2col column order; [2][cout] = (running mean, rstd)
+};
+
+struct BlockPrep {          // BasicBlock: c1 (3x3, stride) c2 (3x3); Bottleneck: c1 (1x1) c2 (3x3, stride) c3 (1x1, x4)
+  ConvPrep c1, c2, c3, sc;
+  bool has_sc;
+};
+
+struct TdnnPrep {           // Conv1d (bias) -> ReLU -> BatchNorm1d(eval): wespeaker ECAPA-TDNN's Conv1dReluBn
+  int cin, cout, k, dil;
+  const float *w, *bias, *gamma, *beta;   // w: k == 1 the checkpoint's [cout][cin]; else the one-row-image view weight
+  float* st;                              // [2][cout] = (running mean, rstd)
+};
+
+struct SeRes2Prep {         // SE_Res2Block: 1x1 TDNN, Res2Net branches, 1x1 TDNN, squeeze-excitation, + input
+  TdnnPrep in, out;
+  std::vector<TdnnPrep> branch;
+  std::string se;           // "...se_res2block.3." (linear1 / linear2)
+};
+
+struct CamBn {              // BatchNorm1d(eval) of a pre-activation D-TDNN layer: (mean, rstd) + affine operands (or ones / zeros)
+  int c;
+  float* st;
+  const float *gamma, *beta;
+};
+struct CamLayer {           // CAMDenseTDNNLayer: BN-ReLU, 1x1 to 128, BN-ReLU, dilated k = 3 conv to 32, context-aware mask
+  int cin, dil;
+  CamBn bn1, bn2;
+  const float *w1, *wloc;   // linear1 [128][cin]; linear_local as the 3 x 3 view of the one-row image [32][9 * 128]
+  const float *l1w, *l1b, *l2w, *l2b;
+};
+struct CamTransit {         // BN-ReLU + 1x1 (bias-free) to half the channels
+  int cin, cout;
+  CamBn bn;
+  const float* w;
+};
+
+struct SpeakerEncoder {
+  // meta: kind 0 wespeaker ResNet, 1 ECAPA-TDNN (wesep_amd/models/ecapa_tdnn.py), 2 CAM++ (wesep_amd/models/campplus.py)
+  int kind = 0, channels = 512, glob = 0, emb_bn = 0, feat_dim = 80;
+  int blocks[4] = {0, 0, 0, 0};
+  int bottleneck = 0, two_emb = 0;    // wespeaker ResNet50 / 101 / 152 blocks; seg_1 -> ReLU -> BN -> seg_2
+  // pooling (meta spk_pool: 0 TSTP, 1 MHASTP, 2 MQMHASTP, 3 ASTP, 4 TAP, 5 TSDP; absent: ASTP for ECAPA-TDNN, TSTP
+  // otherwise).  MHASTP / MQMHASTP: queries x heads of attentive statistics, the weights of every (query, head) in one
+  // pack (include/wesep_hip.h, ws_mhastp_fwd; the 1-D encoders launch ws_mhastp_fwd_split)
+  int pool = 0, pool_q = 1, pool_h = 1, pool_layers = 2, pool_ds = 1;
+  float* pool_pack = nullptr;
+  // ResNet
+  ConvPrep stem;
+  std::vector<BlockPrep> res_blocks;
+  float* seg_bn_st = nullptr;
+  // ECAPA-TDNN
+  TdnnPrep tdnn1;
+  std::vector<SeRes2Prep> se_blocks;
+  float *pool_bn_st = nullptr, *emb_bn_st = nullptr;
+  // CAM++
+  std::vector<ConvPrep> cam_fcm;      // conv1, then per BasicResBlock (conv1, [shortcut], conv2), then conv2
+  std::vector<int> cam_fcm_kind;      // 0 plain, 1 block conv1, 2 shortcut, 3 block conv2 (+ residual)
+  const float* cam_tdnn_w = nullptr;  // xvector.tdnn as the 5 x 5 view weight
+  CamBn cam_tdnn_bn, cam_out_bn, cam_dense_bn;
+  std::vector<std::vector<CamLayer>> cam_blocks;
+  std::vector<CamTransit> cam_transit;
+  int cam_init = 128, cam_growth = 32, cam_bn = 128;
+  float *cam_one = nullptr, *cam_zero = nullptr, *cam_id_st = nullptr;   // ones / zeros / (0 x C | 1 x C), C = 1024
+  // front-end: kaldi fbank (meta spk_feat = 1), or the in-model PreEmphasis + MelSpectrogram of spk_feat = False models
+  // (bsrnn.py:231-242,343-350)
+  int feat = 1;
+  float *fb_basis = nullptr, *fb_bank = nullptr, *fb_floor = nullptr;
+  int fb_win = 400, fb_shift = 160, fb_padded = 512;
+  float *mel_basis = nullptr, *mel_fbt = nullptr, mel_coef = 0.97f;
+  int mel_lds = 516, mel_ldp = 260;
+};
+
+// ---- pBSRNN (arch 0; bsrnn_plan.cc) ----
+struct Bsrnn {
+  int num_repeat = 6, fuse = 2, multi_fuse = 0;
+  // band tables (bsrnn.py:190-209)
+  std::vector<int> bw, f0;
+  int K = 0;
+  int *d_band_of_bin = nullptr, *d_f0 = nullptr, *d_bw = nullptr, *d_bw2 = nullptr, *d_off2 = nullptr;
+  std::vector<RnnPrep> rnn;       // 2 per BSNet: band_rnn (time view), band_comm (band view)
+  std::vector<int> sep_kind;      // per entry of separator.separation: 0 fuse layer, 1 BSNet
+  // grouped-GEMM descriptor tables, rebuilt when (R, Tf) changes
+  int desc_R = -1, desc_Tf = -1;
+  ws_group_nt *d_bn = nullptr, *d_l1 = nullptr, *d_l2 = nullptr, *d_l3 = nullptr;
+};
+
+// ---- Conv-TasNet / SpEx+ (arch 1; wesep/models/convtasnet.py; tasnet_plan.cc): geometry and prepared operands ----
+struct TasNet {
+  int N = 512, L = 16, B = 128, H = 512, P = 3, X = 8, R = 3;
+  float* dec_wt = nullptr;   // decoder_1d_1 weight transposed to [L][N]
+  float* bn_st[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};  // eval BN (mean, rstd) [2][C]
+};
+
+// ---- DPCCN (arch 2; wesep/models/dpccn.py; dpccn_plan.cc): prepared operands, in the order the forward consumes them ----
+struct Dpccn {
+  int fuse = 2, causal = 0, tcn_blocks = 10, tcn_layers = 2;
+  float *ana4 = nullptr, *syn4 = nullptr;       // analysis basis [4 * 257][512] (re, im, 0, 0 per bin), synthesis [512][4 * 257]
+  float* w_in = nullptr;                        // conv2d (2 -> 16) as [16][9 * 4] on the (re, im, 0, 0) pixels
+  float *w_out = nullptr, *b_out = nullptr;     // deconv2d (32 -> 2) as [4][9 * 32] + bias[4]: (re, im, 0, 0) per bin
+  float *ones = nullptr, *zeros = nullptr;      // gamma 1, beta 0 of the plain depthwise conv
+  std::map<std::string, float*> w;              // per-layer GEMM weights / conv3x3 packs, keyed by the layer's state_dict prefix
+};
+
+// ---- TF-GridNet (arch 3; gridnet_plan.cc) ----
+struct GridBlock {
+  RnnPrep intra, inter;
+  float *wqkv, *bqkv;                    // [nh*(2E + cp)][C] rows (Q heads | K heads | V heads), bias
+  float *gam[3], *bet[3];                // per projection: [nh][Q*ch], index q*ch + e
+  float *proj_g, *proj_b;                // [Q*C], index q*C + c
+};
+struct GridNet {
+  int n_fft = 128, hop = 64, Q = 65, C = 128, hid = 192, nh = 4, E = 8, layers = 6, fuse = 2;
+  float *ana4 = nullptr, *syn4 = nullptr, *w_in = nullptr, *w_out = nullptr, *b_out = nullptr;
+  float *ones_c = nullptr, *zeros_c = nullptr, *ones_qc = nullptr, *zeros_qc = nullptr;
+  float *id_st = nullptr, *slope1 = nullptr, *film_bias1 = nullptr;
+  std::vector<GridBlock> blocks;
+};
+
+}  // namespace wsrt
+
+struct ws_engine {
+  bool dry = false;
+  int device = 0, cu_count = 0;
+  hipStream_t stream = nullptr;
+  std::map<std::string, int64_t> meta;
+  std::map<std::string, wsrt::Tensor> tensors;
+  std::vector<float> hw;          // host copy of the weight blob
+  float* dw = nullptr;            // device copy
+  wsrt::Arena persist, work;
+  long long n_launches = 0;
+  long long cluster_fallbacks = 0;   // forwards in which a cluster recurrence timed out and the streaming kernels took over
+  unsigned* cl_status = nullptr;     // sticky device word set by ws_lstm_fwd_cluster on a timeout
+  // configuration shared by the plans
+  int arch = 0;                   // 0 pBSRNN, 1 Conv-TasNet, 2 DPCCN, 3 TF-GridNet
+  int sr = 16000, E = 256, use_xform = 0, joint = 0;
+  float *id_st = nullptr, *id_one = nullptr, *id_zero = nullptr;   // identity BatchNorm operands: y = x + res
+  float *slope0 = nullptr, *slope1 = nullptr;     // PReLU slopes 0 (ReLU) and 1 (identity)
+  // the parts
+  wsrt::SpeakerEncoder spk;
+  wsrt::Bsrnn bs;
+  wsrt::TasNet tas;
+  wsrt::Dpccn dp;
+  wsrt::GridNet grid;
+
+  const wsrt::Tensor* find(const std::string& name) const {
+    auto it = tensors.find(name);
+    return it == tensors.end() ? nullptr : &it->second;
+  }
+  const float* dev(const std::string& name) const {
+    const wsrt::Tensor* t = find(name);
+    return t ? dw + t->off : nullptr;
+  }
+  const float* host(const std::string& name) const {
+    const wsrt::Tensor* t = find(name);
+    return t ? hw.data() + t->off : nullptr;
+  }
+};
+
+namespace wsrt {
+
+// A launch "passes" when it succeeded, or -- in a dry run -- when it failed for any reason other than its
+// argument validation (there is no device to launch on).
+bool passes(ws_engine* e, int rc, const char* what);
+
+#define WS_RUN(e, call)                              \
+  do {                                               \
+    const int rc__ = (call);                         \
+    if (!passes((e), rc__, #call)) return rc__ ? rc__ : WS_ERR_LAUNCH; \
+  } while (0)
+
+#define WS_PTR(p)                  \
+  do {                             \
+    if (!(p)) return WS_ERR_LAUNCH; \
+  } while (0)
+
+// ---- shared helpers (engine.cc) ----
+int to_device(ws_engine* e, void* dst, const void* src, size_t bytes);
+int to_host(ws_engine* e, void* dst, const void* src, size_t bytes);
+int zero_device(ws_engine* e, void* p, size_t bytes);
+float* upload(ws_engine* e, Arena& a, const float* src, size_t n);
+int* upload_ints(ws_engine* e, Arena& a, const std::vector<int>& v);
+int64_t meta_or(const ws_engine* e, const char* key, int64_t dflt);
+bool require(ws_engine* e, const std::string& name, std::initializer_list<int64_t> dims);
+float* bn_eval_stats(ws_engine* e, const std::string& bn, int c);
+int vec_bits(std::initializer_list<long long> dims, int base = 3);
+int linear(ws_engine* e, const float* x, int M, int k, const float* W, long long ldw, int nout, const float* bias,
+           int act, float* y);
+int copy_cols(ws_engine* e, float* dst, long long ldd, const float* src, long long lds, int width, long long rows);
+int time_mean(ws_engine* e, const float* x, int R, int T, int C, float* mean2);
+
+// ---- speaker stage (speaker.cc) ----
+int read_speaker_meta(ws_engine* e);
+int prep_spk_transform(ws_engine* e);
+int prep_speaker(ws_engine* e);
+int speaker_embed(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, int Te, float* emb);
+int spk_transform(ws_engine* e, const float* emb, int R, const float** out);
+
+// ---- launch plans ----
+int prepare_bsrnn(ws_engine* e);
+int pack_rnn(ws_engine* e, int C, const float* wih_f, const float* wih_r, const float* const bias[4], const float* proj_w,
+             RnnPrep* r);
+int separate_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est);
+int prepare_tasnet(ws_engine* e);
+int tasnet_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind, int enroll_len,
+                    float* est);
+int tas_row_stats(ws_engine* e, const float* x, long long M, int C, float* st);
+int tas_flat_stats(ws_engine* e, const float* x, int R, long long n, float* st);
+int prepare_dpccn(ws_engine* e);
+int dpccn_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est);
+int dp_conv_view(ws_engine* e, const float* x, int R, int H, int W, int Cin, int mode, int Wo, int sw, const float* Wm, int Cout,
+                 const float* bias, float* y, long long ldy);
+int dp_gemm(ws_engine* e, const float* A, long long M, int K, const float* Wm, int N, const float* bias, const float* Rm, float* C,
+            long long ldc);
+int dp_io_convs(ws_engine* e, const std::string& conv, int cin, const std::string& deconv, int cout, float** w_in, float** w_out,
+                float** b_out);
+int dft_bases(ws_engine* e, int n, float** ana4, float** syn4);
+int dft_istft(ws_engine* e, const float* est4, const float* syn4, int R, int Tf, int n, int hop, int T, float* est);
+int prepare_gridnet(ws_engine* e);
+int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est);
+
+}  // namespace wsrt
+
+#endif  // WESEP_ENGINE_INTERNAL_H_

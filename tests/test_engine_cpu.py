@@ -1,4 +1,4 @@
-"""CPU: the native runtime (include/wesep_engine.h, runtime/engine.cc) without a GPU -- library and symbols, the
+"""CPU: the native runtime (include/wesep_engine.h, runtime/*.cc) without a GPU -- library and symbols, the
 weight container written by `wesep_amd.bin.export_engine`, the engine's DRY RUN (every launch of the plan must pass
 its entry point's argument validation in the real libwesep_hip.so; nothing is computed), the wav reader / writer and
 the `separate_main` command-line tool."""

@@ -1,4 +1,4 @@
-"""GPU: the native runtime (runtime/engine.cc behind include/wesep_engine.h) against the Python module tree on the
+"""GPU: the native runtime (runtime/*.cc behind include/wesep_engine.h) against the Python module tree on the
 same device (same kernels, weights packed once instead of per call -> agreement to rounding), against the CPU oracle,
 and the `separate_main` tool end to end."""
 import os

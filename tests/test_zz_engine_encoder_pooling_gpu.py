@@ -1,4 +1,4 @@
-"""GPU: the native runtime's ECAPA-TDNN and CAM++ launch plans with a non-default pooling layer (runtime/engine.cc,
+"""GPU: the native runtime's ECAPA-TDNN and CAM++ launch plans with a non-default pooling layer (runtime/speaker.cc,
 meta spk_pool; MHASTP / MQMHASTP on ws_mhastp_fwd_split) against the Python module tree in eval mode on the same device:
 pBSRNN with ECAPA-MQMHASTP, CAM++-ASTP and CAM++-MQMHASTP, and a DPCCN with ECAPA-MHASTP."""
 import pytest

@@ -1,4 +1,4 @@
-"""GPU: the native runtime's launch plans for Bottleneck ResNets and `two_emb_layer` (runtime/engine.cc) against the
+"""GPU: the native runtime's launch plans for Bottleneck ResNets and `two_emb_layer` (runtime/speaker.cc) against the
 Python module tree in eval mode on the same device.  Written with the round's last GPU seconds: the case that covers both
 features (ResNet50 + two_emb_layer) ran green on an MI355X, the two single-feature cases had their plans validated by the
 dry run only (tests/test_engine_cpu.py) -- the file sorts last so that their first run cannot hide any other test behind

@@ -1,4 +1,4 @@
-"""GPU: the native runtime's ResNet launch plan with MHASTP / MQMHASTP pooling (runtime/engine.cc, meta spk_pool) against
+"""GPU: the native runtime's ResNet launch plan with MHASTP / MQMHASTP pooling (runtime/speaker.cc, meta spk_pool) against
 the Python module tree in eval mode on the same device: a pBSRNN with ResNet34-MQMHASTP and a DPCCN with ResNet50-MHASTP."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""GPU: the native runtime's DPCCN and TF-GridNet launch plans (runtime/engine.cc, arch 2 / 3) against the Python module
+"""GPU: the native runtime's DPCCN and TF-GridNet launch plans (runtime/dpccn_plan.cc, runtime/gridnet_plan.cc) against the Python module
 tree in eval mode on the same device.  The plan's first execution was a Python-free run of `runtime/separate_main` with the round's last GPU
 seconds (profiles/r03_engine_dpccn_hw_check.json: joint ResNet18 + multiply fusion, 2.2e-5 from the CPU oracle chain);
 the TF-GridNet plan's likewise (profiles/r03_engine_tfgridnet_hw_check.json: 1.1e-5).  These comparisons -- which also cover

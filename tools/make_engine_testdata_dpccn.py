@@ -1,6 +1,6 @@
 """Writes runtime/_testdata/dpccn/: a deterministic joint DPCCN (2 x 4 TCN blocks, multiply fusion, ResNet18 on kaldi
 fbank) as a weight container, three wav files and a wav.scp, plus the CPU oracle's expected outputs (expected.npz) --
-the inputs of a Python-free hardware check of the native runtime's DPCCN plan (runtime/engine.cc, arch 2):
+the inputs of a Python-free hardware check of the native runtime's DPCCN plan (runtime/dpccn_plan.cc, arch 2):
 
     runtime/separate_main --wav_scp runtime/_testdata/dpccn/wav.scp --model runtime/_testdata/dpccn/m.wsw \
                           --output_dir <dir> --raw_out

@@ -1,6 +1,6 @@
 """Writes runtime/_testdata/tfgridnet/: a deterministic joint TF-GridNet (recipe geometry, 2 blocks, multiply fusion,
 ResNet18 on kaldi fbank) as a weight container, three wav files and a wav.scp, plus the CPU oracle's expected outputs
-(expected.npz) -- the inputs of a Python-free hardware check of the native runtime's TF-GridNet plan (runtime/engine.cc,
+(expected.npz) -- the inputs of a Python-free hardware check of the native runtime's TF-GridNet plan (runtime/gridnet_plan.cc,
 arch 3):
 
     runtime/separate_main --wav_scp runtime/_testdata/tfgridnet/wav.scp --model runtime/_testdata/tfgridnet/m.wsw \

@@ -1,5 +1,5 @@
 """Write a pBSRNN, Conv-TasNet / SpEx+, DPCCN or TF-GridNet checkpoint as the flat weight container of the native runtime (include/wesep_engine.h,
-runtime/engine.cc) -- the counterpart of the reference's `wesep/bin/export_jit.py` (TorchScript archive for the
+runtime/*.cc) -- the counterpart of the reference's `wesep/bin/export_jit.py` (TorchScript archive for the
 LibTorch runtime).
 
     python -m wesep_amd.bin.export_engine --config conf.yaml --checkpoint avg_model.pt --out model.wsw

@@ -62,6 +62,8 @@ def build(force=False, verbose=True):
 RUNTIME = os.path.join(os.path.dirname(HERE), "runtime")
 ENGINE_OUT = os.path.join(RUNTIME, "libwesep_engine.so")
 MAIN_OUT = os.path.join(RUNTIME, "separate_main")
+# libwesep_engine.so: one translation unit per part (runtime/engine_internal.h); it exports the C ABI only
+ENGINE_SRCS = ["engine.cc", "speaker.cc", "bsrnn_plan.cc", "tasnet_plan.cc", "dpccn_plan.cc", "gridnet_plan.cc"]
 
 
 def build_runtime(force=False, verbose=True):
@@ -69,12 +71,13 @@ def build_runtime(force=False, verbose=True):
     command-line tool.  Host code only; links libwesep_hip.so (built first)."""
     hipcc = os.environ.get("HIPCC", "hipcc")
     inc = os.path.join(os.path.dirname(HERE), "include")
-    deps = [os.path.join(RUNTIME, f) for f in ("engine.cc", "wav_io.h", "separate_main.cc")] + \
+    deps = [os.path.join(RUNTIME, f) for f in ENGINE_SRCS + ["engine_internal.h", "wav_io.h", "separate_main.cc"]] + \
         [os.path.join(inc, "wesep_engine.h"), os.path.join(inc, "wesep_hip.h"), OUT]
     cmds = []
     if force or _stale(ENGINE_OUT, deps):
-        cmds.append([hipcc, "-O2", "-std=c++17", "-fPIC", "-shared", os.path.join(RUNTIME, "engine.cc"), "-o",
-                     ENGINE_OUT, "-L" + HERE, "-lwesep_hip", "-Wl,-rpath,$ORIGIN/../wesep_amd"])
+        cmds.append([hipcc, "-O2", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-shared"] +
+                    [os.path.join(RUNTIME, f) for f in ENGINE_SRCS] +
+                    ["-o", ENGINE_OUT, "-L" + HERE, "-lwesep_hip", "-Wl,-rpath,$ORIGIN/../wesep_amd"])
     if force or _stale(MAIN_OUT, deps + [ENGINE_OUT]) or cmds:
         cmds.append([hipcc, "-O2", "-std=c++17", "-pthread", os.path.join(RUNTIME, "separate_main.cc"), "-o", MAIN_OUT,
                      "-L" + RUNTIME, "-lwesep_engine", "-L" + HERE, "-lwesep_hip", "-Wl,-rpath,$ORIGIN",
