@@ -30,7 +30,6 @@ def test_blstm_linear_blocked_matches_torch(emu, monkeypatch, nseq, Lr, branch, 
     from wesep_amd import dev
     from wesep_amd import functional_tfgridnet as FG
     monkeypatch.setenv("WESEP_GATES", fmt)
-    monkeypatch.setenv("WESEP_TFG_TNB_A16", "1")     # (the fp16 A operand of the weight-gradient GEMMs: opt-in here, h2 only)
     torch.manual_seed(nseq)
     h = 192
     lstm = torch.nn.LSTM(128, h, 1, batch_first=True, bidirectional=True)
@@ -61,6 +60,68 @@ def test_blstm_linear_blocked_matches_torch(emu, monkeypatch, nseq, Lr, branch, 
     assert float((out - ref).norm() / ref.norm()) < (1e-4 if c2 else 1e-5)
     for k in want:
         assert float((got[k] - want[k]).norm()) <= max(gtol, 6e-4 if c2 else 0.0) * float(want[k].norm()) + 1e-6, k
+
+
+@pytest.mark.parametrize("var,fwd,bwd", [("WESEP_PAIR_RF", "3", "0"), ("WESEP_PAIR_RF", "0", "3")])
+def test_backward_runs_the_forwards_plan_whatever_the_environment_says_by_then(emu, monkeypatch, var, fwd, bwd):
+    """The choices of one BLSTM are made once, in the forward (blstm_core.BlstmPlan): a switch changed between a forward and
+    its backward changes nothing -- every gradient bit for bit that of the forward's value.  (The pair BPTT's arithmetic on
+    the inter-frame geometry: before the plan, the backward handed the kernel the environment's rfmt next to the forward's
+    pack.)"""
+    from wesep_amd import functional_tfgridnet as FG
+    monkeypatch.setenv("WESEP_GATES", "h2")
+    nseq, Lr, h = 5, 70, 192
+    grads = {}
+    for at_backward in (fwd, bwd):
+        torch.manual_seed(3)
+        lstm = torch.nn.LSTM(128, h, 1, batch_first=True, bidirectional=True)
+        lin = torch.nn.Linear(2 * h, 128)
+        y = torch.randn(nseq * Lr, 128, requires_grad=True)
+        res = torch.randn(nseq * Lr, 128, requires_grad=True)
+        probe = torch.randn(nseq * Lr, 128)
+        wf, hf, bf = FG.pad_lstm(lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)
+        wr, hr, br = FG.pad_lstm(lstm.weight_ih_l0_reverse, lstm.weight_hh_l0_reverse, lstm.bias_ih_l0_reverse,
+                                 lstm.bias_hh_l0_reverse)
+        monkeypatch.setenv(var, fwd)
+        out = FG.BlstmLinearBlkFn.apply(y, res, (nseq, Lr), None, None, wf, wr, bf, br, hf, hr,
+                                        FG.pad_hidden_cols(lin.weight, h), lin.bias)
+        monkeypatch.setenv(var, at_backward)
+        (out * probe).sum().backward()
+        grads[at_backward] = [y.grad, res.grad] + [p.grad for p in list(lstm.parameters()) + list(lin.parameters())]
+    assert all(torch.equal(a, b) for a, b in zip(grads[fwd], grads[bwd]))
+
+
+def test_the_per_call_pack_memo_dies_with_the_graph_not_with_the_cycle_collector(emu, monkeypatch):
+    """TF-GridNet's derived weight forms live in a PackCache made per forward: device memory that must go back to the
+    allocator when the graph is released, by reference counting -- a memo caught in a reference cycle stays until the
+    collector happens to run, and the allocator's footprint then depends on when that is."""
+    import gc
+    import weakref
+    from wesep_amd import blstm_core
+    from wesep_amd import functional_tfgridnet as FG
+    monkeypatch.setenv("WESEP_GATES", "h2")
+    made, init = [], blstm_core.PackCache.__init__
+    monkeypatch.setattr(blstm_core.PackCache, "__init__", lambda self: (init(self), made.append(weakref.ref(self)))[0])
+
+    def step():
+        h = 192
+        lstm = torch.nn.LSTM(128, h, 1, batch_first=True, bidirectional=True)
+        lin = torch.nn.Linear(2 * h, 128)
+        y, res = torch.randn(27, 128, requires_grad=True), torch.randn(27, 128, requires_grad=True)
+        wf, hf, bf = FG.pad_lstm(lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)
+        wr, hr, br = FG.pad_lstm(lstm.weight_ih_l0_reverse, lstm.weight_hh_l0_reverse, lstm.bias_ih_l0_reverse,
+                                 lstm.bias_hh_l0_reverse)
+        out = FG.BlstmLinearBlkFn.apply(y, res, (3, 9), None, None, wf, wr, bf, br, hf, hr, FG.pad_hidden_cols(lin.weight, h),
+                                        lin.bias)
+        out.sum().backward()
+
+    gc.collect()
+    gc.disable()
+    try:
+        step()
+        assert len(made) == 1 and made[0]() is None
+    finally:
+        gc.enable()
 
 
 @pytest.mark.parametrize("B,T,Q", [(2, 70, 5), (1, 9, 3)])     # 10 sequences of 70 steps (cluster, padded to 64 via nvalid) / streaming

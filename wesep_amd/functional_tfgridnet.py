@@ -20,6 +20,7 @@ import torch
 from . import _lib as L
 from . import dev
 from .dev import BIG, Rows, SeqMap, flat
+from .blstm_core import PackCache, WeightPacks, blstm_bptt, blstm_dxn, blstm_forward, blstm_weight_grads, consume_once, make_plan
 from .functional import _empty, _need_cuda, _reduce_new
 from .functional_tasnet import _cln_geom, _gemm, _transposed, _wgrad, norm_backward
 
@@ -422,24 +423,24 @@ class BatchedMatmulNNFn(torch.autograd.Function):
 
 
 def blocked_path_ok(C, ks, hs):
-    """The blocked-layout recurrence machinery of the pBSRNN path (functional.ResRNNBlkFn: plain -> BL input
+    """The blocked-layout recurrence machinery shared with the pBSRNN path (blstm_core: plain -> BL input
     projection, 16-sequence / cluster / fused-projection recurrences, BL -> plain output projection with bias and
     residual, BL x BL weight gradients) is built for 128 input features and one position per step -- which is the
     shipped TF-GridNet recipe (emb_dim 128, emb_ks = emb_hs = 1; tfgridnet.yaml).  Default for that geometry since its
     first hardware run (round 2: every stage within 1e-5 of an fp64 statement, tools/diag_tfgrid_blk.py);
     WESEP_TFGRID_BLOCKED=0 selects the row-major path."""
-    import os
     return os.environ.get("WESEP_TFGRID_BLOCKED", "1") != "0" and C == 128 and ks == 1 and hs == 1
 
 
 class BlstmLinearBlkFn(torch.autograd.Function):
     """y [nseq*Lr, 128] (layer-normed), res [nseq*Lr, 128] -> res + Linear(BLSTM(y)) on the blocked layout.
 
-    gridnet_block.py:139-160 for emb_ks = emb_hs = 1.  Same kernels and call sequence as functional.ResRNNBlkFn
-    without its GroupNorm (the LayerNorm over C happens before, per row).  Sequences are the contiguous runs of Lr
-    rows; when the cluster recurrence applies apart from the sequence count (long sequences, few of them: the
-    inter-frame path), the sequences are zero-padded to a multiple of 64 -- padded sequences cost no latency and their
-    rows are dropped.  Weights: pad_lstm / pad_hidden_cols outputs (hidden zero-padded to 256).
+    gridnet_block.py:139-160 for emb_ks = emb_hs = 1.  The BLSTM + projection are blstm_core's steps, the ones
+    functional.ResRNNBlkFn runs, without a GroupNorm (the LayerNorm over C happens before, per row); this node owns the
+    sequence map and its padding.  Sequences are the contiguous runs of Lr rows; when the cluster recurrence applies apart
+    from the sequence count (long sequences, few of them: the inter-frame path), the sequences are zero-padded to a
+    multiple of 64 -- padded sequences cost no latency and their rows are dropped.  Weights: pad_lstm / pad_hidden_cols
+    outputs (hidden zero-padded to 256).
 
     geo = (nseq, Lr): sequences are contiguous runs of Lr rows; geo = (nseq, Lr, div, s1, s2, step_rows): a STRIDED
     sequence map over the rows of y / res (sequence s, step t -> row (s // div) * s1 + (s % div) * s2 + t * step_rows) --
@@ -454,195 +455,53 @@ class BlstmLinearBlkFn(torch.autograd.Function):
         side stream, released under the NEXT inter-frame BPTT (a latency-bound launch on a quarter of the CUs), and reach
         autograd through the carrier; this node returns None for them (round 4: the twelve BLSTMs' weight-gradient GEMMs,
         48 ms of a 336 ms step, ran in line on the main stream before)."""
-        from . import functional as F0
         _need_cuda(y, "TF-GridNet")
         nseq, Lr = geo[:2]
         strided = geo[2:] if len(geo) > 2 else None
-        N, H, G4 = 128, HP, G4P
         d = y.device
         pad = 0
         if Lr >= 64 and nseq % 64 and (-(-nseq // 64) * 64 // 32) * 8 <= dev.cu_count(d):
             pad = -(-nseq // 64) * 64 - nseq
         ns = nseq + pad
         if pad and strided is None:
-            z = torch.zeros(pad * Lr, N, device=d, dtype=torch.float32)
+            z = torch.zeros(pad * Lr, 128, device=d, dtype=torch.float32)
             y, res = torch.cat([y, z], 0), torch.cat([res, z], 0)
         y, res = y.contiguous(), res.contiguous()
         seq = SeqMap(ns, BIG, 0, Lr, 1, Lr) if strided is None else SeqMap(ns, *strided, Lr, nvalid=nseq)
-        nb = dev.bl_num_blocks(seq)
-        zero = torch.zeros(G4, device=d, dtype=torch.float32)
-        wcat, bcat = _empty(d, 2 * G4, N), _empty(d, 2 * G4)
-        dev.lstm_cat_ih(wih_f.contiguous(), wih_r.contiguous(), b_f.contiguous(), zero, b_r.contiguous(), zero, N, wcat,
-                        bcat)
-        pack_f, pack_b = _empty(d, L.LSTM_PACK_FLOATS), _empty(d, L.LSTM_PACK_FLOATS)
-        lmode = dev.lstm_blk_mode(ns)
-        whf, whr = whf.contiguous(), whr.contiguous()
-        dev.lstm_pack(whf, whr, pack_f, pack_b, lmode)
-        xn = _empty(d, nb, 32 * N)
-        cbuf, hcat = _empty(d, nb, 32 * 2 * H), _empty(d, nb, 32 * 2 * H)
-        cluster = dev.lstm_cluster_ok(seq, d)
-        kind = F0._bptt_kind(seq, d, cluster)
-        # storage of the saved gates / d(gates): as in functional.ResRNNBlkFn (wesep_hip.h WS_GATES_*) -- unorm16 gates in a
-        # buffer of half the bytes by default (the twelve BLSTMs' saved gates were 77 of the step's 155 GB in round 3)
-        gfmt = L.GATES_F32 if kind == "cluster" else dev.gates_fmt()
-        h2 = gfmt != L.GATES_F32
-        gates = _empty(d, dev.blh_floats(nb, 2 * G4)) if h2 else _empty(d, nb, 32 * 2 * G4)
-        # fp16 copies of [xn | h] for the weight-gradient GEMMs (functional.ResRNNBlkFn; ws_gemm_tnb a_fmt = 1, ABI v16): the default
-        # since round 6 (WESEP_TFG_TNB_A16=0 turns it off).  Round 5 left it opt-in -- "these GEMMs already hide under the
-        # inter-frame BPTTs": 304.3 vs 310.0 ms for 8 GB more saved state -- but hidden work is not free work on this chip
-        # (profiles/r06_side_stream_tax.md: the clock follows the load): one MFMA per product instead of three on the side stream
-        # is 263.6 -> 248.7 ms per step at config 5's per-GPU shape (two runs each, one box), 123 -> 131 GB
-        a16 = gfmt == L.GATES_H2F and any(ctx.needs_input_grad) and F0.tnb_a16() and \
-            os.environ.get("WESEP_TFG_TNB_A16", "1") != "0"
-        xn16 = _empty(d, dev.blh_floats(nb, N)) if a16 else None
-        hcat16 = _empty(d, dev.blh_floats(nb, 2 * H)) if a16 else None
-        if dev.lstm_fuse_ok(ns, cluster):
-            dev.gemm_p2b(A=y, lda=N, sm=seq, Wpack=None, N=0, C_out=None, A_bl=xn, A_bl16=xn16)
-            fpack = _empty(d, L.LSTM_FUSED_PACK_FLOATS)
-            hf = dev.lstm_fused_hfmt(gfmt)      # round 6: fp16 h in the recurrent part (two terms), as functional.ResRNNBlkFn
-            dev.lstm_pack_fused(wih_f.contiguous(), wih_r.contiguous(), whf, whr, fpack, hfmt=hf)
-            dev.lstm_fwd_fused(gates, cbuf, hcat, xn, fpack, bcat, seq, gfmt=gfmt, hfmt=hf)
-        elif cluster and h2 and dev.lstm_cluster2_on() and os.environ.get("WESEP_TFG_CLUSTER2", "1") != "0":
-            # inter-frame path, 2-byte formats (round 5): ws_lstm_fwd_cluster2 computes x W_ih^T itself from the split-pair
-            # rows ws_gemm_p2b relays into BL(128) (functional.ResRNNBlkFn; lstm_cluster2.hip); the fp32 pre-activations exist
-            # only inside the predicated fall-back behind the launch.  Measured at BASELINE config 5's geometry: 301.0 ->
-            # 277.7 ms/step (same box, together with the fp16 pair BPTT: profiles/r05_ab/r05_c11_tfg_*.json), every parity figure
-            # of the recipe-geometry test unchanged (waveform 1.27e-5 -> 1.33e-5, worst gradient 3.4e-3 -> 3.1e-3, median
-            # 4.1e-4 -> 4.2e-4: profiles/r05_tfg_cfg5_cluster2_bls_input.txt).  The kernel's FIRST cut -- fp16 copy of the input,
-            # two-term x-projection -- was not: median gradient error 7.0e-4 and two scalar PReLU slopes over this model's 5e-3
-            # bound (profiles/r05_tfg_cfg5_precision_split.txt); the input keeps its split pair since.  WESEP_TFG_CLUSTER2=0
-            # selects the round-4 cluster kernel on fp32 pre-activations
-            dev.gemm_p2b(A=y, lda=N, sm=seq, Wpack=None, N=0, C_out=None, A_bl=xn, A_bl16=xn16)
-            tw = dev.lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whf, whr, seq, dbg=F0._cluster_dbg())
-            wih_pack = _empty(d, 2 * G4 * N)
-            dev.pack_w(wcat, 2 * G4, N, N, wih_pack, order=0)
-            pre = dev.fallback_scratch(d, nb * 32 * 2 * G4)      # (untouched after a clean launch; one buffer per stream)
-            dev.gemm_p2b(A=y, lda=N, sm=seq, Wpack=wih_pack, N=2 * G4, C_out=pre, bias=bcat, run_if=tw)
-            dev.lstm_fwd(gates, cbuf, hcat, pack_f, seq, lmode, run_if=tw, gfmt=gfmt, gates_in=pre)
-            del pre
-        else:
-            wih_pack = _empty(d, 2 * G4 * N)
-            dev.pack_w(wcat, 2 * G4, N, N, wih_pack, order=0)
-            pre = _empty(d, nb, 32 * 2 * G4) if h2 else gates      # 2-byte formats: pre-activations in a scratch buffer
-            xproj = dict(A=y, lda=N, sm=seq, Wpack=wih_pack, N=2 * G4, C_out=pre, bias=bcat, A_bl=xn, A_bl16=xn16)
-            rec = dict(gfmt=gfmt, gates_in=pre) if h2 else {}
-            dev.gemm_p2b(**xproj)
-            if cluster:
-                # the streaming pair behind the cluster launch is predicated on its timeout word (wesep_hip.h): empty
-                # launches after a clean run, the whole layer again if the workgroups were not co-resident (the 2-byte
-                # formats leave the pre-activations intact: only the recurrence is repeated)
-                tw = dev.lstm_fwd_cluster(gates, cbuf, hcat, whf, whr, seq, dbg=F0._cluster_dbg(), **rec)
-                if not h2:
-                    dev.gemm_p2b(run_if=tw, **xproj)
-                dev.lstm_fwd(gates, cbuf, hcat, pack_f, seq, lmode, run_if=tw, **rec)
-            else:
-                dev.lstm_fwd(gates, cbuf, hcat, pack_f, seq, lmode, **rec)
-            del pre
-        lw = lin_w.contiguous()
-        lin_pack = _empty(d, N * 2 * H)
-        dev.pack_w(lw, N, 2 * H, 2 * H, lin_pack, order=1)
-        out = torch.empty_like(res)
-        dev.gemm_b2p(A=hcat, K=2 * H, sm=seq, Wpack=lin_pack, C_out=out, ldc=N, bias=lin_b.contiguous(), R=res, a16_out=hcat16)
-        # the backward's weight packs are built HERE, where the GPU serves one stream: built lazily in the backward, these
-        # 5 us launches queue behind the side stream's chip-filling weight-gradient GEMMs for up to a millisecond each
-        # (functional.ResRNNBlkFn does the same; ADVICE round 3)
-        bw_packs = None
-        if any(ctx.needs_input_grad):
-            g2 = gfmt == L.GATES_H2F
-            wlt_pack = _empty(d, 2 * H * N)
-            dev.pack_w(lw, 2 * H, N, 2 * H, wlt_pack, trans=True, order=0)
-            wct_pack = _empty(d, N * 2 * G4)
-            # (d(xn) from the scaled-fp16 d(gates): fp16 hi / lo, or fp16 hi + FP8 lo fragments -- functional.dxn_fmt, round 6)
-            dev.pack_w(wcat, N, 2 * G4, N, wct_pack, trans=True, order=1, f16=(2 if F0.dxn_fmt(2) == 3 else 1) if g2 else 0)
-            ppack = None
-            if kind == "pair":
-                ppack = _empty(d, L.LSTM_PACK_FLOATS)
-                dev.lstm_pack_pair(whf, whr, ppack, f16=F0.pair_rfmt(gfmt))     # (rfmt 1 / 2: fp16 hi, fp16 / FP8 lo of 256 w)
-            elif kind == "stream" and F0.band_rfmt(gfmt, lmode):                # the streaming BPTT's rfmt 2 pack (round 6 default)
-                ppack = _empty(d, L.LSTM_PACK_FLOATS)
-                dev.lstm_pack_bwd_f8(whf, whr, ppack)
-            bw_packs = (wlt_pack, wct_pack, ppack)
-        ctx.bw_packs = bw_packs
-        ctx.save_for_backward(gates, cbuf, hcat, xn16 if a16 else xn, wcat, pack_b, lw, whf, whr, hcat16)
-        ctx.geo = (nseq, Lr, ns, lmode, cluster)
-        ctx.seq = seq
-        ctx.gfmt, ctx.kind = gfmt, kind
-        ctx.F0 = F0
-        ctx.box = box
+        plan = make_plan(seq, d, any(ctx.needs_input_grad))
+        # the weights are fresh autograd outputs of pad_lstm every step: a memo for this forward / backward pair, not a
+        # module-owned cache (across calls a key on data_ptr could hit a recycled address).  b_ih = the summed bias, b_hh = 0
+        zero = torch.zeros(G4P, device=d, dtype=torch.float32)
+        cache = PackCache()
+        sig = cache.begin((wih_f, whf, b_f, wih_r, whr, b_r, lin_w))
+        W = WeightPacks(cache, sig, plan.lmode, plan.pair_rfmt, wih_f, whf, b_f.contiguous(), zero, wih_r, whr,
+                          b_r.contiguous(), zero, lin_w)
+        out, saved = blstm_forward(plan, W, y, seq, res=res, bias=lin_b.contiguous())
+        ctx.save_for_backward(*saved)
+        ctx.geo, ctx.seq, ctx.plan, ctx.packs, ctx.box = (nseq, Lr, ns), seq, plan, W, box
         ctx.consumed = False
         return out[:nseq * Lr] if (pad and strided is None) else out
 
     @staticmethod
     def backward(ctx, dout):
-        import os
-        gates, cbuf, hcat, xn, wcat, pack_b, lw, whf, whr, hcat16 = ctx.saved_tensors     # (xn: its fp16 copy if hcat16)
-        if ctx.consumed:         # same contract as functional.ResRNNBlkFn: BPTT turns the saved gates into d(gates) in place
-            raise L.WesepHipError("TF-GridNet BLSTM: second backward through the same graph (retain_graph / multi-loss "
-                                  "loops): the blocked path consumes its saved gates in place; run the forward again")
-        ctx.consumed = True
-        nseq, Lr, ns, lmode, cluster = ctx.geo
-        N, H, G4 = 128, HP, G4P
+        consume_once(ctx, "TF-GridNet BLSTM")
+        gates, cbuf, hcat, xn, hcat16 = ctx.saved_tensors     # (xn: its fp16 copy if hcat16)
+        nseq, Lr, ns = ctx.geo
+        seq, plan, W, box = ctx.seq, ctx.plan, ctx.packs, ctx.box
         d = dout.device
         dout = dout.contiguous()
         dres = dout
-        seq = ctx.seq
         appended = ns != nseq and not seq.nvalid      # contiguous runs: the padding sequences are rows behind the data
         if appended:
-            dout = torch.cat([dout, torch.zeros((ns - nseq) * Lr, N, device=d, dtype=torch.float32)], 0)
-        nb = dev.bl_num_blocks(seq)
-        wlt_pack, wct_pack, ppack = ctx.bw_packs
-        dh, dout_bl = _empty(d, nb, 32 * 2 * H), _empty(d, nb, 32 * N)
-        amax = ctx.F0.amax_word(d) if ctx.gfmt == L.GATES_H2F else None   # (functional.py)
-        dev.gemm_p2b(A=dout, lda=N, sm=seq, Wpack=wlt_pack, N=2 * H, C_out=dh, A_bl=dout_bl, amax=amax)
-        # BPTT works in place on the saved gates (6.4 GB per BLSTM at the recipe's 8 rows x 6 s: a clone here was 12 copies
-        # = 38 ms of a 490 ms step and the largest transient allocation of the backward)
-        kind, gfmt = ctx.kind, ctx.gfmt
-        g_fmt = {L.GATES_H2: 1, L.GATES_H2F: 2}.get(gfmt, 0)
-        F0, box = ctx.F0, ctx.box
+            dout = torch.cat([dout, torch.zeros((ns - nseq) * Lr, 128, device=d, dtype=torch.float32)], 0)
         # the inter-frame BPTT (few long sequences: pair / cluster kernels on a fraction of the CUs for ~10 ms) is where the
-        # weight-gradient jobs deferred by the BLSTMs before it are released (functional.flush_deferred_wgrads)
-        ready = F0.mark_wgrads_ready(d) if kind in ("pair", "cluster") else None
-        if kind == "cluster":
-            dg = gates
-            dev.lstm_bwd_cluster(gates, cbuf, dh, whf, whr, seq)
-        elif kind == "pair":                                    # few long sequences (the inter-frame path): lstm_pair.hip
-            if gfmt == L.GATES_F32:
-                dg = gates
-                dev.lstm_bwd_pair(gates, cbuf, dh, ppack, seq, dbg=ctx.F0._pair_dbg())
-            else:
-                # d(gates) out of place, the streaming BPTT predicated on the launch's time-out word behind it (functional.py)
-                dg = _empty(d, nb, 32 * 2 * G4) if gfmt == L.GATES_H2S else _empty(d, dev.blh_floats(nb, 2 * G4))
-                tw = dev.lstm_bwd_pair(gates, cbuf, dh, ppack, seq, gfmt=gfmt, dgates=dg, repairable=True,
-                                       dbg=ctx.F0._pair_dbg(), amax=amax, rfmt=ctx.F0.pair_rfmt(gfmt))
-                dev.lstm_bwd(gates, cbuf, hcat, dh, pack_b, seq, lmode, gfmt=gfmt, dgates=dg, run_if=tw, amax=amax)
-        elif gfmt == L.GATES_F32:
-            dg = gates
-            dev.lstm_bwd(gates, cbuf, hcat, dh, pack_b, seq, lmode)
-        else:
-            dg = _empty(d, nb, 32 * 2 * G4) if gfmt == L.GATES_H2S else gates
-            brf = F0.band_rfmt(gfmt, lmode) if ppack is not None else 0
-            dev.lstm_bwd(gates, cbuf, hcat, dh, ppack if brf else pack_b, seq, lmode, gfmt=gfmt,
-                         dgates=dg if gfmt == L.GATES_H2S else None, amax=amax, rfmt=brf)
-        if ready is not None:
-            F0.flush_deferred_wgrads(d, ready)
-        order = (0, 4, 2, 6, 1, 5, 8, 9)       # _weight_grads' list -> this node's weight arguments
-        if box is not None:
-            def job(side, gates=dg, xn=xn, hcat=hcat, dout_bl=dout_bl, seq=seq, nb=nb, box=box, g_fmt=g_fmt, amax=amax,
-                    hcat16=hcat16, prod=torch.cuda.current_stream()):
-                wg_ = F0.ResRNNBlkFn._weight_grads(gates, xn, hcat, dout_bl, seq, nb, 128, g_fmt, amax, hcat16)
-                box.grads = [wg_[i] for i in order]
-                box.event = torch.cuda.Event()
-                box.event.record(side)
-                F0.keep_for_side(box, (gates, xn, hcat, dout_bl, amax, hcat16), side, prod)
-            F0.defer_wgrad(d, job)
-            wgo = [None] * 8
-        else:
-            wg = F0.ResRNNBlkFn._weight_grads(dg, xn, hcat, dout_bl, seq, nb, N, g_fmt, amax, hcat16)
-            wgo = [wg[i] for i in order]
-        dy = _empty(d, (ns if appended else nseq) * Lr, N)
-        dev.gemm_b2p(A=dg, K=2 * G4, sm=seq, Wpack=wct_pack, C_out=dy, ldc=N, a_fmt=F0.dxn_fmt(g_fmt), amax=amax)
+        # weight-gradient jobs deferred by the BLSTMs before it are released
+        dg, dout_bl, amax, dxn2 = blstm_bptt(plan, W, gates, cbuf, hcat, dout, seq, release=plan.bptt in ("pair", "cluster"))
+        # weight_grads' list -> this node's weight arguments (wih_f, wih_r, b_f, b_r, whf, whr, lin_w, lin_b)
+        wg = blstm_weight_grads(plan, dg, xn, hcat, dout_bl, amax, hcat16, seq, box, order=(0, 4, 2, 6, 1, 5, 8, 9))
+        del dout_bl
+        dy, _ = blstm_dxn(plan, W, dg, amax, dxn2, seq, (ns if appended else nseq) * Lr)
         if appended:
             dy = dy[:nseq * Lr]
-        # _weight_grads: [dW_ih_f, dW_hh_f, db_f, db_f (clone), dW_ih_r, dW_hh_r, db_r, db_r (clone), dW_lin, db_lin]
         gd = torch.zeros((), device=d) if box is not None else None     # keeps the carrier node in the graph walk
-        return (dy, dres, None, gd, None) + tuple(wgo)
+        return (dy, dres, None, gd, None) + tuple(wg)
