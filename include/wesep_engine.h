@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define WS_ENGINE_ABI_VERSION 1
+#define WS_ENGINE_ABI_VERSION 2
 
 typedef struct ws_engine ws_engine;
 
@@ -63,6 +63,20 @@ long long ws_engine_info(const ws_engine* e, const char* key);
  * Replaces `model(features, enroll)[0]` of infer.py:101-103 (whole utterance, any T >= 512; no chunking). */
 int ws_engine_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind,
                        int enroll_len, float* est);
+
+/* Ragged batches (engine ABI 2; pBSRNN containers, arch 0): utterances of different lengths in ONE forward.  mix / est
+ * keep the row pitch T; lengths[r] in [512, T] is the number of valid samples of row r.  est[r][0..lengths[r]) is what
+ * ws_engine_separate returns for mix[r][0..lengths[r]) as a batch of one (reflect padding, GroupNorm statistics, the
+ * reverse recurrence over time and the iSTFT envelope all end at the row's own end); est[r][lengths[r]..T) = 0; what the
+ * caller left in mix[r][lengths[r]..T) is never read into a valid output (NaN included).
+ * enroll_lengths (HOST int [R], or NULL = every row has enroll_len): valid samples (WS_ENROLL_WAVE) / frames
+ * (WS_ENROLL_FBANK) of each enrollment row of pitch enroll_len.  The speaker encoder is not ragged: with enroll_lengths
+ * it runs one enrollment at a time, then the separator runs once over all rows.
+ * lengths = enroll_lengths = NULL is ws_engine_separate (any architecture); with either given, a Conv-TasNet, DPCCN or
+ * TF-GridNet container is refused (WS_ERR_INVALID).  The time-view recurrences of a ragged call run over precomputed
+ * gates (the rows' tails are zeroed there); the number of launches depends on (R, T) only, not on the lengths. */
+int ws_engine_separate_ragged(ws_engine* e, const float* mix, int R, int T, const int* lengths, const void* enroll,
+                              int enroll_kind, int enroll_len, const int* enroll_lengths, float* est);
 
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by

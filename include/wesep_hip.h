@@ -178,6 +178,11 @@ typedef struct ws_groups_geom {
   int nbands, pad_;        /* band of group g = g % nbands (per-band widths / gammas) */
 } ws_groups_geom;
 int ws_group_stats(const float* x, const ws_groups_geom* geo, float eps, float* stats, void* stream);
+/* Ragged batches (inference): the statistics of group g cover its first glen[g / glen_div] rows only (device int table,
+ * every entry in [1, L]; pBSRNN's three norms over time: g = r * K + band, glen = the rows' frame counts, glen_div = K).
+ * The rows behind them are neither read nor counted, so nothing a caller left there (NaN included) reaches the result. */
+int ws_group_stats_len(const float* x, const ws_groups_geom* geo, const int* glen, int glen_div, float eps, float* stats,
+                       void* stream);
 
 /* GroupNorm backward, two passes over the same geometry:
  *   pass 1  ab[g] = (mean_g(dxn*gamma), mean_g(dxn*gamma*xhat))
@@ -504,6 +509,15 @@ typedef struct ws_gemm_p2b_args {
                                2-byte A operand of ws_gemm_tnb (a_fmt = 1)                                          */
 } ws_gemm_p2b_args;
 int ws_gemm_p2b(const ws_gemm_p2b_args* a, void* stream);
+/* Ragged batches (inference): per-sequence valid STEP counts, the counterpart of ws_seqmap.nvalid along the other axis.
+ * Sequence s has steps[s / steps_div] valid steps (device int table, entries in [1, L]); the slots of every later step are
+ * treated like padded slots: operand and output exactly ZERO (selected, not multiplied: the rows they stand for may hold
+ * anything; the bias is not added).  A recurrence that enters such a slot with zero state leaves it with zero state
+ * (tanh(0) = 0), so the reverse direction of a BLSTM over precomputed gates (ws_lstm_fwd_cluster, ws_lstm_fwd) reaches the
+ * sequence's last valid step exactly as if it had started there; the forward direction's tail is finite and unused.
+ * The recurrences that compute the x-projection themselves (ws_lstm_fwd_cluster2, ws_lstm_fwd_fused) have no such
+ * operand: ragged callers take the precomputed-gates branch. */
+int ws_gemm_p2b_len(const ws_gemm_p2b_args* a, const int* steps, int steps_div, void* stream);
 
 /* BL -> plain:  C[pos(b,i)][n] = sum_k A[(b,i)][k] * W'[n][k] + bias[n] + R[pos][n]   (N = 128, K % 64 == 0)
  * Replaces ResRNN.proj + residual (bsrnn.py:42-46) and autograd's d(normalised input).      */
@@ -567,6 +581,12 @@ typedef struct ws_bands {
   int nband, nbins;
 } ws_bands;
 int ws_stft_bandsplit(const float* wav, int R, int T, const ws_bands* b, float* xbs, void* stream);
+/* Ragged batches (inference): row r holds lengths[r] valid samples, NFFT / 2 < lengths[r] <= T = the row pitch (device int
+ * table; the callers that have the lengths on the host -- the engine, wesep_amd.dev -- refuse values outside that range,
+ * the kernel clamps them so that no table entry can move a read out of its row).  The reflect padding turns at lengths[r];
+ * frames t >= 1 + lengths[r] / 128 are written as zeros; nothing behind lengths[r] is read.  The valid frames of a row are
+ * bit for bit those of ws_stft_bandsplit on that row alone with T = lengths[r]. */
+int ws_stft_bandsplit_len(const float* wav, int R, int T, const int* lengths, const ws_bands* b, float* xbs, void* stream);
 /* mask3 [R*Tf][4*F]: band g occupies columns [4*f0, 4*f0+4*bw) in the reference's channel
  * order c = glu*2*bw + ri*bw + f (bsrnn.py:366-370).  frames [R*Tf][512] = windowed irfft of
  * (mask * X)  (bsrnn.py:371-381 + the first half of istft).                                */
@@ -574,6 +594,10 @@ int ws_mask_istft_frames(const float* xbs, const float* mask3, int R, int Tf, co
                          float* frames, void* stream);
 /* overlap-add + window-envelope normalisation + centre trim -> wav [R][T]                  */
 int ws_istft_ola(const float* frames, int R, int Tf, int T, float* wav, void* stream);
+/* Ragged batches (inference): only the frames t < 1 + lengths[r] / 128 of row r are added and counted in the window
+ * envelope (the others are not read, so ws_mask_istft_frames runs over the rectangle unchanged); samples >= lengths[r]
+ * are written as zeros.  lengths: device int table as in ws_stft_bandsplit_len. */
+int ws_istft_ola_len(const float* frames, int R, int Tf, int T, const int* lengths, float* wav, void* stream);
 /* backward of the two calls above: dwav [R][T] -> dmask3 [R*Tf][4*F]                        */
 int ws_mask_istft_bwd(const float* dwav, const float* xbs, const float* mask3, int R, int Tf,
                       int T, const ws_bands* b, float* dmask3, void* stream);

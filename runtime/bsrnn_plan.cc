@@ -176,8 +176,12 @@ int build_descriptors(ws_engine* e, int R, int Tf) {
   return WS_OK;
 }
 
-// ResRNN (bsrnn.py:38-46) on the blocked layout; mirrors functional.ResRNNBlkFn.forward with the packs precomputed
-int resrnn(ws_engine* e, const RnnPrep& w, bool time_view, const float* z, int R, int Tf, float* out) {
+// ResRNN (bsrnn.py:38-46) on the blocked layout; mirrors functional.ResRNNBlkFn.forward with the packs precomputed.
+// d_tf (ragged batches, or nullptr): device table of the rows' valid frame counts.  Only the time view reads it: its
+// GroupNorm statistics cover a row's valid frames, and the pre-activations of the frames behind them are exact zeros, so
+// the reverse direction arrives at the row's last valid frame with zero state.  That needs a recurrence over precomputed
+// gates: a ragged time view takes the cluster or the streaming branch, never the one that projects inside the kernel.
+int resrnn(ws_engine* e, const RnnPrep& w, bool time_view, const float* z, int R, int Tf, const int* d_tf, float* out) {
   const int K = e->bs.K;
   ws_groups_geom geo = {};
   ws_seqmap sm = {};
@@ -199,7 +203,8 @@ int resrnn(ws_engine* e, const RnnPrep& w, bool time_view, const float* z, int R
   const int lmode = 2 * ntile <= 128 ? WS_LSTM_BF16X3_BLK16 : WS_LSTM_BF16X3_BLK;
   static const bool no_cluster = getenv("WS_ENGINE_NO_CLUSTER") != nullptr;   // diagnostics: streaming kernels only
   const bool cluster = !no_cluster && sm.nseq % 64 == 0 && (sm.nseq / 32) * 8 <= e->cu_count && sm.L >= 64;
-  const bool fused = !cluster && lmode == WS_LSTM_BF16X3_BLK;
+  const int* steps = time_view ? d_tf : nullptr;
+  const bool fused = !cluster && lmode == WS_LSTM_BF16X3_BLK && !steps;
   void* s = e->stream;
   Arena& a = e->work;
   const Arena::Mark mk = a.mark();
@@ -209,7 +214,10 @@ int resrnn(ws_engine* e, const RnnPrep& w, bool time_view, const float* z, int R
   float* hcat = a.alloc(nb * 32 * 2 * kH);
   float* xn = a.alloc(nb * 32 * kN);      // normalised input in BL(128): operand of the fused recurrence
   WS_PTR(stats && gates && cbuf && hcat && xn);
-  WS_RUN(e, ws_group_stats(z, &geo, kGnEps, stats, s));
+  if (steps)
+    WS_RUN(e, ws_group_stats_len(z, &geo, steps, K, kGnEps, stats, s));
+  else
+    WS_RUN(e, ws_group_stats(z, &geo, kGnEps, stats, s));
   ws_gemm_p2b_args p = {};
   p.A = z;
   p.stats = stats;
@@ -232,7 +240,10 @@ int resrnn(ws_engine* e, const RnnPrep& w, bool time_view, const float* z, int R
     p.bias = w.bcat;
     p.C = gates;
     p.N = 2 * kG4;
-    WS_RUN(e, ws_gemm_p2b(&p, s));
+    if (steps)
+      WS_RUN(e, ws_gemm_p2b_len(&p, steps, K, s));
+    else
+      WS_RUN(e, ws_gemm_p2b(&p, s));
     if (cluster) {
       const int ncl = sm.nseq / 32;
       float* xchg = a.alloc(size_t(ncl) * 2 * 8 * 8192 / 4);
@@ -252,7 +263,10 @@ int resrnn(ws_engine* e, const RnnPrep& w, bool time_view, const float* z, int R
       // be co-resident and a bounded wait can time out.  The streaming pair below is predicated on this launch's
       // timeout word: empty launches after a clean run, the whole layer again after a timeout -- never NaN.
       p.run_if = flags + size_t(ncl) * 8;
-      WS_RUN(e, ws_gemm_p2b(&p, s));
+      if (steps)
+        WS_RUN(e, ws_gemm_p2b_len(&p, steps, K, s));
+      else
+        WS_RUN(e, ws_gemm_p2b(&p, s));
       ws_lstm_args l = {};
       l.gates = gates, l.cbuf = cbuf, l.hcat = hcat;
       l.wpack = lmode == WS_LSTM_BF16X3_BLK16 ? w.pack16 : w.pack32;
@@ -315,8 +329,13 @@ int fuse_layer(ws_engine* e, const std::string& pre, float* z, const float* emb,
   return WS_OK;
 }
 
-// BSRNN.forward (bsrnn.py:300-394) with the embedding already computed: wav [R][T], emb [R][E] -> est [R][T] (device)
-int separate_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est) {
+// BSRNN.forward (bsrnn.py:300-394) with the embedding already computed: wav [R][T], emb [R][E] -> est [R][T] (device).
+// d_len / d_tf (ragged batches, both or neither): device tables [R] of the rows' valid samples and frames (1 + len / 128).
+// The length is known where a row's end matters -- reflect padding, the three GroupNorms over time, the start of the
+// reverse time-view recurrence, the iSTFT envelope -- everything else runs over the rectangle; the frames behind a row's
+// end hold finite values nothing valid reads.
+int separate_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est, const int* d_len,
+                    const int* d_tf) {
   const int K = e->bs.K, Tf = 1 + T / kHop, H1 = 4 * kN;
   const long long M = (long long)R * Tf;
   void* s = e->stream;
@@ -329,7 +348,10 @@ int separate_device(ws_engine* e, const float* wav, int R, int T, const float* e
   float* zB = a.alloc(size_t(R) * K * Tf * kN);
   WS_PTR(xbs && zA && zB);
   // STFT + band split + per-band GroupNorm + Conv1d(k = 1)   (bsrnn.py:309-337)
-  WS_RUN(e, ws_stft_bandsplit(wav, R, T, &bands, xbs, s));
+  if (d_len)
+    WS_RUN(e, ws_stft_bandsplit_len(wav, R, T, d_len, &bands, xbs, s));
+  else
+    WS_RUN(e, ws_stft_bandsplit(wav, R, T, &bands, xbs, s));
   {
     const Arena::Mark mk = a.mark();
     float* stats = a.alloc(size_t(R) * K * 2);
@@ -338,7 +360,10 @@ int separate_device(ws_engine* e, const float* wav, int R, int T, const float* e
     geo.band_w = e->bs.d_bw2, geo.band_off = e->bs.d_off2;
     geo.gs1 = (long long)Tf * 2 * kNBin, geo.gs2 = 0, geo.rs = 2 * kNBin;
     geo.ngroups = R * K, geo.gdiv = K, geo.L = Tf, geo.W = 128, geo.nbands = K;
-    WS_RUN(e, ws_group_stats(xbs, &geo, kGnEps, stats, s));
+    if (d_tf)
+      WS_RUN(e, ws_group_stats_len(xbs, &geo, d_tf, K, kGnEps, stats, s));
+    else
+      WS_RUN(e, ws_group_stats(xbs, &geo, kGnEps, stats, s));
     ws_gemm_nt_args g = {};
     g.A = xbs, g.C = zA, g.stats = stats, g.groups = e->bs.d_bn;
     g.a_div = kBig, g.a_s2 = 2 * kNBin;
@@ -359,8 +384,8 @@ int separate_device(ws_engine* e, const float* wav, int R, int T, const float* e
     if (e->bs.sep_kind[i] == 0) {
       if ((rc = fuse_layer(e, "separator.separation." + std::to_string(i) + ".", z, emb, R, Tf)) != WS_OK) return rc;
     } else {
-      if ((rc = resrnn(e, e->bs.rnn[2 * net], true, z, R, Tf, other)) != WS_OK) return rc;
-      if ((rc = resrnn(e, e->bs.rnn[2 * net + 1], false, other, R, Tf, z)) != WS_OK) return rc;
+      if ((rc = resrnn(e, e->bs.rnn[2 * net], true, z, R, Tf, d_tf, other)) != WS_OK) return rc;
+      if ((rc = resrnn(e, e->bs.rnn[2 * net + 1], false, other, R, Tf, d_tf, z)) != WS_OK) return rc;
       ++net;
     }
   }
@@ -376,7 +401,10 @@ int separate_device(ws_engine* e, const float* wav, int R, int T, const float* e
     ws_groups_geom geo = {};
     geo.gs1 = (long long)Tf * kN, geo.gs2 = 0, geo.rs = kN;
     geo.ngroups = R * K, geo.gdiv = 1, geo.L = Tf, geo.W = kN, geo.nbands = K;
-    WS_RUN(e, ws_group_stats(z, &geo, kGnEps, stats, s));
+    if (d_tf)
+      WS_RUN(e, ws_group_stats_len(z, &geo, d_tf, K, kGnEps, stats, s));
+    else
+      WS_RUN(e, ws_group_stats(z, &geo, kGnEps, stats, s));
     int maxbw = 0;
     for (int b : e->bs.bw) maxbw = b > maxbw ? b : maxbw;
     ws_gemm_nt_args g = {};
@@ -397,7 +425,10 @@ int separate_device(ws_engine* e, const float* wav, int R, int T, const float* e
     g3.M = static_cast<int>(M), g3.ngroups = K, g3.max_n = 4 * maxbw, g3.vec = 3 | 4;
     WS_RUN(e, ws_gemm_nt(&g3, s));
     WS_RUN(e, ws_mask_istft_frames(xbs, m3, R, Tf, &bands, frames, s));
-    WS_RUN(e, ws_istft_ola(frames, R, Tf, T, est, s));
+    if (d_len)
+      WS_RUN(e, ws_istft_ola_len(frames, R, Tf, T, d_len, est, s));
+    else
+      WS_RUN(e, ws_istft_ola(frames, R, Tf, T, est, s));
     a.release(mk);
   }
   return WS_OK;

@@ -344,10 +344,43 @@ WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   return it == e->meta.end() ? -1 : it->second;
 }
 
-WS_ENGINE_API int ws_engine_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind,
-                                  int enroll_len, float* est) {
-  int rc = check_engine(e, "ws_engine_separate");
+// frames of an enrollment of `enroll_len` samples / frames for this model's front-end, or WS_ERR_INVALID (message set)
+static int enroll_frames(const ws_engine* e, int enroll_kind, int enroll_len, int* frames) {
+  int Te = enroll_len;
+  if (enroll_kind == WS_ENROLL_WAVE && e->spk.feat) {          // kaldi fbank, snip-edges framing
+    if (enroll_len < e->spk.fb_win) {
+      set_err("ws_engine_separate: enrollment shorter than one %d-sample frame", e->spk.fb_win);
+      return WS_ERR_INVALID;
+    }
+    Te = 1 + (enroll_len - e->spk.fb_win) / e->spk.fb_shift;
+  } else if (enroll_kind == WS_ENROLL_WAVE) {                  // in-model MelSpectrogram, centred framing
+    if (enroll_len <= 256) {
+      set_err("ws_engine_separate: enrollment must be longer than the 256-sample reflect padding");
+      return WS_ERR_INVALID;
+    }
+    Te = 1 + enroll_len / kHop;
+  } else if (enroll_kind == WS_ENROLL_FBANK && !e->spk.feat) {
+    set_err("ws_engine_separate: this model computes its own features (spk_feat = False): pass the waveform");
+    return WS_ERR_INVALID;
+  }
+  if (enroll_kind != WS_ENROLL_EMBEDDING && Te < 8) {
+    set_err("ws_engine_separate: enrollment of %d frames is too short for the speaker encoder", Te);
+    return WS_ERR_INVALID;
+  }
+  *frames = Te;
+  return WS_OK;
+}
+
+// ws_engine_separate and ws_engine_separate_ragged: lengths / enroll_lengths = nullptr is the rectangular call
+static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int* lengths, const void* enroll, int enroll_kind,
+                         int enroll_len, const int* enroll_lengths, float* est) {
+  int rc = check_engine(e, lengths || enroll_lengths ? "ws_engine_separate_ragged" : "ws_engine_separate");
   if (rc != WS_OK) return rc;
+  if ((lengths || enroll_lengths) && e->arch != 0) {
+    set_err("ws_engine_separate_ragged: per-row lengths are built for pBSRNN (arch 0) only; this container holds arch %d",
+            e->arch);
+    return WS_ERR_INVALID;
+  }
   if (e->arch == 1) return tasnet_separate(e, mix, R, T, enroll, enroll_kind, enroll_len, est);
   if (!mix || !enroll || !est || R < 1 || T < 512 || (long long)R * (1 + T / kHop) * 4 * kNBin > 0x7fffffffLL) {
     set_err("ws_engine_separate: bad arguments (R=%d, T=%d; T >= 512)", R, T);
@@ -372,25 +405,32 @@ WS_ENGINE_API int ws_engine_separate(ws_engine* e, const float* mix, int R, int 
     return WS_ERR_INVALID;
   }
   int Te = enroll_len;
-  if (enroll_kind == WS_ENROLL_WAVE && e->spk.feat) {          // kaldi fbank, snip-edges framing
-    if (enroll_len < e->spk.fb_win) {
-      set_err("ws_engine_separate: enrollment shorter than one %d-sample frame", e->spk.fb_win);
-      return WS_ERR_INVALID;
+  if ((rc = enroll_frames(e, enroll_kind, enroll_len, &Te)) != WS_OK) return rc;
+  std::vector<int> tf, te_row;
+  if (lengths) {
+    // a row's own T: what this surface demands of T, and no more than the row pitch
+    for (int r = 0; r < R; ++r) {
+      if (lengths[r] < 512 || lengths[r] > T) {
+        set_err("ws_engine_separate_ragged: lengths[%d] = %d outside [512, T = %d]", r, lengths[r], T);
+        return WS_ERR_INVALID;
+      }
+      tf.push_back(1 + lengths[r] / kHop);
     }
-    Te = 1 + (enroll_len - e->spk.fb_win) / e->spk.fb_shift;
-  } else if (enroll_kind == WS_ENROLL_WAVE) {                  // in-model MelSpectrogram, centred framing
-    if (enroll_len <= 256) {
-      set_err("ws_engine_separate: enrollment must be longer than the 256-sample reflect padding");
-      return WS_ERR_INVALID;
-    }
-    Te = 1 + enroll_len / kHop;
-  } else if (enroll_kind == WS_ENROLL_FBANK && !e->spk.feat) {
-    set_err("ws_engine_separate: this model computes its own features (spk_feat = False): pass the waveform");
-    return WS_ERR_INVALID;
   }
-  if (enroll_kind != WS_ENROLL_EMBEDDING && Te < 8) {
-    set_err("ws_engine_separate: enrollment of %d frames is too short for the speaker encoder", Te);
-    return WS_ERR_INVALID;
+  if (enroll_lengths) {
+    if (enroll_kind == WS_ENROLL_EMBEDDING) {
+      set_err("ws_engine_separate_ragged: enroll_lengths given with fixed embeddings (they have no length)");
+      return WS_ERR_INVALID;
+    }
+    te_row.resize(R);
+    for (int r = 0; r < R; ++r) {
+      if (enroll_lengths[r] > enroll_len) {
+        set_err("ws_engine_separate_ragged: enroll_lengths[%d] = %d exceeds the row pitch enroll_len = %d", r,
+                enroll_lengths[r], enroll_len);
+        return WS_ERR_INVALID;
+      }
+      if ((rc = enroll_frames(e, enroll_kind, enroll_lengths[r], &te_row[r])) != WS_OK) return rc;
+    }
   }
   if (!e->dry && hipSetDevice(e->device) != hipSuccess) {
     set_err("ws_engine_separate: hipSetDevice(%d) failed", e->device);
@@ -429,13 +469,30 @@ WS_ENGINE_API int ws_engine_separate(ws_engine* e, const float* mix, int R, int 
     mix = mixn.data();
   }
   if ((rc = to_device(e, d_mix, mix, size_t(R) * T * 4)) != WS_OK) return rc;
+  int *d_len = nullptr, *d_tf = nullptr;
+  if (lengths) {
+    d_len = reinterpret_cast<int*>(a.alloc(R));
+    d_tf = reinterpret_cast<int*>(a.alloc(R));
+    WS_PTR(d_len && d_tf);
+    if ((rc = to_device(e, d_len, lengths, size_t(R) * 4)) != WS_OK || (rc = to_device(e, d_tf, tf.data(), size_t(R) * 4)) != WS_OK)
+      return rc;
+  }
   if (enroll_kind == WS_ENROLL_EMBEDDING) {
     if ((rc = to_device(e, d_emb, enroll, size_t(R) * e->E * 4)) != WS_OK) return rc;
+  } else if (enroll_lengths) {
+    // the speaker stage is not ragged: one enrollment at a time into the [R][E] buffer (its convolutions then pad with
+    // zeros at the row's true end and its pooling sees the row's own frames), then the separator once over all rows
+    const size_t pitch = size_t(enroll_len) * (enroll_kind == WS_ENROLL_FBANK ? e->spk.feat_dim : 1);
+    for (int r = 0; r < R; ++r)
+      if ((rc = speaker_embed(e, static_cast<const float*>(enroll) + r * pitch, enroll_kind, 1, enroll_lengths[r], te_row[r],
+                              d_emb + size_t(r) * e->E)) != WS_OK)
+        return rc;
   } else if ((rc = speaker_embed(e, enroll, enroll_kind, R, enroll_len, Te, d_emb)) != WS_OK) {
     return rc;
   }
   rc = e->arch == 2 ? dpccn_device(e, d_mix, R, T, d_emb, d_est)
-                    : e->arch == 3 ? gridnet_device(e, d_mix, R, T, d_emb, d_est) : separate_device(e, d_mix, R, T, d_emb, d_est);
+                    : e->arch == 3 ? gridnet_device(e, d_mix, R, T, d_emb, d_est)
+                                   : separate_device(e, d_mix, R, T, d_emb, d_est, d_len, d_tf);
   if (rc != WS_OK) return rc;
   if ((rc = to_host(e, est, d_est, size_t(R) * T * 4)) != WS_OK) return rc;
   if (e->arch == 3 && !e->dry)
@@ -452,6 +509,16 @@ WS_ENGINE_API int ws_engine_separate(ws_engine* e, const float* mix, int R, int 
   a.reset();
   a.consolidate();
   return WS_OK;
+}
+
+WS_ENGINE_API int ws_engine_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind,
+                                  int enroll_len, float* est) {
+  return separate_impl(e, mix, R, T, nullptr, enroll, enroll_kind, enroll_len, nullptr, est);
+}
+
+WS_ENGINE_API int ws_engine_separate_ragged(ws_engine* e, const float* mix, int R, int T, const int* lengths, const void* enroll,
+                                         int enroll_kind, int enroll_len, const int* enroll_lengths, float* est) {
+  return separate_impl(e, mix, R, T, lengths, enroll, enroll_kind, enroll_len, enroll_lengths, est);
 }
 
 WS_ENGINE_API int ws_engine_forward_pcm16(ws_engine* e, const int16_t* mix, int n, const int16_t* spk1, const int16_t* spk2,

@@ -357,7 +357,8 @@ int spk_transform(ws_engine* e, const float* emb, int R, const float** out);
 int prepare_bsrnn(ws_engine* e);
 int pack_rnn(ws_engine* e, int C, const float* wih_f, const float* wih_r, const float* const bias[4], const float* proj_w,
              RnnPrep* r);
-int separate_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est);
+int separate_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est,
+                    const int* d_len = nullptr, const int* d_tf = nullptr);
 int prepare_tasnet(ws_engine* e);
 int tasnet_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind, int enroll_len,
                     float* est);

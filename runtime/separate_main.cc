@@ -2,7 +2,7 @@
 // runtime/bin/separate_main.cc:24-115:
 //
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
-//                 [--dry_run]
+//                 [--batch 8] [--dry_run]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -12,6 +12,10 @@
 // copy -- 0.3 GB of 288), spread round-robin over --devices.  Engines that share a GPU overlap on the device (round 2
 // serialised them; round 3 removed the cause -- profiles/r03_kernel_race.md -- and WS_ENGINE_SERIALIZE=1 restores one
 // forward at a time per GPU).  The reference tool is single-threaded on CPU cores.
+// --batch N (default 1 = the path above; pBSRNN models): N consecutive lines of the scp go through ONE forward of 2 N rows
+// (ws_engine_separate_ragged: every row keeps its own length, every enrollment its own -- each cut to the shorter of its
+// pair as above -- so the estimates are those of --batch 1); same output names and formats; works with --jobs (a worker
+// takes the next N lines) and --dry_run.  No sorting or bucketing: the rectangle is as long as the longest of the N.
 // --dry_run validates the model file and the launch plan of every utterance without a GPU and writes nothing.
 // --raw_out additionally writes the unquantised estimates as <key>-spk{1,2}.f32 (float32, for parity checks).
 #include <stdio.h>
@@ -103,7 +107,10 @@ int main(int argc, char** argv) {
   }
   int jobs = atoi(args.get("jobs", "1").c_str());
   if (jobs < 1) jobs = 1;
-  if (jobs > static_cast<int>(waves.size())) jobs = static_cast<int>(waves.size());
+  const int batch = atoi(args.get("batch", "1").c_str());
+  if (batch < 1) return die("--batch needs a positive count");
+  const size_t ngroups = (waves.size() + batch - 1) / batch;
+  if (jobs > static_cast<int>(ngroups)) jobs = static_cast<int>(ngroups);
 
   std::mutex io_mu;                 // stdout / first error
   std::string first_error;
@@ -124,7 +131,84 @@ int main(int argc, char** argv) {
       ws_engine_destroy(engine);
       return fail("model sample rate differs from --sample_rate");
     }
-    for (size_t i = next++; i < waves.size() && !failed; i = next++) {
+    // --batch N > 1: group g = lines [g N, g N + N) in one ragged forward, two rows per line
+    for (size_t g = batch > 1 ? next++ : ngroups; g < ngroups && !failed; g = next++) {
+      const size_t i0 = g * batch, B = (i0 + batch <= waves.size() ? i0 + batch : waves.size()) - i0;
+      std::vector<wesep_rt::Wav> mix(B), s1(B), s2(B);
+      std::vector<int> lengths(2 * B), elens(2 * B);
+      std::string err;
+      int T = 0, Te = 0;
+      bool ok = true;
+      for (size_t b = 0; b < B && ok; ++b) {
+        const auto& w = waves[i0 + b];
+        if (!wesep_rt::read_wav(w[1], &mix[b], &err) || !wesep_rt::read_wav(w[2], &s1[b], &err) ||
+            !wesep_rt::read_wav(w[3], &s2[b], &err)) {
+          fail(err);
+          ok = false;
+        } else if (mix[b].sample_rate != sample_rate || s1[b].sample_rate != sample_rate || s2[b].sample_rate != sample_rate) {
+          fail(w[0] + ": sample rate is not " + std::to_string(sample_rate));
+          ok = false;
+        } else {
+          const int n = static_cast<int>(mix[b].samples.size());
+          const int ne = static_cast<int>(s1[b].samples.size() < s2[b].samples.size() ? s1[b].samples.size() : s2[b].samples.size());
+          lengths[2 * b] = lengths[2 * b + 1] = n;
+          elens[2 * b] = elens[2 * b + 1] = ne;
+          T = n > T ? n : T;
+          Te = ne > Te ? ne : Te;
+        }
+      }
+      if (!ok) break;
+      // the rows of ws_engine_forward_pcm16, for B lines: the mixture twice, one row per enrollment, scaled to [-1, 1]
+      std::vector<float> m(2 * B * size_t(T), 0.f), enr(2 * B * size_t(Te), 0.f), out(2 * B * size_t(T), 0.f);
+      for (size_t b = 0; b < B; ++b) {
+        for (int k = 0; k < 2; ++k) {
+          float* mr = m.data() + (2 * b + k) * size_t(T);
+          float* er = enr.data() + (2 * b + k) * size_t(Te);
+          const std::vector<int16_t>& src = k == 0 ? s1[b].samples : s2[b].samples;
+          for (int i = 0; i < lengths[2 * b]; ++i) mr[i] = static_cast<float>(mix[b].samples[i]) / 32768.0f;
+          for (int i = 0; i < elens[2 * b]; ++i) er[i] = static_cast<float>(src[i]) / 32768.0f;
+        }
+      }
+      const auto t0 = std::chrono::steady_clock::now();
+      if (ws_engine_separate_ragged(engine, m.data(), static_cast<int>(2 * B), T, lengths.data(), enr.data(), WS_ENROLL_WAVE, Te,
+                                    elens.data(), out.data()) != 0) {
+        fail(waves[i0][0] + " (batch of " + std::to_string(B) + "): " + ws_engine_last_error());
+        break;
+      }
+      const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      double audio_ms = 0.0;
+      for (size_t b = 0; b < B && ok; ++b) {
+        const std::string& key = waves[i0 + b][0];
+        const int n = lengths[2 * b];
+        const float* o = out.data() + 2 * b * size_t(T);
+        audio_ms += 1000.0 * n / sample_rate;
+        if (!dry && (!wesep_rt::write_wav(out_dir + "/" + key + "-spk1.wav", o, n, sample_rate, &err) ||
+                     !wesep_rt::write_wav(out_dir + "/" + key + "-spk2.wav", o + T, n, sample_rate, &err))) {
+          fail(err);
+          ok = false;
+        }
+        if (ok && !dry && raw_out) {
+          for (int k = 0; k < 2; ++k) {
+            FILE* f = fopen((out_dir + "/" + key + "-spk" + std::to_string(k + 1) + ".f32").c_str(), "wb");
+            if (!f || fwrite(o + size_t(k) * T, 4, n, f) != size_t(n)) fail("cannot write raw output");
+            if (f) fclose(f);
+          }
+        }
+      }
+      if (!ok) break;
+      std::lock_guard<std::mutex> l(io_mu);
+      for (size_t b = 0; b < B; ++b)
+        printf("process: %s RTF: %.4f (batch of %zu: %lld launches, %lld MiB arena)%s\n", waves[i0 + b][0].c_str(), ms / audio_ms,
+               B, ws_engine_info(engine, "n_launches"), ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");
+      if (ws_engine_info(engine, "cluster_fallbacks") > fallbacks_seen) {
+        fallbacks_seen = ws_engine_info(engine, "cluster_fallbacks");
+        printf("note: %s: a cluster recurrence timed out (GPU shared); recomputed by the streaming kernels\n",
+               waves[i0][0].c_str());
+      }
+      total_audio_ms += audio_ms;
+      total_busy_ms += ms;
+    }
+    for (size_t i = batch > 1 ? waves.size() : next++; i < waves.size() && !failed; i = next++) {
       const auto& w = waves[i];
       wesep_rt::Wav mix, s1, s2;
       std::string err;

@@ -176,6 +176,7 @@ _SIGS = {
     "ws_reduce_slabs": (_i, [_p, _i, _ll, _ll, _p, _i, _ll, _p]),
     "ws_transpose": (_i, [_p, _i, _i, _ll, _p, _p]),
     "ws_group_stats": (_i, [_p, C.POINTER(GroupsGeom), _f, _p, _p]),
+    "ws_group_stats_len": (_i, [_p, C.POINTER(GroupsGeom), _p, _i, _f, _p, _p]),
     "ws_gn_bwd_reduce": (_i, [_p, _p, _p, _p, _p, C.POINTER(GroupsGeom), _p, _p]),
     "ws_gn_bwd_apply": (_i, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(GroupsGeom), _p, _p]),
     "ws_gn_param_grad": (_i, [_p, _p, _p, C.POINTER(GroupsGeom), _i, _p, _p]),
@@ -198,11 +199,14 @@ _SIGS = {
     "ws_lstm_cat_ih": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
     "ws_pack_w": (_i, [_p, _i, _i, _ll, _i, _i, _p, _p]),
     "ws_gemm_p2b": (_i, [C.POINTER(GemmP2BArgs), _p]),
+    "ws_gemm_p2b_len": (_i, [C.POINTER(GemmP2BArgs), _p, _i, _p]),
     "ws_gemm_b2p": (_i, [C.POINTER(GemmB2PArgs), _p]),
     "ws_gemm_tnb": (_i, [C.POINTER(GemmTNBArgs), _p]),
     "ws_stft_bandsplit": (_i, [_p, _i, _i, C.POINTER(Bands), _p, _p]),
+    "ws_stft_bandsplit_len": (_i, [_p, _i, _i, _p, C.POINTER(Bands), _p, _p]),
     "ws_mask_istft_frames": (_i, [_p, _p, _i, _i, C.POINTER(Bands), _p, _p]),
     "ws_istft_ola": (_i, [_p, _i, _i, _i, _p, _p]),
+    "ws_istft_ola_len": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "ws_mask_istft_bwd": (_i, [_p, _p, _p, _i, _i, _i, C.POINTER(Bands), _p, _p]),
     "ws_affine_fwd": (_i, [_p, _p, _p, _f, _ll, _i, _i, _p, _p]),
     "ws_affine_bwd": (_i, [_p, _p, _p, _f, _ll, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),

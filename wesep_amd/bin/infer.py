@@ -8,11 +8,27 @@ import torch
 from ..utils.score import cal_SISNRi
 
 
+def peak_normalise_rows(outputs, lengths):
+    """The rule of infer.py:118-128 for a ragged batch, row by row as if each were a batch of one: a row whose maximum over
+    its valid part is positive is scaled to a peak of 0.9 over that part.  outputs: numpy [B, T] (zeros behind lengths[r])."""
+    outputs = np.array(outputs, dtype=np.float32)
+    for r, n in enumerate(lengths):
+        row = outputs[r, :int(n)]
+        if row.max() > 0:
+            outputs[r, :int(n)] = row / np.abs(row).max() * 0.9
+    return outputs
+
+
 @torch.no_grad()
-def extract(model, wav_mix, enroll):
+def extract(model, wav_mix, enroll, lengths=None):
     """wav_mix [B, T], enroll [B, spk_emb_dim] (device tensors) -> numpy [B, T], peak-normalised like
-    infer.py:118-128 (only when every row's maximum is positive, exactly as the reference)."""
+    infer.py:118-128 (only when every row's maximum is positive, exactly as the reference).
+    lengths (B ints; pBSRNN): a ragged batch -- row r holds lengths[r] valid samples and comes out as that utterance alone
+    would (model(..., lengths=)), normalised over its valid part (peak_normalise_rows), zeros behind it."""
     model.eval()
+    if lengths is not None:
+        outputs = model(wav_mix.float(), enroll.float(), lengths=[int(n) for n in lengths])
+        return peak_normalise_rows((outputs[0] if isinstance(outputs, (list, tuple)) else outputs).cpu().numpy(), lengths)
     outputs = model(wav_mix.float(), enroll.float())
     if isinstance(outputs, (list, tuple)):
         outputs = outputs[0]
@@ -21,15 +37,22 @@ def extract(model, wav_mix, enroll):
     return outputs.cpu().numpy()
 
 
-def extract_engine(engine, wav_mix, enroll, kind=None):
+def extract_engine(engine, wav_mix, enroll, kind=None, lengths=None):
     """The same step on the native runtime (`wesep_amd.engine.Engine`, runtime/libwesep_engine.so): host arrays in,
     numpy [B, T] out, peak-normalised by the same rule.  `kind`: an `ENROLL_*` constant; default by rank
-    (2-D embeddings for fixed-embedding models are ENROLL_EMBEDDING, 3-D is fbank; pass ENROLL_WAVE for audio)."""
+    (2-D embeddings for fixed-embedding models are ENROLL_EMBEDDING, 3-D is fbank; pass ENROLL_WAVE for audio).
+    lengths (B ints): a ragged batch, as in extract (Engine.separate_ragged; the enrollment rows keep their full length)."""
     from .. import engine as E
     wav_mix = np.ascontiguousarray(wav_mix, dtype=np.float32)
     enroll = np.ascontiguousarray(enroll, dtype=np.float32)
     if kind is None:
         kind = E.ENROLL_FBANK if enroll.ndim == 3 else E.ENROLL_EMBEDDING
+    if lengths is not None:
+        rows = engine.separate_ragged([wav_mix[r, :int(n)] for r, n in enumerate(lengths)], list(enroll), kind)
+        outputs = np.zeros_like(wav_mix)
+        for r, row in enumerate(rows):
+            outputs[r, :len(row)] = row
+        return peak_normalise_rows(outputs, lengths)
     outputs = engine.separate(wav_mix, enroll, kind)
     if outputs.max(axis=1).min() > 0:
         outputs = outputs / np.abs(outputs).max(axis=1, keepdims=True) * 0.9
@@ -39,15 +62,22 @@ def extract_engine(engine, wav_mix, enroll, kind=None):
 def evaluate(model, batches, device="cuda"):
     """batches: iterable of dicts with `wav_mix` [B, T], `wav_targets` [B, T], `spk_embeds` [B, E]
     (what tse_collate_fn_2spk yields, infer.py:108-116).  Returns (mean SI-SNR, mean SI-SNRi, count):
-    the accumulation of infer.py:150-175."""
+    the accumulation of infer.py:150-175.  A batch may carry `lengths` [B]: utterances of different lengths padded to
+    one T (extract's ragged batch); every row is then scored over its own samples."""
     tot, toti, n = 0.0, 0.0, 0
     for b in batches:
         mix = torch.as_tensor(b["wav_mix"]).float().to(device)
         ref = np.asarray(b["wav_targets"], dtype=np.float32)
-        est = extract(model, mix, torch.as_tensor(b["spk_embeds"]).float().to(device))
+        lengths = b.get("lengths") if hasattr(b, "get") else None
+        if lengths is not None:
+            est = extract(model, mix, torch.as_tensor(b["spk_embeds"]).float().to(device), lengths=lengths)
+        else:
+            est = extract(model, mix, torch.as_tensor(b["spk_embeds"]).float().to(device))
         mixn = mix.cpu().numpy()
         for r in range(est.shape[0]):
             end = min(len(est[r]), len(ref[r]))
+            if lengths is not None:
+                end = min(end, int(lengths[r]))
             s, si = cal_SISNRi(est[r][:end], ref[r][:end], mixn[r][:end])
             tot, toti, n = tot + s, toti + si, n + 1
     return tot / max(n, 1), toti / max(n, 1), n

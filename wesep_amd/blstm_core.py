@@ -493,9 +493,12 @@ class BlstmPlan(NamedTuple):
 _WIHT_KIND = {0: "wihT", 1: "wihT", 2: "wihT16", 3: "wihT8"}     # BlstmPlan.a_fmt -> pack of W_ih^T for the d(xn) GEMM
 
 
-def make_plan(seq, device, grad, gn_geo=None) -> BlstmPlan:
+def make_plan(seq, device, grad, gn_geo=None, ragged=False) -> BlstmPlan:
     """gn_geo: geometry of a GroupNorm in front of the BLSTM whose fused backward can add the two directions' d(xn) (band_dx);
-    None: the caller has no such consumer and d(xn) always comes from the GEMM."""
+    None: the caller has no such consumer and d(xn) always comes from the GEMM.
+    ragged: the sequences have their own step counts (blstm_forward's `steps`): the forward takes a branch over precomputed
+    gates ('cluster' / 'stream'), where ws_gemm_p2b_len zeroes the tails -- 'fused' and 'cluster2' project inside the
+    recurrence and have no length operand."""
     lmode = dev.lstm_blk_mode(seq.nseq)
     cluster = dev.lstm_cluster_ok(seq, device)
     bptt = _bptt_kind(seq, device, cluster)
@@ -503,7 +506,9 @@ def make_plan(seq, device, grad, gn_geo=None) -> BlstmPlan:
     # BLSTMs' saved gates were 77 of the step's 155 GB in round 3); the opt-in cluster BPTT knows the fp32 format only
     gfmt = L.GATES_F32 if bptt == "cluster" else dev.gates_fmt()
     h2 = gfmt != L.GATES_F32
-    if dev.lstm_fuse_ok(seq.nseq, cluster):
+    if ragged:
+        fwd = "cluster" if cluster else "stream"
+    elif dev.lstm_fuse_ok(seq.nseq, cluster):
         fwd = "fused"
     elif cluster:
         fwd = "cluster2" if h2 and dev.lstm_cluster2_on() else "cluster"
@@ -529,13 +534,20 @@ def consume_once(ctx, who):
 # ---------------------------------------------------------------------------------------------
 # the steps, in launch order
 # ---------------------------------------------------------------------------------------------
-def blstm_forward(plan, W, x, seq, res, bias, norm=None):
+def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
     """out = res + Linear(BLSTM(x')) over the rows of the sequence map `seq`; x [rows, 128] plain, x' = x, or GroupNorm(x) with
     norm = dict(stats=, gamma=, beta=, stat_map=) (applied by ws_gemm_p2b on the way into BL).  W: the pack provider
     (WeightPacks).  Returns (out, saved): saved = (gates, cbuf, hcat, xn, hcat16) for ctx.save_for_backward -- xn is its
-    fp16 copy when plan.a16 (the backward never reads the split-pair xn again), hcat16 is None without it."""
+    fp16 copy when plan.a16 (the backward never reads the split-pair xn again), hcat16 is None without it.
+    steps (ragged batches, inference): (int32 device table, div) -- sequence s has table[s // div] valid steps; the
+    pre-activations behind them are exact zeros, so the reverse direction reaches a sequence's last valid step with zero
+    state (plan from make_plan(ragged=True); a branch that was not taught lengths refuses them)."""
     d = x.device
     norm = norm or {}
+    if steps is not None and (plan.fwd in ("fused", "cluster2") or plan.grad):
+        raise L.WesepHipError(f"blstm_forward: per-sequence step counts with forward branch '{plan.fwd}', grad={plan.grad}: "
+                              "only the branches over precomputed gates know them, and only the forward")
+    lens = dict(steps=steps[0], steps_div=steps[1]) if steps is not None else {}
     nb, gfmt, lmode = plan.nb, plan.gfmt, plan.lmode
     h2 = gfmt != L.GATES_F32
     wcat, bcat = W("cat")
@@ -581,7 +593,7 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None):
         # pre-activations: in `gates` itself with the fp32 format (one buffer, three lives); with the 2-byte formats a
         # scratch buffer that dies with this forward (the recurrences read it and write the unorm16 gates next to it)
         pre = _empty(d, nb, 32 * 2 * G4) if h2 else gates
-        xproj = dict(A=x, lda=N, sm=seq, Wpack=W("wih"), N=2 * G4, C_out=pre, bias=bcat, A_bl=xn, A_bl16=xn16, **norm)
+        xproj = dict(A=x, lda=N, sm=seq, Wpack=W("wih"), N=2 * G4, C_out=pre, bias=bcat, A_bl=xn, A_bl16=xn16, **norm, **lens)
         rec = dict(gfmt=gfmt, gates_in=pre) if h2 else {}
         dev.gemm_p2b(**xproj)
         if _h2_probe() & 768 and not torch.cuda.is_available():

@@ -228,8 +228,13 @@ extern "C" int ws_pack_w(const float* W, int N, int K, long long ldw, int trans,
 // waves.  Output orientation D[m = column][n = slot]: a lane holds 4 consecutive columns of its
 // slot = one 16-byte BL cell, 32 lanes = 512 contiguous bytes.
 // ---------------------------------------------------------------------------------------------
+// LEN (ws_gemm_p2b_len): sequence s has steps[s / steps_div] valid steps; the slots of later steps are treated like
+// padded slots -- operand and output exactly zero, no bias -- so a recurrence that enters them with zero state leaves
+// them with zero state (the reverse direction of a ragged time view starts at its sequence's last valid step)
 #define P2B_K 128
-__global__ __launch_bounds__(512, 4) void gemm_p2b_kernel(const ws_gemm_p2b_args p) {
+template <bool LEN>
+__global__ __launch_bounds__(512, 4) void gemm_p2b_kernel(const ws_gemm_p2b_args p, const int* __restrict__ steps,
+                                                          int steps_div) {
   __shared__ __attribute__((aligned(16))) u32x4 wl[2][2048];  // 2 stages x 32 KB
   if (p.run_if && *p.run_if == 0u) return;  // predicated fall-back launch (wesep_hip.h): uniform
   const int tid = threadIdx.x, lane = tid & 63, i = lane & 31, half = lane >> 5;
@@ -240,6 +245,11 @@ __global__ __launch_bounds__(512, 4) void gemm_p2b_kernel(const ws_gemm_p2b_args
   const int bb = active ? b : nblk - 1;
   bool valid;
   const long long pos = seq_pos(p.sm, bb, i, valid);
+  if (LEN) {
+    const int tile = bb / p.sm.L, step = bb - tile * p.sm.L;
+    const int nv = p.sm.nvalid > 0 ? p.sm.nvalid : p.sm.nseq;
+    valid = valid && step < steps[min(tile * 32 + i, nv - 1) / steps_div];
+  }
 
   // ---- activation fragments ---------------------------------------------------------------
   bf16x8 xh[8], xl[8];
@@ -346,20 +356,32 @@ __global__ __launch_bounds__(512, 4) void gemm_p2b_kernel(const ws_gemm_p2b_args
   }
 }
 
-extern "C" int ws_gemm_p2b(const ws_gemm_p2b_args* a, void* stream) {
-  WS_REQUIRE(a && a->A && ((a->Wpack && a->C) || (a->N == 0 && (a->A_bl || a->A_bl16))), "ws_gemm_p2b: null pointer");
-  WS_REQUIRE(a->K == P2B_K, "ws_gemm_p2b: K must be %d (got %d)", P2B_K, a->K);
-  WS_REQUIRE(a->N >= 0 && a->N % 64 == 0, "ws_gemm_p2b: N %% 64 (N=%d)", a->N);
-  WS_REQUIRE(a->lda >= a->K && a->lda % 4 == 0, "ws_gemm_p2b: lda");
-  WS_REQUIRE(a->sm.nseq > 0 && a->sm.L > 0 && a->sm.sq_div > 0, "ws_gemm_p2b: bad sequence map");
-  WS_REQUIRE(!a->stats || (a->gamma && a->beta && a->st_div1 > 0 && a->st_div2 > 0), "ws_gemm_p2b: norm args");
+static int gemm_p2b_launch(const char* who, const ws_gemm_p2b_args* a, const int* steps, int steps_div, void* stream) {
+  WS_REQUIRE(a && a->A && ((a->Wpack && a->C) || (a->N == 0 && (a->A_bl || a->A_bl16))), "%s: null pointer", who);
+  WS_REQUIRE(a->K == P2B_K, "%s: K must be %d (got %d)", who, P2B_K, a->K);
+  WS_REQUIRE(a->N >= 0 && a->N % 64 == 0, "%s: N %% 64 (N=%d)", who, a->N);
+  WS_REQUIRE(a->lda >= a->K && a->lda % 4 == 0, "%s: lda", who);
+  WS_REQUIRE(a->sm.nseq > 0 && a->sm.L > 0 && a->sm.sq_div > 0, "%s: bad sequence map", who);
+  WS_REQUIRE(!a->stats || (a->gamma && a->beta && a->st_div1 > 0 && a->st_div2 > 0), "%s: norm args", who);
   const int nblk = ((a->sm.nseq + 31) / 32) * a->sm.L;
   hipStream_t s = (hipStream_t)stream;
   const bool timed = a->run_if == nullptr;  // a predicated fall-back launch is normally empty: not a sample of this kind
   if (timed) ws_prof_begin(WS_PROF_GEMM_NT, s);
-  hipLaunchKernelGGL(gemm_p2b_kernel, dim3((nblk + 7) / 8), dim3(512), 0, s, *a);
+  if (steps)
+    hipLaunchKernelGGL((gemm_p2b_kernel<true>), dim3((nblk + 7) / 8), dim3(512), 0, s, *a, steps, steps_div);
+  else
+    hipLaunchKernelGGL((gemm_p2b_kernel<false>), dim3((nblk + 7) / 8), dim3(512), 0, s, *a, steps, steps_div);
   if (timed) ws_prof_end(WS_PROF_GEMM_NT, s);
-  return ws_check_launch("ws_gemm_p2b");
+  return ws_check_launch(who);
+}
+
+extern "C" int ws_gemm_p2b(const ws_gemm_p2b_args* a, void* stream) {
+  return gemm_p2b_launch("ws_gemm_p2b", a, nullptr, 1, stream);
+}
+
+extern "C" int ws_gemm_p2b_len(const ws_gemm_p2b_args* a, const int* steps, int steps_div, void* stream) {
+  WS_REQUIRE(steps && steps_div > 0, "ws_gemm_p2b_len: steps table / steps_div");
+  return gemm_p2b_launch("ws_gemm_p2b_len", a, steps, steps_div, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -30,11 +30,13 @@ static bool geom_vec4(const ws_groups_geom* g) {
 template <bool V4>
 __global__ __launch_bounds__(256) void group_stats_kernel(const float* __restrict__ x,
                                                           const ws_groups_geom geo, float eps,
-                                                          float* __restrict__ stats) {
+                                                          float* __restrict__ stats,
+                                                          const int* __restrict__ glen, int glen_div) {
   __shared__ float red[16];
   const int g = blockIdx.x;
   const GroupView v = group_view(geo, g);
-  const int n = geo.L * v.W;
+  // ws_group_stats_len: the statistics cover the first glen[g / glen_div] rows of the group only
+  const int n = (glen ? min(max(glen[g / glen_div], 1), geo.L) : geo.L) * v.W;
   const float* xb = x + v.base;
   float s = 0.f;
   if (V4) {
@@ -78,18 +80,29 @@ static int geom_check(const ws_groups_geom* geo, const char* who) {
   return WS_OK;
 }
 
-extern "C" int ws_group_stats(const float* x, const ws_groups_geom* geo, float eps, float* stats,
-                              void* stream) {
-  int rc = geom_check(geo, "ws_group_stats");
+static int group_stats_launch(const char* who, const float* x, const ws_groups_geom* geo, const int* glen, int glen_div,
+                              float eps, float* stats, void* stream) {
+  int rc = geom_check(geo, who);
   if (rc != WS_OK) return rc;
-  WS_REQUIRE(x && stats, "ws_group_stats: null pointer");
+  WS_REQUIRE(x && stats, "%s: null pointer", who);
   if (geom_vec4(geo))
     hipLaunchKernelGGL((group_stats_kernel<true>), dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream, x,
-                       *geo, eps, stats);
+                       *geo, eps, stats, glen, glen_div);
   else
     hipLaunchKernelGGL((group_stats_kernel<false>), dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream, x,
-                       *geo, eps, stats);
-  return ws_check_launch("ws_group_stats");
+                       *geo, eps, stats, glen, glen_div);
+  return ws_check_launch(who);
+}
+
+extern "C" int ws_group_stats(const float* x, const ws_groups_geom* geo, float eps, float* stats,
+                              void* stream) {
+  return group_stats_launch("ws_group_stats", x, geo, nullptr, 1, eps, stats, stream);
+}
+
+extern "C" int ws_group_stats_len(const float* x, const ws_groups_geom* geo, const int* glen, int glen_div, float eps,
+                                  float* stats, void* stream) {
+  WS_REQUIRE(glen && glen_div > 0, "ws_group_stats_len: glen table / glen_div");
+  return group_stats_launch("ws_group_stats_len", x, geo, glen, glen_div, eps, stats, stream);
 }
 
 template <bool V4>

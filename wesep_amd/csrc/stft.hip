@@ -97,9 +97,12 @@ __device__ __forceinline__ float ola_envelope(const cpx* tw, int q, int Tf) {
 }
 
 // -------------------------------------------------------------------------------------------
+// lengths (optional, ws_stft_bandsplit_len): row r holds lengths[r] valid samples of its T; the reflect padding turns at
+// lengths[r], frames t >= 1 + lengths[r] / HOP are written as zeros and nothing behind lengths[r] is read
 __global__ __launch_bounds__(256) void stft_bandsplit_kernel(const float* __restrict__ wav, int R,
                                                              int T, int Tf, const ws_bands b,
-                                                             float* __restrict__ xbs) {
+                                                             float* __restrict__ xbs,
+                                                             const int* __restrict__ lengths) {
   __shared__ cpx tw[NFFT];
   __shared__ cpx scratch[4 * WAVE_SCRATCH];
   build_twiddles(tw);
@@ -112,13 +115,18 @@ __global__ __launch_bounds__(256) void stft_bandsplit_kernel(const float* __rest
     const bool active = f < nframes;
     const int ff = active ? f : 0;
     const int r = ff / Tf, t = ff - r * Tf;
+    // (a length outside (NFFT / 2, T] is refused by the callers that have it on the host; clamped here so that no
+    // value in the device table can move a read out of the row)
+    const int Tr = lengths ? min(max(lengths[r], NFFT / 2 + 1), T) : T;
+    const bool tail = t > Tr / HOP;
     cpx v[8];
 #pragma unroll
     for (int n1 = 0; n1 < 8; ++n1) {
       const int n = 64 * n1 + lane;
       int pos = t * HOP + n - NFFT / 2;
       if (pos < 0) pos = -pos;
-      if (pos >= T) pos = 2 * (T - 1) - pos;
+      if (pos >= Tr) pos = 2 * (Tr - 1) - pos;
+      if (tail) pos = 0;
       v[n1] = cpx{wav[(long long)r * T + pos] * hann(tw, n), 0.f};
     }
     fft512(v, sc, tw, lane);
@@ -130,24 +138,34 @@ __global__ __launch_bounds__(256) void stft_bandsplit_kernel(const float* __rest
         if (bin < NBIN) {
           const int g = b.band_of_bin[bin];
           const int f0 = b.band_f0[g], bw = b.band_bw[g];
-          row[2 * f0 + (bin - f0)] = v[k3].x;
-          row[2 * f0 + bw + (bin - f0)] = v[k3].y;
+          row[2 * f0 + (bin - f0)] = tail ? 0.f : v[k3].x;
+          row[2 * f0 + bw + (bin - f0)] = tail ? 0.f : v[k3].y;
         }
       }
     }
   }
 }
 
-extern "C" int ws_stft_bandsplit(const float* wav, int R, int T, const ws_bands* b, float* xbs,
-                                 void* stream) {
-  WS_REQUIRE(wav && b && xbs && R > 0, "ws_stft_bandsplit: bad args");
-  WS_REQUIRE(T > NFFT / 2, "ws_stft_bandsplit: T=%d must exceed the reflect pad %d", T, NFFT / 2);
-  WS_REQUIRE(b->nbins == NBIN && b->band_of_bin && b->band_f0 && b->band_bw, "ws_stft_bandsplit: bad bands");
+static int stft_bandsplit_launch(const char* who, const float* wav, int R, int T, const int* lengths, const ws_bands* b,
+                                 float* xbs, void* stream) {
+  WS_REQUIRE(wav && b && xbs && R > 0, "%s: bad args", who);
+  WS_REQUIRE(T > NFFT / 2, "%s: T=%d must exceed the reflect pad %d", who, T, NFFT / 2);
+  WS_REQUIRE(b->nbins == NBIN && b->band_of_bin && b->band_f0 && b->band_bw, "%s: bad bands", who);
   const int Tf = 1 + T / HOP;
   const int nframes = R * Tf;
   hipLaunchKernelGGL(stft_bandsplit_kernel, dim3((nframes + FR_PER_WG - 1) / FR_PER_WG), dim3(256),
-                     0, (hipStream_t)stream, wav, R, T, Tf, *b, xbs);
-  return ws_check_launch("ws_stft_bandsplit");
+                     0, (hipStream_t)stream, wav, R, T, Tf, *b, xbs, lengths);
+  return ws_check_launch(who);
+}
+
+extern "C" int ws_stft_bandsplit(const float* wav, int R, int T, const ws_bands* b, float* xbs,
+                                 void* stream) {
+  return stft_bandsplit_launch("ws_stft_bandsplit", wav, R, T, nullptr, b, xbs, stream);
+}
+
+extern "C" int ws_stft_bandsplit_len(const float* wav, int R, int T, const int* lengths, const ws_bands* b, float* xbs,
+                                     void* stream) {
+  return stft_bandsplit_launch("ws_stft_bandsplit_len", wav, R, T, lengths, b, xbs, stream);
 }
 
 // -------------------------------------------------------------------------------------------
@@ -207,8 +225,11 @@ extern "C" int ws_mask_istft_frames(const float* xbs, const float* mask3, int R,
   return ws_check_launch("ws_mask_istft_frames");
 }
 
+// lengths (optional, ws_istft_ola_len): only the frames t < 1 + lengths[r] / HOP of row r are added and counted in the
+// envelope (the others are never read); samples >= lengths[r] are written as zeros
 __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames, int R,
-                                                        int Tf, int T, float* __restrict__ wav) {
+                                                        int Tf, int T, float* __restrict__ wav,
+                                                        const int* __restrict__ lengths) {
   __shared__ cpx tw[NFFT];
   build_twiddles(tw);
   __syncthreads();
@@ -217,7 +238,8 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
        i += (long long)gridDim.x * blockDim.x) {
     const int r = (int)(i / T), pos = (int)(i - (long long)r * T);
     const int q = pos + NFFT / 2;
-    const int t_hi = min(q / HOP, Tf - 1);
+    const int Tr = lengths ? min(max(lengths[r], 1), T) : T;
+    const int t_hi = min(q / HOP, lengths ? Tr / HOP : Tf - 1);
     const int t_lo = q >= NFFT ? (q - (NFFT - HOP)) / HOP : 0;
     float y = 0.f, e = 0.f;
     for (int t = t_lo; t <= t_hi; ++t) {
@@ -226,18 +248,27 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
       const float w = hann(tw, n);
       e += w * w;
     }
-    wav[i] = y / e;
+    wav[i] = pos < Tr ? y / e : 0.f;
   }
 }
 
-extern "C" int ws_istft_ola(const float* frames, int R, int Tf, int T, float* wav, void* stream) {
-  WS_REQUIRE(frames && wav && R > 0 && Tf > 0 && T > 0, "ws_istft_ola: bad args");
-  WS_REQUIRE(Tf == 1 + T / HOP, "ws_istft_ola: Tf=%d does not match T=%d", Tf, T);
+static int istft_ola_launch(const char* who, const float* frames, int R, int Tf, int T, const int* lengths, float* wav,
+                            void* stream) {
+  WS_REQUIRE(frames && wav && R > 0 && Tf > 0 && T > 0, "%s: bad args", who);
+  WS_REQUIRE(Tf == 1 + T / HOP, "%s: Tf=%d does not match T=%d", who, Tf, T);
   long long blocks = ((long long)R * T + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     frames, R, Tf, T, wav);
-  return ws_check_launch("ws_istft_ola");
+                     frames, R, Tf, T, wav, lengths);
+  return ws_check_launch(who);
+}
+
+extern "C" int ws_istft_ola(const float* frames, int R, int Tf, int T, float* wav, void* stream) {
+  return istft_ola_launch("ws_istft_ola", frames, R, Tf, T, nullptr, wav, stream);
+}
+
+extern "C" int ws_istft_ola_len(const float* frames, int R, int Tf, int T, const int* lengths, float* wav, void* stream) {
+  return istft_ola_launch("ws_istft_ola_len", frames, R, Tf, T, lengths, wav, stream);
 }
 
 // -------------------------------------------------------------------------------------------

@@ -223,11 +223,37 @@ class Geom(NamedTuple):
         return g
 
 
-def group_stats(x, geo: Geom, stats, eps=GN_EPS):
+def group_stats(x, geo: Geom, stats, eps=GN_EPS, glen=None, glen_div=1):
+    """glen (ragged batches): int32 device table; group g's statistics cover its first glen[g // glen_div] rows only."""
     _chk(x, "x")
     _chk(stats, "stats")
     g = geo.c()
+    if glen is not None:
+        _chk_lens(glen, -(-geo.ngroups // glen_div), "ws_group_stats_len")
+        L.check(L.lib().ws_group_stats_len(_p(x), C.byref(g), _tab(glen), glen_div, eps, _p(stats), L.stream_ptr()),
+                "ws_group_stats_len")
+        return
     L.check(L.lib().ws_group_stats(_p(x), C.byref(g), eps, _p(stats), L.stream_ptr()), "ws_group_stats")
+
+
+def _chk_lens(t, n, who):
+    """a length table of the ragged entry points: int32, contiguous, on the device, at least n entries"""
+    _chk(t, f"{who}: length table", torch.int32)
+    if t.numel() < n:
+        raise L.WesepHipError(f"{who}: the length table has {t.numel()} entries, the call needs {n}")
+
+
+def ragged_tables(lengths, T, device, hop=128, min_len=257):
+    """lengths: R ints (sequence / numpy / CPU tensor), the rows' valid samples of a [R, T] batch -> (int32 device tables
+    [R] of the samples and of the frames 1 + n // hop).  Values outside [min_len, T] are refused here, on the host, where
+    they are known: the kernels only clamp."""
+    ln = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    bad = [(r, v) for r, v in enumerate(ln) if v < min_len or v > T]
+    if not ln or bad:
+        raise L.WesepHipError(f"lengths outside [{min_len}, T = {T}] (row, value): {bad[:4]}" if bad else "lengths: empty")
+    t = torch.tensor([ln, [1 + v // hop for v in ln]], dtype=torch.int32)
+    t = t.to(device)
+    return t[0].contiguous(), t[1].contiguous()
 
 
 def _tab(t):
@@ -736,11 +762,18 @@ class BandTables:
         return b
 
 
-def stft_bandsplit(wav, bands: BandTables, xbs):
+def stft_bandsplit(wav, bands: BandTables, xbs, lengths=None):
+    """lengths (ragged batches): int32 device table [R] of the rows' valid samples, each in (256, T] (the callers check the
+    values where they have them on the host: ragged_tables)."""
     _chk(wav, "wav")
     _chk(xbs, "xbs")
     R, T = wav.shape
     b = bands.c()
+    if lengths is not None:
+        _chk_lens(lengths, R, "ws_stft_bandsplit_len")
+        L.check(L.lib().ws_stft_bandsplit_len(_p(wav), R, T, _tab(lengths), C.byref(b), _p(xbs), L.stream_ptr()),
+                "ws_stft_bandsplit_len")
+        return
     L.check(L.lib().ws_stft_bandsplit(_p(wav), R, T, C.byref(b), _p(xbs), L.stream_ptr()),
             "ws_stft_bandsplit")
 
@@ -753,9 +786,13 @@ def mask_istft_frames(xbs, mask3, R, Tf, bands: BandTables, frames):
                                          L.stream_ptr()), "ws_mask_istft_frames")
 
 
-def istft_ola(frames, R, Tf, T, wav):
+def istft_ola(frames, R, Tf, T, wav, lengths=None):
     _chk(frames, "frames")
     _chk(wav, "wav")
+    if lengths is not None:
+        _chk_lens(lengths, R, "ws_istft_ola_len")
+        L.check(L.lib().ws_istft_ola_len(_p(frames), R, Tf, T, _tab(lengths), _p(wav), L.stream_ptr()), "ws_istft_ola_len")
+        return
     L.check(L.lib().ws_istft_ola(_p(frames), R, Tf, T, _p(wav), L.stream_ptr()), "ws_istft_ola")
 
 
@@ -983,9 +1020,11 @@ def pack_w(W, N: int, K: int, ldw: int, out, trans=False, order=0, w_off=0, f16=
 
 
 def gemm_p2b(*, A, lda: int, sm: SeqMap, Wpack, N: int, C_out, K=128, bias=None, A_bl=None, stats=None,
-             gamma=None, beta=None, stat_map: Optional[StatMap] = None, run_if=None, amax=None, A_bl16=None):
+             gamma=None, beta=None, stat_map: Optional[StatMap] = None, run_if=None, amax=None, A_bl16=None, steps=None,
+             steps_div=1):
     """A_bl16 (ABI v16): the (normalised) operand once more as fp16 in BLH(K) (float32 storage of half the element count:
-    blh_floats) -- the 2-byte A operand of gemm_tnb (a_fmt = 1)."""
+    blh_floats) -- the 2-byte A operand of gemm_tnb (a_fmt = 1).  steps (ragged batches): int32 device table; sequence s has
+    steps[s // steps_div] valid steps, the slots of later steps come out as exact zeros (ws_gemm_p2b_len)."""
     for n, t in (("A", A), ("Wpack", Wpack), ("bias", bias), ("C", C_out), ("A_bl", A_bl), ("stats", stats),
                  ("gamma", gamma), ("beta", beta), ("A_bl16", A_bl16)):
         _chk(t, n)
@@ -1004,6 +1043,10 @@ def gemm_p2b(*, A, lda: int, sm: SeqMap, Wpack, N: int, C_out, K=128, bias=None,
         rows = (getattr(sm, "nvalid", 0) or sm.nseq) * sm.L
         _alg("gemm_nt", rows * (4 * K + 4 * N + (4 * K if A_bl is not None else 0) + (2 * K if A_bl16 is not None else 0)) + 4 * N * K,
              2 * rows * N * K)
+    if steps is not None:
+        _chk_lens(steps, -(-(getattr(sm, "nvalid", 0) or sm.nseq) // steps_div), "ws_gemm_p2b_len")
+        L.check(L.lib().ws_gemm_p2b_len(C.byref(a), _tab(steps), steps_div, L.stream_ptr()), "ws_gemm_p2b_len")
+        return
     L.check(L.lib().ws_gemm_p2b(C.byref(a), L.stream_ptr()), "ws_gemm_p2b")
 
 

@@ -7,13 +7,13 @@ import numpy as np
 
 from ._lib import WesepHipError
 
-ENGINE_ABI_VERSION = 1
+ENGINE_ABI_VERSION = 2
 DRY_RUN = 1
 ENROLL_EMBEDDING, ENROLL_FBANK, ENROLL_WAVE = 0, 1, 2
 LIB_PATH = os.environ.get("WESEP_ENGINE_LIB") or os.path.join(
     os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "runtime", "libwesep_engine.so")
 SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", "ws_engine_destroy", "ws_engine_info",
-           "ws_engine_separate", "ws_engine_forward_pcm16")
+           "ws_engine_separate", "ws_engine_separate_ragged", "ws_engine_forward_pcm16")
 _lib = None
 
 
@@ -34,6 +34,9 @@ def lib():
         l.ws_engine_separate.restype = C.c_int
         l.ws_engine_separate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                          C.c_void_p]
+        l.ws_engine_separate_ragged.restype = C.c_int
+        l.ws_engine_separate_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_int, C.c_void_p, C.c_void_p]
         l.ws_engine_forward_pcm16.restype = C.c_int
         l.ws_engine_forward_pcm16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p]
@@ -57,6 +60,25 @@ def _quiesce_torch():
     torch = sys.modules.get("torch")
     if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
         torch.cuda.synchronize()
+
+
+def pack_rows(rows):
+    """List of R float arrays [n_r, ...] with equal trailing dimensions -> (zero-filled [R, max n_r, ...] float32, int32 [R]
+    of the n_r): the rectangle and the length table of a ragged call."""
+    rows = [np.ascontiguousarray(x, dtype=np.float32) for x in rows]
+    if not rows or any(x.ndim < 1 or x.shape[1:] != rows[0].shape[1:] for x in rows):
+        raise ValueError("pack_rows: a non-empty list of arrays with equal trailing dimensions")
+    lengths = np.array([x.shape[0] for x in rows], dtype=np.int32)
+    out = np.zeros((len(rows), int(lengths.max())) + rows[0].shape[1:], dtype=np.float32)
+    for r, x in enumerate(rows):
+        out[r, :x.shape[0]] = x
+    return out, lengths
+
+
+def frames_of(lengths, hop=128):
+    """Valid STFT frames of rows with `lengths` samples (centred framing: 1 + n // hop) -- the table the engine and
+    BSRNN.forward(lengths=) hand to the length-aware kernels."""
+    return 1 + np.asarray(lengths, dtype=np.int64) // hop
 
 
 class Engine:
@@ -96,6 +118,27 @@ class Engine:
         _check(lib().ws_engine_separate(self._h, mix.ctypes.data, R, T, enroll.ctypes.data, kind, length,
                                         est.ctypes.data), "ws_engine_separate")
         return est
+
+    def separate_ragged(self, mixes, enrolls, kind):
+        """Utterances of different lengths in one forward (pBSRNN containers): mixes: list of R float32 [T_r]; enrolls: list
+        of R arrays -- [E] (ENROLL_EMBEDDING), [Te_r, F] (ENROLL_FBANK) or [Tw_r] (ENROLL_WAVE) -> list of R float32 [T_r].
+        Every estimate is what separate() returns for that utterance alone (include/wesep_engine.h,
+        ws_engine_separate_ragged)."""
+        mixes, enrolls = pack_rows(mixes), pack_rows(enrolls)
+        mix, lengths = mixes
+        enroll, elen = enrolls
+        R, T = mix.shape
+        if enroll.shape[0] != R:
+            raise ValueError("one enrollment per mixture row")
+        est = np.zeros((R, T), dtype=np.float32)
+        fixed = kind == ENROLL_EMBEDDING
+        if fixed and len(set(elen.tolist())) != 1:
+            raise ValueError("fixed embeddings have one size")
+        _quiesce_torch()
+        _check(lib().ws_engine_separate_ragged(self._h, mix.ctypes.data, R, T, lengths.ctypes.data, enroll.ctypes.data, kind,
+                                               0 if fixed else enroll.shape[1], None if fixed else elen.ctypes.data,
+                                               est.ctypes.data), "ws_engine_separate_ragged")
+        return [est[r, :n].copy() for r, n in enumerate(lengths.tolist())]
 
     def forward_pcm16(self, mix, spk1, spk2):
         """int16 [n], int16 [n_enroll] x 2 -> float32 [2, n] in [-1, 1] (SeparateEngine::ForwardFunc)."""

@@ -173,6 +173,35 @@ def tail_flush() -> bool:
     return os.environ.get("WESEP_TAIL_FLUSH", "1") != "0"
 
 
+def _resrnn_blk_fwd(z, view, norm_w, norm_b, wparams, cache, grad, frames=None):
+    """The launches of ResRNNBlkFn.forward: statistics, plan, packs, the blocked BLSTM.  z contiguous [R, K, Tf, N].
+    frames (ragged batches, inference): int32 device table [R] of the rows' valid frames -- the time view's statistics
+    cover them only and its pre-activations behind them are zeros (blstm_forward's `steps`); the band view is per frame
+    and ignores it.  Returns (out, stats, plan, W, saved)."""
+    _need_cuda(z, "ResRNN")
+    wih_f, whh_f, proj_b = wparams[0], wparams[1], wparams[9]
+    R, K, Tf, N = z.shape
+    if tuple(whh_f.shape) != (G4, H) or tuple(wih_f.shape) != (G4, N) or N != 128:
+        raise L.WesepHipError(f"blocked ResRNN kernels are built for input 128 / hidden {H}; got "
+                              f"{tuple(wih_f.shape)}, {tuple(whh_f.shape)}")
+    d = z.device
+    geo, smap, seq, _ = _view_maps(view, R, K, Tf, N)
+    ragged = frames is not None and view == "time"
+    stats = _empty(d, geo.ngroups, 2)
+    if ragged:
+        dev.group_stats(z, geo, stats, glen=frames, glen_div=K)
+    else:
+        dev.group_stats(z, geo, stats)
+    cache = cache if cache is not None else _NO_CACHE
+    sig = cache.begin(wparams)
+    plan = make_plan(seq, d, grad, gn_geo=geo, ragged=ragged) if ragged else make_plan(seq, d, grad, gn_geo=geo)
+    W = WeightPacks(cache, sig, plan.lmode, plan.pair_rfmt, *wparams[:9])
+    steps = dict(steps=(frames, K)) if ragged else {}
+    out, saved = blstm_forward(plan, W, z, seq, res=z, bias=proj_b,
+                               norm=dict(stats=stats, gamma=norm_w, beta=norm_b, stat_map=smap), **steps)
+    return out, stats, plan, W, saved
+
+
 class ResRNNBlkFn(torch.autograd.Function):
     """ResRNN on the blocked layout: gates / c / h / d(h) never exist in row-major form; every
     activation byte of the recurrence moves as part of a 512-byte contiguous run (include/wesep_hip.h,
@@ -185,22 +214,11 @@ class ResRNNBlkFn(torch.autograd.Function):
         """dummy/box: None, or the output and the box of this ResRNN's WGradCarrierFn -- then the ten
         LSTM / proj tensors are passed detached and their gradients travel through the box.  cache: the owning
         module's PackCache or None."""
-        _need_cuda(z, "ResRNN")
         z = z.contiguous()
-        R, K, Tf, N = z.shape
-        if tuple(whh_f.shape) != (G4, H) or tuple(wih_f.shape) != (G4, N) or N != 128:
-            raise L.WesepHipError(f"blocked ResRNN kernels are built for input 128 / hidden {H}; got "
-                                  f"{tuple(wih_f.shape)}, {tuple(whh_f.shape)}")
         d = z.device
-        geo, smap, seq, _ = _view_maps(view, R, K, Tf, N)
-        stats = _empty(d, geo.ngroups, 2)
-        dev.group_stats(z, geo, stats)
-        cache = cache if cache is not None else _NO_CACHE
-        sig = cache.begin((wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r, proj_w, proj_b))
-        plan = make_plan(seq, d, any(ctx.needs_input_grad), gn_geo=geo)
-        W = WeightPacks(cache, sig, plan.lmode, plan.pair_rfmt, wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r, proj_w)
-        out, saved = blstm_forward(plan, W, z, seq, res=z, bias=proj_b,
-                                   norm=dict(stats=stats, gamma=norm_w, beta=norm_b, stat_map=smap))
+        out, stats, plan, W, saved = _resrnn_blk_fwd(
+            z, view, norm_w, norm_b, (wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r, proj_w, proj_b), cache,
+            any(ctx.needs_input_grad))
         ctx.save_for_backward(z, stats, norm_w, *saved)
         if view == "time" and box is not None and plan.grad:
             key = (d.type, d.index)
@@ -317,8 +335,15 @@ def make_wgrad_carrier(params, blocked=None):
     return WGradCarrierFn.apply(box, *params), box
 
 
-def resrnn(z, view, norm_w, norm_b, *params, carrier=None, cache=None):
-    """ResRNN forward (autograd-aware) on the path selected by WESEP_RESRNN.  cache: the owning module's PackCache."""
+def resrnn(z, view, norm_w, norm_b, *params, carrier=None, cache=None, frames=None):
+    """ResRNN forward (autograd-aware) on the path selected by WESEP_RESRNN.  cache: the owning module's PackCache.
+    frames (ragged batches): int32 device table [R] of the rows' valid frames; inference on the blocked path only."""
+    if frames is not None:
+        if torch.is_grad_enabled() or resrnn_mode() != "blocked":
+            raise L.WesepHipError("ResRNN: per-row lengths are an inference feature of the blocked path "
+                                  "(torch.no_grad(), WESEP_RESRNN=blocked); training batches are cropped by the collate function")
+        return _resrnn_blk_fwd(z.contiguous(), view, norm_w, norm_b, tuple(p.detach() for p in params), cache, False,
+                               frames=frames)[0]
     if resrnn_mode() != "blocked":
         return ResRNNFn.apply(z, view, norm_w, norm_b, *params)
     if carrier is None:
@@ -618,6 +643,76 @@ class BandPlan:
 # ---------------------------------------------------------------------------------------------
 # STFT + band split + per-band GroupNorm + 1x1 conv     (bsrnn.py:309-336)
 # ---------------------------------------------------------------------------------------------
+def _band_split_fwd(wav, plan, params, lengths=None, frames=None):
+    """The launches of BandSplitFn.forward; wav contiguous [R, T].  lengths / frames (ragged batches, inference: both or
+    neither, dev.ragged_tables): the reflect padding turns at a row's own end, the frames behind it are zeros and the
+    per-band statistics cover its valid frames.  Returns (z0, xbs, stats)."""
+    R, T = wav.shape
+    K, N = plan.K, plan.N
+    Tf = 1 + T // HOP
+    M = R * Tf
+    d = wav.device
+    xbs = _empty(d, M, 2 * NBIN)
+    geo = Geom(R * K, K, Tf * 2 * NBIN, 0, 2 * NBIN, Tf, 128, K, plan.bands.bw2, plan.bands.off2)
+    stats = _empty(d, R * K, 2)
+    if lengths is None:
+        dev.stft_bandsplit(wav, plan.bands, xbs)
+        dev.group_stats(xbs, geo, stats)
+    else:
+        dev.stft_bandsplit(wav, plan.bands, xbs, lengths=lengths)
+        dev.group_stats(xbs, geo, stats, glen=frames, glen_div=K)
+    nt, _, _ = plan.bn_desc(params, R, Tf)
+    z0 = _empty(d, R, K, Tf, N)
+    dev.gemm_nt(A=xbs, a_rows=flat(2 * NBIN), M=M, C_out=z0, c_rows=Rows(Tf, K * Tf * N, N),
+                stats=stats, stat_map=StatMap(Tf, K, 1, 0, 0), groups=nt, ngroups=K, max_n=N, vec=0)
+    return z0, xbs, stats
+
+
+def _mask_decode_fwd(z, xbs, plan, T, params, lengths=None, frames=None):
+    """The launches of MaskDecodeFn.forward; z contiguous [R, K, Tf, N].  lengths / frames as in _band_split_fwd: the
+    statistics of mask[i]'s norm cover a row's valid frames, the overlap-add and its envelope end at the row's own end and
+    the samples behind it are zeros.  Returns (est, stats, h1, h2, m3)."""
+    R, K, Tf, N = z.shape
+    H1 = 4 * N
+    M = R * Tf
+    d = z.device
+    D = plan.mask_desc(params, R, Tf)
+    geo = Geom(R * K, 1, Tf * N, 0, N, Tf, N, K)
+    stats = _empty(d, R * K, 2)
+    if lengths is None:
+        dev.group_stats(z, geo, stats)
+    else:
+        dev.group_stats(z, geo, stats, glen=frames, glen_div=K)
+    h1, h2 = _empty(d, K, M, H1), _empty(d, K, M, H1)
+    dev.gemm_nt(A=z, a_rows=Rows(Tf, K * Tf * N, N), M=M, C_out=h1, c_rows=flat(H1), stats=stats,
+                stat_map=StatMap(Tf, K, 1, 0, 0), act=1, groups=D["l1"], ngroups=K, max_n=H1)
+    dev.gemm_nt(A=h1, a_rows=flat(H1), M=M, C_out=h2, c_rows=flat(H1), act=1, groups=D["l2"],
+                ngroups=K, max_n=H1)
+    m3 = _empty(d, M, 4 * NBIN)
+    dev.gemm_nt(A=h2, a_rows=flat(H1), M=M, C_out=m3, c_rows=flat(4 * NBIN), groups=D["l3"],
+                ngroups=K, max_n=4 * max(plan.bw))
+    fr = _empty(d, M, 512)
+    dev.mask_istft_frames(xbs, m3, R, Tf, plan.bands, fr)
+    est = _empty(d, R, T)
+    if lengths is None:
+        dev.istft_ola(fr, R, Tf, T, est)
+    else:
+        dev.istft_ola(fr, R, Tf, T, est, lengths=lengths)
+    return est, stats, h1, h2, m3
+
+
+def band_split_ragged(wav, plan, params, lengths, frames):
+    """BandSplitFn for a ragged batch (inference): (z0, xbs)."""
+    _need_cuda(wav, "BSRNN")
+    return _band_split_fwd(wav.contiguous(), plan, [p.detach() for p in params], lengths, frames)[:2]
+
+
+def mask_decode_ragged(z, xbs, plan, T, params, lengths, frames):
+    """MaskDecodeFn for a ragged batch (inference): est [R, T], zeros behind every row's length."""
+    _need_cuda(z, "BSRNN")
+    return _mask_decode_fwd(z.contiguous(), xbs, plan, T, [p.detach() for p in params], lengths, frames)[0]
+
+
 class BandSplitFn(torch.autograd.Function):
     """inputs: wav [R, T], plan, then per band (gn.weight, gn.bias, conv.weight, conv.bias).
     outputs: z0 [R, K, Tf, N], xbs [R*Tf, 2F] (band-split mixture spectrogram, no grad)."""
@@ -627,19 +722,8 @@ class BandSplitFn(torch.autograd.Function):
         _need_cuda(wav, "BSRNN")
         wav = wav.contiguous()
         R, T = wav.shape
-        K, N = plan.K, plan.N
         Tf = 1 + T // HOP
-        M = R * Tf
-        d = wav.device
-        xbs = _empty(d, M, 2 * NBIN)
-        dev.stft_bandsplit(wav, plan.bands, xbs)
-        geo = Geom(R * K, K, Tf * 2 * NBIN, 0, 2 * NBIN, Tf, 128, K, plan.bands.bw2, plan.bands.off2)
-        stats = _empty(d, R * K, 2)
-        dev.group_stats(xbs, geo, stats)
-        nt, _, _ = plan.bn_desc(params, R, Tf)
-        z0 = _empty(d, R, K, Tf, N)
-        dev.gemm_nt(A=xbs, a_rows=flat(2 * NBIN), M=M, C_out=z0, c_rows=Rows(Tf, K * Tf * N, N),
-                    stats=stats, stat_map=StatMap(Tf, K, 1, 0, 0), groups=nt, ngroups=K, max_n=N, vec=0)
+        z0, xbs, stats = _band_split_fwd(wav, plan, params)
         ctx.save_for_backward(xbs, stats, *params)
         ctx.plan, ctx.dims = plan, (R, T, Tf)
         ctx.mark_non_differentiable(xbs)
@@ -698,26 +782,7 @@ class MaskDecodeFn(torch.autograd.Function):
     def forward(ctx, z, xbs, plan, T, *params):
         _need_cuda(z, "BSRNN")
         z = z.contiguous()
-        R, K, Tf, N = z.shape
-        H1 = 4 * N
-        M = R * Tf
-        d = z.device
-        D = plan.mask_desc(params, R, Tf)
-        geo = Geom(R * K, 1, Tf * N, 0, N, Tf, N, K)
-        stats = _empty(d, R * K, 2)
-        dev.group_stats(z, geo, stats)
-        h1, h2 = _empty(d, K, M, H1), _empty(d, K, M, H1)
-        dev.gemm_nt(A=z, a_rows=Rows(Tf, K * Tf * N, N), M=M, C_out=h1, c_rows=flat(H1), stats=stats,
-                    stat_map=StatMap(Tf, K, 1, 0, 0), act=1, groups=D["l1"], ngroups=K, max_n=H1)
-        dev.gemm_nt(A=h1, a_rows=flat(H1), M=M, C_out=h2, c_rows=flat(H1), act=1, groups=D["l2"],
-                    ngroups=K, max_n=H1)
-        m3 = _empty(d, M, 4 * NBIN)
-        dev.gemm_nt(A=h2, a_rows=flat(H1), M=M, C_out=m3, c_rows=flat(4 * NBIN), groups=D["l3"],
-                    ngroups=K, max_n=4 * max(plan.bw))
-        frames = _empty(d, M, 512)
-        dev.mask_istft_frames(xbs, m3, R, Tf, plan.bands, frames)
-        est = _empty(d, R, T)
-        dev.istft_ola(frames, R, Tf, T, est)
+        est, stats, h1, h2, m3 = _mask_decode_fwd(z, xbs, plan, T, params)
         ctx.save_for_backward(z, xbs, stats, h1, h2, m3, *params)
         ctx.plan, ctx.T = plan, T
         return est

@@ -13,7 +13,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import dev
 from .. import functional as F_
+from .._lib import WesepHipError
 from ..modules.common.speaker import SpeakerFuseLayer, SpeakerTransform
 
 _EPS = float(torch.finfo(torch.float32).eps)
@@ -61,7 +63,10 @@ class ResRNN(nn.Module):
         """Weight-gradient carrier of this layer (functional.WGradCarrierFn) or None."""
         return F_.make_wgrad_carrier(self._wparams())
 
-    def forward(self, z, view="time", carrier=None):
+    def forward(self, z, view="time", carrier=None, frames=None):
+        """frames: ragged batches (BSRNN.forward(lengths=)): int32 device table [R] of the rows' valid frames."""
+        if frames is not None:
+            return F_.resrnn(z, view, self.norm.weight, self.norm.bias, *self._wparams(), cache=self._packs, frames=frames)
         return F_.resrnn(z, view, self.norm.weight, self.norm.bias, *self._wparams(), carrier=carrier,
                          cache=self._packs)
 
@@ -76,8 +81,10 @@ class BSNet(nn.Module):
         self.band_rnn = ResRNN(self.feature_dim, self.feature_dim * 2, bidirectional)
         self.band_comm = ResRNN(self.feature_dim, self.feature_dim * 2, bidirectional)
 
-    def forward(self, z, dummy: Optional[torch.Tensor] = None, carriers=None):
+    def forward(self, z, dummy: Optional[torch.Tensor] = None, carriers=None, frames=None):
         c_t, c_b = carriers if carriers is not None else (None, None)
+        if frames is not None:      # ragged batch (inference): only the time view has to know where a row ends
+            return self.band_comm(self.band_rnn(z, "time", frames=frames), "band")
         return self.band_comm(self.band_rnn(z, "time", c_t), "band", c_b)
 
 
@@ -113,11 +120,13 @@ class FuseSeparation(nn.Module):
         return {i: (l.band_rnn.make_carrier(), l.band_comm.make_carrier())
                 for i, l in enumerate(self.separation) if isinstance(l, BSNet)}
 
-    def forward(self, z, spk_embedding, nch=None, carriers=None):
+    def forward(self, z, spk_embedding, nch=None, carriers=None, frames=None):
         if carriers is None:
             carriers = self.make_carriers(z.device)
         for i, layer in enumerate(self.separation):
-            if isinstance(layer, BSNet):
+            if isinstance(layer, BSNet) and frames is not None:
+                z = layer(z, frames=frames)
+            elif isinstance(layer, BSNet):
                 z = layer(z, spk_embedding, carriers[i])
             else:
                 z = layer(z, spk_embedding)
@@ -210,6 +219,21 @@ class BSRNN(nn.Module):
                     seq[5].weight, seq[5].bias]
         return out
 
+    def _forward_ragged(self, wav, embeddings, plan, lengths):
+        if torch.is_grad_enabled():
+            raise WesepHipError("BSRNN.forward(lengths=...): per-row lengths are an inference feature; call it under "
+                                "torch.no_grad() (training batches are cropped to the shortest row by the collate function)")
+        R, T = wav.shape
+        if len(lengths) != R:
+            raise WesepHipError(f"BSRNN.forward: {len(lengths)} lengths for {R} rows")
+        if not wav.is_cuda:
+            raise WesepHipError("BSRNN: wesep_amd has no CPU path; move the model and inputs to the GPU")
+        n, frames = dev.ragged_tables(lengths, T, wav.device)
+        z, xbs = F_.band_split_ragged(wav, plan, self._bn_params(), n, frames)
+        e, predict_speaker_lable = self._speaker(embeddings)
+        z = self.separator(z, e, carriers={}, frames=frames)
+        return F_.mask_decode_ragged(z, xbs, plan, T, self._mask_params(), n, frames), predict_speaker_lable
+
     def _plan(self, device):
         key = (device.type, device.index)
         if key not in self._plans:
@@ -232,13 +256,19 @@ class BSRNN(nn.Module):
                                      if self.multi_task else embeddings)
         return self.spk_transform(embeddings.float().contiguous()), predict_speaker_lable
 
-    def forward(self, input, embeddings):
+    def forward(self, input, embeddings, *, lengths=None):
         """input: mixture [R, T] fp32; embeddings: [R, spk_emb_dim] (fixed) or fbank [R, Te, 80] (joint training)
-        -> (est [R, T], 0-d dummy | speaker logits (multi_task) | the embedding (joint, no multi_task))."""
+        -> (est [R, T], 0-d dummy | speaker logits (multi_task) | the embedding (joint, no multi_task)).
+        lengths (keyword only; inference): R ints, the valid samples of each row of a ragged batch, 256 < lengths[r] <= T.
+        est[r, :lengths[r]] is then what the model returns for input[r, :lengths[r]] alone, est[r, lengths[r]:] is zero,
+        and nothing of input[r, lengths[r]:] reaches a valid output.  The enrollment stays a rectangle (the speaker encoder
+        is not ragged).  With gradients enabled it raises: training batches are cropped by the collate function."""
         if input.dim() != 2:
             raise RuntimeError("BSRNN expects a [batch, samples] mixture")
         wav = input.float().contiguous()
         plan = self._plan(wav.device)
+        if lengths is not None:
+            return self._forward_ragged(wav, embeddings, plan, lengths)
         carriers = self.separator.make_carriers(wav.device) if hasattr(self.separator, "make_carriers") else None
         z, xbs = F_.BandSplitFn.apply(wav, plan, *self._bn_params())
         e, predict_speaker_lable = self._speaker(embeddings)

@@ -28,9 +28,12 @@ class BSRNN_Multi(BSRNN):
             raise NotImplementedError("BSRNN_Multi: the self-enrollment pass needs joint_training=True, spk_feat=False, "
                                       "feat_type='consistent' (bsrnn_multi_optim.yaml)")
 
-    def forward(self, input, embeddings):
+    def forward(self, input, embeddings, *, lengths=None):
         """input [R, T] mixture, embeddings [R, Tw] enrollment waveform -> grad mode: (s, self_s, second output of
-        pass 1, of pass 2); no-grad mode: (s, second output)."""
+        pass 1, of pass 2); no-grad mode: (s, second output).  lengths: the inference-only ragged batches of BSRNN.forward
+        (the self-enrollment pass exists in grad mode only and is never ragged)."""
+        if lengths is not None:
+            return super().forward(input, embeddings, lengths=lengths)
         if input.dim() != 2:
             raise RuntimeError("BSRNN_Multi expects a [batch, samples] mixture")
         wav = input.float().contiguous()
