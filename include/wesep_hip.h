@@ -122,6 +122,13 @@ typedef struct ws_group_tn {
  * bslab[split][bout_off + n] = sum_m G[m][n]; the caller then sums the splits with
  * ws_reduce_slabs (deterministic, no atomics).  m' = m + shift_rows with the row zeroed
  * when the step index ((m / seq_div) % seq_len) +/- 1 leaves [0, seq_len) (h_{t-1} for dW_hh).
+ * With a shift M is a whole number of sequences, M % (seq_div * seq_len) == 0 (checked: row m' then lies in [0, M)); it is
+ * the OPERAND that is zeroed -- with norm-on-load too a zeroed row contributes 0, not beta -- and the stat index is taken
+ * from m, not m'.  Split s covers the rows [s * rows_per_split, min(M, (s + 1) * rows_per_split)): rows_per_split is any
+ * positive number (no multiple of the kernels' 32-row tile is needed), nsplit * rows_per_split >= M (checked), and a
+ * trailing split whose range is empty writes zeros to its slab and bias slab.  Per group, ws_group_tn's gamma / beta /
+ * st_base / out_off / bout_off / Nn / Kk REPLACE the argument's, g_off / a_off are added (ws_group_nt likewise: W / bias /
+ * gamma / beta / st_base / K / N / ldw replace, a_off / c_off are added).
  * Replaces the autograd weight-gradient of the same reference lines as ws_gemm_nt.         */
 typedef struct ws_gemm_tn_args {
   const float* G;

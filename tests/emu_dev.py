@@ -70,12 +70,14 @@ def gemm_nt(*, A, a_rows, M, C_out, c_rows, N=0, K=0, W=None, ldw=0, bias=None, 
         A, a_rows = _conv_matrix(A, M, conv), (1 << 30, 0, K)
         conv = None
     if groups is not None:   # grouped launch (per-group descriptors with raw pointers, _lib.GROUP_NT_DTYPE)
-        assert stats is None and R is None and T is None and W is None
-        for gd in _descs(groups, ngroups, "nt"):
+        assert W is None
+        for gd in _descs(groups, ngroups, "nt"):   # per group: W / bias / gamma / beta / st_base replace, a_off / c_off add
             Kg, Ng = int(gd["K"]), int(gd["N"])
             gemm_nt(A=A, a_rows=a_rows, M=M, C_out=C_out, c_rows=c_rows, N=Ng, K=Kg,
                     W=_at(gd["W"], (Kg if vec & 8 else Ng) * int(gd["ldw"])),
-                    ldw=int(gd["ldw"]), bias=_at(gd["bias"], Ng) if gd["bias"] else None, act=act,
+                    ldw=int(gd["ldw"]), bias=_at(gd["bias"], Ng) if gd["bias"] else None, act=act, R=R, T=T, stats=stats,
+                    gamma=_at(gd["gamma"], Kg) if gd["gamma"] else None, beta=_at(gd["beta"], Kg) if gd["beta"] else None,
+                    stat_map=tuple(stat_map[:4]) + (int(gd["st_base"]),) if stats is not None else None,
                     a_off=a_off + int(gd["a_off"]), c_off=c_off + int(gd["c_off"]), vec=vec)
         return
     a = _gather(A, a_off, M, a_rows, K)
@@ -114,10 +116,14 @@ def gemm_tn(*, G, g_rows, A, a_rows, M, slab, slab_stride, nsplit, rows_per_spli
         assert conv[0] == 0 and groups is None and stats is None and not shift_rows and a_off == 0
         A, a_rows = _conv_matrix(A, M, conv), (1 << 30, 0, Kk)
     if groups is not None:   # grouped launch (_lib.GROUP_TN_DTYPE): one output block per group in every split's slab
-        assert stats is None and not shift_rows and bslab is None
-        for gd in _descs(groups, ngroups, "tn"):
+        for gd in _descs(groups, ngroups, "tn"):   # gamma / beta / st_base / out_off / bout_off replace, g_off / a_off add
+            kg = int(gd["Kk"])
             gemm_tn(G=G, g_rows=g_rows, A=A, a_rows=a_rows, M=M, slab=slab, slab_stride=slab_stride, nsplit=nsplit,
-                    rows_per_split=rows_per_split, Nn=int(gd["Nn"]), Kk=int(gd["Kk"]), out_off=out_off + int(gd["out_off"]),
+                    rows_per_split=rows_per_split, Nn=int(gd["Nn"]), Kk=kg, out_off=int(gd["out_off"]),
+                    bslab=bslab, bslab_stride=bslab_stride, bout_off=int(gd["bout_off"]), stats=stats,
+                    gamma=_at(gd["gamma"], kg) if gd["gamma"] else None, beta=_at(gd["beta"], kg) if gd["beta"] else None,
+                    stat_map=tuple(stat_map[:4]) + (int(gd["st_base"]),) if stats is not None else None,
+                    shift_rows=shift_rows, seq_div=seq_div, seq_len=seq_len,
                     g_off=g_off + int(gd["g_off"]), a_off=a_off + int(gd["a_off"]))
         return
     g = _gather(G, g_off, M, g_rows, Nn)
@@ -137,6 +143,8 @@ def gemm_tn(*, G, g_rows, A, a_rows, M, slab, slab_stride, nsplit, rows_per_spli
         s = (m // d1) * m1 + (m % d2) * m2 + base
         st = stats.reshape(-1, 2)
         a = (a - st[s, 0:1]) * st[s, 1:2] * gamma.reshape(-1)[:Kk] + beta.reshape(-1)[:Kk]
+        if shift_rows:  # the zeroed row is the OPERAND (both kernels select after the norm), not the raw load
+            a = a * ok.unsqueeze(1)
     sl = slab.reshape(-1)
     for sp in range(nsplit):
         lo, hi = sp * rows_per_split, min(M, (sp + 1) * rows_per_split)

@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gemm_contract as gc
+
 pytestmark = pytest.mark.gpu
 
 
@@ -520,7 +522,7 @@ def test_clip_adam_matches_reference_semantics():
 # ----------------------------------------------------------------------------------------------
 # GEMMs between the plain Z layout and the blocked layout BL (gemm_blk.hip)
 # ----------------------------------------------------------------------------------------------
-BLK_DIMS = [(2, 5, 11), (3, 32, 37)]   # (R, K, Tf): padded tiles in both views / full tiles in the time view
+BLK_DIMS = [(2, 5, 11), (3, 32, 37), (1, 1, 3), (5, 9, 33)]   # (R, K, Tf): padded tiles in both views / full tiles in the time view / one sequence / odd everything
 
 
 def _blk_setup(view, dims):
@@ -563,6 +565,9 @@ def test_gemm_p2b_vs_torch(view, dims, norm):
     assert not torch.isnan(C).any() and not torch.isnan(Ab).any()   # padded slots are written (zeros)
     ref = An.double() @ W.double().t() + b.double()
     assert rel(dev.from_blocked(C.view(nb, Nout // 4, 32, 4), seq, P), ref) < 4e-5
+    # element-wise, against eps * S with S = |A| @ |W|^T (+ |b|): the Frobenius ratio above would hide single elements
+    bound = gc.eps_for(True, N) * (An.double().abs() @ W.double().abs().t() + b.double().abs())
+    gc.assert_elementwise(dev.from_blocked(C.view(nb, Nout // 4, 32, 4), seq, P), ref, bound, "gemm_p2b")
     assert rel(dev.from_blocked(Ab.view(nb, N // 4, 32, 4), seq, P, split=True), An) < 1e-5   # BLS: 2^-17
     assert torch.equal(C.view(nb, Nout // 4, 32, 4), dev.to_blocked(dev.from_blocked(C.view(nb, Nout // 4, 32, 4), seq, P), seq))
 
@@ -587,12 +592,15 @@ def test_gemm_b2p_vs_torch(view, dims, Kd):
     assert torch.equal(outs[0], outs[1])
     ref = A.double() @ W.double().t() + b.double() + Rr.double()
     assert rel(outs[0], ref) < 4e-5
+    S = A.double().abs() @ W.double().abs().t()
+    gc.assert_elementwise(outs[0], ref, gc.eps_for(True, Kd) * (S + b.double().abs()) + gc.U * Rr.double().abs(), "gemm_b2p")
     # transposed packing (the data-gradient form): W'[n][k] = W2[k][n]
     W2 = W.t().contiguous()                       # [Kd][N]
     dev.pack_w(W2.to(d), N, Kd, N, wp, trans=True, order=1)
     C = torch.empty(P, N, device=d)
     dev.gemm_b2p(A=Ab, K=Kd, sm=seq, Wpack=wp, C_out=C, ldc=N)
     assert rel(C, A.double() @ W.double().t()) < 4e-5
+    gc.assert_elementwise(C, A.double() @ W.double().t(), gc.eps_for(True, Kd) * S, "gemm_b2p, transposed pack")
 
 
 @pytest.mark.parametrize("dims", BLK_DIMS)
@@ -631,6 +639,9 @@ def test_gemm_tnb_vs_torch(view, dims):
         Gs = G[:, g_off:g_off + g_cols].double()
         ref = torch.cat([Gs.t() @ A0.double(), Gs.t() @ A1s.double()], 1)
         assert rel(out, ref) < 4e-5
+        # element-wise: P rows summed per element (in splits, then the splits in fp32), S = |G|^T @ |A|
+        S = torch.cat([Gs.abs().t() @ A0.double().abs(), Gs.abs().t() @ A1s.double().abs()], 1)
+        gc.assert_elementwise(out, ref, gc.eps_for(True, P + ns) * S, "gemm_tnb")
         assert rel(bslab.sum(0), Gs.sum(0)) < 1e-5
         assert rel(aslab.sum(0), torch.cat([A0.double().sum(0), A1s.double().sum(0)])) < 1e-5
     # single A tile (dW_proj^T form): G = A1 (512 columns), A = A0
@@ -639,6 +650,8 @@ def test_gemm_tnb_vs_torch(view, dims):
     dev.gemm_tnb(G=A1b, g_width=512, g_off=0, g_cols=512, A0=A0b, a0_width=N, a0_off=0, a0_cols=N, nblk=nb,
                  L_=seq.L, slab=slab, nsplit=ns, blocks_per_split=bps, aslab=aslab)
     assert rel(slab.sum(0).view(512, 128), A1.double().t() @ A0.double()) < 4e-5
+    gc.assert_elementwise(slab.sum(0).view(512, 128), A1.double().t() @ A0.double(),
+                          gc.eps_for(True, P + ns) * (A1.double().abs().t() @ A0.double().abs()), "gemm_tnb, single A tile")
     assert rel(aslab.sum(0), A0.double().sum(0)) < 1e-5
 
 

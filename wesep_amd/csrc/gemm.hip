@@ -389,6 +389,10 @@ extern "C" int ws_gemm_tn(const ws_gemm_tn_args* a, void* stream) {
   WS_REQUIRE(a->g_div > 0 && a->a_div > 0, "ws_gemm_tn: bad row divisors");
   WS_REQUIRE(!a->stats || (a->st_div1 > 0 && a->st_div2 > 0), "ws_gemm_tn: bad stat divisors");
   WS_REQUIRE(a->shift_rows == 0 || (a->seq_div > 0 && a->seq_len > 0), "ws_gemm_tn: bad shift");
+  // a kept row m + shift_rows must lie in [0, M): the step test only sees the step index, so M holds whole sequences
+  WS_REQUIRE(a->shift_rows == 0 || a->M % ((long long)a->seq_div * a->seq_len) == 0,
+             "ws_gemm_tn: shift needs whole sequences, M %% (seq_div * seq_len) == 0 (M=%d seq_div=%d seq_len=%d)", a->M,
+             a->seq_div, a->seq_len);
   const int ng = a->groups ? a->ngroups : 1;
   const int maxn = a->groups ? a->max_n : a->Nn, maxk = a->groups ? a->max_k : a->Kk;
   WS_REQUIRE(ng > 0 && maxn > 0 && maxk > 0, "ws_gemm_tn: bad group dims");
