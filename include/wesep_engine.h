@@ -48,7 +48,8 @@ void ws_engine_destroy(ws_engine* e);
  * "feat_dim", "n_tensors", "n_launches" (entry-point calls issued by the last forward), "arena_bytes",
  * "cluster_fallbacks" (forwards so far in which a weight-stationary cluster recurrence timed out -- its workgroups were
  * not co-resident, e.g. several engines on one GPU -- and the predicated streaming kernels recomputed the layer;
- * wesep_hip.h, ws_lstm_fwd_cluster)}; unknown key -> -1. */
+ * wesep_hip.h, ws_lstm_fwd_cluster), "ragged_speaker" (1: enroll_lengths of ws_engine_separate_ragged run the speaker
+ * encoder once over all rows, 0: one row at a time)}; unknown key -> -1. */
 long long ws_engine_info(const ws_engine* e, const char* key);
 
 /* enrollment kinds */
@@ -70,8 +71,13 @@ int ws_engine_separate(ws_engine* e, const float* mix, int R, int T, const void*
  * reverse recurrence over time and the iSTFT envelope all end at the row's own end); est[r][lengths[r]..T) = 0; what the
  * caller left in mix[r][lengths[r]..T) is never read into a valid output (NaN included).
  * enroll_lengths (HOST int [R], or NULL = every row has enroll_len): valid samples (WS_ENROLL_WAVE) / frames
- * (WS_ENROLL_FBANK) of each enrollment row of pitch enroll_len.  The speaker encoder is not ragged: with enroll_lengths
- * it runs one enrollment at a time, then the separator runs once over all rows.
+ * (WS_ENROLL_FBANK) of each enrollment row of pitch enroll_len.  The speaker stage is ragged too: the ResNets and
+ * ECAPA-TDNN (TSTP / TAP / TSDP / ASTP pooling) run ONCE over all R enrollment rows -- every layer's input is exactly
+ * zero behind the row's own width, which follows the convolutions' geometry, and the reductions over time (pooling, the
+ * SE mean, CMN) take the row's length; each row gets the embedding it gets as a batch of one, and what the caller left
+ * behind enroll_lengths[r] never reaches it (NaN included).  ws_engine_info(e, "ragged_speaker") is 1 for such a
+ * container.  CAM++ and the MHASTP / MQMHASTP pools report 0 and run one enrollment at a time, as does every container
+ * with WS_ENGINE_RAGGED_SPK=0 in the environment; the separator runs once over all rows either way.
  * lengths = enroll_lengths = NULL is ws_engine_separate (any architecture); with either given, a Conv-TasNet, DPCCN or
  * TF-GridNet container is refused (WS_ERR_INVALID).  The time-view recurrences of a ragged call run over precomputed
  * gates (the rows' tails are zeroed there); the number of launches depends on (R, T) only, not on the lengths. */

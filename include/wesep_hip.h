@@ -1010,6 +1010,33 @@ typedef struct ws_heads_args {
 int ws_heads_fwd(const ws_heads_args* a, void* stream);
 int ws_heads_bwd(const ws_heads_args* a, void* stream);
 
+/* Ragged speaker stage (ragged_spk.hip): enrollments of different lengths in ONE encoder pass over the
+ * rectangle.  Invariant at the input of every layer: row r is exactly zero at time positions w >= W_r, its own valid
+ * width there -- a convolution at w < W_r' then reads what it reads on the row alone.  Length tables are device int[R];
+ * every kernel clamps the entries it reads so that none moves an access out of its row; a NULL table is WS_ERR_INVALID.
+ * Zeros are selected, not multiplied: NaN / Inf behind a row's end never reach a valid output.
+ *   ws_bn_prelu_fwd_len  ws_bn_prelu_fwd on rows [M][C]; row m belongs to r = m / rows_per_r and sits at w = m % W
+ *                        (W divides rows_per_r, rows_per_r divides M): u and y are zeros where w >= wlen[r], and bit for
+ *                        bit what ws_bn_prelu_fwd writes elsewhere; x and res are not read behind wlen[r]
+ *   ws_tstp_fwd_len      ws_tstp_fwd over t < tlen[r] (callers guarantee tlen[r] >= 2); F = 1: ASTP's global context
+ *   ws_astp_fwd_len      ws_astp_fwd with softmax, mean and second moment over t < tlen[r]
+ *   ws_time_mean_len     mean [R][C] over t < tlen[r] of x [R][T][C] (the SE squeeze)
+ *   ws_cmn_len           y[r][t][:] = t < tlen[r] ? x[r][t][:] - mean_r[:] : 0, mean_r over t < tlen[r]; y may be x
+ *   ws_tail_select_len   y[r][t][:] = t < tlen[r] ? x[r][t][:] : 0 on [R][T][C], C % 4 == 0; y may be x
+ *   ws_preemph_pad_len   ws_preemph_pad whose reflect padding turns at lengths[r] (clamped to (pad, T]); zeros from
+ *                        lengths[r] + 2 pad on; nothing behind lengths[r] is read */
+int ws_bn_prelu_fwd_len(const float* x, const float* stats, const float* gamma, const float* beta, const float* res,
+                        const float* a, long long M, int C, int rows_per_r, int W, const int* wlen, float* u, float* y,
+                        void* stream);
+int ws_tstp_fwd_len(const float* x, int R, int F, int T, int C, const int* tlen, float eps, float* stats, void* stream);
+int ws_astp_fwd_len(const float* x, const float* logits, int R, int T, int C, const int* tlen, float floor_, float* out,
+                    float* aux, void* stream);
+int ws_time_mean_len(const float* x, int R, int T, int C, const int* tlen, float* mean, void* stream);
+int ws_cmn_len(const float* x, int R, int T, int C, const int* tlen, float* y, void* stream);
+int ws_tail_select_len(const float* x, int R, int T, int C, const int* tlen, float* y, void* stream);
+int ws_preemph_pad_len(const float* x, int R, int T, int pad, int ldo, float coef, const int* lengths, float* out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

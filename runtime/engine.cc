@@ -330,6 +330,13 @@ WS_ENGINE_API int ws_engine_create(const char* weights_path, int device, int fla
   return WS_OK;
 }
 
+// WS_ENGINE_RAGGED_SPK=0: the speaker stage of a ragged call runs one enrollment at a time, as it did before the batched
+// pass existed (an escape hatch and a measurement arm, like WS_ENGINE_SERIALIZE)
+static bool ragged_speaker_enabled() {
+  static const bool on = !(getenv("WS_ENGINE_RAGGED_SPK") != nullptr && atoi(getenv("WS_ENGINE_RAGGED_SPK")) == 0);
+  return on;
+}
+
 WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   if (!e || !key) return -1;
   const std::string k(key);
@@ -340,6 +347,8 @@ WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   if (k == "nband") return e->bs.K;
   if (k == "arch") return e->arch;
   if (k == "spk_pool" && (e->arch == 0 || e->arch == 2)) return e->spk.pool;   // meta, or the encoder's default
+  // 1: enroll_lengths of ws_engine_separate_ragged run the speaker encoder once over all rows; 0: one row at a time
+  if (k == "ragged_speaker") return e->arch == 0 && ragged_speaker_covered(e) && ragged_speaker_enabled() ? 1 : 0;
   auto it = e->meta.find(k);
   return it == e->meta.end() ? -1 : it->second;
 }
@@ -479,9 +488,14 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
   }
   if (enroll_kind == WS_ENROLL_EMBEDDING) {
     if ((rc = to_device(e, d_emb, enroll, size_t(R) * e->E * 4)) != WS_OK) return rc;
+  } else if (enroll_lengths && ragged_speaker_covered(e) && ragged_speaker_enabled()) {
+    // one encoder pass over all rows: masked epilogues keep every row zero behind its own frames, the reductions over
+    // time take the row's length (speaker.cc)
+    if ((rc = speaker_embed(e, enroll, enroll_kind, R, enroll_len, Te, d_emb, enroll_lengths, te_row.data())) != WS_OK) return rc;
   } else if (enroll_lengths) {
-    // the speaker stage is not ragged: one enrollment at a time into the [R][E] buffer (its convolutions then pad with
-    // zeros at the row's true end and its pooling sees the row's own frames), then the separator once over all rows
+    // CAM++, the attentive multi-head pools, WS_ENGINE_RAGGED_SPK=0: one enrollment at a time into the [R][E] buffer
+    // (its convolutions then pad with zeros at the row's true end and its pooling sees the row's own frames), then the
+    // separator once over all rows
     const size_t pitch = size_t(enroll_len) * (enroll_kind == WS_ENROLL_FBANK ? e->spk.feat_dim : 1);
     for (int r = 0; r < R; ++r)
       if ((rc = speaker_embed(e, static_cast<const float*>(enroll) + r * pitch, enroll_kind, 1, enroll_lengths[r], te_row[r],

@@ -292,6 +292,8 @@ struct ws_engine {
   int arch = 0;                   // 0 pBSRNN, 1 Conv-TasNet, 2 DPCCN, 3 TF-GridNet
   int sr = 16000, E = 256, use_xform = 0, joint = 0;
   float *id_st = nullptr, *id_one = nullptr, *id_zero = nullptr;   // identity BatchNorm operands: y = x + res
+  // ragged speaker pass (speaker.cc): device int[R] tables of this forward, one per distinct set of per-row widths
+  std::vector<std::pair<std::vector<int>, const int*>> spk_tabs;
   float *slope0 = nullptr, *slope1 = nullptr;     // PReLU slopes 0 (ReLU) and 1 (identity)
   // the parts
   wsrt::SpeakerEncoder spk;
@@ -350,7 +352,11 @@ int time_mean(ws_engine* e, const float* x, int R, int T, int C, float* mean2);
 int read_speaker_meta(ws_engine* e);
 int prep_spk_transform(ws_engine* e);
 int prep_speaker(ws_engine* e);
-int speaker_embed(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, int Te, float* emb);
+// enroll_lengths / te_row (host, [R]; both or neither): the rows' own samples or frames and their frame counts -- one
+// encoder pass over the rectangle with masked epilogues and length-aware reductions (ragged_speaker_covered encoders only)
+int speaker_embed(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, int Te, float* emb,
+                  const int* enroll_lengths = nullptr, const int* te_row = nullptr);
+bool ragged_speaker_covered(const ws_engine* e);
 int spk_transform(ws_engine* e, const float* emb, int R, const float** out);
 
 // ---- launch plans ----

@@ -2,7 +2,7 @@
 // runtime/bin/separate_main.cc:24-115:
 //
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
-//                 [--batch 8] [--dry_run]
+//                 [--batch 8] [--sort_by_length] [--dry_run]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -15,13 +15,18 @@
 // --batch N (default 1 = the path above; pBSRNN models): N consecutive lines of the scp go through ONE forward of 2 N rows
 // (ws_engine_separate_ragged: every row keeps its own length, every enrollment its own -- each cut to the shorter of its
 // pair as above -- so the estimates are those of --batch 1); same output names and formats; works with --jobs (a worker
-// takes the next N lines) and --dry_run.  No sorting or bucketing: the rectangle is as long as the longest of the N.
+// takes the next N lines) and --dry_run.  The rectangle is as long as the longest of the N.
+// --sort_by_length (off by default; with --batch N): the scp lines are ordered by the mixture's sample count, longest
+// first (stable), before they are grouped N at a time, so a rectangle holds rows of similar length.  The counts come from
+// the wav headers (no file is loaded for it).  Outputs are still named by key and the total is unchanged; the "process:"
+// lines appear in processing order.  Without --batch the flag is accepted and changes nothing.
 // --dry_run validates the model file and the launch plan of every utterance without a GPU and writes nothing.
 // --raw_out additionally writes the unquantised estimates as <key>-spk{1,2}.f32 (float32, for parity checks).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <fstream>
@@ -109,6 +114,27 @@ int main(int argc, char** argv) {
   if (jobs < 1) jobs = 1;
   const int batch = atoi(args.get("batch", "1").c_str());
   if (batch < 1) return die("--batch needs a positive count");
+  if (args.has("help")) {
+    printf("usage: separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1]\n"
+           "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
+           "  --batch N          N scp lines per forward (pBSRNN models), every row at its own length\n"
+           "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
+           "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
+           "                     is accepted and changes nothing\n");
+    return 0;
+  }
+  if (args.has("sort_by_length") && batch > 1) {
+    std::vector<size_t> count(waves.size()), order(waves.size());
+    for (size_t i = 0; i < waves.size(); ++i) {
+      std::string err;
+      if (!wesep_rt::peek_wav_frames(waves[i][1], &count[i], &err)) return die(err);
+      order[i] = i;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return count[a] > count[b]; });
+    std::vector<std::vector<std::string>> sorted;
+    for (size_t i : order) sorted.push_back(waves[i]);
+    waves.swap(sorted);
+  }
   const size_t ngroups = (waves.size() + batch - 1) / batch;
   if (jobs > static_cast<int>(ngroups)) jobs = static_cast<int>(ngroups);
 

@@ -111,6 +111,30 @@ int prep_pool(ws_engine* e, const std::string& prefix, int Fp, int C, int glob) 
   }
 }
 
+// ---- ragged pass: per-row widths -------------------------------------------------------------------
+// The device table of a set of per-row widths; speaker_embed uploads every set of the forward before the first launch
+const int* len_tab(ws_engine* e, const std::vector<int>& w) {
+  for (const auto& t : e->spk_tabs)
+    if (t.first == w) return t.second;
+  set_err("engine: no device table for a per-row width set of the ragged speaker pass");
+  return nullptr;
+}
+
+// a row's width after a convolution along time: (W + 2p - k) / s + 1 with the layer's own k, p, s
+std::vector<int> conv_widths(const std::vector<int>& w, int k, int s, int p) {
+  std::vector<int> o(w.size());
+  for (size_t i = 0; i < w.size(); ++i) o[i] = (w[i] + 2 * p - k) / s + 1;
+  return o;
+}
+
+// which encoders run the batched ragged pass: the ResNets and ECAPA-TDNN with TSTP / TAP / TSDP / ASTP.  CAM++ and the
+// attentive multi-head pools keep one enrollment at a time
+bool ragged_speaker_covered(const ws_engine* e) {
+  if (!e->joint || e->spk.kind > 1) return false;
+  const int p = e->spk.pool;
+  return p == kPoolTSTP || p == kPoolTAP || p == kPoolTSDP || (e->spk.kind == 1 && p == kPoolASTP);
+}
+
 // width of the pooled statistics of [R][F'][T][C]
 int pool_width(const ws_engine* e, int Fp, int C) {
   const int P = Fp * C;
@@ -122,8 +146,15 @@ int pool_width(const ws_engine* e, int Fp, int C) {
 // the pooling layer's forward: x [R][F'][T][C] -> pooled [R][pool_width].  TSTP: ws_tstp_fwd; TAP / TSDP: one half of the
 // TSTP statistics; ASTP: the attention MLP, then ws_astp_fwd; MHASTP / MQMHASTP: the ResNets' single ws_mhastp_fwd
 // launch, the 1-D encoders' ws_mhastp_fwd_split (two launches, the grid split over T)
-int run_pool(ws_engine* e, const std::string& prefix, const float* x, int R, int Fp, int T, int C, int glob, float* pooled) {
+// tl: the rows' valid frames (ragged pass; TSTP / TAP / TSDP / ASTP only) or nullptr
+int run_pool(ws_engine* e, const std::string& prefix, const float* x, int R, int Fp, int T, int C, int glob, float* pooled,
+             const std::vector<int>* tl = nullptr) {
   const int B = 128;
+  const int* tab = nullptr;
+  if (tl) {
+    if (e->spk.pool == kPoolMHASTP || e->spk.pool == kPoolMQMHASTP) return no_pool_plan(e);
+    WS_PTR(tab = len_tab(e, *tl));
+  }
   const long long M = (long long)R * T;
   void* s = e->stream;
   Arena& a = e->work;
@@ -131,14 +162,20 @@ int run_pool(ws_engine* e, const std::string& prefix, const float* x, int R, int
   int rc;
   switch (e->spk.pool) {
     case kPoolTSTP:
-      WS_RUN(e, ws_tstp_fwd(x, R, Fp, T, C, kTstpEps, pooled, s));
+      if (tab)
+        WS_RUN(e, ws_tstp_fwd_len(x, R, Fp, T, C, tab, kTstpEps, pooled, s));
+      else
+        WS_RUN(e, ws_tstp_fwd(x, R, Fp, T, C, kTstpEps, pooled, s));
       break;
     case kPoolTAP:
     case kPoolTSDP: {         // mean || std, keep one half
       const int P = Fp * C;
       float* st = a.alloc(size_t(R) * 2 * P);
       WS_PTR(st);
-      WS_RUN(e, ws_tstp_fwd(x, R, Fp, T, C, kTstpEps, st, s));
+      if (tab)
+        WS_RUN(e, ws_tstp_fwd_len(x, R, Fp, T, C, tab, kTstpEps, st, s));
+      else
+        WS_RUN(e, ws_tstp_fwd(x, R, Fp, T, C, kTstpEps, st, s));
       if ((rc = copy_cols(e, pooled, P, st + (e->spk.pool == kPoolTSDP ? P : 0), 2 * P, P, R)) != WS_OK) return rc;
       break;
     }
@@ -155,7 +192,10 @@ int run_pool(ws_engine* e, const std::string& prefix, const float* x, int R, int
         float* ctx = a.alloc(size_t(R) * 2 * C);
         float* rb = a.alloc(size_t(R) * B);
         WS_PTR(ctx && rb);
-        WS_RUN(e, ws_tstp_fwd(x, R, 1, T, C, kTstpEps, ctx, s));
+        if (tab)
+          WS_RUN(e, ws_tstp_fwd_len(x, R, 1, T, C, tab, kTstpEps, ctx, s));
+        else
+          WS_RUN(e, ws_tstp_fwd(x, R, 1, T, C, kTstpEps, ctx, s));
         if ((rc = linear(e, ctx, R, 2 * C, W1 + C, 3 * C, B, e->dev(prefix + "linear1.bias"), 0, rb)) != WS_OK) return rc;
         if ((rc = linear(e, x, static_cast<int>(M), C, W1, 3 * C, B, nullptr, 0, att)) != WS_OK) return rc;
         rowbias = rb;
@@ -166,7 +206,10 @@ int run_pool(ws_engine* e, const std::string& prefix, const float* x, int R, int
       if ((rc = linear(e, att, static_cast<int>(M), B, e->dev(prefix + "linear2.weight"), B, C, e->dev(prefix + "linear2.bias"),
                        0, logits)) != WS_OK)
         return rc;
-      WS_RUN(e, ws_astp_fwd(x, logits, R, T, C, kAstpFloor, pooled, aux, s));
+      if (tab)
+        WS_RUN(e, ws_astp_fwd_len(x, logits, R, T, C, tab, kAstpFloor, pooled, aux, s));
+      else
+        WS_RUN(e, ws_astp_fwd(x, logits, R, T, C, kAstpFloor, pooled, aux, s));
       break;
     }
     default: {                // MHASTP / MQMHASTP
@@ -552,8 +595,10 @@ int read_speaker_meta(ws_engine* e) {
 // conv + BatchNorm(eval) + ReLU/identity (+ residual), channels-last (functional_resnet.py:15-46).  The convolution is
 // one GEMM on the implicit patch matrix of x (ws_conv_view, nothing materialised); the 1-channel stem, whose patch
 // rows are not float4-addressable, writes its 9-column patch matrix with ws_im2col first.
+// win / wout (ragged pass): the rows' valid widths of x, which is zero behind them, and of y, whose tail the masked
+// epilogue selects to zero again.
 int conv_bn_act(ws_engine* e, const ConvPrep& c, const float* x, const float* res, int R, int H, int W, float* y,
-                int* Ho_out, int* Wo_out) {
+                int* Ho_out, int* Wo_out, const std::vector<int>* win = nullptr, std::vector<int>* wout = nullptr) {
   const int pad = c.k / 2, sw = c.sw ? c.sw : c.stride;
   const int Ho = (H + 2 * pad - c.k) / c.stride + 1, Wo = (W + 2 * pad - c.k) / sw + 1;
   const long long M = (long long)R * Ho * Wo;
@@ -587,7 +632,15 @@ int conv_bn_act(ws_engine* e, const ConvPrep& c, const float* x, const float* re
     g.A = patches;
   }
   WS_RUN(e, ws_gemm_nt(&g, s));
-  WS_RUN(e, ws_bn_prelu_fwd(conv, c.st, c.gamma, c.beta, res, c.relu ? e->slope0 : e->slope1, M, c.cout, u, y, s));
+  if (win) {
+    *wout = conv_widths(*win, c.k, sw, pad);
+    const int* tab = len_tab(e, *wout);
+    WS_PTR(tab);
+    WS_RUN(e, ws_bn_prelu_fwd_len(conv, c.st, c.gamma, c.beta, res, c.relu ? e->slope0 : e->slope1, M, c.cout, Ho * Wo, Wo,
+                                  tab, u, y, s));
+  } else {
+    WS_RUN(e, ws_bn_prelu_fwd(conv, c.st, c.gamma, c.beta, res, c.relu ? e->slope0 : e->slope1, M, c.cout, u, y, s));
+  }
   a.release(mk);
   *Ho_out = Ho;
   *Wo_out = Wo;
@@ -596,7 +649,8 @@ int conv_bn_act(ws_engine* e, const ConvPrep& c, const float* x, const float* re
 
 // fbank [R][Te][F] (device) -> embedding [R][E]   (wespeaker ResNet, eval mode; models/resnet.py: BasicBlock and
 // Bottleneck stacks, TSTP, one or two embedding layers)
-int resnet_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
+// tl (ragged pass): the rows' valid frames; fbank is zero behind them
+int resnet_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb, const std::vector<int>* tl) {
   const int F = e->spk.feat_dim, ex = e->spk.bottleneck ? 4 : 1;
   void* s = e->stream;
   Arena& a = e->work;
@@ -612,7 +666,12 @@ int resnet_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
   float* bufs[4] = {a.alloc(act), a.alloc(act), a.alloc(act), nullptr};
   bufs[3] = e->spk.bottleneck ? a.alloc(act) : bufs[0];        // BasicBlock stacks rotate through three
   WS_PTR(bufs[0] && bufs[1] && bufs[2] && bufs[3]);
-  if ((rc = conv_bn_act(e, e->spk.stem, x, nullptr, R, H, W, bufs[0], &Ho, &Wo)) != WS_OK) return rc;
+  // per-row widths of the block input (w), of the block's intermediate tensors and of its shortcut
+  std::vector<int> w, w1, w2, ws;
+  const std::vector<int>* in = tl;
+  auto out = [&](std::vector<int>* v) { return tl ? v : nullptr; };
+  if ((rc = conv_bn_act(e, e->spk.stem, x, nullptr, R, H, W, bufs[0], &Ho, &Wo, in, out(&w))) != WS_OK) return rc;
+  in = out(&w);
   int cur = 0, C = 32;
   for (const BlockPrep& b : e->spk.res_blocks) {
     float* y = bufs[cur];
@@ -622,25 +681,25 @@ int resnet_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
     int H1, W1, H2, W2, Hs, Ws;
     const float* shortcut = y;
     if (e->spk.bottleneck) {
-      if ((rc = conv_bn_act(e, b.c1, y, nullptr, R, H, W, t1, &H1, &W1)) != WS_OK) return rc;
-      if ((rc = conv_bn_act(e, b.c2, t1, nullptr, R, H1, W1, t2, &H2, &W2)) != WS_OK) return rc;
+      if ((rc = conv_bn_act(e, b.c1, y, nullptr, R, H, W, t1, &H1, &W1, in, out(&w1))) != WS_OK) return rc;
+      if ((rc = conv_bn_act(e, b.c2, t1, nullptr, R, H1, W1, t2, &H2, &W2, out(&w1), out(&w2))) != WS_OK) return rc;
       if (b.has_sc) {
-        if ((rc = conv_bn_act(e, b.sc, y, nullptr, R, H, W, t1, &Hs, &Ws)) != WS_OK) return rc;
+        if ((rc = conv_bn_act(e, b.sc, y, nullptr, R, H, W, t1, &Hs, &Ws, in, out(&ws))) != WS_OK) return rc;
         shortcut = t1;
       }
-      if ((rc = conv_bn_act(e, b.c3, t2, shortcut, R, H2, W2, t3, &H2, &W2)) != WS_OK) return rc;
+      if ((rc = conv_bn_act(e, b.c3, t2, shortcut, R, H2, W2, t3, &H2, &W2, out(&w2), out(&w))) != WS_OK) return rc;
       cur = (cur + 3) % 4;
       C = b.c3.cout;
     } else {                     // three of the buffers: conv2 writes over the block input unless that is the shortcut
       float* o = bufs[(cur + 1) % 3];
       float* sc = bufs[(cur + 2) % 3];
-      if ((rc = conv_bn_act(e, b.c1, y, nullptr, R, H, W, o, &H1, &W1)) != WS_OK) return rc;
+      if ((rc = conv_bn_act(e, b.c1, y, nullptr, R, H, W, o, &H1, &W1, in, out(&w1))) != WS_OK) return rc;
       if (b.has_sc) {
-        if ((rc = conv_bn_act(e, b.sc, y, nullptr, R, H, W, sc, &Hs, &Ws)) != WS_OK) return rc;
+        if ((rc = conv_bn_act(e, b.sc, y, nullptr, R, H, W, sc, &Hs, &Ws, in, out(&ws))) != WS_OK) return rc;
         shortcut = sc;
       }
       float* dst = b.has_sc ? y : sc;
-      if ((rc = conv_bn_act(e, b.c2, o, shortcut, R, H1, W1, dst, &H2, &W2)) != WS_OK) return rc;
+      if ((rc = conv_bn_act(e, b.c2, o, shortcut, R, H1, W1, dst, &H2, &W2, out(&w1), out(&w))) != WS_OK) return rc;
       cur = b.has_sc ? cur : (cur + 2) % 3;
       C = b.c2.cout;
     }
@@ -650,7 +709,7 @@ int resnet_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
   const int pooled = pool_width(e, H, C);
   float* stats = a.alloc(size_t(R) * pooled);
   WS_PTR(stats);
-  if ((rc = run_pool(e, p + "pool.", bufs[cur], R, H, W, C, 0, stats)) != WS_OK) return rc;
+  if ((rc = run_pool(e, p + "pool.", bufs[cur], R, H, W, C, 0, stats, in)) != WS_OK) return rc;
   if (!e->spk.two_emb) {
     rc = linear(e, stats, R, pooled, e->dev(p + "seg_1.weight"), pooled, e->E, e->dev(p + "seg_1.bias"), 0, emb);
   } else {
@@ -668,14 +727,21 @@ int resnet_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
 }
 
 // y = x + res on [M][c] (c <= spk_channels): the BatchNorm kernel with identity operands
-int add_rows(ws_engine* e, const float* x, const float* res, long long M, int c, float* scratch, float* y) {
-  WS_RUN(e, ws_bn_prelu_fwd(x, e->id_st + (e->spk.channels - c), e->id_one, e->id_zero, res, e->slope1, M, c, scratch, y,
-                            e->stream));
+// (T, tab: the ragged pass -- rows of T frames, zeros selected behind tab[r])
+int add_rows(ws_engine* e, const float* x, const float* res, long long M, int c, float* scratch, float* y, int T = 0,
+             const int* tab = nullptr) {
+  if (tab)
+    WS_RUN(e, ws_bn_prelu_fwd_len(x, e->id_st + (e->spk.channels - c), e->id_one, e->id_zero, res, e->slope1, M, c, T, T, tab,
+                                  scratch, y, e->stream));
+  else
+    WS_RUN(e, ws_bn_prelu_fwd(x, e->id_st + (e->spk.channels - c), e->id_one, e->id_zero, res, e->slope1, M, c, scratch, y,
+                              e->stream));
   return WS_OK;
 }
 
 // y [M][cout] = BN(ReLU(conv1d(x [R][T][cin]))), x rows lda apart (k == 1) or dense (k > 1)   (functional_ecapa.py:23-51)
-int tdnn(ws_engine* e, const TdnnPrep& t, const float* x, long long lda, int R, int T, float* y) {
+// tab (ragged pass): x is zero behind tab[r] frames of row r, and so is y ('same' padding: the widths never change)
+int tdnn(ws_engine* e, const TdnnPrep& t, const float* x, long long lda, int R, int T, float* y, const int* tab = nullptr) {
   const long long M = (long long)R * T;
   void* s = e->stream;
   Arena& a = e->work;
@@ -695,13 +761,16 @@ int tdnn(ws_engine* e, const TdnnPrep& t, const float* x, long long lda, int R, 
     g.conv.k = t.k, g.conv.sh = 1, g.conv.sw = 1, g.conv.p = t.dil * (t.k / 2), g.conv.dil = t.dil;
   }
   WS_RUN(e, ws_gemm_nt(&g, s));
-  WS_RUN(e, ws_bn_prelu_fwd(c, t.st, t.gamma, t.beta, nullptr, e->slope1, M, t.cout, u, y, s));
+  if (tab)
+    WS_RUN(e, ws_bn_prelu_fwd_len(c, t.st, t.gamma, t.beta, nullptr, e->slope1, M, t.cout, T, T, tab, u, y, s));
+  else
+    WS_RUN(e, ws_bn_prelu_fwd(c, t.st, t.gamma, t.beta, nullptr, e->slope1, M, t.cout, u, y, s));
   a.release(mk);
   return WS_OK;
 }
 
 // SE_Res2Block (models/ecapa_tdnn.py:78-92): x [M][C] dense -> out [M][C] dense
-int se_res2_block(ws_engine* e, const SeRes2Prep& b, const float* x, int R, int T, float* out) {
+int se_res2_block(ws_engine* e, const SeRes2Prep& b, const float* x, int R, int T, float* out, const int* tab = nullptr) {
   const int C = e->spk.channels, scale = 8, w = C / scale, B = 128;
   const long long M = (long long)R * T;
   void* s = e->stream;
@@ -715,29 +784,32 @@ int se_res2_block(ws_engine* e, const SeRes2Prep& b, const float* x, int R, int 
   float* scratch = a.alloc(size_t(M) * C);
   WS_PTR(h && r2 && slice && in && y && scratch);
   int rc;
-  if ((rc = tdnn(e, b.in, x, C, R, T, h)) != WS_OK) return rc;
+  if ((rc = tdnn(e, b.in, x, C, R, T, h, tab)) != WS_OK) return rc;
   for (int i = 0; i < scale - 1; ++i) {       // group i >= 1 adds the previous group's output before its own TDNN
     const float* src = slice;
     if ((rc = copy_cols(e, slice, w, h + size_t(i) * w, C, w, M)) != WS_OK) return rc;
     if (i > 0) {
-      if ((rc = add_rows(e, y, slice, M, w, scratch, in)) != WS_OK) return rc;
+      if ((rc = add_rows(e, y, slice, M, w, scratch, in, T, tab)) != WS_OK) return rc;
       src = in;
     }
-    if ((rc = tdnn(e, b.branch[i], src, w, R, T, y)) != WS_OK) return rc;
+    if ((rc = tdnn(e, b.branch[i], src, w, R, T, y, tab)) != WS_OK) return rc;
     if ((rc = copy_cols(e, r2 + size_t(i) * w, C, y, w, w, M)) != WS_OK) return rc;
   }
   if ((rc = copy_cols(e, r2 + size_t(scale - 1) * w, C, h + size_t(scale - 1) * w, C, w, M)) != WS_OK) return rc;
-  if ((rc = tdnn(e, b.out, r2, C, R, T, h)) != WS_OK) return rc;
+  if ((rc = tdnn(e, b.out, r2, C, R, T, h, tab)) != WS_OK) return rc;
   // squeeze-excitation: gate [R][C] = sigmoid(W2 relu(W1 mean_t + b1) + b2), broadcast over the frames
   float* mean2 = a.alloc(size_t(R) * 2 * C);
   float* z = a.alloc(size_t(R) * B);
   float* gate = a.alloc(size_t(R) * C);
   WS_PTR(mean2 && z && gate);
-  if ((rc = time_mean(e, h, R, T, C, mean2)) != WS_OK) return rc;
+  if (tab)                                     // the mean over the row's own frames, dense [R][C]
+    WS_RUN(e, ws_time_mean_len(h, R, T, C, tab, mean2, s));
+  else if ((rc = time_mean(e, h, R, T, C, mean2)) != WS_OK)
+    return rc;
   {
     ws_gemm_nt_args g = {};
     g.A = mean2, g.W = e->dev(b.se + "linear1.weight"), g.bias = e->dev(b.se + "linear1.bias"), g.C = z;
-    g.a_div = kBig, g.a_s2 = 2 * C, g.c_div = kBig, g.c_s2 = B, g.st_div1 = 1, g.st_div2 = 1;
+    g.a_div = kBig, g.a_s2 = tab ? C : 2 * C, g.c_div = kBig, g.c_s2 = B, g.st_div1 = 1, g.st_div2 = 1;
     g.M = R, g.N = B, g.K = C, g.ldw = C, g.act = 2, g.vec = 3 | 4;
     WS_RUN(e, ws_gemm_nt(&g, s));
   }
@@ -747,13 +819,14 @@ int se_res2_block(ws_engine* e, const SeRes2Prep& b, const float* x, int R, int 
   WS_RUN(e, ws_bcast_rows(gate, 1.0f, T, M, C, r2, s));
   WS_RUN(e, ws_maskmul_fwd(h, C, r2, M, C, scratch, s));
   float* u = r2;                               // free again: pre-activation scratch of the residual add
-  if ((rc = add_rows(e, scratch, x, M, C, u, out)) != WS_OK) return rc;
+  if ((rc = add_rows(e, scratch, x, M, C, u, out, T, tab)) != WS_OK) return rc;   // the gated sum's tail selected to zero
   a.release(mk);
   return WS_OK;
 }
 
 // fbank [R][Te][F] (device) -> embedding [R][E]   (wespeaker ECAPA-TDNN, eval mode; models/ecapa_tdnn.py:135-160)
-int ecapa_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
+// tl (ragged pass): the rows' valid frames; fbank is zero behind them
+int ecapa_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb, const std::vector<int>* tl) {
   const int C = e->spk.channels, P = 1536, T = Te;
   const long long M = (long long)R * T;
   const std::string p = "spk_model.";
@@ -765,9 +838,11 @@ int ecapa_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
   float* cat = a.alloc(size_t(M) * 3 * C);
   WS_PTR(cur && nxt && cat);
   int rc;
-  if ((rc = tdnn(e, e->spk.tdnn1, fbank, e->spk.feat_dim, R, T, cur)) != WS_OK) return rc;
+  const int* tab = nullptr;
+  if (tl) WS_PTR(tab = len_tab(e, *tl));
+  if ((rc = tdnn(e, e->spk.tdnn1, fbank, e->spk.feat_dim, R, T, cur, tab)) != WS_OK) return rc;
   for (int li = 0; li < 3; ++li) {
-    if ((rc = se_res2_block(e, e->spk.se_blocks[li], cur, R, T, nxt)) != WS_OK) return rc;
+    if ((rc = se_res2_block(e, e->spk.se_blocks[li], cur, R, T, nxt, tab)) != WS_OK) return rc;
     if ((rc = copy_cols(e, cat + size_t(li) * C, 3 * C, nxt, C, C, M)) != WS_OK) return rc;
     std::swap(cur, nxt);
   }
@@ -779,7 +854,7 @@ int ecapa_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
   WS_PTR(h && pooled && normed && u);
   if ((rc = linear(e, cat, static_cast<int>(M), 3 * C, e->dev(p + "conv.weight"), 3 * C, P, e->dev(p + "conv.bias"), 2, h)) != WS_OK)
     return rc;
-  if ((rc = run_pool(e, p + "pool.", h, R, 1, T, P, e->spk.glob, pooled)) != WS_OK) return rc;
+  if ((rc = run_pool(e, p + "pool.", h, R, 1, T, P, e->spk.glob, pooled, tl)) != WS_OK) return rc;
   WS_RUN(e, ws_bn_prelu_fwd(pooled, e->spk.pool_bn_st, e->dev(p + "bn.weight"), e->dev(p + "bn.bias"), nullptr, e->slope1, R,
                             D, u, normed, s));
   if (e->spk.emb_bn) {
@@ -886,7 +961,11 @@ int cam_layer(ws_engine* e, const CamLayer& l, float* cat, long long ld, int R, 
 }
 
 // fbank [R][Te][F] (device) -> embedding [R][E]   (wespeaker CAMPPlus, eval mode; models/campplus.py:225-262)
-int campplus_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb) {
+int campplus_embed(ws_engine* e, const float* fbank, int R, int Te, float* emb, const std::vector<int>* tl) {
+  if (tl) {
+    set_err("engine: CAM++ has no ragged pass (one enrollment at a time)");
+    return WS_ERR_INVALID;
+  }
   const int F = e->spk.feat_dim, mc = 32;
   void* s = e->stream;
   Arena& a = e->work;
@@ -1008,7 +1087,9 @@ int subtract_time_mean(ws_engine* e, float* feats, int R, int Te, int nb) {
 
 // waveform [R][Tw] in [-1, 1] (device) -> mean-normalised kaldi fbank [R][Te][F]  (utils/funcs.py compute_fbank +
 // apply_cmvn with dither 0; reference: SeparateEngine::ExtractFeature, separate_engine.cc:53-74)
-int kaldi_fbank(ws_engine* e, const float* wav, int R, int Tw, float* feats, int Te) {
+// te_tab (ragged pass, device int[R]): the rows' own frame counts.  With snip-edges framing frame f < te_tab[r] reads only
+// samples below the row's length, so the GEMMs run over the rectangle; CMN over the row's frames, the tail zeroed
+int kaldi_fbank(ws_engine* e, const float* wav, int R, int Tw, float* feats, int Te, const int* te_tab = nullptr) {
   const int win = e->spk.fb_win, shift = e->spk.fb_shift, nf = e->spk.fb_padded / 2, nb = e->spk.feat_dim;
   const long long M = (long long)R * Te;
   void* s = e->stream;
@@ -1034,7 +1115,9 @@ int kaldi_fbank(ws_engine* e, const float* wav, int R, int Tw, float* feats, int
   // log(max(x, eps)) = log(relu(x - eps) + eps)
   WS_RUN(e, ws_prelu_fwd(mel, e->spk.fb_floor, e->slope0, M, nb, static_cast<int>(M), feats, s));
   WS_RUN(e, ws_log_eps(feats, M * nb, kGnEps, s));
-  {
+  if (te_tab) {
+    WS_RUN(e, ws_cmn_len(feats, R, Te, nb, te_tab, feats, s));
+  } else {
     const int rc = subtract_time_mean(e, feats, R, Te, nb);
     if (rc != WS_OK) return rc;
   }
@@ -1044,7 +1127,10 @@ int kaldi_fbank(ws_engine* e, const float* wav, int R, int Tw, float* feats, int
 
 // waveform [R][Tw] (device) -> log-mel features [R][Te][F], mean-normalised over time: the in-model front-end of
 // spk_feat = False models (bsrnn.py:343-350; modules/common/frontend.py fbank_frontend); Te = 1 + Tw / 128
-int mel_frontend(ws_engine* e, const float* wav, int R, int Tw, float* feats, int Te) {
+// len_tab_ / te_tab (ragged pass, device int[R]): the rows' samples and frames 1 + n / 128 -- the reflect padding turns at
+// the row's own end, CMN runs over the row's frames, the tail is zeroed
+int mel_frontend(ws_engine* e, const float* wav, int R, int Tw, float* feats, int Te, const int* len_tab_ = nullptr,
+                 const int* te_tab = nullptr) {
   const int n = 512, hop = kHop, pad = n / 2, nf = n / 2 + 1, nm = e->spk.feat_dim;
   const int ldo = (Tw + 2 * pad + 3) / 4 * 4;
   const long long M = (long long)R * Te;
@@ -1057,7 +1143,10 @@ int mel_frontend(ws_engine* e, const float* wav, int R, int Tw, float* feats, in
   WS_PTR(xp && spec && power);
   int rc = zero_device(e, xp, size_t(R) * ldo * 4);
   if (rc != WS_OK) return rc;
-  WS_RUN(e, ws_preemph_pad(wav, R, Tw, pad, ldo, e->spk.mel_coef, xp, s));
+  if (len_tab_)
+    WS_RUN(e, ws_preemph_pad_len(wav, R, Tw, pad, ldo, e->spk.mel_coef, len_tab_, xp, s));
+  else
+    WS_RUN(e, ws_preemph_pad(wav, R, Tw, pad, ldo, e->spk.mel_coef, xp, s));
   ws_gemm_nt_args g = {};
   g.A = xp, g.W = e->spk.mel_basis, g.C = spec;
   g.a_div = Te, g.a_s1 = ldo, g.a_s2 = hop;             // centred frames as an overlapping row view
@@ -1071,7 +1160,10 @@ int mel_frontend(ws_engine* e, const float* wav, int R, int Tw, float* feats, in
   h.M = static_cast<int>(M), h.N = nm, h.K = e->spk.mel_ldp, h.ldw = e->spk.mel_ldp, h.vec = 3;
   WS_RUN(e, ws_gemm_nt(&h, s));
   WS_RUN(e, ws_log_eps(feats, M * nm, 1e-8f, s));
-  if ((rc = subtract_time_mean(e, feats, R, Te, nm)) != WS_OK) return rc;
+  if (te_tab)
+    WS_RUN(e, ws_cmn_len(feats, R, Te, nm, te_tab, feats, s));
+  else if ((rc = subtract_time_mean(e, feats, R, Te, nm)) != WS_OK)
+    return rc;
   a.release(mk);
   return WS_OK;
 }
@@ -1101,7 +1193,7 @@ int spk_transform(ws_engine* e, const float* emb, int R, const float** out) {
 // ---- the speaker stage as the separator plans see it -------------------------------------------------------------
 struct EncoderPlan {        // per meta spk_kind
   int (*prep)(ws_engine* e);
-  int (*embed)(ws_engine* e, const float* fbank, int R, int Te, float* emb);
+  int (*embed)(ws_engine* e, const float* fbank, int R, int Te, float* emb, const std::vector<int>* tl);
 };
 const EncoderPlan kEncoders[3] = {{prep_resnet, resnet_embed}, {prep_ecapa, ecapa_embed}, {prep_campplus, campplus_embed}};
 
@@ -1125,24 +1217,55 @@ int prep_speaker(ws_engine* e) {
 }
 
 // enrollment -> embedding emb [R][E] (device): enroll is the host fbank [R][Te][F] (WS_ENROLL_FBANK) or waveform
-// [R][enroll_len] (WS_ENROLL_WAVE, through the model's front-end to Te frames)
-int speaker_embed(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, int Te, float* emb) {
+// [R][enroll_len] (WS_ENROLL_WAVE, through the model's front-end to Te frames).  enroll_lengths / te_row: the ragged pass --
+// every row's own length and frame count; the rectangle's tail may hold anything (it is selected away, never multiplied)
+int speaker_embed(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, int Te, float* emb,
+                  const int* enroll_lengths, const int* te_row) {
   Arena& a = e->work;
   const Arena::Mark mk = a.mark();
   int rc;
+  const bool ragged = enroll_lengths && te_row;
+  std::vector<int> tl;
+  const int *d_len = nullptr, *d_te = nullptr;
+  e->spk_tabs.clear();
+  if (ragged) {
+    if (!ragged_speaker_covered(e)) {
+      set_err("engine: this speaker encoder has no ragged pass");
+      return WS_ERR_INVALID;
+    }
+    // every width set of the forward in one upload, before the first launch: the rows' samples (WAVE), their frames, and
+    // for the ResNets the frames after each of the three stride-2 stages (3x3, padding 1; the 1x1 stride-2 shortcut agrees)
+    tl.assign(te_row, te_row + R);
+    std::vector<std::vector<int>> sets;
+    sets.push_back(std::vector<int>(enroll_lengths, enroll_lengths + R));
+    sets.push_back(tl);
+    if (e->spk.kind == 0)
+      for (int i = 0; i < 3; ++i) sets.push_back(conv_widths(sets.back(), 3, 2, 1));
+    std::vector<int> all;
+    for (const auto& v : sets) all.insert(all.end(), v.begin(), v.end());
+    const int* d = upload_ints(e, a, all);
+    WS_PTR(d);
+    d_len = d;
+    d_te = d + R;
+    for (size_t i = 1; i < sets.size(); ++i) e->spk_tabs.emplace_back(sets[i], d + i * R);
+  }
   float* fb = a.alloc(size_t(R) * Te * e->spk.feat_dim);
   WS_PTR(fb);
   if (enroll_kind == WS_ENROLL_FBANK) {
     if ((rc = to_device(e, fb, enroll, size_t(R) * Te * e->spk.feat_dim * 4)) != WS_OK) return rc;
+    // the caller's rectangle: whatever lies behind a row's frames is selected to zero
+    if (ragged) WS_RUN(e, ws_tail_select_len(fb, R, Te, e->spk.feat_dim, d_te, fb, e->stream));
   } else {
     float* d_wave = a.alloc(size_t(R) * enroll_len);
     WS_PTR(d_wave);
     if ((rc = to_device(e, d_wave, enroll, size_t(R) * enroll_len * 4)) != WS_OK) return rc;
-    if ((rc = e->spk.feat ? kaldi_fbank(e, d_wave, R, enroll_len, fb, Te) : mel_frontend(e, d_wave, R, enroll_len, fb, Te)) !=
-        WS_OK)
+    if ((rc = e->spk.feat ? kaldi_fbank(e, d_wave, R, enroll_len, fb, Te, d_te)
+                          : mel_frontend(e, d_wave, R, enroll_len, fb, Te, d_len, d_te)) != WS_OK)
       return rc;
   }
-  if ((rc = kEncoders[e->spk.kind].embed(e, fb, R, Te, emb)) != WS_OK) return rc;
+  rc = kEncoders[e->spk.kind].embed(e, fb, R, Te, emb, ragged ? &tl : nullptr);
+  e->spk_tabs.clear();
+  if (rc != WS_OK) return rc;
   a.release(mk);
   return WS_OK;
 }

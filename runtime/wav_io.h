@@ -79,6 +79,54 @@ inline bool read_wav(const std::string& path, Wav* out, std::string* err) {
   return fail("no data chunk");
 }
 
+// The sample count per channel that read_wav would return, from the header alone (the chunk walk of read_wav; the data
+// chunk's size is bounded by what the file holds, and no sample is read)
+inline bool peek_wav_frames(const std::string& path, size_t* frames, std::string* err) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) {
+    *err = "cannot open " + path;
+    return false;
+  }
+  auto fail = [&](const char* why) {
+    *err = path + ": " + why;
+    fclose(f);
+    return false;
+  };
+  char id[4];
+  uint32_t size = 0;
+  if (fread(id, 1, 4, f) != 4 || memcmp(id, "RIFF", 4) || fread(&size, 4, 1, f) != 1 || fread(id, 1, 4, f) != 4 ||
+      memcmp(id, "WAVE", 4))
+    return fail("not a RIFF/WAVE file");
+  bool have_fmt = false;
+  uint16_t format = 0, channels = 0, bits = 0;
+  while (fread(id, 1, 4, f) == 4 && fread(&size, 4, 1, f) == 1) {
+    if (!memcmp(id, "fmt ", 4)) {
+      uint8_t buf[16];
+      if (size < 16 || fread(buf, 1, 16, f) != 16) return fail("short fmt chunk");
+      memcpy(&format, buf, 2);
+      memcpy(&channels, buf + 2, 2);
+      memcpy(&bits, buf + 14, 2);
+      if (size > 16) fseek(f, size - 16 + (size & 1), SEEK_CUR);
+      have_fmt = true;
+    } else if (!memcmp(id, "data", 4)) {
+      if (!have_fmt) return fail("data chunk before fmt chunk");
+      if (format != 1 || bits != 16 || channels < 1) return fail("only 16-bit PCM is supported");
+      size_t remaining = 0;
+      const long here = ftell(f);
+      if (here >= 0 && fseek(f, 0, SEEK_END) == 0) {
+        const long end = ftell(f);
+        if (end > here) remaining = static_cast<size_t>(end - here);
+      }
+      *frames = (size < remaining ? size : remaining) / (2u * channels);
+      fclose(f);
+      return true;
+    } else {
+      fseek(f, size + (size & 1), SEEK_CUR);
+    }
+  }
+  return fail("no data chunk");
+}
+
 // data in [-1, 1] -> 16-bit PCM, rounded and saturated
 inline bool write_wav(const std::string& path, const float* data, size_t n, int sample_rate, std::string* err) {
   FILE* f = fopen(path.c_str(), "wb");

@@ -291,6 +291,14 @@ _SIGS = {
     "ws_grad_norms": (_i, [_p, _i, _p, _p, _p]),
     "ws_clip_adam_step": (_i, [_p, _i, _p, _f, _f, _f, _f, _f, _f, _i, _i, _p, _p, _p, _p]),
     "ws_guard_commit": (_i, [_p, _p, _p]),
+    # ragged speaker stage (ragged_spk.hip)
+    "ws_bn_prelu_fwd_len": (_i, [_p, _p, _p, _p, _p, _p, _ll, _i, _i, _i, _p, _p, _p, _p]),
+    "ws_tstp_fwd_len": (_i, [_p, _i, _i, _i, _i, _p, C.c_float, _p, _p]),
+    "ws_astp_fwd_len": (_i, [_p, _p, _i, _i, _i, _p, C.c_float, _p, _p, _p]),
+    "ws_time_mean_len": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "ws_cmn_len": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "ws_tail_select_len": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "ws_preemph_pad_len": (_i, [_p, _i, _i, _i, _i, C.c_float, _p, _p, _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

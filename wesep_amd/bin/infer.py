@@ -20,16 +20,19 @@ def peak_normalise_rows(outputs, lengths):
 
 
 @torch.no_grad()
-def extract(model, wav_mix, enroll, lengths=None):
+def extract(model, wav_mix, enroll, lengths=None, enroll_lengths=None):
     """wav_mix [B, T], enroll [B, spk_emb_dim] (device tensors) -> numpy [B, T], peak-normalised like
     infer.py:118-128 (only when every row's maximum is positive, exactly as the reference).
     lengths (B ints; pBSRNN): a ragged batch -- row r holds lengths[r] valid samples and comes out as that utterance alone
-    would (model(..., lengths=)), normalised over its valid part (peak_normalise_rows), zeros behind it."""
+    would (model(..., lengths=)), normalised over its valid part (peak_normalise_rows), zeros behind it.
+    enroll_lengths (B ints; joint pBSRNN): the valid samples (spk_feat=False) or frames (spk_feat=True) of every enrollment
+    row -- the speaker encoder runs once over the rectangle (model(..., enroll_lengths=))."""
     model.eval()
+    kw = {} if enroll_lengths is None else {"enroll_lengths": [int(n) for n in enroll_lengths]}
     if lengths is not None:
-        outputs = model(wav_mix.float(), enroll.float(), lengths=[int(n) for n in lengths])
+        outputs = model(wav_mix.float(), enroll.float(), lengths=[int(n) for n in lengths], **kw)
         return peak_normalise_rows((outputs[0] if isinstance(outputs, (list, tuple)) else outputs).cpu().numpy(), lengths)
-    outputs = model(wav_mix.float(), enroll.float())
+    outputs = model(wav_mix.float(), enroll.float(), **kw)
     if isinstance(outputs, (list, tuple)):
         outputs = outputs[0]
     if torch.min(outputs.max(dim=1).values) > 0:

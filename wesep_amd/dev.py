@@ -1534,6 +1534,75 @@ def log_eps(x, eps: float):
     _call("ws_log_eps", _p(x), x.numel(), eps)
 
 
+# ---- ragged speaker stage (ragged_spk.hip) ------------------------------------------------------
+def conv_widths(widths, k: int, s: int, p: int):
+    """Per-row output widths of a convolution along time: W' = (W + 2p - k) // s + 1 with the layer's own k, p, s."""
+    return [(int(w) + 2 * p - k) // s + 1 for w in widths]
+
+
+def length_table(lengths, R: int, hi: int, device, lo: int = 1, what="lengths"):
+    """lengths: R ints (sequence / numpy / CPU tensor) -> int32 device table [R].  Values outside [lo, hi] and a wrong
+    count are refused here, on the host, where they are known: the kernels only clamp."""
+    ln = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(ln) != R:
+        raise L.WesepHipError(f"{what} for {len(ln)} rows, the batch has {R}")
+    bad = [(r, v) for r, v in enumerate(ln) if v < lo or v > hi]
+    if bad:
+        raise L.WesepHipError(f"{what} outside [{lo}, {hi}] (row, value): {bad[:4]}")
+    return torch.tensor(ln, dtype=torch.int32).to(device)
+
+
+def bn_prelu_fwd_len(x, stats, gamma, beta, res, a, M: int, Cc: int, rows_per_r: int, W: int, wlen, u, y):
+    for n, t in (("x", x), ("stats", stats), ("gamma", gamma), ("beta", beta), ("res", res), ("a", a), ("u", u),
+                 ("y", y)):
+        _chk(t, n)
+    _chk_lens(wlen, M // max(rows_per_r, 1), "ws_bn_prelu_fwd_len")
+    _call("ws_bn_prelu_fwd_len", _p(x), _p(stats), _p(gamma), _p(beta), _p(res), _p(a), M, Cc, rows_per_r, W, _tab(wlen),
+          _p(u), _p(y))
+
+
+def tstp_fwd_len(x, R: int, F: int, T: int, Cc: int, tlen, stats, eps=1e-7):
+    _chk(x, "x")
+    _chk(stats, "stats")
+    _chk_lens(tlen, R, "ws_tstp_fwd_len")
+    _call("ws_tstp_fwd_len", _p(x), R, F, T, Cc, _tab(tlen), eps, _p(stats))
+
+
+def astp_fwd_len(x, logits, R: int, T: int, Cc: int, tlen, out, aux):
+    for n, t in (("x", x), ("logits", logits), ("out", out), ("aux", aux)):
+        _chk(t, n)
+    _chk_lens(tlen, R, "ws_astp_fwd_len")
+    _call("ws_astp_fwd_len", _p(x), _p(logits), R, T, Cc, _tab(tlen), ASTP_FLOOR, _p(out), _p(aux))
+
+
+def time_mean_len(x, R: int, T: int, Cc: int, tlen, mean):
+    _chk(x, "x")
+    _chk(mean, "mean")
+    _chk_lens(tlen, R, "ws_time_mean_len")
+    _call("ws_time_mean_len", _p(x), R, T, Cc, _tab(tlen), _p(mean))
+
+
+def cmn_len(x, R: int, T: int, Cc: int, tlen, y):
+    _chk(x, "x")
+    _chk(y, "y")
+    _chk_lens(tlen, R, "ws_cmn_len")
+    _call("ws_cmn_len", _p(x), R, T, Cc, _tab(tlen), _p(y))
+
+
+def tail_select_len(x, R: int, T: int, Cc: int, tlen, y):
+    _chk(x, "x")
+    _chk(y, "y")
+    _chk_lens(tlen, R, "ws_tail_select_len")
+    _call("ws_tail_select_len", _p(x), R, T, Cc, _tab(tlen), _p(y))
+
+
+def preemph_pad_len(x, R: int, T: int, pad: int, ldo: int, coef: float, lengths, out):
+    _chk(x, "x")
+    _chk(out, "out")
+    _chk_lens(lengths, R, "ws_preemph_pad_len")
+    _call("ws_preemph_pad_len", _p(x), R, T, pad, ldo, coef, _tab(lengths), _p(out))
+
+
 # ---- DPCCN pieces (conv2d.hip) --------------------------------------------------------------------------
 IN_EPS = 1e-5  # nn.InstanceNorm{1,2}d default
 

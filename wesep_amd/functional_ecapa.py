@@ -17,12 +17,14 @@ from .functional_tasnet import _gemm, _wgrad
 
 
 class Conv1dReluBnFn(torch.autograd.Function):
-    """x [R*T, Cin] -> BN(ReLU(conv1d(x, w [Cout, Cin, k], b; dilation, 'same' padding))) [R*T, Cout]."""
+    """x [R*T, Cin] -> BN(ReLU(conv1d(x, w [Cout, Cin, k], b; dilation, 'same' padding))) [R*T, Cout].  A fifth entry of
+    geo (inference only): the int32 device table of the rows' valid frames -- zeros are written behind them."""
 
     @staticmethod
     def forward(ctx, x, geo, w, b, gamma, beta, rm, rv):
         _need_cuda(x, "ECAPA-TDNN")
-        R, T, dil, training = geo
+        R, T, dil, training = geo[:4]
+        tlen = geo[4] if len(geo) > 4 else None
         Cout, Cin, k = w.shape
         M = R * T
         x = x.contiguous()
@@ -46,7 +48,10 @@ class Conv1dReluBnFn(torch.autograd.Function):
             st[1].copy_(torch.rsqrt(rv + dev.BN_EPS))
         one = torch.ones(1, device=d, dtype=torch.float32)
         u, y = _empty(d, M, Cout), _empty(d, M, Cout)
-        dev.bn_prelu_fwd(c, st, gamma, beta, None, one, M, Cout, u, y)       # slope 1: no activation after the norm
+        if tlen is not None:
+            dev.bn_prelu_fwd_len(c, st, gamma, beta, None, one, M, Cout, T, T, tlen, u, y)
+        else:
+            dev.bn_prelu_fwd(c, st, gamma, beta, None, one, M, Cout, u, y)   # slope 1: no activation after the norm
         del u
         ctx.save_for_backward(x, c, st, W2, gamma)
         ctx.geo = (R, T, dil, training, Cin, Cout, k, w.shape)
@@ -77,14 +82,19 @@ class Conv1dReluBnFn(torch.autograd.Function):
 
 
 class TimeMeanFn(torch.autograd.Function):
-    """x [R*T, C] -> mean over the T frames of each row [R, C] (SE squeeze)."""
+    """x [R*T, C] -> mean over the T frames of each row [R, C] (SE squeeze).  A third entry of geo (inference only): the
+    int32 device table of the rows' valid frames."""
 
     @staticmethod
     def forward(ctx, x, geo):
-        R, T = geo
+        R, T = geo[:2]
         x = x.contiguous()
         Cc = x.shape[1]
         ctx.geo = (R, T, Cc)
+        if len(geo) > 2 and geo[2] is not None:
+            m = _empty(x.device, R, Cc)
+            dev.time_mean_len(x, R, T, Cc, geo[2], m)
+            return m
         return dev.chan_sums(x, None, None, 1, T, R, Cc)[:, 0].contiguous() / T
 
     @staticmethod
@@ -122,16 +132,20 @@ class RowBiasActFn(torch.autograd.Function):
 
 
 class AstpFn(torch.autograd.Function):
-    """x, logits [R*T, C] -> [R, 2C] = softmax_T(logits)-weighted mean || std."""
+    """x, logits [R*T, C] -> [R, 2C] = softmax_T(logits)-weighted mean || std.  A third entry of geo (inference only):
+    the int32 device table of the rows' valid frames."""
 
     @staticmethod
     def forward(ctx, x, logits, geo):
         _need_cuda(x, "ECAPA-TDNN")
-        R, T = geo
+        R, T = geo[:2]
         x, logits = x.contiguous(), logits.contiguous()
         Cc = x.shape[1]
         out, aux = _empty(x.device, R, 2 * Cc), _empty(x.device, R, 4 * Cc)
-        dev.astp_fwd(x, logits, R, T, Cc, out, aux)
+        if len(geo) > 2 and geo[2] is not None:
+            dev.astp_fwd_len(x, logits, R, T, Cc, geo[2], out, aux)
+        else:
+            dev.astp_fwd(x, logits, R, T, Cc, out, aux)
         ctx.save_for_backward(x, logits, out, aux)
         ctx.geo = (R, T, Cc)
         return out

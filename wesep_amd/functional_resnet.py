@@ -15,12 +15,15 @@ from .functional_tasnet import _gemm, _transposed, _wgrad
 
 class ConvBnActFn(torch.autograd.Function):
     """x [R*H*W, Cin] -> act(BN(conv2d(x, w)) (+ res)) [R*Ho*Wo, Cout]; act = ReLU or identity.  `stride` of geo: an int,
-    or (sh, sw) for the mel-axis-only strides of CAM++'s FCM head (implicit-patch path, Cin % 4 == 0)."""
+    or (sh, sw) for the mel-axis-only strides of CAM++'s FCM head (implicit-patch path, Cin % 4 == 0).  A seventh entry of
+    geo (inference only): the int32 device table of the rows' valid OUTPUT widths -- the masked epilogue writes zeros behind
+    them (ragged batches)."""
 
     @staticmethod
     def forward(ctx, x, res, geo, w, gamma, beta, rm, rv):
         _need_cuda(x, "ResNet speaker encoder")
-        R, H, W, stride, relu, training = geo
+        R, H, W, stride, relu, training = geo[:6]
+        wlen = geo[6] if len(geo) > 6 else None
         Cout, Cin, k, _ = w.shape
         pad = k // 2
         sh, sw = stride if isinstance(stride, tuple) else (stride, stride)
@@ -49,7 +52,11 @@ class ConvBnActFn(torch.autograd.Function):
             st[1].copy_(torch.rsqrt(rv + dev.BN_EPS))
         slope = torch.full((1,), 0.0 if relu else 1.0, device=d, dtype=torch.float32)
         u, y = _empty(d, M, Cout), _empty(d, M, Cout)
-        dev.bn_prelu_fwd(c, st, gamma, beta, res.contiguous() if res is not None else None, slope, M, Cout, u, y)
+        res = res.contiguous() if res is not None else None
+        if wlen is not None:
+            dev.bn_prelu_fwd_len(c, st, gamma, beta, res, slope, M, Cout, Ho * Wo, Wo, wlen, u, y)
+        else:
+            dev.bn_prelu_fwd(c, st, gamma, beta, res, slope, M, Cout, u, y)
         ctx.save_for_backward(x, c, st, u, W2, gamma, slope)
         ctx.geo = (R, H, W, Cin, Cout, k, (sh, sw), pad, Ho, Wo, ldp, res is not None, training, w.shape)
         return y
@@ -97,15 +104,20 @@ class ConvBnActFn(torch.autograd.Function):
 
 
 class TstpFn(torch.autograd.Function):
-    """x [R*F*T, C] -> [R, 2*C*F]: mean || sqrt(unbiased var + 1e-7) over T, feature index c*F + f."""
+    """x [R*F*T, C] -> [R, 2*C*F]: mean || sqrt(unbiased var + 1e-7) over T, feature index c*F + f.  A fourth entry of
+    geo (inference only): the int32 device table of the rows' valid frames."""
 
     @staticmethod
     def forward(ctx, x, geo):
-        R, Fq, T = geo
+        R, Fq, T = geo[:3]
+        tlen = geo[3] if len(geo) > 3 else None
         x = x.contiguous()
         Cc = x.shape[1]
         stats = _empty(x.device, R, 2 * Cc * Fq)
-        dev.tstp_fwd(x, R, Fq, T, Cc, stats)
+        if tlen is not None:
+            dev.tstp_fwd_len(x, R, Fq, T, Cc, tlen, stats)
+        else:
+            dev.tstp_fwd(x, R, Fq, T, Cc, stats)
         ctx.save_for_backward(x, stats)
         ctx.geo = (R, Fq, T, Cc)
         return stats

@@ -219,7 +219,7 @@ class BSRNN(nn.Module):
                     seq[5].weight, seq[5].bias]
         return out
 
-    def _forward_ragged(self, wav, embeddings, plan, lengths):
+    def _forward_ragged(self, wav, embeddings, plan, lengths, enroll_lengths=None):
         if torch.is_grad_enabled():
             raise WesepHipError("BSRNN.forward(lengths=...): per-row lengths are an inference feature; call it under "
                                 "torch.no_grad() (training batches are cropped to the shortest row by the collate function)")
@@ -230,7 +230,7 @@ class BSRNN(nn.Module):
             raise WesepHipError("BSRNN: wesep_amd has no CPU path; move the model and inputs to the GPU")
         n, frames = dev.ragged_tables(lengths, T, wav.device)
         z, xbs = F_.band_split_ragged(wav, plan, self._bn_params(), n, frames)
-        e, predict_speaker_lable = self._speaker(embeddings)
+        e, predict_speaker_lable = self._speaker(embeddings, enroll_lengths)
         z = self.separator(z, e, carriers={}, frames=frames)
         return F_.mask_decode_ragged(z, xbs, plan, T, self._mask_params(), n, frames), predict_speaker_lable
 
@@ -240,38 +240,59 @@ class BSRNN(nn.Module):
             self._plans[key] = F_.BandPlan(self.band_width, self.feature_dim, device)
         return self._plans[key]
 
-    def _speaker(self, embeddings):
-        """enrollment -> (fused-in embedding [R, E], second output) (bsrnn.py:339-360)."""
+    def _speaker(self, embeddings, enroll_lengths=None):
+        """enrollment -> (fused-in embedding [R, E], second output) (bsrnn.py:339-360).  enroll_lengths (inference): the
+        rows' valid samples (spk_feat=False) or frames (spk_feat=True) -- one encoder pass over the rectangle."""
+        if enroll_lengths is not None:
+            if not self.joint_training:
+                raise WesepHipError("BSRNN.forward(enroll_lengths=...): this model takes fixed embeddings, which have no length")
+            if self.training or torch.is_grad_enabled():
+                raise WesepHipError("BSRNN.forward(enroll_lengths=...): per-row enrollment lengths are an inference feature; "
+                                    "call the model in eval mode under torch.no_grad()")
+            import inspect
+            if "lengths" not in inspect.signature(self.spk_model.forward).parameters:
+                raise NotImplementedError(f"enroll_lengths with the speaker encoder {type(self.spk_model).__name__}: the "
+                                          "ResNets and ECAPA-TDNN take per-row lengths")
         # dummy, bsrnn.py:339-340.  torch.zeros: a fill on the stream -- torch.tensor(0.0, device=...) is a pageable host-to-device copy
         # that SYNCHRONISES the stream (the host sat out the whole previous step here, 71 of its 86 ms per step; round 6)
         predict_speaker_lable = torch.zeros((), device=embeddings.device)
         if self.joint_training:             # fbank [R, Te, F] -> wespeaker encoder -> embedding (bsrnn.py:341-357)
             if not self.spk_feat:           # raw enrollment waveform [R, Tw] -> log-mel, CMN (no_grad, :343-350)
                 from ..modules.common.frontend import fbank_frontend
-                embeddings = fbank_frontend(embeddings, self.preEmphasis, self.spk_encoder)
-            out = self.spk_model(embeddings.float().contiguous())
+                embeddings = fbank_frontend(embeddings, self.preEmphasis, self.spk_encoder, lengths=enroll_lengths)
+                if enroll_lengths is not None:
+                    from ..modules.common.frontend import frontend_frames
+                    enroll_lengths = frontend_frames(enroll_lengths, self.spk_encoder.hop)
+            if enroll_lengths is not None:
+                out = self.spk_model(embeddings.float().contiguous(), lengths=enroll_lengths)
+            else:
+                out = self.spk_model(embeddings.float().contiguous())
             embeddings = out[-1] if isinstance(out, tuple) else out
             # pred_linear is nn.Identity without multi_task: the reference then returns the embedding (bsrnn.py:357)
             predict_speaker_lable = (F_.LinearFn.apply(embeddings, self.pred_linear.weight, self.pred_linear.bias)
                                      if self.multi_task else embeddings)
         return self.spk_transform(embeddings.float().contiguous()), predict_speaker_lable
 
-    def forward(self, input, embeddings, *, lengths=None):
+    def forward(self, input, embeddings, *, lengths=None, enroll_lengths=None):
         """input: mixture [R, T] fp32; embeddings: [R, spk_emb_dim] (fixed) or fbank [R, Te, 80] (joint training)
         -> (est [R, T], 0-d dummy | speaker logits (multi_task) | the embedding (joint, no multi_task)).
         lengths (keyword only; inference): R ints, the valid samples of each row of a ragged batch, 256 < lengths[r] <= T.
         est[r, :lengths[r]] is then what the model returns for input[r, :lengths[r]] alone, est[r, lengths[r]:] is zero,
-        and nothing of input[r, lengths[r]:] reaches a valid output.  The enrollment stays a rectangle (the speaker encoder
-        is not ragged).  With gradients enabled it raises: training batches are cropped by the collate function."""
+        and nothing of input[r, lengths[r]:] reaches a valid output.  With gradients enabled it raises: training batches are
+        cropped by the collate function.
+        enroll_lengths (keyword only; inference; joint models; independent of `lengths`): R ints, the valid part of each
+        enrollment row -- samples for spk_feat=False, frames for spk_feat=True.  The speaker encoder (ResNets, ECAPA-TDNN;
+        TSTP / TAP / TSDP / ASTP) then runs once over the rectangle and gives every row the embedding it gets alone;
+        nothing behind a row's length reaches it."""
         if input.dim() != 2:
             raise RuntimeError("BSRNN expects a [batch, samples] mixture")
         wav = input.float().contiguous()
         plan = self._plan(wav.device)
         if lengths is not None:
-            return self._forward_ragged(wav, embeddings, plan, lengths)
+            return self._forward_ragged(wav, embeddings, plan, lengths, enroll_lengths)
         carriers = self.separator.make_carriers(wav.device) if hasattr(self.separator, "make_carriers") else None
         z, xbs = F_.BandSplitFn.apply(wav, plan, *self._bn_params())
-        e, predict_speaker_lable = self._speaker(embeddings)
+        e, predict_speaker_lable = self._speaker(embeddings, enroll_lengths)
         z = self.separator(z, e, carriers=carriers) if carriers is not None else self.separator(z, e)
         est = F_.MaskDecodeFn.apply(z, xbs, plan, wav.shape[1], *self._mask_params())
         return est, predict_speaker_lable

@@ -15,11 +15,13 @@ from .. import functional_ecapa as FE
 from ..functional import LinearFn
 
 
-def _crb(x, R, T, m, training):
-    """Conv1dReluBn module -> Conv -> ReLU -> BN launches."""
+def _crb(x, R, T, m, training, tl=None):
+    """Conv1dReluBn module -> Conv -> ReLU -> BN launches.  tl (every `run` below; ragged batches, inference): the int32
+    device table of the rows' valid frames -- x is zero behind them, and so is the output ('same' padding and stride 1
+    everywhere: the widths never change)."""
     if training:
         m.bn.num_batches_tracked += 1
-    return FE.Conv1dReluBnFn.apply(x, (R, T, m.conv.dilation[0], training), m.conv.weight, m.conv.bias, m.bn.weight,
+    return FE.Conv1dReluBnFn.apply(x, (R, T, m.conv.dilation[0], training, tl), m.conv.weight, m.conv.bias, m.bn.weight,
                                    m.bn.bias, m.bn.running_mean, m.bn.running_var)
 
 
@@ -31,8 +33,8 @@ class Conv1dReluBn(nn.Module):
         self.conv = nn.Conv1d(in_channels, out_channels, kernel_size, stride, padding, dilation, bias=bias)
         self.bn = nn.BatchNorm1d(out_channels)
 
-    def run(self, x, R, T):
-        return _crb(x, R, T, self, self.training)
+    def run(self, x, R, T, tl=None):
+        return _crb(x, R, T, self, self.training, tl)
 
 
 class Res2Conv1dReluBn(nn.Module):
@@ -49,14 +51,14 @@ class Res2Conv1dReluBn(nn.Module):
                                     for _ in range(self.nums)])
         self.bns = nn.ModuleList([nn.BatchNorm1d(self.width) for _ in range(self.nums)])
 
-    def run(self, x, R, T):
+    def run(self, x, R, T, tl=None):
         spx = torch.split(x, self.width, 1)
         out, sp = [], None
         for i, (conv, bn) in enumerate(zip(self.convs, self.bns)):
             sp = spx[i].contiguous() if i == 0 else sp + spx[i]
             if self.training:
                 bn.num_batches_tracked += 1
-            sp = FE.Conv1dReluBnFn.apply(sp, (R, T, conv.dilation[0], self.training), conv.weight, conv.bias, bn.weight,
+            sp = FE.Conv1dReluBnFn.apply(sp, (R, T, conv.dilation[0], self.training, tl), conv.weight, conv.bias, bn.weight,
                                          bn.bias, bn.running_mean, bn.running_var)
             out.append(sp)
         if self.scale != 1:
@@ -70,8 +72,8 @@ class SE_Connect(nn.Module):
         self.linear1 = nn.Linear(channels, se_bottleneck_dim)
         self.linear2 = nn.Linear(se_bottleneck_dim, channels)
 
-    def run(self, x, R, T):
-        m = FE.TimeMeanFn.apply(x, (R, T))                                             # [R, C]
+    def run(self, x, R, T, tl=None):
+        m = FE.TimeMeanFn.apply(x, (R, T, tl))                                         # [R, C]
         h = torch.relu(LinearFn.apply(m, self.linear1.weight, self.linear1.bias))      # [R, 128]: a few thousand numbers
         s = FE.RowBiasActFn.apply(LinearFn.apply(h, self.linear2.weight, self.linear2.bias), None, 1, 3)
         return FE.GateFn.apply(x, s, (R, T))                                           # x * gate[r, c]
@@ -86,11 +88,11 @@ class SE_Res2Block(nn.Module):
             Conv1dReluBn(channels, channels, kernel_size=1, stride=1, padding=0),
             SE_Connect(channels))
 
-    def run(self, x, R, T):
+    def run(self, x, R, T, tl=None):
         y = x
         for m in self.se_res2block:
-            y = m.run(y, R, T)
-        return x + y
+            y = m.run(y, R, T, tl)
+        return x + y                  # (ragged: both are zero behind the row's frames -- the gate is finite)
 
 
 class ASTP(nn.Module):
@@ -106,21 +108,21 @@ class ASTP(nn.Module):
         self.out_dim = 2 * self.in_dim
         return self.out_dim
 
-    def run(self, x, R, T):
+    def run(self, x, R, T, tl=None):
         from .. import functional_resnet as FR
         C = self.in_dim
         w1 = self.linear1.weight.view(self.linear1.weight.shape[0], -1)
         rb = None
         if self.global_context_att:
             # cat(x, mean.expand, std.expand) W1^T = x Wx^T + (mean Wm^T + std Ws^T): the context is a per-row bias
-            ctxt = FR.TstpFn.apply(x, (R, 1, T))                                         # [R, 2C] mean || sqrt(var + 1e-7)
+            ctxt = FR.TstpFn.apply(x, (R, 1, T, tl))                                     # [R, 2C] mean || sqrt(var + 1e-7)
             rb = LinearFn.apply(ctxt, w1[:, C:].contiguous(), self.linear1.bias)        # [R, 128]
             a = LinearFn.apply(x, w1[:, :C].contiguous(), torch.zeros_like(self.linear1.bias))
         else:
             a = LinearFn.apply(x, w1, self.linear1.bias)
         a = FE.RowBiasActFn.apply(a, rb, T, 1)                                            # tanh
         logits = LinearFn.apply(a, self.linear2.weight.view(C, -1), self.linear2.bias)   # [R*T, C]
-        return FE.AstpFn.apply(x, logits, (R, T))
+        return FE.AstpFn.apply(x, logits, (R, T, tl))
 
 
 class ECAPA_TDNN(nn.Module):
@@ -146,8 +148,12 @@ class ECAPA_TDNN(nn.Module):
         self.bn2 = nn.BatchNorm1d(embed_dim) if emb_bn else nn.Identity()
         self.feat_dim, self.embed_dim = feat_dim, embed_dim
 
-    def forward(self, x):
-        """x [R, T, F] fbank -> embedding [R, embed_dim]."""
+    def forward(self, x, lengths=None):
+        """x [R, T, F] fbank -> embedding [R, embed_dim].  lengths (eval mode under torch.no_grad() only): the valid frames
+        of every row -- one pass over the rectangle gives each row the embedding it gets alone; whatever x holds behind a
+        row's frames is ignored."""
+        from .resnet import ragged_guard, run_pool
+        ragged_guard(self, "ECAPA-TDNN", self.pooling_func, lengths)
         if not x.is_cuda:
             from .._lib import WesepHipError
             raise WesepHipError("ECAPA-TDNN speaker encoder: wesep_amd has no CPU path")
@@ -156,14 +162,20 @@ class ECAPA_TDNN(nn.Module):
             raise NotImplementedError("ECAPA-TDNN: feat_dim must be a multiple of 4")
         tr = self.training
         y = x.float().contiguous().view(R * T, Fq)                                    # already channels-last
-        out1 = self.layer1.run(y, R, T)
-        out2 = self.layer2.run(out1, R, T)
-        out3 = self.layer3.run(out2, R, T)
-        out4 = self.layer4.run(out3, R, T)
+        tl = None
+        if lengths is not None:
+            from .. import dev
+            tl = dev.length_table(lengths, R, T, x.device, lo=1)
+            y0 = torch.empty_like(y)
+            dev.tail_select_len(y, R, T, Fq, tl, y0)
+            y = y0
+        out1 = self.layer1.run(y, R, T, tl)
+        out2 = self.layer2.run(out1, R, T, tl)
+        out3 = self.layer3.run(out2, R, T, tl)
+        out4 = self.layer4.run(out3, R, T, tl)
         cat = torch.cat([out2, out3, out4], 1)
         h = FE.LinearReluFn.apply(cat, self.conv.weight.view(self.conv.weight.shape[0], -1), self.conv.bias)
-        from .resnet import run_pool
-        stats = run_pool(self.pool, self.pooling_func, h, R, T)
+        stats = run_pool(self.pool, self.pooling_func, h, R, T, tl)
         if tr:
             self.bn.num_batches_tracked += 1
         stats = FE.BatchNormRowsFn.apply(stats, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var, tr)

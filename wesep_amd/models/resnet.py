@@ -126,6 +126,21 @@ def _mhastp_run(queries, cache, y, R, Fq, T, split=False):
 
 
 POOLING_FUNCS = ("TSTP", "TAP", "TSDP", "ASTP", "MHASTP", "MQMHASTP")
+RAGGED_POOLING_FUNCS = ("TSTP", "TAP", "TSDP", "ASTP")      # the pools with a length-aware kernel (csrc/ragged_spk.hip)
+
+
+def ragged_guard(module, who, pooling_func, lengths):
+    """`lengths=` of a speaker encoder's forward: inference only (batch statistics over ragged rows are out of scope),
+    and only with a pool that has a length-aware kernel."""
+    if lengths is None:
+        return
+    from .._lib import WesepHipError
+    if module.training or torch.is_grad_enabled():
+        raise WesepHipError(f"{who}: lengths= is built for inference (eval mode under torch.no_grad()); ragged training "
+                            "and BatchNorm statistics over ragged rows are out of scope")
+    if pooling_func not in RAGGED_POOLING_FUNCS:
+        raise NotImplementedError(f"{who}: lengths= with pooling_func {pooling_func}: {', '.join(RAGGED_POOLING_FUNCS)} "
+                                  "have a length-aware kernel")
 
 
 def _pooling_layer(name, in_dim, **kwargs):
@@ -143,14 +158,17 @@ def _pooling_layer(name, in_dim, **kwargs):
     raise NotImplementedError(f"pooling_func {name!r}: TSTP, TAP, TSDP, ASTP, MHASTP and MQMHASTP are built")
 
 
-def run_pool(pool, name, y, R, T):
+def run_pool(pool, name, y, R, T, tl=None):
     """A pooling layer of _pooling_layer on the channels-last frames y [R*T, C] of a 1-D encoder (F' = 1) ->
-    [R, pool.get_out_dim()]; MHASTP / MQMHASTP on the grid split over T."""
+    [R, pool.get_out_dim()]; MHASTP / MQMHASTP on the grid split over T.  tl: the int32 device table of the rows' valid
+    frames (ragged batches; RAGGED_POOLING_FUNCS)."""
     if name == "ASTP":
-        return pool.run(y, R, T)
+        return pool.run(y, R, T, tl)
     if name in ("MHASTP", "MQMHASTP"):
+        if tl is not None:
+            raise NotImplementedError(f"lengths= with pooling_func {name}")
         return pool.run(y, R, 1, T, split=True)
-    stats = FR.TstpFn.apply(y, (R, 1, T))                                   # mean || sqrt(var + 1e-7), each [C]
+    stats = FR.TstpFn.apply(y, (R, 1, T, tl))                               # mean || sqrt(var + 1e-7), each [C]
     half = stats.shape[1] // 2
     if name == "TAP":
         return stats[:, :half].contiguous()
@@ -203,6 +221,12 @@ def _cba(x, res, R, H, W, stride, relu, conv, bn, training):
                                 bn.running_mean, bn.running_var)
 
 
+def _cba_len(x, res, R, H, W, stride, relu, conv, bn, wlen):
+    """_cba of a ragged inference pass: the masked epilogue writes zeros behind the rows' valid output widths `wlen`."""
+    return FR.ConvBnActFn.apply(x, res, (R, H, W, stride, relu, False, wlen), conv.weight, bn.weight, bn.bias,
+                                bn.running_mean, bn.running_var)
+
+
 class ResNet(nn.Module):
     def __init__(self, block, num_blocks, m_channels=32, feat_dim=40, embed_dim=128, pooling_func="TSTP",
                  two_emb_layer=True):
@@ -236,39 +260,63 @@ class ResNet(nn.Module):
             self.in_planes = planes * block.expansion
         return nn.Sequential(*layers)
 
-    def forward(self, x):
-        """x [R, T, F] fbank -> (tensor(0.), embed_a [R, embed_dim]), or (embed_a, embed_b) with two_emb_layer."""
+    def forward(self, x, lengths=None):
+        """x [R, T, F] fbank -> (tensor(0.), embed_a [R, embed_dim]), or (embed_a, embed_b) with two_emb_layer.
+        lengths (eval mode under torch.no_grad() only): the valid frames of every row.  One pass over the rectangle then
+        gives each row the embedding it gets alone: every layer's input is exactly zero behind the row's own width, which
+        follows the convolutions' geometry (ragged_widths); whatever x holds behind a row's frames is ignored."""
+        ragged_guard(self, "ResNet speaker encoder", self.pooling_func, lengths)
         if not x.is_cuda:
             from .._lib import WesepHipError
             raise WesepHipError("ResNet speaker encoder: wesep_amd has no CPU path")
         R, T, Fq = x.shape
         tr = self.training
+        tabs = None
+        if lengths is not None:
+            from .. import dev
+            tl = dev.length_table(lengths, R, T, x.device, lo=1)
+            xs = torch.empty(R, T, Fq, device=x.device, dtype=torch.float32)
+            if Fq % 4:
+                raise NotImplementedError("ResNet speaker encoder: lengths= needs feat_dim % 4 == 0")
+            dev.tail_select_len(x.float().contiguous(), R, T, Fq, tl, xs)
+            x = xs
+            tabs = _WidthTables(lengths, x.device)
+        wl = (lambda k, s, p: tabs.step(k, s, p)) if tabs is not None else (lambda k, s, p: None)
+
+        def cba(x, res, R, H, W, stride, relu, conv, bn, wlen):
+            if wlen is None:
+                return _cba(x, res, R, H, W, stride, relu, conv, bn, tr)
+            return _cba_len(x, res, R, H, W, stride, relu, conv, bn, wlen)
         y = x.float().transpose(1, 2).contiguous().view(R * Fq * T, 1)      # [R, F, T, 1]
         H, W = Fq, T
-        y = _cba(y, None, R, H, W, 1, True, self.conv1, self.bn1, tr)
+        y = cba(y, None, R, H, W, 1, True, self.conv1, self.bn1, wl(3, 1, 1))
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for blk in layer:
                 s = blk.stride
                 Ho, Wo = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
+                # the rows' widths behind this block: the 3x3 stride-s convolution's, which the 1x1 stride-s shortcut
+                # shares; every other convolution of the block keeps the width it is given
+                w_in, w_out = wl(1, 1, 0), wl(3, s, 1)
                 sc = y
                 if len(blk.shortcut) > 0:
-                    sc = _cba(y, None, R, H, W, s, False, blk.shortcut[0], blk.shortcut[1], tr)
+                    sc = cba(y, None, R, H, W, s, False, blk.shortcut[0], blk.shortcut[1], w_out)
                 if isinstance(blk, Bottleneck):
-                    o = _cba(y, None, R, H, W, 1, True, blk.conv1, blk.bn1, tr)
-                    o = _cba(o, None, R, H, W, s, True, blk.conv2, blk.bn2, tr)
-                    y = _cba(o, sc, R, Ho, Wo, 1, True, blk.conv3, blk.bn3, tr)
+                    o = cba(y, None, R, H, W, 1, True, blk.conv1, blk.bn1, w_in)
+                    o = cba(o, None, R, H, W, s, True, blk.conv2, blk.bn2, w_out)
+                    y = cba(o, sc, R, Ho, Wo, 1, True, blk.conv3, blk.bn3, w_out)
                 else:
-                    o = _cba(y, None, R, H, W, s, True, blk.conv1, blk.bn1, tr)
-                    y = _cba(o, sc, R, Ho, Wo, 1, True, blk.conv2, blk.bn2, tr)
+                    o = cba(y, None, R, H, W, s, True, blk.conv1, blk.bn1, w_out)
+                    y = cba(o, sc, R, Ho, Wo, 1, True, blk.conv2, blk.bn2, w_out)
                 H, W = Ho, Wo
+        tl = wl(1, 1, 0)                                                     # the rows' frames at the pooling layer
         if self.pooling_func == "ASTP":      # [R, F', T, C] -> frames [R*T, C * F'] (feature index c * F' + f), then ASTP
             Cc = y.shape[1]
             frames = y.view(R, H, W, Cc).permute(0, 2, 3, 1).reshape(R * W, Cc * H)
-            stats = self.pool.run(frames, R, W)
+            stats = self.pool.run(frames, R, W, tl)
         elif self.pooling_func in ("MHASTP", "MQMHASTP"):      # straight from the [R, F', T', C] layout
             stats = self.pool.run(y, R, H, W)
         else:
-            stats = FR.TstpFn.apply(y, (R, H, W))                               # mean || std, each [C * F']
+            stats = FR.TstpFn.apply(y, (R, H, W, tl))                           # mean || std, each [C * F']
             half = stats.shape[1] // 2
             if self.pooling_func == "TAP":
                 stats = stats[:, :half].contiguous()
@@ -285,6 +333,50 @@ class ResNet(nn.Module):
         o = FE.BatchNormRowsFn.apply(torch.relu(embed_a), ones, zeros, self.seg_bn_1.running_mean,
                                      self.seg_bn_1.running_var, tr)          # affine=False; [R, E]: a few thousand numbers
         return embed_a, LinearFn.apply(o, self.seg_2.weight, self.seg_2.bias)
+
+
+def ragged_widths(lengths, num_blocks, bottleneck=False):
+    """The per-layer width tables of a ragged ResNet pass, on the host: for every conv + BN + activation of the forward, in
+    launch order (stem; per block: [shortcut,] conv1, conv2 [, conv3]), the rows' valid OUTPUT widths
+    W' = (W + 2p - k) // s + 1 with that layer's own k, p, s.  The last entry is what the pooling layer reduces over."""
+    from ..dev import conv_widths
+    w = conv_widths(lengths, 3, 1, 1)
+    out = [w]
+    for li, n in enumerate(num_blocks):
+        for bi in range(n):
+            s = 2 if (li > 0 and bi == 0) else 1
+            has_sc = s != 1 or (li == 0 and bi == 0 and bottleneck)
+            if has_sc:
+                out.append(conv_widths(w, 1, s, 0))
+            if bottleneck:
+                w1 = conv_widths(w, 1, 1, 0)
+                w2 = conv_widths(w1, 3, s, 1)
+                w = conv_widths(w2, 1, 1, 0)
+                out += [w1, w2, w]
+            else:
+                w1 = conv_widths(w, 3, s, 1)
+                w = conv_widths(w1, 3, 1, 1)
+                out += [w1, w]
+    return out
+
+
+class _WidthTables:
+    """The rows' current widths on the host and one small int32 device table per distinct width set."""
+
+    def __init__(self, lengths, device):
+        self.w = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        self.device, self.tabs = device, {}
+
+    def step(self, k, s, p):
+        """The table of the widths behind a convolution (k, stride s, padding p) of the current ones; s > 1 advances."""
+        from ..dev import conv_widths
+        w = conv_widths(self.w, k, s, p)
+        if s > 1:
+            self.w = w
+        key = tuple(w)
+        if key not in self.tabs:
+            self.tabs[key] = torch.tensor(w, dtype=torch.int32).to(self.device)
+        return self.tabs[key]
 
 
 def ResNet18(feat_dim, embed_dim, pooling_func="TSTP", two_emb_layer=True):

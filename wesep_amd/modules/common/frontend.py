@@ -83,8 +83,17 @@ class MelSpectrogram(nn.Module):
 
 
 @torch.no_grad()
-def fbank_frontend(wav, pre: PreEmphasis, mel: MelSpectrogram):
-    """wav [R, Tw] -> log-mel features [R, Tf, n_mels], mean-normalised over time (bsrnn.py:343-350)."""
+def frontend_frames(lengths, hop=128):
+    """Frames of the centred MelSpectrogram framing for rows of `lengths` samples: 1 + n // hop."""
+    return [1 + int(n) // hop for n in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+
+
+@torch.no_grad()
+def fbank_frontend(wav, pre: PreEmphasis, mel: MelSpectrogram, lengths=None):
+    """wav [R, Tw] -> log-mel features [R, Tf, n_mels], mean-normalised over time (bsrnn.py:343-350).
+    lengths: the valid samples of every row (n_fft / 2 < lengths[r] <= Tw).  Row r then gets, in its first
+    1 + lengths[r] // hop frames, the features of wav[r, :lengths[r]] alone -- the reflect padding turns at the row's own
+    end and the mean runs over its own frames -- and zeros behind them; nothing of wav[r, lengths[r]:] is read."""
     if not wav.is_cuda:
         from ..._lib import WesepHipError
         raise WesepHipError("fbank front-end: wesep_amd has no CPU path")
@@ -96,7 +105,13 @@ def fbank_frontend(wav, pre: PreEmphasis, mel: MelSpectrogram):
     basis, fbt = mel.tables(d)
     ldo = -(-(T + 2 * pad) // 4) * 4
     xp = torch.zeros(R, ldo, device=d, dtype=torch.float32)
-    dev.preemph_pad(wav, R, T, pad, ldo, pre.coef, xp)
+    n_tab = te_tab = None
+    if lengths is not None:
+        n_tab = dev.length_table(lengths, R, T, d, lo=pad + 1, what="fbank front-end: lengths")
+        te_tab = torch.tensor(frontend_frames(lengths, hop), dtype=torch.int32).to(d)
+        dev.preemph_pad_len(wav, R, T, pad, ldo, pre.coef, n_tab, xp)
+    else:
+        dev.preemph_pad(wav, R, T, pad, ldo, pre.coef, xp)
     Tf = 1 + T // hop
     M = R * Tf
     lds = basis.shape[0]
@@ -110,6 +125,9 @@ def fbank_frontend(wav, pre: PreEmphasis, mel: MelSpectrogram):
     dev.gemm_nt(A=power, a_rows=flat(ldp), M=M, N=nm, K=ldp, W=fbt, ldw=ldp, C_out=feats, c_rows=flat(nm), vec=3,
                 mode="f32")
     dev.log_eps(feats, 1e-8)
+    if te_tab is not None:
+        dev.cmn_len(feats, R, Tf, nm, te_tab, feats)
+        return feats.view(R, Tf, nm)
     neg_mean = dev.chan_sums(feats, None, None, 1, Tf, R, nm)[:, 0, :].contiguous()
     dev.affine_fwd(neg_mean, None, None, -1.0 / Tf, R, 1, nm, neg_mean)
     dev.affine_fwd(feats, None, neg_mean, 1.0, M, Tf, nm, feats)
