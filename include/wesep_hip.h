@@ -480,10 +480,14 @@ typedef struct ws_seqmap {
 } ws_seqmap;
 
 /* out (bf16 pairs, N*K*4 bytes) <- W'[n][k] = trans ? W[k*ldw + n] : W[n*ldw + k], split into
- * bf16 hi/lo and ordered for ws_gemm_p2b (order 0) or ws_gemm_b2p (order 1).                */
+ * bf16 hi/lo and ordered for ws_gemm_p2b (order 0) or ws_gemm_b2p (order 1): hi = bf16(w), lo = bf16(w - hi), both round
+ * to nearest even, in 16-byte units of 8 consecutive k for the MFMA lane that loads them --
+ *   element j of unit u*64 + lane = part(W'[32*nt + (lane & 31)][16*ks + 8*(lane >> 5) + j]),  part 0 = hi, 1 = lo,
+ *   u = (nt*(K/16) + ks)*2 + part (order 0)   or   u = (ks*(N/32) + nt)*2 + part (order 1).   N % 32 == 0, K % 16 == 0. */
 int ws_pack_w(const float* W, int N, int K, long long ldw, int trans, int order, float* out,
               void* stream);
-/* The same units with fp16 hi / lo of 256 * W' (ABI v15): the weight operand of ws_gemm_b2p with a_fmt = 2 (whose A
+/* The same units with fp16 hi = fp16(256 w) / lo = fp16(256 w - hi) (|W'| < 255: 256 w has to fit fp16; 22 bits, less where
+ * the remainder is an fp16 subnormal) (ABI v15): the weight operand of ws_gemm_b2p with a_fmt = 2 (whose A
  * operand, the scaled-fp16 d(gates) of WS_GATES_H2F, then feeds v_mfma_f32_32x32x16_f16 without conversion).   */
 int ws_pack_w_f16(const float* W, int N, int K, long long ldw, int trans, int order, float* out,
                   void* stream);
@@ -542,8 +546,9 @@ typedef struct ws_gemm_b2p_args {
                         is then a ws_pack_w_f16 pack.  3 (ABI v20): as 2 with the lo term of the product on
                         v_mfma_scale_f32_32x32x64_f8f6f4 (Wpack from ws_pack_w_f16f8; e4m3 of A / 256 built in registers) */
   const unsigned* amax;
-  void* a16_out;     /* optional (ABI v16, a_fmt 0 only): the A operand once more as fp16 elements in BLH(K) -- every block
-                        is read by exactly one wave here, so the copy costs no extra read (hcat -> ws_gemm_tnb a_fmt = 1) */
+  void* a16_out;     /* optional (ABI v16, a_fmt 0 only: any other a_fmt with a16_out is refused): the A operand once more as
+                        fp16(hi + lo) elements in BLH(K), padded slots included -- every block is read by exactly one wave
+                        here, so the copy costs no extra read (hcat -> ws_gemm_tnb a_fmt = 1) */
 } ws_gemm_b2p_args;
 int ws_gemm_b2p(const ws_gemm_b2p_args* a, void* stream);
 
@@ -553,7 +558,10 @@ int ws_gemm_b2p(const ws_gemm_b2p_args* a, void* stream);
  * Acat = columns [a0_off, a0_off + a0_cols) of A0 (BL(a0_width), shifted by a0_shift steps
  * inside the tile, zero outside [0, L)) followed by a1_cols columns of A1 likewise; Acat has 128
  * or 384 columns, g_cols is a multiple of 128.  aslab[split][a] (optional) = column sums of Acat.
- * G, A0 and A1 hold BLS elements; a0_shift must be 0 (only A1 is ever the step-shifted h).
+ * G, A0 and A1 hold BLS elements; a0_shift must be 0 (only A1 is ever the step-shifted h); a1_shift is any number of
+ * steps (|a1_shift| >= L: every shifted term is zero).  Split s owns blocks [s, s + 1) * blocks_per_split; a split behind
+ * nblk writes zero slabs.  With g_fmt = 2 and BLS A operands the product runs on the fp16 instruction (the pair's terms lifted
+ * by 2^6): |A| <= 1020 (bf16(|A|) * 64 <= 65504) is a precondition (the callers pass the normalised input and h), terms below 2^-20 are truncated.
  * Replaces autograd's dW_ih / dW_hh / db (nn.LSTM) and dW_proj / db_proj.                       */
 typedef struct ws_gemm_tnb_args {
   const float* G;

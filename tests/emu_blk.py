@@ -109,7 +109,7 @@ def dgates_scale(amax):
 
 
 def gemm_p2b(*, A, lda, sm, Wpack, N, C_out, K=128, bias=None, A_bl=None, stats=None, gamma=None, beta=None,
-             stat_map=None, run_if=None, amax=None, A_bl16=None):
+             stat_map=None, run_if=None, amax=None, A_bl16=None, steps=None, steps_div=1):
     if _skip(run_if):
         return
     nt, L = _ntile(sm), sm.L
@@ -120,7 +120,11 @@ def gemm_p2b(*, A, lda, sm, Wpack, N, C_out, K=128, bias=None, A_bl=None, stats=
         s = (pos // d1) * m1 + (pos % d2) * m2 + base
         st = stats.reshape(-1, 2)
         rows = (rows - st[s, 0].unsqueeze(-1)) * st[s, 1].unsqueeze(-1) * gamma.reshape(-1)[:K] + beta.reshape(-1)[:K]
-    rows = rows * _valid(sm)
+    live = _valid(sm).bool().expand(nt * 32, L, 1)
+    if steps is not None:      # ws_gemm_p2b_len: sequence s has steps[s / steps_div] valid steps; later slots are padding
+        sq = torch.arange(nt * 32).clamp(max=_nv(sm) - 1)
+        live = live & (torch.arange(L).view(1, -1, 1) < steps.reshape(-1)[sq // steps_div].long().view(-1, 1, 1))
+    rows = torch.where(live, rows, torch.zeros(()))      # selected, not multiplied: the rows behind may hold anything
     if A_bl is not None:
         bl_put(A_bl, rows, nt, L, K)
     if A_bl16 is not None:                 # ABI v16: the operand once more as fp16 in BLH(K)
@@ -131,9 +135,10 @@ def gemm_p2b(*, A, lda, sm, Wpack, N, C_out, K=128, bias=None, A_bl=None, stats=
         out = rows @ _PACKS[Wpack.data_ptr()].t()
         if bias is not None:
             out = out + bias.reshape(-1)[:N]
-        bl_put(C_out, out * _valid(sm), nt, L, N)
+        out = torch.where(live, out, torch.zeros(()))    # (no bias in a padded slot)
+        bl_put(C_out, out, nt, L, N)
         if amax is not None:       # atomic max on the float bits of max |C|
-            m = (out * _valid(sm)).abs().max().reshape(1).float()
+            m = out.abs().max().reshape(1).float()
             amax.reshape(-1)[0] = max(int(amax.reshape(-1)[0]), int(m.view(torch.int32)[0]))
 
 
@@ -392,6 +397,8 @@ def gemm_tnb(*, G, g_width, g_off, g_cols, A0, a0_width, a0_off, a0_cols, nblk, 
         out = torch.zeros_like(x)
         if shift == 0:
             return x
+        if abs(shift) >= L_:               # every shifted step lies outside [0, L)
+            return out
         if shift > 0:                      # Acat(b) = A(b + shift)
             out[:, : L_ - shift] = x[:, shift:]
         else:
@@ -402,14 +409,18 @@ def gemm_tnb(*, G, g_width, g_off, g_cols, A0, a0_width, a0_off, a0_cols, nblk, 
     if A1 is not None:
         a = torch.cat([a, shifted(A1, a1_width, a1_off, a1_cols, a1_shift)], 2)
     acols = a.shape[2]
-    slab.reshape(-1)[: nsplit * g_cols * acols] = 0.0
-    slab.reshape(-1)[: g_cols * acols] = torch.einsum("slg,sla->ga", g, a).reshape(-1)
-    if bslab is not None:
-        bslab.reshape(-1)[: nsplit * g_cols] = 0.0
-        bslab.reshape(-1)[:g_cols] = g.sum((0, 1))
-    if aslab is not None:
-        aslab.reshape(-1)[: nsplit * acols] = 0.0
-        aslab.reshape(-1)[:acols] = a.sum((0, 1))
+
+    def blocks(x):             # [nt * 32, L, C] -> [block b = tile * L + step][slot][C]
+        return x.reshape(nt, 32, L_, -1).permute(0, 2, 1, 3).reshape(nblk, 32, -1)
+    gb, ab = blocks(g), blocks(a)
+    for sp in range(nsplit):   # split sp owns blocks [sp, sp + 1) * blocks_per_split; trailing splits may be empty: zero slabs
+        lo, hi = sp * blocks_per_split, min(nblk, (sp + 1) * blocks_per_split)
+        gs, as_ = gb[lo:max(hi, lo)].reshape(-1, g_cols), ab[lo:max(hi, lo)].reshape(-1, acols)
+        slab.reshape(-1)[sp * g_cols * acols: (sp + 1) * g_cols * acols] = (gs.t() @ as_).reshape(-1)
+        if bslab is not None:
+            bslab.reshape(-1)[sp * g_cols: (sp + 1) * g_cols] = gs.sum(0)
+        if aslab is not None:
+            aslab.reshape(-1)[sp * acols: (sp + 1) * acols] = as_.sum(0)
 
 
 # ---- GroupNorm(1, C) pieces on the general group geometry of norm.hip (no per-band widths) -------------------------

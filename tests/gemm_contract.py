@@ -458,7 +458,7 @@ RULES = {"gemm_nt": NT_RULES, "gemm_tn": TN_RULES, "conv_wgrad": WG_RULES}
 
 def _values(entry, d):
     v = list(DIMS[entry][d])
-    if entry != "conv_wgrad" and (d in CONV_SUB or d in ("M", "K", "Kk", "a_rows")):
+    if entry in ("gemm_nt", "gemm_tn") and (d in CONV_SUB or d in ("M", "K", "Kk", "a_rows")):
         v = v + [NA]
     return v
 
@@ -541,6 +541,10 @@ def all_pairs(entry):
 
 
 _CACHE = {}
+# Other contract suites (tests/blk_contract.py) add their entry points to DIMS / RULES / TOPUP / INST / SEEDS and name, in
+# PLANNERS, the function (dims, seed) -> targets that mirrors their dispatcher; cases(entry) then serves them as well.
+SEEDS = {"gemm_nt": 1, "gemm_tn": 2, "conv_wgrad": 3}
+PLANNERS = {}
 
 
 def invalid_pairs(entry):
@@ -585,7 +589,7 @@ def cases(entry):
         out = _reduce_cases()
         _CACHE[entry] = (out, {})
         return out
-    rng = np.random.default_rng({"gemm_nt": 1, "gemm_tn": 2, "conv_wgrad": 3}[entry])
+    rng = np.random.default_rng(SEEDS[entry])
     todo = all_pairs(entry)
     covered, invalid, chosen = set(), {}, []
     for pr in todo:
@@ -628,7 +632,7 @@ def cases(entry):
 
 
 def _mk_case(entry, a, i):
-    b = build(Case(entry, "", a, (), 1000 + i), plan_only=True)
+    b = PLANNERS[entry](a, 1000 + i) if entry in PLANNERS else build(Case(entry, "", a, (), 1000 + i), plan_only=True)
     name = f"{i:03d}-" + "-".join(f"{v[0]}x{v[1]}" if isinstance(v, tuple) else str(v) for v in a.values() if v != NA)
     return Case(entry, name, a, b, 1000 + i)
 
@@ -714,6 +718,9 @@ def draw(g, rows, cols):
 
 def _alloc(n, fill):
     return torch.full((int(n) + 2 * GUARD,), fill, dtype=torch.float32)
+
+
+alloc, gen, pairs_of = _alloc, _gen, _pairs_of      # public names of the helpers other contract suites share
 
 
 def _rows_layout(kind, M, width, vec4):
@@ -929,6 +936,9 @@ def _tn_split(kind, M, unit=1):
         return ns + 1, rows
     rows = 37 if n > 37 else max(1, n - 1)      # "odd": not a multiple of 32
     return -(-n // rows), rows
+
+
+tn_split = _tn_split      # (public: tests/blk_contract.py splits block ranges with the same kinds)
 
 
 def _build_tn(case, plan_only):

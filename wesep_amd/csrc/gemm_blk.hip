@@ -599,7 +599,7 @@ extern "C" int ws_gemm_b2p(const ws_gemm_b2p_args* a, void* stream) {
   WS_REQUIRE(a && a->A && a->Wpack && a->C, "ws_gemm_b2p: null pointer");
   WS_REQUIRE(a->N == 128, "ws_gemm_b2p: N must be 128 (got %d)", a->N);
   WS_REQUIRE(a->a_fmt >= 0 && a->a_fmt <= 3 && (a->a_fmt < 2 || a->amax), "ws_gemm_b2p: a_fmt %d (2 / 3 need amax)", a->a_fmt);
-  WS_REQUIRE(a->a_fmt != 3 || !a->a16_out, "ws_gemm_b2p: a16_out goes with a_fmt 0");
+  WS_REQUIRE(a->a_fmt == 0 || !a->a16_out, "ws_gemm_b2p: a16_out goes with a_fmt 0 (got a_fmt %d)", a->a_fmt);
   WS_REQUIRE(a->K > 0 && a->K % 64 == 0, "ws_gemm_b2p: K %% 64 (K=%d)", a->K);
   WS_REQUIRE(a->ldc >= a->N && a->ldc % 4 == 0, "ws_gemm_b2p: ldc >= N and ldc %% 4 == 0 (16-byte row pieces)");
   WS_REQUIRE(a->sm.nseq > 0 && a->sm.L > 0 && a->sm.sq_div > 0, "ws_gemm_b2p: bad sequence map");
@@ -868,7 +868,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tnb16_kernel(const ws_gemm_tnb_ar
   constexpr int TA = 3, TN = 3;
   // GFMT 3 = the scaled-fp16 G of g_fmt 2 on v_mfma_f32_32x32x16_f16: G needs no split (its 11 bits ARE an fp16), the A
   // operand's bf16 hi / lo terms convert exactly to fp16 after a power-of-two lift (x 2^6: one packed exponent add per
-  // BLS word; keeps lo terms of |x| >= 5e-4 out of the fp16 denormals, |x| < 1023 finite) -> G A_hi + G A_lo, TWO MFMAs
+  // BLS word; keeps lo terms of |x| >= 5e-4 out of the fp16 denormals; |x| <= 1020 -- bf16(|x|) * 64 <= 65504 -- is the caller's precondition, wesep_hip.h) -> G A_hi + G A_lo, TWO MFMAs
   // per product instead of three (G_hi A_hi + G_hi A_lo + G_lo A_hi on the bf16 instruction)
   constexpr bool F16 = GFMT == 3;
   constexpr int NTERM = AF ? 1 : (GFMT == 2 ? 3 : 2);
