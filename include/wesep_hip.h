@@ -905,6 +905,7 @@ int ws_conv3x3(const ws_conv3x3_args* a, void* stream);
 /* ABI v19: the packed weights of ws_conv3x3 in ONE launch from up to WS_C3_NSRC strided views of weight tensors -- the logical
  * W[n][tap][c] (n < Cout rows, c < Cin columns, zero-padded to the fragment grid) takes column c from the source k whose range
  * [col_off, col_off + cols) holds it:  W = w_k[n * s_row + (c - col_off) * s_col + (flip ? 8 - tap : tap) * s_tap].
+ * A column that no source covers is zero.  The sources' column ranges must not overlap.
  * A layer's forward: one source, nn.Conv2d weight [co][ci][3][3] -> (s_row, s_col, s_tap) = (9 Ci, 9, 1), flip 0.  The input
  * gradient of a channel block [lo, hi) of a dense block (convs.py:80-112): sources = the weights of the layers that read the
  * block, pointers advanced to input channel lo, rows = the block's channels (s_row = 9), columns = the layers' output channels
@@ -929,7 +930,8 @@ int ws_conv3x3_pack(const ws_conv3x3_pack_args* a, void* stream);
  *   bslab[split][n]                    = sum over the split's pixels of G[m][n]                       (bslab may be NULL)
  * G [B*H*Wd rows, stride ldg >= Nn]; X [B][H][Wx] pixels of stride ldx >= Cin, Wd = (Wx - 1) / sw + 1.  The gradient grid
  * is cut into tiles of 30 rows x 4 columns (B * ceil(H / 30) * ceil(Wd / 4) of them, column-fastest); split s owns tiles
- * [s, s + 1) * tiles_per_split.  The caller sums the nsplit slabs (ws_reduce_slabs: deterministic, no atomics).
+ * [s, s + 1) * tiles_per_split.  A split that owns no tile writes zeros to its slab and its bslab.  The caller sums the
+ * nsplit slabs (ws_reduce_slabs: deterministic, no atomics).
  * Cin % 4 == 0, Nn % 4 == 0. */
 typedef struct ws_conv3x3_wgrad_args {
   const float* G;

@@ -455,15 +455,19 @@ def conv3x3_pack(W2, Cin, Cout):
     return W2.reshape(Cout, 9 * Cin).contiguous()       # the emulation keeps the plain rows
 
 
-def conv3x3_pack_srcs(srcs, Cin, Cout, flip=False):
-    """ws_conv3x3_pack: W[n][tap][c] = w_k.flat[off + n * s_row + (c - col_off) * s_col + (8 - tap if flip else tap) * s_tap]."""
+def conv3x3_pack_srcs(srcs, Cin, Cout, flip=False, out=None):
+    """ws_conv3x3_pack: W[n][tap][c] = w_k.flat[off + n * s_row + (c - col_off) * s_col + (8 - tap if flip else tap) * s_tap].
+    The emulation keeps the plain rows [Cout, 9 * Cin]; with `out` they go to its first Cout * 9 * Cin floats."""
     W = torch.zeros(Cout, 9, Cin)
     n = torch.arange(Cout).view(-1, 1, 1)
     tap = torch.arange(9).view(1, -1, 1)
     for w, off, s_row, s_col, s_tap, col_off, cols in srcs:
         c = torch.arange(cols).view(1, 1, -1)
         W[:, :, col_off:col_off + cols] = w.reshape(-1)[off + n * s_row + c * s_col + ((8 - tap) if flip else tap) * s_tap]
-    return W.reshape(Cout, 9 * Cin).contiguous()
+    W = W.reshape(Cout, 9 * Cin).contiguous()
+    if out is not None:
+        out.reshape(-1)[:Cout * 9 * Cin] = W.reshape(-1)
+    return W
 
 
 def conv3x3(*, X, ldx, W, ldw, B, H, Wd, Cin, Cout, Y, ldy, bias=None, R=None, x_off=0, y_off=0):
@@ -480,23 +484,30 @@ def conv3x3_wgrad_tiles(B, H, Wd):
     return B * (-(-H // 30)) * (-(-Wd // 4))
 
 
-def conv3x3_wgrad(*, G, ldg, X, ldx, B, H, Wd, Cin, Nn, slab, nsplit, tiles_per_split, bslab=None, sw=1, Wx=0, g_off=0):
-    """Slab 0 carries the whole gradient (the split of the pixels is a device detail), the others are zero."""
-    assert nsplit * tiles_per_split >= conv3x3_wgrad_tiles(B, H, Wd)
+def conv3x3_wgrad(*, G, ldg, X, ldx, B, H, Wd, Cin, Nn, slab, nsplit, tiles_per_split, bslab=None, sw=1, Wx=0, g_off=0,
+                  slab_stride=0, bslab_stride=0, x_off=0):
+    """Every split's slab by the header's tile ranges: tiles of 30 rows x 4 columns of the gradient grid, column-fastest,
+    split s owns tiles [s, s + 1) * tiles_per_split (a split that owns no tile writes zeros)."""
+    ntiles = conv3x3_wgrad_tiles(B, H, Wd)
+    assert nsplit * tiles_per_split >= ntiles
     Wx = Wx or Wd
     assert sw in (1, 2) and (Wx - 1) // sw + 1 == Wd
+    slab_stride, bslab_stride = slab_stride or Nn * 9 * Cin, bslab_stride or Nn
+    assert slab_stride >= Nn * 9 * Cin and bslab_stride >= Nn
     M, Mx = B * H * Wd, B * H * Wx
-    img = X.reshape(-1)[:Mx * ldx].reshape(B, H, Wx, ldx)[..., :Cin].permute(0, 3, 1, 2)
+    img = X.reshape(-1)[:Mx * ldx].reshape(B, H, Wx, ldx)[..., x_off:x_off + Cin].permute(0, 3, 1, 2)
     g = G.reshape(-1)[:M * ldg].reshape(B, H, Wd, ldg)[..., g_off:g_off + Nn].permute(0, 3, 1, 2)
-    # dW[n][c][ky][kx] = sum g[b][n][h][w] * xpad[b][c][h + ky][sw*w + kx]
-    dw = torch.nn.grad.conv2d_weight(img, (Nn, Cin, 3, 3), g, stride=(1, sw), padding=1)
-    sl = slab.reshape(-1)[:nsplit * Nn * 9 * Cin].reshape(nsplit, Nn * 9 * Cin)
-    sl.zero_()
-    sl[0] = dw.permute(0, 2, 3, 1).reshape(-1)
-    if bslab is not None:
-        bs = bslab.reshape(-1)[:nsplit * Nn].reshape(nsplit, Nn)
-        bs.zero_()
-        bs[0] = g.sum((0, 2, 3))
+    ncg, nrt = -(-Wd // 4), -(-H // 30)
+    tile = ((torch.arange(B).view(-1, 1, 1) * nrt + torch.arange(H).view(1, -1, 1) // 30) * ncg
+            + torch.arange(Wd).view(1, 1, -1) // 4)
+    owner = (tile // tiles_per_split).unsqueeze(1)                    # [B, 1, H, Wd]
+    for s in range(nsplit):
+        gs = torch.where(owner == s, g, torch.zeros(()))
+        # dW[n][c][ky][kx] = sum g[b][n][h][w] * xpad[b][c][h + ky][sw*w + kx]
+        dw = torch.nn.grad.conv2d_weight(img, (Nn, Cin, 3, 3), gs, stride=(1, sw), padding=1)
+        slab.reshape(-1)[s * slab_stride:s * slab_stride + Nn * 9 * Cin] = dw.permute(0, 2, 3, 1).reshape(-1)
+        if bslab is not None:
+            bslab.reshape(-1)[s * bslab_stride:s * bslab_stride + Nn] = gs.sum((0, 2, 3))
 
 
 IN_ELU_PRE, IN_ELU_POST = 1, 2

@@ -1668,14 +1668,20 @@ def conv3x3_pack_floats(Cin: int, Cout: int) -> int:
     return nch * 9 * ntp * 2 * 64 * 8 // 2
 
 
-def conv3x3_pack_srcs(srcs, Cin: int, Cout: int, flip: bool = False):
+def conv3x3_pack_srcs(srcs, Cin: int, Cout: int, flip: bool = False, out=None):
     """The packed weights of conv3x3 in ONE launch (ws_conv3x3_pack, ABI v19).  srcs: up to five (w, elem_off, s_row, s_col,
-    s_tap, col_off, cols) -- column c of the logical W[n][tap][c] comes from the source whose [col_off, col_off + cols) holds it:
+    s_tap, col_off, cols) -- column c of the logical W[n][tap][c] comes from the source whose [col_off, col_off + cols) holds it
+    (the ranges must not overlap; a column no source covers is zero):
     w.flat[elem_off + n * s_row + (c - col_off) * s_col + (8 - tap if flip else tap) * s_tap].  Replaces conv3x3_pack's ATen
-    composition (zeros, slice copy, casts, stack, permute: ~9 launches per pack)."""
+    composition (zeros, slice copy, casts, stack, permute: ~9 launches per pack).  out: where to write the
+    conv3x3_pack_floats(Cin, Cout) floats (default: a new tensor)."""
     if not 0 < len(srcs) <= 5:
         raise L.WesepHipError("conv3x3_pack_srcs: 1 .. 5 sources")
-    out = torch.empty(conv3x3_pack_floats(Cin, Cout), device=srcs[0][0].device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(conv3x3_pack_floats(Cin, Cout), device=srcs[0][0].device, dtype=torch.float32)
+    _chk(out, "conv3x3_pack_srcs out")
+    if out.numel() < conv3x3_pack_floats(Cin, Cout):
+        raise L.WesepHipError(f"conv3x3_pack_srcs: out holds {out.numel()} floats, the pack needs {conv3x3_pack_floats(Cin, Cout)}")
     a = L.Conv3x3PackArgs()
     for k, (w, off, s_row, s_col, s_tap, col_off, cols) in enumerate(srcs):
         _chk(w, "conv3x3_pack_srcs w")
@@ -1709,15 +1715,19 @@ def conv3x3_wgrad_tiles(B: int, H: int, Wd: int) -> int:
 
 
 def conv3x3_wgrad(*, G, ldg: int, X, ldx: int, B: int, H: int, Wd: int, Cin: int, Nn: int, slab, nsplit: int,
-                  tiles_per_split: int, bslab=None, sw: int = 1, Wx: int = 0, g_off: int = 0):
+                  tiles_per_split: int, bslab=None, sw: int = 1, Wx: int = 0, g_off: int = 0, slab_stride: int = 0,
+                  bslab_stride: int = 0, x_off: int = 0):
     """Weight (+ bias) gradient slabs of a 3 x 3 / padding 1 convolution with stride (1, sw), one pass over the image
-    (conv3x3.hip): slab [nsplit, Nn * 9 * Cin], bslab [nsplit, Nn].  Wd = width of the gradient grid, Wx = of the image."""
+    (conv3x3.hip): slab [nsplit, Nn * 9 * Cin], bslab [nsplit, Nn].  Wd = width of the gradient grid, Wx = of the image.
+    g_off / x_off: the gradient is columns [g_off, g_off + Nn) of rows of stride ldg, the image columns [x_off, x_off + Cin)
+    of pixels of stride ldx.  slab_stride / bslab_stride: floats between the splits' slabs (0: Nn * 9 * Cin / Nn)."""
     for n, t in (("G", G), ("X", X), ("slab", slab), ("bslab", bslab)):
         _chk(t, n)
     _cols_ok(G, B * H * Wd, ldg, g_off, Nn, "conv3x3_wgrad G")
+    _cols_ok(X, B * H * (Wx or Wd), ldx, x_off, Cin, "conv3x3_wgrad X")
     a = L.Conv3x3WgradArgs()
-    a.G, a.X, a.slab, a.bslab = _p(G, g_off), _p(X), _p(slab), _p(bslab)
-    a.ldg, a.ldx, a.slab_stride, a.bslab_stride = ldg, ldx, Nn * 9 * Cin, Nn
+    a.G, a.X, a.slab, a.bslab = _p(G, g_off), _p(X, x_off), _p(slab), _p(bslab)
+    a.ldg, a.ldx, a.slab_stride, a.bslab_stride = ldg, ldx, slab_stride or Nn * 9 * Cin, bslab_stride or Nn
     a.B, a.H, a.Wd, a.Wx, a.sw, a.Cin, a.Nn, a.nsplit, a.tiles_per_split = B, H, Wd, Wx or Wd, sw, Cin, Nn, nsplit, tiles_per_split
     _alg("gemm_tn", 4 * (B * H * (Wx or Wd) * Cin + B * H * Wd * Nn * (-(-Cin // 32)) + nsplit * Nn * 9 * Cin),
          2 * B * H * Wd * Nn * 9 * Cin)
