@@ -49,7 +49,8 @@ void ws_engine_destroy(ws_engine* e);
  * "cluster_fallbacks" (forwards so far in which a weight-stationary cluster recurrence timed out -- its workgroups were
  * not co-resident, e.g. several engines on one GPU -- and the predicated streaming kernels recomputed the layer;
  * wesep_hip.h, ws_lstm_fwd_cluster), "ragged_speaker" (1: enroll_lengths of ws_engine_separate_ragged run the speaker
- * encoder once over all rows, 0: one row at a time)}; unknown key -> -1. */
+ * encoder once over all rows, 0: one row at a time), "ragged_separator" (1: the separator takes the lengths of
+ * ws_engine_separate_ragged -- pBSRNN and TF-GridNet; 0: it refuses them)}; unknown key -> -1. */
 long long ws_engine_info(const ws_engine* e, const char* key);
 
 /* enrollment kinds */
@@ -65,8 +66,9 @@ long long ws_engine_info(const ws_engine* e, const char* key);
 int ws_engine_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind,
                        int enroll_len, float* est);
 
-/* Ragged batches (engine ABI 2; pBSRNN containers, arch 0): utterances of different lengths in ONE forward.  mix / est
- * keep the row pitch T; lengths[r] in [512, T] is the number of valid samples of row r.  est[r][0..lengths[r]) is what
+/* Ragged batches (engine ABI 2; pBSRNN and TF-GridNet containers, arch 0 and 3): utterances of different lengths in ONE
+ * forward.  mix / est keep the row pitch T; lengths[r] in [512, T] (TF-GridNet: [2 n_fft, T]) is the number of valid samples
+ * of row r.  est[r][0..lengths[r]) is what
  * ws_engine_separate returns for mix[r][0..lengths[r]) as a batch of one (reflect padding, GroupNorm statistics, the
  * reverse recurrence over time and the iSTFT envelope all end at the row's own end); est[r][lengths[r]..T) = 0; what the
  * caller left in mix[r][lengths[r]..T) is never read into a valid output (NaN included).
@@ -78,9 +80,11 @@ int ws_engine_separate(ws_engine* e, const float* mix, int R, int T, const void*
  * behind enroll_lengths[r] never reaches it (NaN included).  ws_engine_info(e, "ragged_speaker") is 1 for such a
  * container.  CAM++ and the MHASTP / MQMHASTP pools report 0 and run one enrollment at a time, as does every container
  * with WS_ENGINE_RAGGED_SPK=0 in the environment; the separator runs once over all rows either way.
- * lengths = enroll_lengths = NULL is ws_engine_separate (any architecture); with either given, a Conv-TasNet, DPCCN or
- * TF-GridNet container is refused (WS_ERR_INVALID).  The time-view recurrences of a ragged call run over precomputed
- * gates (the rows' tails are zeroed there); the number of launches depends on (R, T) only, not on the lengths. */
+ * lengths = enroll_lengths = NULL is ws_engine_separate (any architecture); with either given, a Conv-TasNet or DPCCN
+ * container is refused (WS_ERR_INVALID).  The recurrences over time of a ragged call (pBSRNN's time view, TF-GridNet's
+ * inter-frame path) run over precomputed gates (the rows' tails are zeroed there); the number of launches depends on
+ * (R, T) only, not on the lengths.  TF-GridNet: the row's standard deviation, its scaling and the scale-back run over its
+ * own samples; the frames follow the model's hop; the keys behind a row's last frame are masked out of the attention. */
 int ws_engine_separate_ragged(ws_engine* e, const float* mix, int R, int T, const int* lengths, const void* enroll,
                               int enroll_kind, int enroll_len, const int* enroll_lengths, float* est);
 

@@ -1047,6 +1047,30 @@ int ws_tail_select_len(const float* x, int R, int T, int C, const int* tlen, flo
 int ws_preemph_pad_len(const float* x, int R, int T, int pad, int ldo, float coef, const int* lengths, float* out,
                        void* stream);
 
+/* Ragged TF-GridNet (ragged_grid.hip): mixtures of different lengths in ONE forward over the rectangle
+ * [R][Tf][Q][C].  Per-frame layers run over the rectangle unchanged; these take the row's frame count where the model
+ * reduces over time, and replace per-(head, row) launch loops of the attention by one launch.  Length tables as above:
+ * device int[R], clamped where read, NULL is WS_ERR_INVALID; zeros are selected, never multiplied.
+ *   ws_flat_stats_len     ws_flat_stats whose group g covers its first glen[g] * per_step floats (glen[g] clamped to
+ *                         [1, n_per_group / per_step]; per_step % 4 == 0 divides n_per_group): stats[g] = (mean, 1 / sqrt(
+ *                         biased var + eps)) of them.  The chunked two-pass (count, mean, M2) scheme and fixed merge order
+ *                         of ws_flat_stats; a group's nchunk chunks divide its own count; scratch [ngroups][nchunk][4];
+ *                         nothing behind the count is read
+ *   ws_ola_norm_len       frames [R][Tf][n] (windowed synthesis frames, hop = n / 2, n % 8 == 0, Tf = 1 + T / hop), win [n]
+ *                         (the synthesis window) -> est [R][T]: est[r][i] = (sum over t < Tf_r of frames[r][t][i + n/2 - t hop])
+ *                         / (sum over the same t of win[i + n/2 - t hop]^2) for i < lengths[r] (clamped to [0, T]), Tf_r =
+ *                         1 + lengths[r] / hop; exact zeros from lengths[r] on.  The envelope is summed and inverted in
+ *                         double and rounded once.  Frames t >= Tf_r are not read
+ *   ws_transpose_batched  dst[g][c][r] = src[g][r][c] for G matrices in one launch (rows % 4 == 0, cols % 4 == 0; no overlap)
+ *   ws_heads_merge_fwd    o[r][p][h * cp + e] = ov[h][r][p][e]: the attention's head merge, [nh][R][P][cp] -> [R][P][nh * cp]
+ *                         (cp % 4 == 0; P = frames * bins of a row) */
+int ws_flat_stats_len(const float* x, int ngroups, long long n_per_group, const int* glen, int per_step, float eps,
+                      int nchunk, float* scratch, float* stats, void* stream);
+int ws_ola_norm_len(const float* frames, const float* win, int R, int Tf, int n, int T, const int* lengths, float* est,
+                    void* stream);
+int ws_transpose_batched(const float* src, int G, int rows, int cols, float* dst, void* stream);
+int ws_heads_merge_fwd(const float* ov, int nh, int R, long long P, int cp, float* o, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

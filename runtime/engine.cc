@@ -348,7 +348,9 @@ WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   if (k == "arch") return e->arch;
   if (k == "spk_pool" && (e->arch == 0 || e->arch == 2)) return e->spk.pool;   // meta, or the encoder's default
   // 1: enroll_lengths of ws_engine_separate_ragged run the speaker encoder once over all rows; 0: one row at a time
-  if (k == "ragged_speaker") return e->arch == 0 && ragged_speaker_covered(e) && ragged_speaker_enabled() ? 1 : 0;
+  if (k == "ragged_speaker") return (e->arch == 0 || e->arch == 3) && ragged_speaker_covered(e) && ragged_speaker_enabled() ? 1 : 0;
+  // 1: lengths of ws_engine_separate_ragged are taken (pBSRNN, TF-GridNet); 0: this separator refuses them
+  if (k == "ragged_separator") return e->arch == 0 || e->arch == 3 ? 1 : 0;
   auto it = e->meta.find(k);
   return it == e->meta.end() ? -1 : it->second;
 }
@@ -385,13 +387,15 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
                          int enroll_len, const int* enroll_lengths, float* est) {
   int rc = check_engine(e, lengths || enroll_lengths ? "ws_engine_separate_ragged" : "ws_engine_separate");
   if (rc != WS_OK) return rc;
-  if ((lengths || enroll_lengths) && e->arch != 0) {
-    set_err("ws_engine_separate_ragged: per-row lengths are built for pBSRNN (arch 0) only; this container holds arch %d",
-            e->arch);
+  if ((lengths || enroll_lengths) && e->arch != 0 && e->arch != 3) {
+    set_err("ws_engine_separate_ragged: per-row lengths are built for pBSRNN (arch 0) and TF-GridNet (arch 3) only; this "
+            "container holds arch %d", e->arch);
     return WS_ERR_INVALID;
   }
   if (e->arch == 1) return tasnet_separate(e, mix, R, T, enroll, enroll_kind, enroll_len, est);
-  if (!mix || !enroll || !est || R < 1 || T < 512 || (long long)R * (1 + T / kHop) * 4 * kNBin > 0x7fffffffLL) {
+  // (TF-GridNet's own lower bound is 2 * n_fft, checked below: a ragged row of that length is compared with this call)
+  const int t_min = e->arch == 3 && T >= 2 * e->grid.n_fft ? 2 * e->grid.n_fft : 512;
+  if (!mix || !enroll || !est || R < 1 || T < t_min || (long long)R * (1 + T / kHop) * 4 * kNBin > 0x7fffffffLL) {
     set_err("ws_engine_separate: bad arguments (R=%d, T=%d; T >= 512)", R, T);
     return WS_ERR_INVALID;
   }
@@ -417,13 +421,14 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
   if ((rc = enroll_frames(e, enroll_kind, enroll_len, &Te)) != WS_OK) return rc;
   std::vector<int> tf, te_row;
   if (lengths) {
-    // a row's own T: what this surface demands of T, and no more than the row pitch
+    // a row's own T: what this surface demands of T, and no more than the row pitch; frames with the model's own hop
+    const int lo = e->arch == 3 ? 2 * e->grid.n_fft : 512, hop = e->arch == 3 ? e->grid.hop : kHop;
     for (int r = 0; r < R; ++r) {
-      if (lengths[r] < 512 || lengths[r] > T) {
-        set_err("ws_engine_separate_ragged: lengths[%d] = %d outside [512, T = %d]", r, lengths[r], T);
+      if (lengths[r] < lo || lengths[r] > T) {
+        set_err("ws_engine_separate_ragged: lengths[%d] = %d outside [%d, T = %d]", r, lengths[r], lo, T);
         return WS_ERR_INVALID;
       }
-      tf.push_back(1 + lengths[r] / kHop);
+      tf.push_back(1 + lengths[r] / hop);
     }
   }
   if (enroll_lengths) {
@@ -460,20 +465,22 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
   float* d_est = a.alloc(size_t(R) * T);
   float* d_emb = a.alloc(size_t(R) * e->E);
   WS_PTR(d_mix && d_est && d_emb);
-  // TF-GridNet scales the mixture by its (unbiased) standard deviation and the estimate back (tfgridnet.py:222-226,292)
+  // TF-GridNet scales the mixture by its (unbiased) standard deviation and the estimate back (tfgridnet.py:222-226,292);
+  // a ragged row over its own samples (the tail of the scaled copy is zeros: nothing behind a length is read)
   std::vector<float> mixn, stds;
   if (e->arch == 3) {
-    mixn.resize(size_t(R) * T);
+    mixn.assign(size_t(R) * T, 0.f);
     stds.resize(R);
     for (int r = 0; r < R; ++r) {
       const float* x = mix + size_t(r) * T;
+      const int n = lengths ? lengths[r] : T;
       double m = 0.0, v = 0.0;
-      for (int i = 0; i < T; ++i) m += x[i];
-      m /= T;
-      for (int i = 0; i < T; ++i) v += (x[i] - m) * (x[i] - m);
-      stds[r] = static_cast<float>(sqrt(v / (T - 1.0)));
+      for (int i = 0; i < n; ++i) m += x[i];
+      m /= n;
+      for (int i = 0; i < n; ++i) v += (x[i] - m) * (x[i] - m);
+      stds[r] = static_cast<float>(sqrt(v / (n - 1.0)));
       const float inv = 1.0f / stds[r];
-      for (int i = 0; i < T; ++i) mixn[size_t(r) * T + i] = x[i] * inv;
+      for (int i = 0; i < n; ++i) mixn[size_t(r) * T + i] = x[i] * inv;
     }
     mix = mixn.data();
   }
@@ -505,13 +512,13 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
     return rc;
   }
   rc = e->arch == 2 ? dpccn_device(e, d_mix, R, T, d_emb, d_est)
-                    : e->arch == 3 ? gridnet_device(e, d_mix, R, T, d_emb, d_est)
+                    : e->arch == 3 ? gridnet_device(e, d_mix, R, T, d_emb, d_est, lengths ? tf.data() : nullptr, d_len, d_tf)
                                    : separate_device(e, d_mix, R, T, d_emb, d_est, d_len, d_tf);
   if (rc != WS_OK) return rc;
   if ((rc = to_host(e, est, d_est, size_t(R) * T * 4)) != WS_OK) return rc;
   if (e->arch == 3 && !e->dry)
     for (int r = 0; r < R; ++r)
-      for (int i = 0; i < T; ++i) est[size_t(r) * T + i] *= stds[r];
+      for (int i = 0, n = lengths ? lengths[r] : T; i < n; ++i) est[size_t(r) * T + i] *= stds[r];
   if (e->cl_status && !e->dry) {   // did a cluster recurrence time out (and the predicated streaming pair repair it)?
     unsigned st = 0;
     if ((rc = to_host(e, &st, e->cl_status, 4)) != WS_OK) return rc;

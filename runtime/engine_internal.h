@@ -381,7 +381,10 @@ int dp_io_convs(ws_engine* e, const std::string& conv, int cin, const std::strin
 int dft_bases(ws_engine* e, int n, float** ana4, float** syn4);
 int dft_istft(ws_engine* e, const float* est4, const float* syn4, int R, int Tf, int n, int hop, int T, float* est);
 int prepare_gridnet(ws_engine* e);
-int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est);
+// h_tf (host), d_len / d_tf (device), [R], all or none: the rows' own frame counts 1 + lengths[r] / hop, samples and frame
+// counts -- one forward over the rectangle, the length where the model reduces over time (gridnet_plan.cc)
+int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est, const int* h_tf = nullptr,
+                   const int* d_len = nullptr, const int* d_tf = nullptr);
 
 }  // namespace wsrt
 

@@ -9,6 +9,9 @@
 // projection GEMM for Q / K / V, ws_heads_fwd, grouped logits GEMM with the padded keys masked, row softmax, grouped
 // value GEMM, head merge, projection + PReLU + LayerNorm over (bins, channels), residual); ConvTranspose2d(C -> 2).
 // The mixture is scaled by its standard deviation on the host (tfgridnet.py:222-226), the estimate scaled back.
+// Ragged batches: with per-row lengths the same plan runs over the rectangle; the row's frame count
+// Tf_r = 1 + lengths[r] / hop goes to the reflect padding, the zero frames the two 3x3 convolutions read behind a row's
+// end, the GroupNorm statistics, the inter-frame BLSTM's gates, the key mask and the overlap-add -- nowhere else.
 // =================================================================================================================
 #include "engine_internal.h"
 
@@ -164,14 +167,17 @@ int prepare_gridnet(ws_engine* e) {
 }
 
 // out = res + Linear(BLSTM(xn)) on the sequences of `sm` (rows of 128 features; xn = the layer-normed rows): the body of
-// resrnn() without its GroupNorm (functional_tfgridnet.BlstmLinearBlkFn)
-int grid_rnn(ws_engine* e, const RnnPrep& w, const ws_seqmap& sm, const float* xn_rows, const float* res, float* out) {
+// resrnn() without its GroupNorm (functional_tfgridnet.BlstmLinearBlkFn).  steps (device, ragged inter-frame path): sequence
+// s has steps[s / steps_div] valid steps -- the gates behind them are zeros (ws_gemm_p2b_len), so the reverse direction
+// reaches a row's last frame with zero state; only the branches over precomputed gates know such a table
+int grid_rnn(ws_engine* e, const RnnPrep& w, const ws_seqmap& sm, const float* xn_rows, const float* res, float* out,
+             const int* steps = nullptr, int steps_div = 1) {
   const int ntile = (sm.nseq + 31) / 32;
   const size_t nb = size_t(ntile) * sm.L;
   const int lmode = 2 * ntile <= 128 ? WS_LSTM_BF16X3_BLK16 : WS_LSTM_BF16X3_BLK;
   static const bool no_cluster = getenv("WS_ENGINE_NO_CLUSTER") != nullptr;
   const bool cluster = !no_cluster && sm.nseq % 64 == 0 && (sm.nseq / 32) * 8 <= e->cu_count && sm.L >= 64;
-  const bool fused = !cluster && lmode == WS_LSTM_BF16X3_BLK;
+  const bool fused = !cluster && lmode == WS_LSTM_BF16X3_BLK && !steps;
   void* s = e->stream;
   Arena& a = e->work;
   const Arena::Mark mk = a.mark();
@@ -192,7 +198,10 @@ int grid_rnn(ws_engine* e, const RnnPrep& w, const ws_seqmap& sm, const float* x
     WS_RUN(e, ws_lstm_fwd_fused(&f, s));
   } else {
     p.Wpack = w.wih_pack, p.bias = w.bcat, p.C = gates, p.N = 2 * kG4;
-    WS_RUN(e, ws_gemm_p2b(&p, s));
+    if (steps)
+      WS_RUN(e, ws_gemm_p2b_len(&p, steps, steps_div, s));
+    else
+      WS_RUN(e, ws_gemm_p2b(&p, s));
     ws_lstm_args l = {};
     l.gates = gates, l.cbuf = cbuf, l.hcat = hcat;
     l.wpack = lmode == WS_LSTM_BF16X3_BLK16 ? w.pack16 : w.pack32;
@@ -213,7 +222,10 @@ int grid_rnn(ws_engine* e, const RnnPrep& w, const ws_seqmap& sm, const float* x
       c.xchg = xchg, c.flags = flags, c.nseq = sm.nseq, c.L = sm.L, c.status = e->cl_status;
       WS_RUN(e, ws_lstm_fwd_cluster(&c, s));
       p.run_if = flags + size_t(ncl) * 8;      // the streaming pair repeats the layer only after a cluster time-out
-      WS_RUN(e, ws_gemm_p2b(&p, s));
+      if (steps)
+        WS_RUN(e, ws_gemm_p2b_len(&p, steps, steps_div, s));
+      else
+        WS_RUN(e, ws_gemm_p2b(&p, s));
       l.run_if = p.run_if;
     }
     WS_RUN(e, ws_lstm_fwd(&l, s));
@@ -225,20 +237,29 @@ int grid_rnn(ws_engine* e, const RnnPrep& w, const ws_seqmap& sm, const float* x
   return WS_OK;
 }
 
-// C[g][M][N] = A[g][M][K] W[g][N][K]^T (+ bias[N]) for G groups in one launch (functional_tfgridnet.BatchedMatmulNTFn)
-int grid_bmm(ws_engine* e, const float* A, const float* W, const float* bias, int G, int M, int K, int N, float* C) {
+// the group table of grid_bmm on the device (an upload: it synchronises the stream).  bias_rows = 0: every group adds
+// bias[N]; else group g adds row g % bias_rows of bias [bias_rows][N] (the ragged key mask of row r = g % R)
+ws_group_nt* grid_bmm_table(ws_engine* e, const float* W, const float* bias, int bias_rows, int G, int M, int K, int N) {
   std::vector<ws_group_nt> tab(G);
   for (int g = 0; g < G; ++g) {
     ws_group_nt d = {};
-    d.W = W + size_t(g) * N * K, d.bias = bias, d.a_off = (long long)g * M * K, d.c_off = (long long)g * M * N;
+    d.W = W + size_t(g) * N * K, d.a_off = (long long)g * M * K, d.c_off = (long long)g * M * N;
+    d.bias = bias && bias_rows ? bias + size_t(g % bias_rows) * N : bias;
     d.K = K, d.N = N, d.ldw = K;
     tab[g] = d;
   }
   const size_t nf = (sizeof(ws_group_nt) * G + 3) / 4;
   ws_group_nt* dt = reinterpret_cast<ws_group_nt*>(e->work.alloc(nf));
+  if (!dt || to_device(e, dt, tab.data(), sizeof(ws_group_nt) * G) != WS_OK) return nullptr;
+  return dt;
+}
+
+// C[g][M][N] = A[g][M][K] W[g][N][K]^T (+ bias[N]) for G groups in one launch (functional_tfgridnet.BatchedMatmulNTFn);
+// dt: a table built before (the ragged plan uploads both of its tables once, ahead of the first launch), or NULL
+int grid_bmm(ws_engine* e, const float* A, const float* W, const float* bias, int G, int M, int K, int N, float* C,
+             const ws_group_nt* dt = nullptr) {
+  if (!dt) dt = grid_bmm_table(e, W, bias, 0, G, M, K, N);
   WS_PTR(dt);
-  int rc = to_device(e, dt, tab.data(), sizeof(ws_group_nt) * G);
-  if (rc != WS_OK) return rc;
   ws_gemm_nt_args g = {};
   g.A = A, g.C = C, g.groups = dt;
   g.a_div = kBig, g.a_s2 = K, g.c_div = kBig, g.c_s2 = N, g.st_div1 = 1, g.st_div2 = 1;
@@ -249,7 +270,8 @@ int grid_bmm(ws_engine* e, const float* A, const float* W, const float* bias, in
 }
 
 // wav [R][T] (already divided by its standard deviation), emb [R][E] -> est [R][T] (still in normalised units)
-int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est) {
+int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est, const int* h_tf,
+                   const int* d_len, const int* d_tf) {
   const GridNet& n = e->grid;
   const int nf = n.n_fft, hop = n.hop, pad = nf / 2, Tf = 1 + T / hop, Q = n.Q, C = n.C, nh = n.nh, E = n.E, cp = C / nh;
   const int ld4 = 4 * Q, Tp = (Tf + 3) / 4 * 4, G = nh * R, D = Q * E, Dv = Q * cp, ldq = 2 * nh * E + C;
@@ -257,6 +279,11 @@ int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* em
   void* s = e->stream;
   Arena& a = e->work;
   int rc;
+  const bool ragged = h_tf != nullptr;
+  if (ragged && !(d_len && d_tf)) {
+    set_err("engine: the ragged TF-GridNet plan needs the host and both device length tables");
+    return WS_ERR_INVALID;
+  }
   // ---- STFT ----
   const int ldo = (T + 2 * pad + 3) / 4 * 4;
   float* xp = a.alloc(size_t(R) * ldo);
@@ -265,8 +292,30 @@ int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* em
   float* hB = a.alloc(size_t(M) * C);
   float* hC = a.alloc(size_t(M) * C);
   WS_PTR(xp && spec4 && hA && hB && hC);
+  // ---- ragged: every table of the forward goes up before the first launch (an upload synchronises the stream), so the
+  //      attention's operands live outside the block loop and their two group tables are built once ----
+  float *mask = nullptr, *win = nullptr, *Qa = nullptr, *Ka = nullptr, *VaT = nullptr, *logits = nullptr, *att = nullptr, *ov = nullptr;
+  const ws_group_nt *tab_qk = nullptr, *tab_av = nullptr;
+  if (ragged) {
+    std::vector<float> mask_h(size_t(R) * Tp, 0.f), win_h(nf);
+    for (int r = 0; r < R; ++r)
+      for (int t = h_tf[r]; t < Tp; ++t) mask_h[size_t(r) * Tp + t] = -1e30f;       // keys behind the row's own frames
+    const double pi = 3.14159265358979323846;
+    for (int k = 0; k < nf; ++k) win_h[k] = static_cast<float>(0.5 - 0.5 * cos(2.0 * pi * k / nf));   // as dft_istft's envelope
+    mask = upload(e, a, mask_h.data(), mask_h.size());
+    win = upload(e, a, win_h.data(), win_h.size());
+    Qa = a.alloc(size_t(G) * Tf * D), Ka = a.alloc(size_t(G) * Tp * D), VaT = a.alloc(size_t(G) * Tp * Dv);
+    logits = a.alloc(size_t(G) * Tf * Tp), att = a.alloc(size_t(G) * Tf * Tp), ov = a.alloc(size_t(G) * Tf * Dv);
+    WS_PTR(mask && win && Qa && Ka && VaT && logits && att && ov);
+    tab_qk = grid_bmm_table(e, Ka, mask, R, G, Tf, D, Tp);          // group (head, r) = head * R + r reads mask row r
+    tab_av = grid_bmm_table(e, VaT, nullptr, 0, G, Tf, Tp, Dv);
+    WS_PTR(tab_qk && tab_av);
+  }
   if ((rc = zero_device(e, xp, size_t(R) * ldo * 4)) != WS_OK) return rc;
-  WS_RUN(e, ws_preemph_pad(wav, R, T, pad, ldo, 0.0f, xp, s));
+  if (ragged)      // the reflect padding turns at the row's own end; nothing behind lengths[r] is read
+    WS_RUN(e, ws_preemph_pad_len(wav, R, T, pad, ldo, 0.0f, d_len, xp, s));
+  else
+    WS_RUN(e, ws_preemph_pad(wav, R, T, pad, ldo, 0.0f, xp, s));
   {
     ws_gemm_nt_args g = {};
     g.A = xp, g.W = n.ana4, g.C = spec4;
@@ -274,12 +323,25 @@ int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* em
     g.M = R * Tf, g.N = ld4, g.K = nf, g.ldw = nf, g.vec = 3;
     WS_RUN(e, ws_gemm_nt(&g, s));
   }
+  // frame Tf_r still overlaps the reflected samples: the 3x3 convolution reads zeros there, as its padding on the row alone
+  if (ragged) WS_RUN(e, ws_tail_select_len(spec4, R, Tf, ld4, d_tf, spec4, s));
   // ---- Conv2d(2 -> C) + GroupNorm(1, C) ----
   if ((rc = dp_conv_view(e, spec4, R, Tf, Q, 4, 0, Q, 1, n.w_in, C, e->dev("conv.0.bias"), hB, C)) != WS_OK) return rc;
   {
     float* st = a.alloc(size_t(R) * 2);
     WS_PTR(st);
-    if ((rc = tas_flat_stats(e, hB, R, (long long)Tf * Q * C, st)) != WS_OK) return rc;
+    if (ragged) {                          // over the row's own frames; the chunk count of tas_flat_stats
+      const long long npg = (long long)Tf * Q * C;
+      int nchunk = static_cast<int>(npg / 16384);
+      const int cap = 512 / R > 1 ? 512 / R : 1;
+      if (nchunk > cap) nchunk = cap;
+      if (nchunk < 1) nchunk = 1;
+      float* scratch = a.alloc(size_t(R) * nchunk * 4);
+      WS_PTR(scratch);
+      WS_RUN(e, ws_flat_stats_len(hB, R, npg, d_tf, Q * C, kLnEps, nchunk, scratch, st, s));
+    } else if ((rc = tas_flat_stats(e, hB, R, (long long)Tf * Q * C, st)) != WS_OK) {
+      return rc;
+    }
     WS_RUN(e, ws_dwconv_fwd(hB, st, e->dev("conv.1.weight"), e->dev("conv.1.bias"), n.ones_c, n.zeros_c, R, Tf * Q, C, 1, 1, Tf * Q,
                             hA, s));
   }
@@ -299,10 +361,12 @@ int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* em
   } else if ((rc = linear(e, emb, R, e->E, e->dev("spk_fuse.fc.linear.weight"), e->E, Q, e->dev("spk_fuse.fc.linear.bias"), 0, sf)) != WS_OK) {
     return rc;
   }
-  std::vector<float> mask_h(Tp, 0.f);
-  for (int t = Tf; t < Tp; ++t) mask_h[t] = -1e30f;
-  float* mask = upload(e, a, mask_h.data(), mask_h.size());
-  WS_PTR(mask);
+  if (!ragged) {
+    std::vector<float> mask_h(Tp, 0.f);
+    for (int t = Tf; t < Tp; ++t) mask_h[t] = -1e30f;
+    mask = upload(e, a, mask_h.data(), mask_h.size());
+    WS_PTR(mask);
+  }
   ws_seqmap intra = {}, inter = {};
   intra.nseq = R * Tf, intra.sq_div = kBig, intra.sq_s1 = 0, intra.sq_s2 = Q, intra.step_rows = 1, intra.L = Q;
   inter.nseq = R * Q, inter.sq_div = Q, inter.sq_s1 = (long long)Tf * Q, inter.sq_s2 = 1, inter.step_rows = Q, inter.L = Tf;
@@ -328,17 +392,14 @@ int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* em
     if ((rc = grid_rnn(e, b.intra, intra, y, x, hC)) != WS_OK) return rc;
     // inter-frame path: hC -> x  (strided sequences: no transposes)
     WS_RUN(e, ws_rowln_fwd(hC, b.inter.norm_w, b.inter.norm_b, M, C, kLnEps, y, lnst, s));
-    if ((rc = grid_rnn(e, b.inter, inter, y, hC, x)) != WS_OK) return rc;
+    if ((rc = grid_rnn(e, b.inter, inter, y, hC, x, d_tf, Q)) != WS_OK) return rc;       // sequence (r, q): Tf_r steps
     // attention on `x` (the block's `inter` tensor)
     float* qkv = a.alloc(size_t(M) * ldq);
-    float* Qa = a.alloc(size_t(G) * Tf * D);
-    float* Ka = a.alloc(size_t(G) * Tp * D);
+    if (!ragged) Qa = a.alloc(size_t(G) * Tf * D), Ka = a.alloc(size_t(G) * Tp * D);
     float* Va = a.alloc(size_t(G) * Tp * Dv);
-    float* VaT = a.alloc(size_t(G) * Tp * Dv);
+    if (!ragged) VaT = a.alloc(size_t(G) * Tp * Dv);
     float* hst = a.alloc(size_t(nh) * R * Tf * 2);
-    float* logits = a.alloc(size_t(G) * Tf * Tp);
-    float* att = a.alloc(size_t(G) * Tf * Tp);
-    float* ov = a.alloc(size_t(G) * Tf * Dv);
+    if (!ragged) logits = a.alloc(size_t(G) * Tf * Tp), att = a.alloc(size_t(G) * Tf * Tp), ov = a.alloc(size_t(G) * Tf * Dv);
     WS_PTR(qkv && Qa && Ka && Va && VaT && hst && logits && att && ov);
     if ((rc = dp_gemm(e, x, M, C, b.wqkv, ldq, b.bqkv, nullptr, qkv, ldq)) != WS_OK) return rc;
     const char* norm[3] = {"attn_norm_Q.", "attn_norm_K.", "attn_norm_V."};
@@ -351,18 +412,25 @@ int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* em
       ha.eps = kLnEps;
       WS_RUN(e, ws_heads_fwd(&ha, s));
     }
-    if ((rc = grid_bmm(e, Qa, Ka, mask, G, Tf, D, Tp, logits)) != WS_OK) return rc;
+    // (ragged: the keys t >= Tf_r of row r carry -1e30, so their weights are exact zeros on finite values)
+    if ((rc = grid_bmm(e, Qa, Ka, mask, G, Tf, D, Tp, logits, tab_qk)) != WS_OK) return rc;
     WS_RUN(e, ws_softmax_rows_fwd(logits, (long long)G * Tf, Tp, 1.0f / sqrtf(static_cast<float>(D)), att, s));
-    for (int g = 0; g < G; ++g)
-      WS_RUN(e, ws_transpose(Va + size_t(g) * Tp * Dv, Tp, Dv, Dv, VaT + size_t(g) * Tp * Dv, s));
-    if ((rc = grid_bmm(e, att, VaT, nullptr, G, Tf, Tp, Dv, ov)) != WS_OK) return rc;
+    if (ragged)
+      WS_RUN(e, ws_transpose_batched(Va, G, Tp, Dv, VaT, s));
+    else
+      for (int g = 0; g < G; ++g)
+        WS_RUN(e, ws_transpose(Va + size_t(g) * Tp * Dv, Tp, Dv, Dv, VaT + size_t(g) * Tp * Dv, s));
+    if ((rc = grid_bmm(e, att, VaT, nullptr, G, Tf, Tp, Dv, ov, tab_av)) != WS_OK) return rc;
     // head merge: ov [nh][R][Tf][Q][cp] -> [R][Tf][Q][nh*cp]
     float* o = y;                          // y is free again
-    for (int hd = 0; hd < nh; ++hd)
-      for (int r = 0; r < R; ++r)
-        if ((rc = copy_cols(e, o + (size_t(r) * Tf * Q) * C + hd * cp, C, ov + (size_t(hd) * R + r) * Tf * Dv, cp, cp,
-                            (long long)Tf * Q)) != WS_OK)
-          return rc;
+    if (ragged)
+      WS_RUN(e, ws_heads_merge_fwd(ov, nh, R, (long long)Tf * Q, cp, o, s));
+    else
+      for (int hd = 0; hd < nh; ++hd)
+        for (int r = 0; r < R; ++r)
+          if ((rc = copy_cols(e, o + (size_t(r) * Tf * Q) * C + hd * cp, C, ov + (size_t(hd) * R + r) * Tf * Dv, cp, cp,
+                              (long long)Tf * Q)) != WS_OK)
+            return rc;
     // projection + PReLU + LayerNorm over (bins, channels) + residual -> the next block's input
     float* p1 = a.alloc(size_t(M) * C);
     float* p2 = a.alloc(size_t(M) * C);
@@ -380,8 +448,21 @@ int gridnet_device(ws_engine* e, const float* wav, int R, int T, const float* em
   // ---- ConvTranspose2d(C -> 2) and the inverse STFT ----
   float* est4 = a.alloc(size_t(M) * 4);
   WS_PTR(est4);
+  // (ragged: the transposed 3x3 convolution at frame Tf_r - 1 reads zeros at frame Tf_r, as its padding on the row alone)
+  if (ragged) WS_RUN(e, ws_tail_select_len(h, R, Tf, Q * C, d_tf, h, s));
   if ((rc = dp_conv_view(e, h, R, Tf, Q, C, 1, Q, 1, n.w_out, 4, n.b_out, est4, 4)) != WS_OK) return rc;
-  return dft_istft(e, est4, n.syn4, R, Tf, nf, hop, T, est);
+  if (!ragged) return dft_istft(e, est4, n.syn4, R, Tf, nf, hop, T, est);
+  // dft_istft's synthesis GEMM, then one launch for overlap-add over t < Tf_r, 1 / envelope over those frames, centre trim
+  // and the zeros from lengths[r] on
+  float* fr = a.alloc(size_t(R) * Tf * nf);
+  WS_PTR(fr);
+  ws_gemm_nt_args g = {};
+  g.A = est4, g.W = n.syn4, g.C = fr;
+  g.a_div = kBig, g.a_s2 = ld4, g.c_div = kBig, g.c_s2 = nf, g.st_div1 = 1, g.st_div2 = 1;
+  g.M = R * Tf, g.N = nf, g.K = ld4, g.ldw = ld4, g.vec = 3;
+  WS_RUN(e, ws_gemm_nt(&g, s));
+  WS_RUN(e, ws_ola_norm_len(fr, win, R, Tf, nf, T, d_len, est, s));
+  return WS_OK;
 }
 
 }  // namespace wsrt

@@ -12,7 +12,7 @@
 // copy -- 0.3 GB of 288), spread round-robin over --devices.  Engines that share a GPU overlap on the device (round 2
 // serialised them; round 3 removed the cause -- profiles/r03_kernel_race.md -- and WS_ENGINE_SERIALIZE=1 restores one
 // forward at a time per GPU).  The reference tool is single-threaded on CPU cores.
-// --batch N (default 1 = the path above; pBSRNN models): N consecutive lines of the scp go through ONE forward of 2 N rows
+// --batch N (default 1 = the path above; pBSRNN and TF-GridNet models): N consecutive lines of the scp go through ONE forward of 2 N rows
 // (ws_engine_separate_ragged: every row keeps its own length, every enrollment its own -- each cut to the shorter of its
 // pair as above -- so the estimates are those of --batch 1); same output names and formats; works with --jobs (a worker
 // takes the next N lines) and --dry_run.  The rectangle is as long as the longest of the N.
@@ -117,7 +117,7 @@ int main(int argc, char** argv) {
   if (args.has("help")) {
     printf("usage: separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1]\n"
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
-           "  --batch N          N scp lines per forward (pBSRNN models), every row at its own length\n"
+           "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
            "                     is accepted and changes nothing\n");

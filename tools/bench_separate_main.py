@@ -11,7 +11,8 @@
 Workload (the one of profiles/ragged_batch.md, now reproducible): 64 utterances, mixtures uniform in 1-8 s, two
 enrollments per utterance uniform in 3-6 s, 16 kHz int16 noise; models with random weights: joint pBSRNN (6 repeats,
 multiply fusion, no multi-fuse) + ResNet34 (TSTP) on waveform enrollment ("resnet34"), and the same separator with
-ECAPA-TDNN c512 + ASTP ("ecapa").  Everything is written under --work; nothing outside the tree is read.
+ECAPA-TDNN c512 + ASTP ("ecapa"); with --models tfgridnet the recipe's TF-GridNet (6 blocks) + ResNet34.  Everything
+is written under --work; nothing outside the tree is read.
 
 An arm is NAME=EXE[:ARG,ARG...[:ENV=VALUE,...]].  The runner warms every arm up once per model, then runs the arms
 alternating, --runs times each, and records per run the tool's own total (engine ms: the sum of the forwards' host times,
@@ -32,7 +33,13 @@ MODELS = {
     "resnet34": dict(spk_model="ResNet34", spk_emb_dim=256,
                      spk_args=dict(feat_dim=80, embed_dim=256, pooling_func="TSTP", two_emb_layer=False)),
     "ecapa": dict(spk_model="ECAPA_TDNN_c512", spk_emb_dim=192, spk_args=dict(feat_dim=80, embed_dim=192, pooling_func="ASTP")),
+    # --models tfgridnet (not in the default set): the recipe's TF-GridNet, 6 blocks, joint ResNet34 (profiles/ragged_gridnet.md)
+    "tfgridnet": dict(separator="TFGridNet", spk_model="ResNet34", spk_emb_dim=256,
+                      spk_args=dict(feat_dim=80, embed_dim=256, pooling_func="TSTP", two_emb_layer=False)),
 }
+DEFAULT_MODELS = ("resnet34", "ecapa")
+TFGRIDNET = dict(n_fft=128, stride=64, n_layers=6, lstm_hidden_units=192, attn_n_head=4, attn_approx_qk_dim=512, emb_dim=128,
+                 emb_ks=1, emb_hs=1, spk_fuse_type="multiply", use_spk_transform=False)
 
 
 def _write_wav(path, x, sr=16000):
@@ -49,7 +56,7 @@ def workload(seed=2024, n=64, sr=16000):
     return rng.integers(1 * sr, 8 * sr + 1, n), rng.integers(3 * sr, 6 * sr + 1, (n, 2)), rng
 
 
-def generate(work, seed=2024, n=64, models=tuple(MODELS)):
+def generate(work, seed=2024, n=64, models=DEFAULT_MODELS):
     sys.path.insert(0, ROOT)
     import torch
     from wesep_amd.bin.export_engine import export_engine
@@ -66,8 +73,12 @@ def generate(work, seed=2024, n=64, models=tuple(MODELS)):
         f.writelines(lines)
     for name in models:
         torch.manual_seed(seed)
-        model = get_model("BSRNN")(num_repeat=6, spk_fuse_type="multiply", multi_fuse=False, use_spk_transform=False,
-                                   joint_training=True, spk_feat=True, **MODELS[name])
+        kw = dict(MODELS[name])
+        if kw.pop("separator", "BSRNN") == "TFGridNet":
+            model = get_model("TFGridNet")(joint_training=True, spk_feat=True, **TFGRIDNET, **kw)
+        else:
+            model = get_model("BSRNN")(num_repeat=6, spk_fuse_type="multiply", multi_fuse=False, use_spk_transform=False,
+                                       joint_training=True, spk_feat=True, **kw)
         with torch.no_grad():
             for key, buf in model.named_buffers():
                 if key.endswith("running_var"):
@@ -107,7 +118,7 @@ def main():
     ap.add_argument("--gen", action="store_true")
     ap.add_argument("--run", action="store_true")
     ap.add_argument("--arm", action="append", default=[])
-    ap.add_argument("--models", default=",".join(MODELS))
+    ap.add_argument("--models", default=",".join(DEFAULT_MODELS))
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--utterances", type=int, default=64)

@@ -299,6 +299,10 @@ _SIGS = {
     "ws_cmn_len": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "ws_tail_select_len": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "ws_preemph_pad_len": (_i, [_p, _i, _i, _i, _i, C.c_float, _p, _p, _p]),
+    "ws_flat_stats_len": (_i, [_p, _i, _ll, _p, _i, C.c_float, _i, _p, _p, _p]),
+    "ws_ola_norm_len": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "ws_transpose_batched": (_i, [_p, _i, _i, _i, _p, _p]),
+    "ws_heads_merge_fwd": (_i, [_p, _i, _i, _ll, _i, _p, _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -1603,6 +1603,37 @@ def preemph_pad_len(x, R: int, T: int, pad: int, ldo: int, coef: float, lengths,
     _call("ws_preemph_pad_len", _p(x), R, T, pad, ldo, coef, _tab(lengths), _p(out))
 
 
+# ---- ragged TF-GridNet (ragged_grid.hip) -----------------------------------------------------------
+def flat_stats_len(x, ngroups: int, n_per_group: int, glen, per_step: int, stats, eps=LN_EPS, nchunk=None):
+    """(mean, rstd) of the first glen[g] * per_step floats of contiguous groups; nchunk = None: the rule of flat_stats."""
+    if nchunk is None:
+        nchunk = max(1, min(max(1, 512 // ngroups), n_per_group // 16384))
+    scratch = torch.empty(ngroups, nchunk, 4, device=x.device, dtype=torch.float32)
+    _chk(x, "x")
+    _chk(stats, "stats")
+    _chk_lens(glen, ngroups, "ws_flat_stats_len")
+    _call("ws_flat_stats_len", _p(x), ngroups, n_per_group, _tab(glen), per_step, eps, nchunk, _p(scratch), _p(stats))
+
+
+def ola_norm_len(frames, win, R: int, Tf: int, n: int, T: int, lengths, est):
+    for nm, t in (("frames", frames), ("win", win), ("est", est)):
+        _chk(t, nm)
+    _chk_lens(lengths, R, "ws_ola_norm_len")
+    _call("ws_ola_norm_len", _p(frames), _p(win), R, Tf, n, T, _tab(lengths), _p(est))
+
+
+def transpose_batched(src, G: int, rows: int, cols: int, dst):
+    _chk(src, "src")
+    _chk(dst, "dst")
+    _call("ws_transpose_batched", _p(src), G, rows, cols, _p(dst))
+
+
+def heads_merge_fwd(ov, nh: int, R: int, P: int, cp: int, o):
+    _chk(ov, "ov")
+    _chk(o, "o")
+    _call("ws_heads_merge_fwd", _p(ov), nh, R, P, cp, _p(o))
+
+
 # ---- DPCCN pieces (conv2d.hip) --------------------------------------------------------------------------
 IN_EPS = 1e-5  # nn.InstanceNorm{1,2}d default
 

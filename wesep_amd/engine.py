@@ -120,7 +120,7 @@ class Engine:
         return est
 
     def separate_ragged(self, mixes, enrolls, kind):
-        """Utterances of different lengths in one forward (pBSRNN containers): mixes: list of R float32 [T_r]; enrolls: list
+        """Utterances of different lengths in one forward (pBSRNN and TF-GridNet containers): mixes: list of R float32 [T_r]; enrolls: list
         of R arrays -- [E] (ENROLL_EMBEDDING), [Te_r, F] (ENROLL_FBANK) or [Tw_r] (ENROLL_WAVE) -> list of R float32 [T_r].
         Every estimate is what separate() returns for that utterance alone (include/wesep_engine.h,
         ws_engine_separate_ragged)."""
