@@ -174,15 +174,23 @@ int ws_reduce_slabs(const float* slab, int nsplit, long long stride, long long c
 int ws_transpose(const float* src, int rows, int cols, long long lds, float* dst, void* stream);
 
 /* ---- GroupNorm(1, C, eps) pieces (bsrnn.py:26,256,275; eps = FLT_EPSILON) ---------------
- * A "group" g covers L rows x W contiguous floats:
- *   base(g) = (g / gdiv) * gs1 + (g % gdiv) * gs2 (+ band_off[g % gdiv]),  row stride rs,
- *   W = band_w ? band_w[g % nbands] : W.                                                   */
+ * A "group" g covers L rows x W_g contiguous floats:
+ *   base(g) = (g / gdiv) * gs1 + (g % gdiv) * gs2 (+ band_off[g % nbands]),  row stride rs,
+ *   W_g = band_w ? band_w[g % nbands] : W;  means and variances are over the L * W_g floats of the group.
+ * band_off, like band_w and gamma_tab, is indexed by the BAND of the group, g % nbands, whatever gdiv is (the band-split
+ * norm passes gdiv == nbands; tests/norm_contract.py holds a geometry with gdiv != nbands to this reading).
+ * Alignment: with band_w == NULL, band_off == NULL and W, rs, gs1, gs2 all multiples of 4 the kernels use 16-byte accesses;
+ * every data pointer of the call (x, dxn, dxn2, res, dx, gamma and the gamma_tab entries) must then be 16-byte aligned.  Any
+ * other geometry takes the scalar kernels, which need 4-byte alignment only.  ws_gn_bwd_fused2, ws_gn_bwd_apply_pg, ws_rowln_*
+ * and ws_flat_stats* are vectorised always (x, dy, res, dx, y, gamma, beta 16-byte aligned).
+ * W <= 128 binds ws_gn_param_grad and the band_w tables (its slabs are [..][2][W], 128 column threads) only: ws_group_stats,
+ * ws_gn_bwd_reduce and ws_gn_bwd_apply take any W > 0 (Conv-TasNet's cLN: L = 1, W = C up to 3N).                */
 typedef struct ws_groups_geom {
   const int* band_w;   /* device int[nbands], or NULL */
-  const int* band_off; /* device int[nbands], or NULL */
+  const int* band_off; /* device int[nbands], or NULL; indexed by g % nbands */
   long long gs1, gs2, rs;
-  int ngroups, gdiv, L, W; /* W: width (max width when band_w is given), <= 128 */
-  int nbands, pad_;        /* band of group g = g % nbands (per-band widths / gammas) */
+  int ngroups, gdiv, L, W; /* W: width (max width when band_w is given; then and for ws_gn_param_grad <= 128) */
+  int nbands, pad_;        /* band of group g = g % nbands (per-band widths / offsets / gammas) */
 } ws_groups_geom;
 int ws_group_stats(const float* x, const ws_groups_geom* geo, float eps, float* stats, void* stream);
 /* Ragged batches (inference): the statistics of group g cover its first glen[g / glen_div] rows only (device int table,
@@ -202,8 +210,10 @@ int ws_gn_bwd_reduce(const float* x, const float* dxn, const float* stats, const
 int ws_gn_bwd_apply(const float* x, const float* dxn, const float* stats, const float* ab,
                     const float* gamma, const float* const* gamma_tab, const float* res,
                     const ws_groups_geom* geo, float* dx, void* stream);
-/* dgamma/dbeta partials: slab[split][band][2][W]; band b owns groups {g : g % nbands == b}
- * (nbands = 1: every group).  Caller reduces the splits.                                    */
+/* dgamma/dbeta partials: slab[split][band][2][W] (row 0 dgamma, row 1 dbeta); band b owns groups {g : g % nbands == b}
+ * (nbands = 1: every group).  Caller reduces the splits; which groups a split sums is the kernel's choice.  Every element
+ * of the nsplit * nbands * 2 * W floats is written: columns [band_w[b], W) of band b hold zeros, and so does the whole slab
+ * of a split that owns no group (nsplit above the groups of a band).  W <= 128, ngroups % nbands == 0.            */
 int ws_gn_param_grad(const float* x, const float* dxn, const float* stats,
                      const ws_groups_geom* geo, int nsplit, float* slab, void* stream);
 
@@ -222,11 +232,14 @@ int ws_gn_bwd_fused2(const float* x, const float* dxn, const float* dxn2, const 
                      float* pout, unsigned* counter, void* stream);
 /* ABI v15: pout [2][128] (optional) = (dgamma, dbeta) summed over the workgroups BY the workgroups of the launch (the last
  * finisher of every 32 consecutive workgroups adds their shares up in index order, the last of those the group sums:
- * deterministic; no ws_reduce_slabs launch behind it).  pslab then needs nwg + ceil(nwg / 32) rows of [2][128];
- * `counter`: 1 + ceil(nwg / 32) device words that are 0 at launch (the kernel leaves them at 0).
+ * deterministic; no ws_reduce_slabs launch behind it).  pslab then needs nwg + ceil(nwg / 32) rows of [2][128]: the first
+ * nwg rows are the workgroups' shares (all written; zeros where a workgroup owns no group), the ceil(nwg / 32) rows behind
+ * them are SCRATCH of the two-level sum -- whatever they hold afterwards is no result.  Without pout exactly nwg rows are
+ * written.  `counter`: 1 + ceil(nwg / 32) device words that are 0 at launch (the kernel leaves them at 0).
  * ws_gn_bwd_apply_pg: pass 2 of the two-pass form for single-band groups of 128-float rows (the time view of ResRNN.norm)
  * WITH the parameter sums: one partial [2][128] per group to pslab [ngroups][2][128], summed into pout [2][128] by the last
- * workgroup -- replaces ws_gn_bwd_apply + ws_gn_param_grad + ws_reduce_slabs there.                                */
+ * workgroup -- replaces ws_gn_bwd_apply + ws_gn_param_grad + ws_reduce_slabs there.  It sums in the same two levels: pslab
+ * needs ngroups + ceil(ngroups / 32) rows (the extra ones scratch, as above) and `counter` 1 + ceil(ngroups / 32) zero words.  */
 int ws_gn_bwd_apply_pg(const float* x, const float* dxn, const float* stats, const float* ab,
                        const float* gamma, const float* res, const ws_groups_geom* geo, float* dx,
                        float* pslab, float* pout, unsigned* counter, void* stream);
@@ -675,7 +688,9 @@ int ws_clip_adam_step(const ws_tensor_ref* tab, int ntensors, const float* norms
  * ConvTranspose1d overlap-add (decoder.py:92-114).                                                   */
 
 /* mean / rstd of `ngroups` contiguous groups of n_per_group floats (gLN: one row's T'*C), chunked over
- * nchunk workgroups per group; scratch [ngroups][nchunk][4]; stats [ngroups][2] = (mean, 1/sqrt(var+eps)) */
+ * nchunk workgroups per group; scratch [ngroups][nchunk][4]; stats [ngroups][2] = (mean, 1/sqrt(var+eps)).
+ * n_per_group % 4 == 0, x 16-byte aligned; any nchunk > 0: a chunk is ceil(n / 4 / nchunk) quads, the chunks behind the
+ * group's end are empty and count for nothing (nchunk may exceed n / 4); above 64 chunks a lane merges several in turn.  */
 int ws_flat_stats(const float* x, int ngroups, long long n_per_group, float eps, int nchunk,
                   float* scratch, float* stats, void* stream);
 /* x += rb[m / rows_per_r] (rb may be NULL; x is updated in place = the saved pre-activation);

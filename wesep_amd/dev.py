@@ -1115,9 +1115,10 @@ def _call(name, *args):
     L.check(getattr(L.lib(), name)(*args, L.stream_ptr()), name)
 
 
-def flat_stats(x, ngroups: int, n_per_group: int, stats, eps=LN_EPS):
-    """(mean, rstd) of contiguous groups, chunked over the chip."""
-    nchunk = max(1, min(max(1, 512 // ngroups), n_per_group // 16384))
+def flat_stats(x, ngroups: int, n_per_group: int, stats, eps=LN_EPS, nchunk=None):
+    """(mean, rstd) of contiguous groups, chunked over the chip; nchunk = None: one chunk per 16384 floats, at most 512 in all."""
+    if nchunk is None:
+        nchunk = max(1, min(max(1, 512 // ngroups), n_per_group // 16384))
     scratch = torch.empty(ngroups, nchunk, 4, device=x.device, dtype=torch.float32)
     for n, t in (("x", x), ("stats", stats)):
         _chk(t, n)
@@ -1872,12 +1873,16 @@ def rowln_fwd(x, gamma, beta, M: int, W: int, y, stats, eps=LN_EPS):
     _call("ws_rowln_fwd", _p(x), _p(gamma), _p(beta), M, W, eps, _p(y), _p(stats))
 
 
-def rowln_bwd(x, dy, stats, gamma, M: int, W: int, dx, res=None):
-    """dx (may alias dy) and the [2, W] sums (d(beta), d(gamma)), reduced from the kernel's per-workgroup slabs."""
-    for nm, t in (("x", x), ("dy", dy), ("stats", stats), ("gamma", gamma), ("dx", dx), ("res", res)):
+def rowln_bwd(x, dy, stats, gamma, M: int, W: int, dx, res=None, slab=None):
+    """dx (may alias dy) and the [2, W] sums (d(beta), d(gamma)), reduced from the kernel's per-workgroup slabs
+    (slab: ws_rowln_grid(M, W) * 2 * W floats of the caller's; None: a new tensor)."""
+    for nm, t in (("x", x), ("dy", dy), ("stats", stats), ("gamma", gamma), ("dx", dx), ("res", res), ("slab", slab)):
         _chk(t, nm)
     n = L.lib().ws_rowln_grid(M, W)
-    slab = torch.empty(n, 2 * W, device=x.device, dtype=torch.float32)
+    if slab is None:
+        slab = torch.empty(n, 2 * W, device=x.device, dtype=torch.float32)
+    elif slab.numel() < n * 2 * W:
+        raise L.WesepHipError(f"rowln_bwd: slab holds {slab.numel()} floats, the launch needs {n * 2 * W}")
     _call("ws_rowln_bwd", _p(x), _p(dy), _p(stats), _p(gamma), _p(res), M, W, _p(dx), _p(slab))
     tot = torch.empty(2, W, device=x.device, dtype=torch.float32)
     reduce_slabs(slab, n, 2 * W, 2 * W, tot)
