@@ -50,7 +50,8 @@ void ws_engine_destroy(ws_engine* e);
  * not co-resident, e.g. several engines on one GPU -- and the predicated streaming kernels recomputed the layer;
  * wesep_hip.h, ws_lstm_fwd_cluster), "ragged_speaker" (1: enroll_lengths of ws_engine_separate_ragged run the speaker
  * encoder once over all rows, 0: one row at a time), "ragged_separator" (1: the separator takes the lengths of
- * ws_engine_separate_ragged -- pBSRNN and TF-GridNet; 0: it refuses them)}; unknown key -> -1. */
+ * ws_engine_separate_ragged -- pBSRNN and TF-GridNet; 0: it refuses them), "long_windows" / "long_forwards" (windows per
+ * target speaker and separator forwards of the last ws_engine_separate_long; 0 after any other call)}; unknown key -> -1. */
 long long ws_engine_info(const ws_engine* e, const char* key);
 
 /* enrollment kinds */
@@ -60,9 +61,11 @@ long long ws_engine_info(const ws_engine* e, const char* key);
                                  computed on the device (what SeparateEngine::ExtractFeature does on the host,
                                  separate_engine.cc:53-74); spk_feat = False models: their in-model PreEmphasis +
                                  MelSpectrogram + log + CMN front-end (bsrnn.py:343-350) */
+#define WS_ENROLL_SPEAKER 3   /* float [R][spk_emb_dim]: what ws_engine_embed returned (joint containers) */
 
 /* est[r][0..T) = target-speaker estimate for mix[r][0..T) given enrollment r.  All pointers are HOST pointers.
- * Replaces `model(features, enroll)[0]` of infer.py:101-103 (whole utterance, any T >= 512; no chunking). */
+ * Replaces `model(features, enroll)[0]` of infer.py:101-103 (whole utterance, any T >= 512; ws_engine_separate_long
+ * below cuts a long recording into windows). */
 int ws_engine_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind,
                        int enroll_len, float* est);
 
@@ -87,6 +90,35 @@ int ws_engine_separate(ws_engine* e, const float* mix, int R, int T, const void*
  * own samples; the frames follow the model's hop; the keys behind a row's last frame are masked out of the attention. */
 int ws_engine_separate_ragged(ws_engine* e, const float* mix, int R, int T, const int* lengths, const void* enroll,
                               int enroll_kind, int enroll_len, const int* enroll_lengths, float* est);
+
+/* The speaker stage alone (joint containers): emb[r] = the speaker encoder's embedding of enrollment r, BEFORE the model's
+ * SpeakerTransform -- what the separator receives from the speaker stage of ws_engine_separate.  enroll / enroll_kind
+ * (WS_ENROLL_FBANK or WS_ENROLL_WAVE) / enroll_len / enroll_lengths (or NULL; pBSRNN and TF-GridNet containers) as in
+ * ws_engine_separate_ragged, and the same passes run: once over all rows where "ragged_speaker" is 1, one row at a time
+ * otherwise (WS_ENGINE_RAGGED_SPK=0 included); a SpEx+ container runs its encoder on the waveform.  emb: HOST
+ * [R][spk_emb_dim].  Passing it back as WS_ENROLL_SPEAKER (ws_engine_separate, _ragged, _long) uploads it where the speaker
+ * stage would have written: with the same R the estimates are bit for bit those of the call with the raw enrollment, and
+ * the encoder does not run.  A container that takes fixed embeddings has no speaker stage and is refused. */
+int ws_engine_embed(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, const int* enroll_lengths,
+                    float* emb);
+
+/* Long recordings: ONE mixture mix [n], K >= 1 target speakers (enroll: K rows, any kind the container takes), est HOST
+ * [K][n].  The mixture is cut into W windows of `window` samples that overlap by `overlap` (0 <= overlap <= window / 2;
+ * hop = window - overlap): W = 1 + ceil((n - window) / hop), window w starts at min(w hop, n - window) -- the last one is
+ * aligned to the end, so every window has full length and the architecture's rectangular plan runs on it.  The K W rows
+ * go through the separator in groups of at most max_rows rows (the arena holds one group's working set); a row is what
+ * ws_engine_separate makes of it as a mixture of its own (TF-GridNet: the window's own standard deviation and scale-back;
+ * a window of constant samples has none, as in the whole-utterance call).  The estimates are cross-faded on the device:
+ * linear ramps over the overlapping samples, normalised by the sum of the weights that cover a sample (wesep_hip.h,
+ * ws_xfade_ola), in a fixed order.  The enrollment fixes which speaker comes out, so windows need no permutation alignment.
+ * The speaker stage runs ONCE over the K enrollments, or not at all (WS_ENROLL_EMBEDDING / WS_ENROLL_SPEAKER).
+ * n <= window with K <= max_rows is ws_engine_separate on [K][n], bit for bit.  Refused before any launch: a window below
+ * the architecture's minimum T (its own message), overlap outside [0, window / 2], max_rows < 1, a group of
+ * min(max_rows, K W) rows of `window` samples over the architecture's 2^31 guard, and a Conv-TasNet window that is not
+ * L + k L / 2 samples (its last samples would be the plan's zero extension, not model output).  Memory and time grow
+ * linearly in n; "long_windows" / "long_forwards" of ws_engine_info report W and the number of groups. */
+int ws_engine_separate_long(ws_engine* e, const float* mix, int n, int K, const void* enroll, int enroll_kind, int enroll_len,
+                            const int* enroll_lengths, int window, int overlap, int max_rows, float* est);
 
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by

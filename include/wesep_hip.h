@@ -1086,6 +1086,25 @@ int ws_ola_norm_len(const float* frames, const float* win, int R, int Tf, int n,
 int ws_transpose_batched(const float* src, int G, int rows, int cols, float* dst, void* stream);
 int ws_heads_merge_fwd(const float* ov, int nh, int R, long long P, int cp, float* o, void* stream);
 
+/* Long recordings (longform.hip): one mixture x [n] as W overlapping windows of S samples, overlap O with
+ * 0 <= O <= S / 2, hop H = S - O.  The layout is a pure function of (n, S, O): n <= S is one window [0, n) of L = n
+ * samples; otherwise W = 1 + ceil((n - S) / H) windows of L = S samples with start_w = min(w H, n - S) -- the last window is
+ * aligned to the end, so every window has full length.  The kernels compute the starts; no table of them is passed.
+ * NULL x / rows / y / out, an overlap outside [0, S / 2] and a W that is not the one of (n, S, H) are WS_ERR_INVALID
+ * before any launch.  Offsets are 64-bit (n up to 2^31 - 1).
+ *   ws_window_rows  rows[(k W + w)][j] = x[start_w + j] * (scale ? scale[w] : 1), k < reps, j < L: every window once per
+ *                   target speaker.  No alignment of the starts is assumed.  scale: device [W] or NULL (the runtime's
+ *                   TF-GridNet plan scales a window by 1 / its standard deviation)
+ *   ws_xfade_ola    y [K][W][L] -> out [K][n].  Window w weighs its local sample j with
+ *                     g_w(j) = (w > 0 ? min(1, (j + 1) / (O + 1)) : 1) * (w < W - 1 ? min(1, (L - j) / (O + 1)) : 1)
+ *                   and out[k][i] = (sum over the windows that cover i, ascending w, of g_w y (* scale[w])) / (sum of the
+ *                   same g_w).  Two regular neighbours' ramps add up to 1: a linear cross-fade.  The end-aligned last
+ *                   window may overlap its predecessor by up to S - 1 samples and a third window with it; the division
+ *                   covers that (every g > 0; at most ceil(S / H) + 1 terms).  Fixed order, no atomics; every out[k][i],
+ *                   i < n, is written; y is read inside [0, L) of a window only.  scale: device [W] or NULL */
+int ws_window_rows(const float* x, int n, int W, int S, int H, int reps, const float* scale, float* rows, void* stream);
+int ws_xfade_ola(const float* y, int K, int W, int S, int O, int n, const float* scale, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

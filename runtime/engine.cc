@@ -274,8 +274,6 @@ int check_engine(const ws_engine* e, const char* who) {
 
 using namespace wsrt;
 
-static std::mutex g_device_mutex[16];   // see ws_engine_separate
-
 // ---- C ABI ----------------------------------------------------------------------------------------------------
 WS_ENGINE_API int ws_engine_abi_version(void) { return WS_ENGINE_ABI_VERSION; }
 WS_ENGINE_API const char* ws_engine_last_error(void) { return g_err; }
@@ -351,9 +349,14 @@ WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   if (k == "ragged_speaker") return (e->arch == 0 || e->arch == 3) && ragged_speaker_covered(e) && ragged_speaker_enabled() ? 1 : 0;
   // 1: lengths of ws_engine_separate_ragged are taken (pBSRNN, TF-GridNet); 0: this separator refuses them
   if (k == "ragged_separator") return e->arch == 0 || e->arch == 3 ? 1 : 0;
+  // windows per target speaker and separator forwards of the last ws_engine_separate_long (0 after any other call)
+  if (k == "long_windows") return e->long_windows;
+  if (k == "long_forwards") return e->long_forwards;
   auto it = e->meta.find(k);
   return it == e->meta.end() ? -1 : it->second;
 }
+
+namespace wsrt {
 
 // frames of an enrollment of `enroll_len` samples / frames for this model's front-end, or WS_ERR_INVALID (message set)
 static int enroll_frames(const ws_engine* e, int enroll_kind, int enroll_len, int* frames) {
@@ -374,7 +377,7 @@ static int enroll_frames(const ws_engine* e, int enroll_kind, int enroll_len, in
     set_err("ws_engine_separate: this model computes its own features (spk_feat = False): pass the waveform");
     return WS_ERR_INVALID;
   }
-  if (enroll_kind != WS_ENROLL_EMBEDDING && Te < 8) {
+  if (enroll_kind != WS_ENROLL_EMBEDDING && enroll_kind != WS_ENROLL_SPEAKER && Te < 8) {
     set_err("ws_engine_separate: enrollment of %d frames is too short for the speaker encoder", Te);
     return WS_ERR_INVALID;
   }
@@ -382,20 +385,11 @@ static int enroll_frames(const ws_engine* e, int enroll_kind, int enroll_len, in
   return WS_OK;
 }
 
-// ws_engine_separate and ws_engine_separate_ragged: lengths / enroll_lengths = nullptr is the rectangular call
-static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int* lengths, const void* enroll, int enroll_kind,
-                         int enroll_len, const int* enroll_lengths, float* est) {
-  int rc = check_engine(e, lengths || enroll_lengths ? "ws_engine_separate_ragged" : "ws_engine_separate");
-  if (rc != WS_OK) return rc;
-  if ((lengths || enroll_lengths) && e->arch != 0 && e->arch != 3) {
-    set_err("ws_engine_separate_ragged: per-row lengths are built for pBSRNN (arch 0) and TF-GridNet (arch 3) only; this "
-            "container holds arch %d", e->arch);
-    return WS_ERR_INVALID;
-  }
-  if (e->arch == 1) return tasnet_separate(e, mix, R, T, enroll, enroll_kind, enroll_len, est);
+int check_rows(ws_engine* e, bool ptrs, int R, int T) {
+  if (e->arch == 1) return tasnet_check_rows(e, ptrs, R, T);
   // (TF-GridNet's own lower bound is 2 * n_fft, checked below: a ragged row of that length is compared with this call)
   const int t_min = e->arch == 3 && T >= 2 * e->grid.n_fft ? 2 * e->grid.n_fft : 512;
-  if (!mix || !enroll || !est || R < 1 || T < t_min || (long long)R * (1 + T / kHop) * 4 * kNBin > 0x7fffffffLL) {
+  if (!ptrs || R < 1 || T < t_min || (long long)R * (1 + T / kHop) * 4 * kNBin > 0x7fffffffLL) {
     set_err("ws_engine_separate: bad arguments (R=%d, T=%d; T >= 512)", R, T);
     return WS_ERR_INVALID;
   }
@@ -413,13 +407,131 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
             "R * frames * 257 * 160 below 2^31 (R=%d, T=%d)", 31 * kHop, R, T);
     return WS_ERR_INVALID;
   }
-  if ((enroll_kind == WS_ENROLL_EMBEDDING) == (e->joint != 0) || enroll_kind < 0 || enroll_kind > WS_ENROLL_WAVE) {
+  return WS_OK;
+}
+
+int check_enroll(ws_engine* e, int R, int enroll_kind, int enroll_len, const int* enroll_lengths, int* Te,
+                 std::vector<int>* te_row) {
+  int rc;
+  if (e->arch == 1) {
+    if (enroll_lengths) {
+      set_err("ws_engine_separate_ragged: per-row lengths are built for pBSRNN (arch 0) and TF-GridNet (arch 3) only; this "
+              "container holds arch %d", e->arch);
+      return WS_ERR_INVALID;
+    }
+    *Te = enroll_len;
+    return tasnet_check_enroll(e, enroll_kind, enroll_len);
+  }
+  const bool fits = enroll_kind == WS_ENROLL_SPEAKER ? e->joint != 0 : (enroll_kind == WS_ENROLL_EMBEDDING) != (e->joint != 0);
+  if (!fits || enroll_kind < 0 || enroll_kind > WS_ENROLL_SPEAKER) {
     set_err("ws_engine_separate: enrollment kind %d does not fit this model (joint_training = %d)", enroll_kind, e->joint);
     return WS_ERR_INVALID;
   }
+  if ((rc = enroll_frames(e, enroll_kind, enroll_len, Te)) != WS_OK) return rc;
+  if (enroll_lengths) {
+    if (enroll_kind == WS_ENROLL_EMBEDDING || enroll_kind == WS_ENROLL_SPEAKER) {
+      set_err("ws_engine_separate_ragged: enroll_lengths given with fixed embeddings (they have no length)");
+      return WS_ERR_INVALID;
+    }
+    te_row->resize(R);
+    for (int r = 0; r < R; ++r) {
+      if (enroll_lengths[r] > enroll_len) {
+        set_err("ws_engine_separate_ragged: enroll_lengths[%d] = %d exceeds the row pitch enroll_len = %d", r,
+                enroll_lengths[r], enroll_len);
+        return WS_ERR_INVALID;
+      }
+      if ((rc = enroll_frames(e, enroll_kind, enroll_lengths[r], &(*te_row)[r])) != WS_OK) return rc;
+    }
+  }
+  return WS_OK;
+}
+
+static std::mutex g_device_mutex[16];   // see ForwardTurn
+
+// Engines that share a GPU overlap on the device.  Round 2 serialised them here (one forward at a time per GPU)
+// because ws_gemm_b2p / the grouped ws_gemm_nt / ws_gemm_tn disturbed this plan's STFT / iSTFT kernels on another
+// stream.  Round 3 named the victim class -- packed FP32 instructions with an operand selection -- and the library is
+// built without them (profiles/r03_kernel_race.md; tests/test_cross_stream_gpu.py), so the lock is opt-in:
+// WS_ENGINE_SERIALIZE=1 restores one forward at a time (e.g. beside third-party kernels on the same GPU).
+ForwardTurn::ForwardTurn(ws_engine* e) : turn(g_device_mutex[e->device & 15], std::defer_lock) {
+  static const bool serialize = getenv("WS_ENGINE_SERIALIZE") != nullptr && atoi(getenv("WS_ENGINE_SERIALIZE")) != 0;
+  if (!e->dry && hipSetDevice(e->device) != hipSuccess) {
+    set_err("ws_engine_separate: hipSetDevice(%d) failed", e->device);
+    rc = WS_ERR_LAUNCH;
+    return;
+  }
+  if (serialize) turn.lock();
+}
+
+// the speaker stage of every forward: host enrollment -> device emb [R][E], the encoder's embedding before SpeakerTransform
+// (what the plans receive as emb_in).  Fixed embeddings and WS_ENROLL_SPEAKER are uploaded where the encoder would write.
+int speaker_stage(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, int Te, const int* enroll_lengths,
+                  const int* te_row, float* d_emb) {
+  int rc;
+  if (enroll_kind == WS_ENROLL_EMBEDDING || enroll_kind == WS_ENROLL_SPEAKER) {
+    if ((rc = to_device(e, d_emb, enroll, size_t(R) * e->E * 4)) != WS_OK) return rc;
+  } else if (e->arch == 1) {
+    // SpEx+: the enrollment waveform through the separator's own encoder (convtasnet.py:179-187)
+    if ((rc = tasnet_speaker(e, static_cast<const float*>(enroll), R, enroll_len, d_emb)) != WS_OK) return rc;
+  } else if (enroll_lengths && ragged_speaker_covered(e) && ragged_speaker_enabled()) {
+    // one encoder pass over all rows: masked epilogues keep every row zero behind its own frames, the reductions over
+    // time take the row's length (speaker.cc)
+    if ((rc = speaker_embed(e, enroll, enroll_kind, R, enroll_len, Te, d_emb, enroll_lengths, te_row)) != WS_OK) return rc;
+  } else if (enroll_lengths) {
+    // CAM++, the attentive multi-head pools, WS_ENGINE_RAGGED_SPK=0: one enrollment at a time into the [R][E] buffer
+    // (its convolutions then pad with zeros at the row's true end and its pooling sees the row's own frames), then the
+    // separator once over all rows
+    const size_t pitch = size_t(enroll_len) * (enroll_kind == WS_ENROLL_FBANK ? e->spk.feat_dim : 1);
+    for (int r = 0; r < R; ++r)
+      if ((rc = speaker_embed(e, static_cast<const float*>(enroll) + r * pitch, enroll_kind, 1, enroll_lengths[r], te_row[r],
+                              d_emb + size_t(r) * e->E)) != WS_OK)
+        return rc;
+  } else if ((rc = speaker_embed(e, enroll, enroll_kind, R, enroll_len, Te, d_emb)) != WS_OK) {
+    return rc;
+  }
+  return WS_OK;
+}
+
+int note_cluster_status(ws_engine* e) {
+  if (e->cl_status && !e->dry) {   // did a cluster recurrence time out (and the predicated streaming pair repair it)?
+    unsigned st = 0;
+    int rc;
+    if ((rc = to_host(e, &st, e->cl_status, 4)) != WS_OK) return rc;
+    if (st) {
+      ++e->cluster_fallbacks;
+      if ((rc = zero_device(e, e->cl_status, 4)) != WS_OK) return rc;
+    }
+  }
+  return WS_OK;
+}
+
+void row_std_scale(const float* x, int n, float* std_out, float* scaled) {
+  double m = 0.0, v = 0.0;
+  for (int i = 0; i < n; ++i) m += x[i];
+  m /= n;
+  for (int i = 0; i < n; ++i) v += (x[i] - m) * (x[i] - m);
+  *std_out = static_cast<float>(sqrt(v / (n - 1.0)));
+  if (!scaled) return;
+  const float inv = 1.0f / *std_out;
+  for (int i = 0; i < n; ++i) scaled[i] = x[i] * inv;
+}
+
+// ws_engine_separate and ws_engine_separate_ragged: lengths / enroll_lengths = nullptr is the rectangular call
+int separate_impl(ws_engine* e, const float* mix, int R, int T, const int* lengths, const void* enroll, int enroll_kind,
+                  int enroll_len, const int* enroll_lengths, float* est) {
+  int rc = check_engine(e, lengths || enroll_lengths ? "ws_engine_separate_ragged" : "ws_engine_separate");
+  if (rc != WS_OK) return rc;
+  if ((lengths || enroll_lengths) && e->arch != 0 && e->arch != 3) {
+    set_err("ws_engine_separate_ragged: per-row lengths are built for pBSRNN (arch 0) and TF-GridNet (arch 3) only; this "
+            "container holds arch %d", e->arch);
+    return WS_ERR_INVALID;
+  }
+  e->long_windows = e->long_forwards = 0;
+  if (e->arch == 1) return tasnet_separate(e, mix, R, T, enroll, enroll_kind, enroll_len, est);
+  if ((rc = check_rows(e, mix && enroll && est, R, T)) != WS_OK) return rc;
   int Te = enroll_len;
-  if ((rc = enroll_frames(e, enroll_kind, enroll_len, &Te)) != WS_OK) return rc;
   std::vector<int> tf, te_row;
+  if ((rc = check_enroll(e, R, enroll_kind, enroll_len, nullptr, &Te, &te_row)) != WS_OK) return rc;
   if (lengths) {
     // a row's own T: what this surface demands of T, and no more than the row pitch; frames with the model's own hop
     const int lo = e->arch == 3 ? 2 * e->grid.n_fft : 512, hop = e->arch == 3 ? e->grid.hop : kHop;
@@ -431,33 +543,9 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
       tf.push_back(1 + lengths[r] / hop);
     }
   }
-  if (enroll_lengths) {
-    if (enroll_kind == WS_ENROLL_EMBEDDING) {
-      set_err("ws_engine_separate_ragged: enroll_lengths given with fixed embeddings (they have no length)");
-      return WS_ERR_INVALID;
-    }
-    te_row.resize(R);
-    for (int r = 0; r < R; ++r) {
-      if (enroll_lengths[r] > enroll_len) {
-        set_err("ws_engine_separate_ragged: enroll_lengths[%d] = %d exceeds the row pitch enroll_len = %d", r,
-                enroll_lengths[r], enroll_len);
-        return WS_ERR_INVALID;
-      }
-      if ((rc = enroll_frames(e, enroll_kind, enroll_lengths[r], &te_row[r])) != WS_OK) return rc;
-    }
-  }
-  if (!e->dry && hipSetDevice(e->device) != hipSuccess) {
-    set_err("ws_engine_separate: hipSetDevice(%d) failed", e->device);
-    return WS_ERR_LAUNCH;
-  }
-  // Engines that share a GPU overlap on the device.  Round 2 serialised them here (one forward at a time per GPU)
-  // because ws_gemm_b2p / the grouped ws_gemm_nt / ws_gemm_tn disturbed this plan's STFT / iSTFT kernels on another
-  // stream.  Round 3 named the victim class -- packed FP32 instructions with an operand selection -- and the library is
-  // built without them (profiles/r03_kernel_race.md; tests/test_cross_stream_gpu.py), so the lock is opt-in:
-  // WS_ENGINE_SERIALIZE=1 restores one forward at a time (e.g. beside third-party kernels on the same GPU).
-  static const bool serialize = getenv("WS_ENGINE_SERIALIZE") != nullptr && atoi(getenv("WS_ENGINE_SERIALIZE")) != 0;
-  std::unique_lock<std::mutex> device_turn(g_device_mutex[e->device & 15], std::defer_lock);
-  if (serialize) device_turn.lock();
+  if (enroll_lengths && (rc = check_enroll(e, R, enroll_kind, enroll_len, enroll_lengths, &Te, &te_row)) != WS_OK) return rc;
+  ForwardTurn turn(e);
+  if (turn.rc != WS_OK) return turn.rc;
   e->n_launches = 0;
   Arena& a = e->work;
   a.reset();
@@ -471,17 +559,7 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
   if (e->arch == 3) {
     mixn.assign(size_t(R) * T, 0.f);
     stds.resize(R);
-    for (int r = 0; r < R; ++r) {
-      const float* x = mix + size_t(r) * T;
-      const int n = lengths ? lengths[r] : T;
-      double m = 0.0, v = 0.0;
-      for (int i = 0; i < n; ++i) m += x[i];
-      m /= n;
-      for (int i = 0; i < n; ++i) v += (x[i] - m) * (x[i] - m);
-      stds[r] = static_cast<float>(sqrt(v / (n - 1.0)));
-      const float inv = 1.0f / stds[r];
-      for (int i = 0; i < n; ++i) mixn[size_t(r) * T + i] = x[i] * inv;
-    }
+    for (int r = 0; r < R; ++r) row_std_scale(mix + size_t(r) * T, lengths ? lengths[r] : T, &stds[r], mixn.data() + size_t(r) * T);
     mix = mixn.data();
   }
   if ((rc = to_device(e, d_mix, mix, size_t(R) * T * 4)) != WS_OK) return rc;
@@ -493,24 +571,7 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
     if ((rc = to_device(e, d_len, lengths, size_t(R) * 4)) != WS_OK || (rc = to_device(e, d_tf, tf.data(), size_t(R) * 4)) != WS_OK)
       return rc;
   }
-  if (enroll_kind == WS_ENROLL_EMBEDDING) {
-    if ((rc = to_device(e, d_emb, enroll, size_t(R) * e->E * 4)) != WS_OK) return rc;
-  } else if (enroll_lengths && ragged_speaker_covered(e) && ragged_speaker_enabled()) {
-    // one encoder pass over all rows: masked epilogues keep every row zero behind its own frames, the reductions over
-    // time take the row's length (speaker.cc)
-    if ((rc = speaker_embed(e, enroll, enroll_kind, R, enroll_len, Te, d_emb, enroll_lengths, te_row.data())) != WS_OK) return rc;
-  } else if (enroll_lengths) {
-    // CAM++, the attentive multi-head pools, WS_ENGINE_RAGGED_SPK=0: one enrollment at a time into the [R][E] buffer
-    // (its convolutions then pad with zeros at the row's true end and its pooling sees the row's own frames), then the
-    // separator once over all rows
-    const size_t pitch = size_t(enroll_len) * (enroll_kind == WS_ENROLL_FBANK ? e->spk.feat_dim : 1);
-    for (int r = 0; r < R; ++r)
-      if ((rc = speaker_embed(e, static_cast<const float*>(enroll) + r * pitch, enroll_kind, 1, enroll_lengths[r], te_row[r],
-                              d_emb + size_t(r) * e->E)) != WS_OK)
-        return rc;
-  } else if ((rc = speaker_embed(e, enroll, enroll_kind, R, enroll_len, Te, d_emb)) != WS_OK) {
-    return rc;
-  }
+  if ((rc = speaker_stage(e, enroll, enroll_kind, R, enroll_len, Te, enroll_lengths, te_row.data(), d_emb)) != WS_OK) return rc;
   rc = e->arch == 2 ? dpccn_device(e, d_mix, R, T, d_emb, d_est)
                     : e->arch == 3 ? gridnet_device(e, d_mix, R, T, d_emb, d_est, lengths ? tf.data() : nullptr, d_len, d_tf)
                                    : separate_device(e, d_mix, R, T, d_emb, d_est, d_len, d_tf);
@@ -519,18 +580,13 @@ static int separate_impl(ws_engine* e, const float* mix, int R, int T, const int
   if (e->arch == 3 && !e->dry)
     for (int r = 0; r < R; ++r)
       for (int i = 0, n = lengths ? lengths[r] : T; i < n; ++i) est[size_t(r) * T + i] *= stds[r];
-  if (e->cl_status && !e->dry) {   // did a cluster recurrence time out (and the predicated streaming pair repair it)?
-    unsigned st = 0;
-    if ((rc = to_host(e, &st, e->cl_status, 4)) != WS_OK) return rc;
-    if (st) {
-      ++e->cluster_fallbacks;
-      if ((rc = zero_device(e, e->cl_status, 4)) != WS_OK) return rc;
-    }
-  }
+  if ((rc = note_cluster_status(e)) != WS_OK) return rc;
   a.reset();
   a.consolidate();
   return WS_OK;
 }
+
+}  // namespace wsrt
 
 WS_ENGINE_API int ws_engine_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind,
                                   int enroll_len, float* est) {
@@ -540,6 +596,48 @@ WS_ENGINE_API int ws_engine_separate(ws_engine* e, const float* mix, int R, int 
 WS_ENGINE_API int ws_engine_separate_ragged(ws_engine* e, const float* mix, int R, int T, const int* lengths, const void* enroll,
                                          int enroll_kind, int enroll_len, const int* enroll_lengths, float* est) {
   return separate_impl(e, mix, R, T, lengths, enroll, enroll_kind, enroll_len, enroll_lengths, est);
+}
+
+// the speaker stage alone: what a service with one enrolled user runs once, to pass the result as WS_ENROLL_SPEAKER
+WS_ENGINE_API int ws_engine_embed(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, const int* enroll_lengths,
+                               float* emb) {
+  int rc = check_engine(e, "ws_engine_embed");
+  if (rc != WS_OK) return rc;
+  if (!e->joint) {
+    set_err("ws_engine_embed: this container takes fixed embeddings (joint_training = 0): it holds no speaker encoder");
+    return WS_ERR_INVALID;
+  }
+  if (!enroll || !emb || R < 1 || (enroll_kind != WS_ENROLL_FBANK && enroll_kind != WS_ENROLL_WAVE)) {
+    set_err("ws_engine_embed: bad arguments (R=%d, enrollment kind %d; WS_ENROLL_FBANK or WS_ENROLL_WAVE)", R, enroll_kind);
+    return WS_ERR_INVALID;
+  }
+  if (enroll_lengths && e->arch != 0 && e->arch != 3) {
+    set_err("ws_engine_embed: per-row lengths are built for pBSRNN (arch 0) and TF-GridNet (arch 3) only; this container "
+            "holds arch %d", e->arch);
+    return WS_ERR_INVALID;
+  }
+  int Te = enroll_len;
+  std::vector<int> te_row;
+  if ((rc = check_enroll(e, R, enroll_kind, enroll_len, enroll_lengths, &Te, &te_row)) != WS_OK) return rc;
+  ForwardTurn turn(e);
+  if (turn.rc != WS_OK) return turn.rc;
+  e->long_windows = e->long_forwards = 0;
+  e->n_launches = 0;
+  Arena& a = e->work;
+  a.reset();
+  float* d_emb = a.alloc(size_t(R) * e->E);
+  WS_PTR(d_emb);
+  if ((rc = speaker_stage(e, enroll, enroll_kind, R, enroll_len, Te, enroll_lengths, te_row.data(), d_emb)) != WS_OK) return rc;
+  if ((rc = to_host(e, emb, d_emb, size_t(R) * e->E * 4)) != WS_OK) return rc;
+  a.reset();
+  a.consolidate();
+  return WS_OK;
+}
+
+WS_ENGINE_API int ws_engine_separate_long(ws_engine* e, const float* mix, int n, int K, const void* enroll, int enroll_kind,
+                                       int enroll_len, const int* enroll_lengths, int window, int overlap, int max_rows,
+                                       float* est) {
+  return separate_long(e, mix, n, K, enroll, enroll_kind, enroll_len, enroll_lengths, window, overlap, max_rows, est);
 }
 
 WS_ENGINE_API int ws_engine_forward_pcm16(ws_engine* e, const int16_t* mix, int n, const int16_t* spk1, const int16_t* spk2,

@@ -8,6 +8,7 @@
 //   tasnet_plan.cc   Conv-TasNet / SpEx+ (arch 1)
 //   dpccn_plan.cc    DPCCN (arch 2)
 //   gridnet_plan.cc  TF-GridNet (arch 3)
+//   longform.cc      ws_engine_separate_long: one long mixture as overlapping windows through the rectangular plans
 // Everything here lives in namespace wsrt and is built with -fvisibility=hidden: the library exports the C ABI only
 // (WS_ENGINE_API).  Host code only: no kernels in the runtime.
 #ifndef WESEP_ENGINE_INTERNAL_H_
@@ -23,6 +24,7 @@
 #include <algorithm>
 #include <initializer_list>
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -286,6 +288,7 @@ struct ws_engine {
   float* dw = nullptr;            // device copy
   wsrt::Arena persist, work;
   long long n_launches = 0;
+  long long long_windows = 0, long_forwards = 0;   // of the last ws_engine_separate_long
   long long cluster_fallbacks = 0;   // forwards in which a cluster recurrence timed out and the streaming kernels took over
   unsigned* cl_status = nullptr;     // sticky device word set by ws_lstm_fwd_cluster on a timeout
   // configuration shared by the plans
@@ -348,6 +351,27 @@ int linear(ws_engine* e, const float* x, int M, int k, const float* W, long long
 int copy_cols(ws_engine* e, float* dst, long long ldd, const float* src, long long lds, int width, long long rows);
 int time_mean(ws_engine* e, const float* x, int R, int T, int C, float* mean2);
 
+// ---- the pieces of a forward that the entry points share (engine.cc) ----
+int check_engine(const ws_engine* e, const char* who);
+// the separator's demands on a rectangle of R rows of T samples (the architecture's own message); ptrs: no NULL argument
+int check_rows(ws_engine* e, bool ptrs, int R, int T);
+// enrollment kind and lengths against the container; Te / te_row: the frames of the rectangle / of every row
+int check_enroll(ws_engine* e, int R, int enroll_kind, int enroll_len, const int* enroll_lengths, int* Te, std::vector<int>* te_row);
+struct ForwardTurn {     // hipSetDevice + the opt-in one-forward-at-a-time lock (WS_ENGINE_SERIALIZE), held while it lives
+  std::unique_lock<std::mutex> turn;
+  int rc = WS_OK;
+  explicit ForwardTurn(ws_engine* e);
+};
+int speaker_stage(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, int Te, const int* enroll_lengths,
+                  const int* te_row, float* d_emb);
+int note_cluster_status(ws_engine* e);
+// TF-GridNet's (unbiased) standard deviation of x[0..n) and, if wanted, x / std
+void row_std_scale(const float* x, int n, float* std_out, float* scaled);
+int separate_impl(ws_engine* e, const float* mix, int R, int T, const int* lengths, const void* enroll, int enroll_kind,
+                  int enroll_len, const int* enroll_lengths, float* est);
+int separate_long(ws_engine* e, const float* mix, int n, int K, const void* enroll, int enroll_kind, int enroll_len,
+                  const int* enroll_lengths, int window, int overlap, int max_rows, float* est);
+
 // ---- speaker stage (speaker.cc) ----
 int read_speaker_meta(ws_engine* e);
 int prep_spk_transform(ws_engine* e);
@@ -368,6 +392,11 @@ int separate_device(ws_engine* e, const float* wav, int R, int T, const float* e
 int prepare_tasnet(ws_engine* e);
 int tasnet_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind, int enroll_len,
                     float* est);
+int tasnet_check_rows(ws_engine* e, bool ptrs, int R, int T);
+int tasnet_check_enroll(ws_engine* e, int enroll_kind, int enroll_len);
+int tasnet_speaker(ws_engine* e, const float* enroll_wave, int R, int Te, float* emb);
+int tasnet_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, const float* enroll_wave, int Te,
+                  float* est);
 int tas_row_stats(ws_engine* e, const float* x, long long M, int C, float* st);
 int tas_flat_stats(ws_engine* e, const float* x, int R, long long n, float* st);
 int prepare_dpccn(ws_engine* e);

@@ -2,7 +2,7 @@
 // runtime/bin/separate_main.cc:24-115:
 //
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
-//                 [--batch 8] [--sort_by_length] [--dry_run]
+//                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -20,6 +20,11 @@
 // first (stable), before they are grouped N at a time, so a rectangle holds rows of similar length.  The counts come from
 // the wav headers (no file is loaded for it).  Outputs are still named by key and the total is unchanged; the "process:"
 // lines appear in processing order.  Without --batch the flag is accepted and changes nothing.
+// --chunk_seconds S [--overlap_seconds O, default S / 4] [--chunk_rows N, default 8] (long recordings; any model): every
+// line goes through ws_engine_separate_long with its two enrollments -- the mixture as windows of S seconds that overlap by
+// O, N window rows per forward, the estimates cross-faded on the device, the speaker encoder run once per line.  Memory
+// grows with N, not with the recording.  Scaling, output names and formats as above; works with --jobs and --dry_run; not
+// together with --batch N > 1 (a rectangle of whole utterances).  A mixture no longer than S is the whole-utterance forward.
 // --dry_run validates the model file and the launch plan of every utterance without a GPU and writes nothing.
 // --raw_out additionally writes the unquantised estimates as <key>-spk{1,2}.f32 (float32, for parity checks).
 #include <stdio.h>
@@ -114,15 +119,28 @@ int main(int argc, char** argv) {
   if (jobs < 1) jobs = 1;
   const int batch = atoi(args.get("batch", "1").c_str());
   if (batch < 1) return die("--batch needs a positive count");
+  const bool chunked = args.has("chunk_seconds");
+  const double chunk_s = atof(args.get("chunk_seconds", "0").c_str());
+  const double overlap_s = args.has("overlap_seconds") ? atof(args.get("overlap_seconds", "0").c_str()) : chunk_s / 4;
+  const int chunk_rows = atoi(args.get("chunk_rows", "8").c_str());
+  const int window = static_cast<int>(chunk_s * sample_rate + 0.5), overlap = static_cast<int>(overlap_s * sample_rate + 0.5);
   if (args.has("help")) {
     printf("usage: separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1]\n"
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
+           "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
-           "                     is accepted and changes nothing\n");
+           "                     is accepted and changes nothing\n"
+           "  --chunk_seconds S  long recordings: windows of S seconds through the separator, cross-faded; the speaker\n"
+           "                     encoder runs once per line.  Not together with --batch N > 1\n"
+           "  --overlap_seconds O  overlap of neighbouring windows, 0 <= O <= S / 2 (default S / 4)\n"
+           "  --chunk_rows N     window rows per forward (default 8): memory grows with N, not with the recording\n");
     return 0;
   }
+  if (chunked && batch > 1) return die("--chunk_seconds and --batch " + std::to_string(batch) + " conflict: a batch is a rectangle of "
+                                       "whole utterances, --chunk_seconds cuts one recording into windows (use --jobs for more lines at a time)");
+  if (chunked && (chunk_s <= 0 || overlap_s < 0)) return die("--chunk_seconds needs a positive length and --overlap_seconds none below 0");
   if (args.has("sort_by_length") && batch > 1) {
     std::vector<size_t> count(waves.size()), order(waves.size());
     for (size_t i = 0; i < waves.size(); ++i) {
@@ -251,8 +269,21 @@ int main(int argc, char** argv) {
       const int n_enroll = static_cast<int>(s1.samples.size() < s2.samples.size() ? s1.samples.size() : s2.samples.size());
       std::vector<float> out(size_t(2) * n, 0.f);
       const auto t0 = std::chrono::steady_clock::now();
-      if (ws_engine_forward_pcm16(engine, mix.samples.data(), n, s1.samples.data(), s2.samples.data(), n_enroll,
-                                  out.data()) != 0) {
+      int rc;
+      if (chunked) {
+        // the rows of ws_engine_forward_pcm16, the mixture once: scaled to [-1, 1], one enrollment row per target speaker
+        std::vector<float> m(n), enr(size_t(2) * n_enroll);
+        for (int i = 0; i < n; ++i) m[i] = static_cast<float>(mix.samples[i]) / 32768.0f;
+        for (int i = 0; i < n_enroll; ++i) {
+          enr[i] = static_cast<float>(s1.samples[i]) / 32768.0f;
+          enr[size_t(n_enroll) + i] = static_cast<float>(s2.samples[i]) / 32768.0f;
+        }
+        rc = ws_engine_separate_long(engine, m.data(), n, 2, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, window, overlap,
+                                     chunk_rows, out.data());
+      } else {
+        rc = ws_engine_forward_pcm16(engine, mix.samples.data(), n, s1.samples.data(), s2.samples.data(), n_enroll, out.data());
+      }
+      if (rc != 0) {
         fail(w[0] + ": " + ws_engine_last_error());
         break;
       }
@@ -271,8 +302,13 @@ int main(int argc, char** argv) {
         }
       }
       std::lock_guard<std::mutex> l(io_mu);
-      printf("process: %s RTF: %.4f (%lld launches, %lld MiB arena)%s\n", w[0].c_str(), ms / audio_ms,
-             ws_engine_info(engine, "n_launches"), ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");
+      if (chunked)
+        printf("process: %s RTF: %.4f (%lld windows in %lld forwards: %lld launches, %lld MiB arena)%s\n", w[0].c_str(), ms / audio_ms,
+               ws_engine_info(engine, "long_windows"), ws_engine_info(engine, "long_forwards"), ws_engine_info(engine, "n_launches"),
+               ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");
+      else
+        printf("process: %s RTF: %.4f (%lld launches, %lld MiB arena)%s\n", w[0].c_str(), ms / audio_ms,
+               ws_engine_info(engine, "n_launches"), ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");
       if (ws_engine_info(engine, "cluster_fallbacks") > fallbacks_seen) {
         fallbacks_seen = ws_engine_info(engine, "cluster_fallbacks");
         printf("note: %s: a cluster recurrence timed out (GPU shared); recomputed by the streaming kernels\n", w[0].c_str());

@@ -362,24 +362,56 @@ int prepare_tasnet(ws_engine* e) {
   return WS_OK;
 }
 
-// host-facing forward of a Conv-TasNet engine (same contract as ws_engine_separate)
-int tasnet_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind, int enroll_len,
-                    float* est) {
+// the argument checks of a Conv-TasNet forward, shared by ws_engine_separate and ws_engine_separate_long
+int tasnet_check_rows(ws_engine* e, bool ptrs, int R, int T) {
   const int L = e->tas.L, stride = L / 2;
-  if (!mix || !enroll || !est || R < 1 || T < 160 || (long long)R * ((T - L) / stride + 1) * 3 * e->tas.N > 0x7fffffffLL) {
+  if (!ptrs || R < 1 || T < 160 || (long long)R * ((T - L) / stride + 1) * 3 * e->tas.N > 0x7fffffffLL) {
     set_err("ws_engine_separate: bad arguments (R=%d, T=%d; Conv-TasNet needs T >= 160)", R, T);
     return WS_ERR_INVALID;
   }
+  return WS_OK;
+}
+
+int tasnet_check_enroll(ws_engine* e, int enroll_kind, int enroll_len) {
+  const int L = e->tas.L, stride = L / 2;
   const bool want_wave = e->joint != 0;
-  if ((enroll_kind == WS_ENROLL_WAVE) != want_wave || (enroll_kind != WS_ENROLL_WAVE && enroll_kind != WS_ENROLL_EMBEDDING)) {
+  const bool fits = want_wave ? enroll_kind == WS_ENROLL_WAVE || enroll_kind == WS_ENROLL_SPEAKER : enroll_kind == WS_ENROLL_EMBEDDING;
+  if (!fits) {
     set_err("ws_engine_separate: a Conv-TasNet engine takes %s (got enrollment kind %d)",
             want_wave ? "the enrollment waveform (SpEx+ speaker encoder on the shared encoder)" : "fixed embeddings", enroll_kind);
     return WS_ERR_INVALID;
   }
-  if (want_wave && ((enroll_len - L) / stride + 1) / 27 < 1) {
+  if (enroll_kind == WS_ENROLL_WAVE && ((enroll_len - L) / stride + 1) / 27 < 1) {
     set_err("ws_engine_separate: enrollment of %d samples is too short for three MaxPool1d(3) stages", enroll_len);
     return WS_ERR_INVALID;
   }
+  return WS_OK;
+}
+
+// the SpEx+ speaker stage alone: host enrollment waveforms [R][Te] -> device emb [R][E] (what tasnet_device computes into
+// emb_own when it is handed the waveform)
+int tasnet_speaker(ws_engine* e, const float* enroll_wave, int R, int Te, float* emb) {
+  const int L = e->tas.L, stride = L / 2, Tpa = (Te - L) / stride + 1;
+  Arena& a = e->work;
+  const Arena::Mark mk = a.mark();
+  float* d_enr = a.alloc(size_t(R) * Te);
+  float* cat_aux = a.alloc(size_t(R) * Tpa * 3 * e->tas.N);
+  WS_PTR(d_enr && cat_aux);
+  int rc;
+  if ((rc = to_device(e, d_enr, enroll_wave, size_t(R) * Te * 4)) != WS_OK) return rc;
+  if ((rc = tas_encode(e, d_enr, R, Te, cat_aux, nullptr)) != WS_OK) return rc;
+  if ((rc = tas_spk_embed(e, cat_aux, R, Tpa, emb)) != WS_OK) return rc;
+  a.release(mk);
+  return WS_OK;
+}
+
+// host-facing forward of a Conv-TasNet engine (same contract as ws_engine_separate)
+int tasnet_separate(ws_engine* e, const float* mix, int R, int T, const void* enroll, int enroll_kind, int enroll_len,
+                    float* est) {
+  int rc;
+  if ((rc = tasnet_check_rows(e, mix && enroll && est, R, T)) != WS_OK) return rc;
+  if ((rc = tasnet_check_enroll(e, enroll_kind, enroll_len)) != WS_OK) return rc;
+  const bool want_wave = enroll_kind == WS_ENROLL_WAVE;   // else [R][E]: fixed embeddings, or what ws_engine_embed returned
   if (!e->dry && hipSetDevice(e->device) != hipSuccess) {
     set_err("ws_engine_separate: hipSetDevice(%d) failed", e->device);
     return WS_ERR_LAUNCH;
@@ -387,7 +419,6 @@ int tasnet_separate(ws_engine* e, const float* mix, int R, int T, const void* en
   e->n_launches = 0;
   Arena& a = e->work;
   a.reset();
-  int rc;
   float* d_mix = a.alloc(size_t(R) * T);
   float* d_est = a.alloc(size_t(R) * T);
   float* d_enr = a.alloc(want_wave ? size_t(R) * enroll_len : size_t(R) * e->E);

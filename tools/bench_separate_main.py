@@ -7,6 +7,11 @@
         --arm loop8=runtime/separate_main:--batch,8:WS_ENGINE_RAGGED_SPK=0 \
         --arm sort8=runtime/separate_main:--batch,8,--sort_by_length \
         --arm parent8=../parent/runtime/separate_main:--batch,8  --runs 2 --out DIR/result.json
+    python tools/bench_separate_main.py --work DIR --run \
+        --arm whole=runtime/separate_main --arm parent=../parent/runtime/separate_main       # the path without the new flags
+    python tools/bench_separate_main.py --work DIR --gen --long_seconds 600 --utterances 1   # one synthetic 10-minute mixture
+    python tools/bench_separate_main.py --work DIR --run --timeout 900 \
+        --arm chunk4=runtime/separate_main:--chunk_seconds,4,--chunk_rows,8                  # windows of 4 s (profiles/longform.md)
 
 Workload (the one of profiles/ragged_batch.md, now reproducible): 64 utterances, mixtures uniform in 1-8 s, two
 enrollments per utterance uniform in 3-6 s, 16 kHz int16 noise; models with random weights: joint pBSRNN (6 repeats,
@@ -36,6 +41,11 @@ MODELS = {
     # --models tfgridnet (not in the default set): the recipe's TF-GridNet, 6 blocks, joint ResNet34 (profiles/ragged_gridnet.md)
     "tfgridnet": dict(separator="TFGridNet", spk_model="ResNet34", spk_emb_dim=256,
                       spk_args=dict(feat_dim=80, embed_dim=256, pooling_func="TSTP", two_emb_layer=False)),
+    # --models dpccn,spexplus (long recordings, profiles/longform.md): the constructors' default geometries, DPCCN with a
+    # joint ResNet34, Conv-TasNet with its own SpEx+ speaker encoder on the waveform
+    "dpccn": dict(separator="DPCCN", spk_model="ResNet34", spk_emb_dim=256, spk_feat=True,
+                  spk_args=dict(feat_dim=80, embed_dim=256, pooling_func="TSTP", two_emb_layer=False)),
+    "spexplus": dict(separator="ConvTasNet", N=256, spk_emb_dim=256),
 }
 DEFAULT_MODELS = ("resnet34", "ecapa")
 TFGRIDNET = dict(n_fft=128, stride=64, n_layers=6, lstm_hidden_units=192, attn_n_head=4, attn_approx_qk_dim=512, emb_dim=128,
@@ -50,19 +60,22 @@ def _write_wav(path, x, sr=16000):
         w.writeframes(np.asarray(x, dtype=np.int16).tobytes())
 
 
-def workload(seed=2024, n=64, sr=16000):
-    """(mixture samples [n], enrollment samples [n, 2]) of the seeded workload."""
+def workload(seed=2024, n=64, sr=16000, long_seconds=None):
+    """(mixture samples [n], enrollment samples [n, 2]) of the seeded workload; long_seconds: every mixture that long."""
     rng = np.random.default_rng(seed)
-    return rng.integers(1 * sr, 8 * sr + 1, n), rng.integers(3 * sr, 6 * sr + 1, (n, 2)), rng
+    mix_n, enr_n = rng.integers(1 * sr, 8 * sr + 1, n), rng.integers(3 * sr, 6 * sr + 1, (n, 2))
+    if long_seconds:
+        mix_n[:] = int(long_seconds * sr)
+    return mix_n, enr_n, rng
 
 
-def generate(work, seed=2024, n=64, models=DEFAULT_MODELS):
+def generate(work, seed=2024, n=64, models=DEFAULT_MODELS, long_seconds=None):
     sys.path.insert(0, ROOT)
     import torch
     from wesep_amd.bin.export_engine import export_engine
     from wesep_amd.models import get_model
     os.makedirs(os.path.join(work, "wav"), exist_ok=True)
-    mix_n, enr_n, rng = workload(seed, n)
+    mix_n, enr_n, rng = workload(seed, n, long_seconds=long_seconds)
     lines = []
     for i in range(n):
         paths = [os.path.join(work, "wav", f"{kind}{i:02d}.wav") for kind in ("mix", "a", "b")]
@@ -74,8 +87,11 @@ def generate(work, seed=2024, n=64, models=DEFAULT_MODELS):
     for name in models:
         torch.manual_seed(seed)
         kw = dict(MODELS[name])
-        if kw.pop("separator", "BSRNN") == "TFGridNet":
+        separator = kw.pop("separator", "BSRNN")
+        if separator == "TFGridNet":
             model = get_model("TFGridNet")(joint_training=True, spk_feat=True, **TFGRIDNET, **kw)
+        elif separator in ("DPCCN", "ConvTasNet"):
+            model = get_model(separator)(joint_training=True, **kw)
         else:
             model = get_model("BSRNN")(num_repeat=6, spk_fuse_type="multiply", multi_fuse=False, use_spk_transform=False,
                                        joint_training=True, spk_feat=True, **kw)
@@ -123,12 +139,13 @@ def main():
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--utterances", type=int, default=64)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per process")
+    ap.add_argument("--long_seconds", type=float, default=None, help="--gen: every mixture this long (long recordings)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     models = [m for m in a.models.split(",") if m]
     result = {}
     if a.gen:
-        result["workload"] = generate(a.work, a.seed, a.utterances, models)
+        result["workload"] = generate(a.work, a.seed, a.utterances, models, a.long_seconds)
     if a.run:
         arms = [parse_arm(s) for s in a.arm]
         if len(arms) < 1:

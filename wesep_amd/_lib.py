@@ -303,6 +303,9 @@ _SIGS = {
     "ws_ola_norm_len": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "ws_transpose_batched": (_i, [_p, _i, _i, _i, _p, _p]),
     "ws_heads_merge_fwd": (_i, [_p, _i, _i, _ll, _i, _p, _p]),
+    # long recordings (longform.hip)
+    "ws_window_rows": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ws_xfade_ola": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -40,23 +40,35 @@ def extract(model, wav_mix, enroll, lengths=None, enroll_lengths=None):
     return outputs.cpu().numpy()
 
 
-def extract_engine(engine, wav_mix, enroll, kind=None, lengths=None):
+def extract_engine(engine, wav_mix, enroll, kind=None, lengths=None, window=None, overlap=None):
     """The same step on the native runtime (`wesep_amd.engine.Engine`, runtime/libwesep_engine.so): host arrays in,
     numpy [B, T] out, peak-normalised by the same rule.  `kind`: an `ENROLL_*` constant; default by rank
     (2-D embeddings for fixed-embedding models are ENROLL_EMBEDDING, 3-D is fbank; pass ENROLL_WAVE for audio).
-    lengths (B ints): a ragged batch, as in extract (Engine.separate_ragged; the enrollment rows keep their full length)."""
+    lengths (B ints): a ragged batch, as in extract (Engine.separate_ragged; the enrollment rows keep their full length).
+    window (samples; overlap defaults to window // 4): long recordings -- every mixture goes through
+    Engine.separate_long on its own (over its own samples when lengths is given), and the peak normalisation is applied
+    to the assembled estimate, not per window."""
     from .. import engine as E
     wav_mix = np.ascontiguousarray(wav_mix, dtype=np.float32)
     enroll = np.ascontiguousarray(enroll, dtype=np.float32)
     if kind is None:
         kind = E.ENROLL_FBANK if enroll.ndim == 3 else E.ENROLL_EMBEDDING
-    if lengths is not None:
+    if window is not None:
+        overlap = int(window) // 4 if overlap is None else overlap
+        outputs = np.zeros_like(wav_mix)
+        for r in range(wav_mix.shape[0]):
+            n = wav_mix.shape[1] if lengths is None else int(lengths[r])
+            outputs[r, :n] = engine.separate_long(wav_mix[r, :n], enroll[r:r + 1], kind, window, overlap)[0]
+        if lengths is not None:
+            return peak_normalise_rows(outputs, lengths)
+    elif lengths is not None:
         rows = engine.separate_ragged([wav_mix[r, :int(n)] for r, n in enumerate(lengths)], list(enroll), kind)
         outputs = np.zeros_like(wav_mix)
         for r, row in enumerate(rows):
             outputs[r, :len(row)] = row
         return peak_normalise_rows(outputs, lengths)
-    outputs = engine.separate(wav_mix, enroll, kind)
+    else:
+        outputs = engine.separate(wav_mix, enroll, kind)
     if outputs.max(axis=1).min() > 0:
         outputs = outputs / np.abs(outputs).max(axis=1, keepdims=True) * 0.9
     return outputs

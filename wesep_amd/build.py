@@ -63,7 +63,8 @@ RUNTIME = os.path.join(os.path.dirname(HERE), "runtime")
 ENGINE_OUT = os.path.join(RUNTIME, "libwesep_engine.so")
 MAIN_OUT = os.path.join(RUNTIME, "separate_main")
 # libwesep_engine.so: one translation unit per part (runtime/engine_internal.h); it exports the C ABI only
-ENGINE_SRCS = ["engine.cc", "speaker.cc", "bsrnn_plan.cc", "tasnet_plan.cc", "dpccn_plan.cc", "gridnet_plan.cc"]
+ENGINE_SRCS = ["engine.cc", "speaker.cc", "bsrnn_plan.cc", "tasnet_plan.cc", "dpccn_plan.cc", "gridnet_plan.cc",
+               "longform.cc"]
 
 
 def build_runtime(force=False, verbose=True):

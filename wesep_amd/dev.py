@@ -1635,6 +1635,34 @@ def heads_merge_fwd(ov, nh: int, R: int, P: int, cp: int, o):
     _call("ws_heads_merge_fwd", _p(ov), nh, R, P, cp, _p(o))
 
 
+# ---- long recordings (longform.hip) -----------------------------------------------------------------
+def _chk_room(t, need: int, who: str, name: str):
+    if t.numel() < need:
+        raise L.WesepHipError(f"{who}: {name} holds {t.numel()} floats, the call needs {need}")
+
+
+def window_rows(x, n: int, W: int, S: int, H: int, reps: int, rows, scale=None):
+    """rows[(k * W + w)][j] = x[min(w * H, n - S) + j] (* scale[w]), k < reps: the windows of wesep_amd.engine.long_windows."""
+    for nm, t in (("x", x), ("rows", rows), ("scale", scale)):
+        _chk(t, nm)
+    _chk_room(x, n, "ws_window_rows", "x")
+    _chk_room(rows, reps * W * min(n, S), "ws_window_rows", "rows")
+    if scale is not None:
+        _chk_room(scale, W, "ws_window_rows", "scale")
+    _call("ws_window_rows", _p(x), n, W, S, H, reps, _p(scale), _p(rows))
+
+
+def xfade_ola(y, K: int, W: int, S: int, O: int, n: int, out, scale=None):
+    """y [K][W][min(n, S)] -> out [K][n]: the windows' estimates cross-faded over the O overlapping samples."""
+    for nm, t in (("y", y), ("out", out), ("scale", scale)):
+        _chk(t, nm)
+    _chk_room(y, K * W * min(n, S), "ws_xfade_ola", "y")
+    _chk_room(out, K * n, "ws_xfade_ola", "out")
+    if scale is not None:
+        _chk_room(scale, W, "ws_xfade_ola", "scale")
+    _call("ws_xfade_ola", _p(y), K, W, S, O, n, _p(scale), _p(out))
+
+
 # ---- DPCCN pieces (conv2d.hip) --------------------------------------------------------------------------
 IN_EPS = 1e-5  # nn.InstanceNorm{1,2}d default
 

@@ -10,10 +10,12 @@ from ._lib import WesepHipError
 ENGINE_ABI_VERSION = 2
 DRY_RUN = 1
 ENROLL_EMBEDDING, ENROLL_FBANK, ENROLL_WAVE = 0, 1, 2
+ENROLL_SPEAKER = 3      # [R, E]: what Engine.embed returned (joint containers)
 LIB_PATH = os.environ.get("WESEP_ENGINE_LIB") or os.path.join(
     os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "runtime", "libwesep_engine.so")
 SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", "ws_engine_destroy", "ws_engine_info",
-           "ws_engine_separate", "ws_engine_separate_ragged", "ws_engine_forward_pcm16")
+           "ws_engine_separate", "ws_engine_separate_ragged", "ws_engine_forward_pcm16", "ws_engine_embed",
+           "ws_engine_separate_long")
 _lib = None
 
 
@@ -40,6 +42,11 @@ def lib():
         l.ws_engine_forward_pcm16.restype = C.c_int
         l.ws_engine_forward_pcm16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p]
+        l.ws_engine_embed.restype = C.c_int
+        l.ws_engine_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.ws_engine_separate_long.restype = C.c_int
+        l.ws_engine_separate_long.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         if l.ws_engine_abi_version() != ENGINE_ABI_VERSION:
             raise WesepHipError("libwesep_engine.so ABI version mismatch; rebuild")
         _lib = l
@@ -79,6 +86,37 @@ def frames_of(lengths, hop=128):
     """Valid STFT frames of rows with `lengths` samples (centred framing: 1 + n // hop) -- the table the engine and
     BSRNN.forward(lengths=) hand to the length-aware kernels."""
     return 1 + np.asarray(lengths, dtype=np.int64) // hop
+
+
+def long_windows(n, S, O):
+    """Starts of the windows that ws_engine_separate_long cuts a recording of n samples into (window S, overlap O with
+    0 <= O <= S // 2, hop S - O): [0] when n <= S (one window [0, n)), else 1 + ceil((n - S) / hop) windows of exactly S
+    samples at w * hop, the last one aligned to the end (n - S)."""
+    n, S, O = int(n), int(S), int(O)
+    if n < 1 or S < 1 or O < 0 or O > S // 2:
+        raise ValueError(f"long_windows: n = {n}, window = {S}, overlap = {O} (0 <= overlap <= window // 2)")
+    if n <= S:
+        return [0]
+    H = S - O
+    W = 1 + -(-(n - S) // H)
+    return [min(w * H, n - S) for w in range(W)]
+
+
+def _enroll_rows(enrolls, kind, lengths):
+    """(rectangle, row pitch, int32 length table or None) of a list / array of enrollments for the C ABI"""
+    fixed = kind in (ENROLL_EMBEDDING, ENROLL_SPEAKER)
+    if isinstance(enrolls, (list, tuple)) and not fixed and lengths is None:
+        enroll, elen = pack_rows(enrolls)
+        lengths = elen if len(set(elen.tolist())) > 1 else None
+    else:
+        enroll = np.ascontiguousarray(enrolls, dtype=np.float32)
+    if lengths is not None:
+        if fixed:
+            raise ValueError("embeddings have no lengths")
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        if lengths.shape != (enroll.shape[0],):
+            raise ValueError("one enrollment length per row")
+    return enroll, (0 if fixed else enroll.shape[1]), lengths
 
 
 class Engine:
@@ -139,6 +177,36 @@ class Engine:
                                                0 if fixed else enroll.shape[1], None if fixed else elen.ctypes.data,
                                                est.ctypes.data), "ws_engine_separate_ragged")
         return [est[r, :n].copy() for r, n in enumerate(lengths.tolist())]
+
+    def embed(self, enroll, kind, lengths=None):
+        """The speaker stage alone (joint containers): enroll [R, Te, F] (ENROLL_FBANK) or [R, Tw] (ENROLL_WAVE), or a list
+        of R such rows of different lengths; lengths: valid frames / samples per row of a rectangle -> [R, E] float32, the
+        encoder's embedding before SpeakerTransform.  separate(mix, emb, ENROLL_SPEAKER) with the same R returns bit for
+        bit what separate(mix, enroll, kind) does, without running the encoder again."""
+        enroll, pitch, lengths = _enroll_rows(enroll, kind, lengths)
+        E = self.info("spk_emb_dim")
+        emb = np.zeros((enroll.shape[0], E if E > 0 else 256), dtype=np.float32)
+        _quiesce_torch()
+        _check(lib().ws_engine_embed(self._h, enroll.ctypes.data, kind, enroll.shape[0], pitch,
+                                     None if lengths is None else lengths.ctypes.data, emb.ctypes.data), "ws_engine_embed")
+        return emb
+
+    def separate_long(self, mix, enrolls, kind, window, overlap, max_rows=8):
+        """One long mixture [n] and K enrollments (an array as in separate(), or a list of rows of different lengths) ->
+        [K, n] float32: the mixture as overlapping windows (long_windows(n, window, overlap)) through the separator,
+        max_rows rows per forward, cross-faded on the device; the speaker stage runs once (include/wesep_engine.h,
+        ws_engine_separate_long)."""
+        mix = np.ascontiguousarray(mix, dtype=np.float32)
+        if mix.ndim != 1:
+            raise ValueError("separate_long: one mixture [n]")
+        enroll, pitch, lengths = _enroll_rows(enrolls, kind, None)
+        K, n = enroll.shape[0], mix.shape[0]
+        est = np.zeros((K, n), dtype=np.float32)
+        _quiesce_torch()
+        _check(lib().ws_engine_separate_long(self._h, mix.ctypes.data, n, K, enroll.ctypes.data, kind, pitch,
+                                             None if lengths is None else lengths.ctypes.data, int(window), int(overlap),
+                                             int(max_rows), est.ctypes.data), "ws_engine_separate_long")
+        return est
 
     def forward_pcm16(self, mix, spk1, spk2):
         """int16 [n], int16 [n_enroll] x 2 -> float32 [2, n] in [-1, 1] (SeparateEngine::ForwardFunc)."""
