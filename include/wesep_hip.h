@@ -1105,6 +1105,33 @@ int ws_heads_merge_fwd(const float* ov, int nh, int R, long long P, int cp, floa
 int ws_window_rows(const float* x, int n, int W, int S, int H, int reps, const float* scale, float* rows, void* stream);
 int ws_xfade_ola(const float* y, int K, int W, int S, int O, int n, const float* scale, float* out, void* stream);
 
+/* ---- streaming Conv-TasNet (stream.hip; wesep_amd/streaming.py) -- new symbols, ABI 20 unchanged --------
+ * The two kernels of a causal Conv-TasNet that look across time, in a chunked form with state carried on the device.
+ *   ws_dwconv_stream_fwd  ws_dwconv_ex_fwd(causal = 1) on one chunk of Tc frames whose first frame has absolute index t0.
+ *                   x [R][Tc][C] is the pre-norm activation, normalised on load with statistics row m / st_div over the
+ *                   chunk's rows (cLN: 1; eval-mode BN: identity statistics, st_div = R * Tc).  ring [R][cap][C] holds the
+ *                   NORMALISED frame of absolute index a in slot a % cap.
+ *                     y[r][t][c] = b[c] + sum_p w[c][p] * xn(r, t0 + t - (P - 1 - p) * dil),  ascending p,
+ *                   xn(a) = the chunk's own value for a >= t0, the ring slot for 0 <= a < t0, and no term for a < 0 (the
+ *                   ring is not read there: it needs no initialisation).  The same launch writes every chunk frame's
+ *                   normalised value to its slot.  Contract: cap >= (P - 1) * dil + Tc -- then the slot written for frame
+ *                   a last held frame a - cap, which no output of this chunk reads, and the launch is race-free without a
+ *                   second buffer.  Over any chunking the outputs are bit for bit ws_dwconv_ex_fwd(causal = 1) on the
+ *                   concatenated sequence (given the same statistics).  WS_ERR_INVALID before any launch: cap below the
+ *                   bound, C % 4 != 0, P not odd or above 7, t0 < 0, a NULL pointer, y overlapping x.
+ *   ws_ola_stream_fwd  frames [R][Tc][L] -> est [R][Tc * hop], carry [R][L - hop] updated in place.  carry holds, for the
+ *                   L - hop samples that are not final yet, bias + the contributions of earlier frames, accumulated in
+ *                   ascending frame order (the association of ws_ola_fwd).  The call emits the Tc * hop samples that become
+ *                   final and leaves the new carry; samples past the old carry start from bias[0] (NULL: 0).  A reset fills
+ *                   carry with the bias; after the last chunk, carry is the last L - hop samples.  The concatenation is bit
+ *                   for bit ws_ola_fwd over all frames with Tout = (T' - 1) * hop + L.  Any L >= hop with L % hop == 0
+ *                   (L - hop <= 16384; carry may be NULL when L == hop). */
+int ws_dwconv_stream_fwd(const float* x, const float* stats, const float* gamma, const float* beta, const float* w,
+                         const float* b, int R, int Tc, int C, int P, int dil, int st_div, long long t0, int cap,
+                         float* ring, float* y, void* stream);
+int ws_ola_stream_fwd(const float* frames, const float* bias, int R, int Tc, int L, int hop, float* carry, float* est,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,7 @@
 // (deterministic, no atomics).  The 1x1 convolutions run on the generic MFMA GEMMs (gemm*.hip) with
 // the normalisation applied on operand load.
 #include "common.h"
-
-#define TN_MAXP 7
+#include "tasnet_dw.h"
 
 static inline unsigned ew_blocks(long long n, int per_block) {
   long long b = (n + per_block - 1) / per_block;
@@ -165,19 +164,9 @@ extern "C" int ws_prelu_bwd(const float* pre, const float* dy, const float* a, l
 //   xn[r][t][c] = (x - mean_s) * rstd_s * gamma[c] + beta[c],  s = m / st_div  (gLN: T', cLN: 1)
 //   y[r][t][c]  = b[c] + sum_p w[c][p] * xn[r][t + (p - ctr) * dil][c]          (zero outside [0, T'))
 // ctr = (P-1)/2 (non-causal), or P-1 for the causal blocks (convs.py:61-62,91-92: padding dil*(P-1) on both sides, the
-// last dil*(P-1) outputs cut -- every tap at or before t)
+// last dil*(P-1) outputs cut -- every tap at or before t).  DwGeom, dw_xn and dw_tap live in tasnet_dw.h: the chunked
+// kernel of stream.hip shares them.
 // ---------------------------------------------------------------------------------------------
-struct DwGeom {
-  int R, Tp, C, P, dil, st_div, ctr;
-};
-
-__device__ __forceinline__ f32x4 dw_xn(const float* __restrict__ x, const float* __restrict__ stats,
-                                       const f32x4& gm, const f32x4& bt, const DwGeom& g, long long row, int c) {
-  const long long s = row / g.st_div;
-  const float mean = stats[2 * s], rstd = stats[2 * s + 1];
-  return (*reinterpret_cast<const f32x4*>(x + row * g.C + c) - mean) * rstd * gm + bt;
-}
-
 __global__ void dwconv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ stats,
                                   const float* __restrict__ gamma, const float* __restrict__ beta,
                                   const float* __restrict__ w, const float* __restrict__ b, DwGeom g,
@@ -195,9 +184,7 @@ __global__ void dwconv_fwd_kernel(const float* __restrict__ x, const float* __re
     for (int p = 0; p < g.P; ++p) {
       const int tt = t + (p - ctr) * g.dil;
       if (tt < 0 || tt >= g.Tp) continue;
-      const f32x4 v = dw_xn(x, stats, gm, bt, g, row + (tt - t), c);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] += w[(c + j) * g.P + p] * v[j];
+      dw_tap(acc, w, c, g.P, p, dw_xn(x, stats, gm, bt, g, row + (tt - t), c));
     }
     *reinterpret_cast<f32x4*>(y + i * 4) = acc;
   }

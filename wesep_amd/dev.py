@@ -1663,6 +1663,33 @@ def xfade_ola(y, K: int, W: int, S: int, O: int, n: int, out, scale=None):
     _call("ws_xfade_ola", _p(y), K, W, S, O, n, _p(scale), _p(out))
 
 
+# ---- streaming Conv-TasNet (stream.hip; wesep_amd/streaming.py) ---------------------------------------------------
+def dwconv_stream_fwd(x, stats, gamma, beta, w, b, R: int, Tc: int, Cc: int, P: int, dil: int, st_div: int, t0: int,
+                      ring, y):
+    """dwconv_fwd(causal=True) on the chunk of Tc frames that starts at absolute frame t0; ring [R, cap, C] carries the
+    normalised frames of earlier chunks (slot = frame % cap) and receives this chunk's.  cap >= (P - 1) * dil + Tc."""
+    for n, t in (("x", x), ("stats", stats), ("gamma", gamma), ("beta", beta), ("w", w), ("b", b), ("ring", ring), ("y", y)):
+        _chk(t, n)
+    if ring.dim() != 3 or ring.shape[0] != R or ring.shape[2] != Cc:
+        raise L.WesepHipError(f"ws_dwconv_stream_fwd: ring is {tuple(ring.shape)}, the call needs [{R}, cap, {Cc}]")
+    _chk_room(x, R * Tc * Cc, "ws_dwconv_stream_fwd", "x")
+    _chk_room(y, R * Tc * Cc, "ws_dwconv_stream_fwd", "y")
+    _call("ws_dwconv_stream_fwd", _p(x), _p(stats), _p(gamma), _p(beta), _p(w), _p(b), R, Tc, Cc, P, dil, st_div, t0,
+          ring.shape[1], _p(ring), _p(y))
+
+
+def ola_stream_fwd(frames, bias, R: int, Tc: int, Lk: int, hop: int, carry, est):
+    """frames [R*Tc, L] -> est [R, Tc*hop] (the samples that become final); carry [R, L - hop] (bias + earlier frames'
+    contributions to the samples that are not final yet) is updated in place."""
+    for n, t in (("frames", frames), ("bias", bias), ("carry", carry), ("est", est)):
+        _chk(t, n)
+    _chk_room(frames, R * Tc * Lk, "ws_ola_stream_fwd", "frames")
+    _chk_room(est, R * Tc * hop, "ws_ola_stream_fwd", "est")
+    if carry is not None:
+        _chk_room(carry, R * (Lk - hop), "ws_ola_stream_fwd", "carry")
+    _call("ws_ola_stream_fwd", _p(frames), _p(bias), R, Tc, Lk, hop, _p(carry), _p(est))
+
+
 # ---- DPCCN pieces (conv2d.hip) --------------------------------------------------------------------------
 IN_EPS = 1e-5  # nn.InstanceNorm{1,2}d default
 
