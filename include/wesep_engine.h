@@ -51,7 +51,10 @@ void ws_engine_destroy(ws_engine* e);
  * wesep_hip.h, ws_lstm_fwd_cluster), "ragged_speaker" (1: enroll_lengths of ws_engine_separate_ragged run the speaker
  * encoder once over all rows, 0: one row at a time), "ragged_separator" (1: the separator takes the lengths of
  * ws_engine_separate_ragged -- pBSRNN and TF-GridNet; 0: it refuses them), "long_windows" / "long_forwards" (windows per
- * target speaker and separator forwards of the last ws_engine_separate_long; 0 after any other call)}; unknown key -> -1. */
+ * target speaker and separator forwards of the last ws_engine_separate_long; 0 after any other call), "causal" / "norm"
+ * (Conv-TasNet containers: 1 / 1 for causal blocks with cLN; absent, i.e. -1, in containers written before these keys, which
+ * load as non-causal gLN), "streaming" (1: ws_engine_stream_open takes this container), "stream_state_bytes" (device state
+ * of the stream opened last)}; unknown key -> -1. */
 long long ws_engine_info(const ws_engine* e, const char* key);
 
 /* enrollment kinds */
@@ -119,6 +122,49 @@ int ws_engine_embed(ws_engine* e, const void* enroll, int enroll_kind, int R, in
  * linearly in n; "long_windows" / "long_forwards" of ws_engine_info report W and the number of groups. */
 int ws_engine_separate_long(ws_engine* e, const float* mix, int n, int K, const void* enroll, int enroll_kind, int enroll_len,
                             const int* enroll_lengths, int window, int overlap, int max_rows, float* est);
+
+/* Streaming (new symbols, engine ABI 2 unchanged): a causal cLN Conv-TasNet / SpEx+ container (meta "causal" = 1, "norm" = 1;
+ * ws_engine_info(e, "streaming") == 1) fed audio as it arrives, in chunks of any size.  The concatenation of what the pushes
+ * and the flush return is the model-output part of ws_engine_separate's row on the concatenated input: its first
+ * (T' - 1) s + L samples, T' = (N - L) / s + 1, s = L / 2, to the rounding of a forward over another number of frames.  Every
+ * encoder frame, block frame and output sample is computed once.  All pointers are HOST pointers.
+ *
+ * Emission rule, with N samples pushed so far: frame k runs once k s + 160 <= N (160: the longest encoder window); after K
+ * frames, K s samples a row have been returned.  ws_engine_stream_push(chunk [rows][n], n >= 1) writes the samples that
+ * became final to est [rows][*n_out] (row pitch *n_out, possibly 0); est must hold est_cap >= *n_out samples a row --
+ * WS_STREAM_PUSH_CAP(n, L) always suffices.  ws_engine_stream_flush zero-extends the pending samples as the whole-utterance
+ * encoder does, runs the frames up to T' and returns the rest ((T' - 1) s + L samples in all; at most WS_STREAM_FLUSH_CAP a
+ * row in this call).  ws_engine_stream_reset returns to sample 0 and keeps the enrollment.
+ *
+ * ws_engine_stream_open runs the speaker stage once -- enrollment kinds as for ws_engine_separate on this container:
+ * WS_ENROLL_EMBEDDING for fixed embeddings, WS_ENROLL_WAVE or WS_ENROLL_SPEAKER for SpEx+ --, then SpeakerTransform and the
+ * row biases W_e e + b of the stacks' first blocks, and keeps the results.  A container that is not arch 1 with causal blocks
+ * and cLN is refused by name.  Carried state is ONE device allocation owned by the stream, made at open and freed at close:
+ * per block a ring [rows][(P - 1) dil + max_chunk_frames][H] of normalised frames, the overlap-add carry [rows][L - s]
+ * (reset: the decoder bias), two pending-sample buffers [rows][max_chunk_frames s + 160] used in turn, the embedding and
+ * the row biases.  It does not grow with n: frames run in groups of at most max_chunk_frames, and a long chunk is taken in
+ * pieces.  Transient activations come from the engine's arena and are returned before the call ends, so any other engine
+ * call between two pushes leaves the stream as it was, and several streams may be open on one engine (callers serialise, as
+ * for every engine call).  Close every stream before ws_engine_destroy.
+ *
+ * Launches: a group of frames is WS_STREAM_GROUP_LAUNCHES(R, X) = 3 R X + 10 entry-point calls -- 3 framing GEMMs, row
+ * statistics, projection; per block GEMM, ws_tcn_mid_stream_fwd, GEMM; mask GEMM, ws_maskmul_fwd, synthesis GEMM,
+ * ws_ola_stream_fwd; the copy of the unconsumed pending samples to the other buffer.  ws_engine_info(e, "n_launches") after
+ * a push or flush is that figure times the groups the call ran (0 when no frame became complete); it does not depend on n
+ * for a push that runs one group.  The copies to and from the host are not counted.  One host synchronisation per push, on
+ * the engine's own stream, after the device-to-host copy.
+ * WS_ERR_INVALID with a message and nothing launched: est_cap below what the call emits, flush with N < L, push or flush after
+ * a flush, n < 1, a NULL pointer. */
+#define WS_STREAM_PUSH_CAP(n, L) (((n) / ((L) / 2) + 1) * ((L) / 2))
+#define WS_STREAM_FLUSH_CAP 160
+#define WS_STREAM_GROUP_LAUNCHES(R, X) (3 * (R) * (X) + 10)
+typedef struct ws_stream ws_stream;
+int ws_engine_stream_open(ws_engine* e, int rows, const void* enroll, int enroll_kind, int enroll_len, int max_chunk_frames,
+                          ws_stream** out);
+int ws_engine_stream_push(ws_stream* s, const float* chunk, int n, float* est, int est_cap, int* n_out);
+int ws_engine_stream_flush(ws_stream* s, float* est, int est_cap, int* n_out);
+int ws_engine_stream_reset(ws_stream* s);
+void ws_engine_stream_close(ws_stream* s);
 
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by

@@ -1131,6 +1131,27 @@ int ws_dwconv_stream_fwd(const float* x, const float* stats, const float* gamma,
                          float* ring, float* y, void* stream);
 int ws_ola_stream_fwd(const float* frames, const float* bias, int R, int Tc, int L, int hop, float* carry, float* est,
                       void* stream);
+/*   ws_tcn_mid_stream_fwd  everything between the two GEMMs of a causal cLN block on one chunk, in ONE launch (in place of
+ *                   ws_prelu_fwd, ws_group_stats, ws_dwconv_stream_fwd, ws_prelu_fwd, ws_group_stats).  c [R][Tc][H] is the
+ *                   first 1x1 convolution's output for the frames t0 .. t0 + Tc - 1 (read only), rb [R][H] the concatConv
+ *                   row bias or NULL.  For row r, chunk frame t:
+ *                     y1 = prelu(c[r][t][:] + rb[r][:], a1[0]);  (m1, s1) = mean and 1 / sqrt(biased var + eps) of y1 over H
+ *                     (two passes, as ws_group_stats);  xn(r, t0 + t) = (y1 - m1) * s1 * gamma1 + beta1, written to
+ *                     ring[r][(t0 + t) % cap][:];  z = bd + sum_p wd[ch][p] * xn(r, t0 + t - (P - 1 - p) * dil), ascending p,
+ *                     with the tap rules of ws_dwconv_stream_fwd (chunk frames from the chunk -- recomputed from c, never read
+ *                     from the ring --, 0 <= a < t0 from slot a % cap, a < 0 no term and no read);
+ *                     y2[r][t][:] = prelu(z, a2[0]);  st2[r * Tc + t] = (mean, rstd) of y2 over H.
+ *                   The block's second GEMM normalises on load from st2.  Contract: cap >= (P - 1) * dil + Tc (race-free, as
+ *                   above), and over any chunking y2, st2 and the written ring slots are bit for bit those of one chunk with
+ *                   the whole sequence: a frame's xn is one expression reduced in one fixed order (inside a wave, then across
+ *                   waves through LDS) wherever it is computed.  No atomics, nothing waits on another workgroup; results are
+ *                   the same from run to run.  WS_ERR_INVALID before any launch: a NULL pointer other than rb, H % 4 != 0,
+ *                   H above WS_TCN_MID_MAXH (2 H + 16 floats of LDS per workgroup), P not odd or above 7, dil < 1, t0 < 0, cap
+ *                   below the bound, y2 overlapping c (other frames' workgroups re-read c). */
+#define WS_TCN_MID_MAXH 4096
+int ws_tcn_mid_stream_fwd(const float* c, const float* rb, const float* a1, const float* gamma1, const float* beta1,
+                          const float* wd, const float* bd, const float* a2, int R, int Tc, int H, int P, int dil,
+                          float eps, long long t0, int cap, float* ring, float* y2, float* st2, void* stream);
 
 #ifdef __cplusplus
 }

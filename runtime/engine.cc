@@ -352,6 +352,9 @@ WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   // windows per target speaker and separator forwards of the last ws_engine_separate_long (0 after any other call)
   if (k == "long_windows") return e->long_windows;
   if (k == "long_forwards") return e->long_forwards;
+  // 1: ws_engine_stream_open takes this container (causal cLN Conv-TasNet / SpEx+); the state bytes of the stream opened last
+  if (k == "streaming") return tas_streamable(e) ? 1 : 0;
+  if (k == "stream_state_bytes") return e->stream_state_bytes;
   auto it = e->meta.find(k);
   return it == e->meta.end() ? -1 : it->second;
 }

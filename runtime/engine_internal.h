@@ -9,6 +9,7 @@
 //   dpccn_plan.cc    DPCCN (arch 2)
 //   gridnet_plan.cc  TF-GridNet (arch 3)
 //   longform.cc      ws_engine_separate_long: one long mixture as overlapping windows through the rectangular plans
+//   stream.cc        ws_engine_stream_*: causal cLN Conv-TasNet fed audio as it arrives, state carried on the device
 // Everything here lives in namespace wsrt and is built with -fvisibility=hidden: the library exports the C ABI only
 // (WS_ENGINE_API).  Host code only: no kernels in the runtime.
 #ifndef WESEP_ENGINE_INTERNAL_H_
@@ -247,6 +248,7 @@ struct Bsrnn {
 // ---- Conv-TasNet / SpEx+ (arch 1; wesep/models/convtasnet.py; tasnet_plan.cc): geometry and prepared operands ----
 struct TasNet {
   int N = 512, L = 16, B = 128, H = 512, P = 3, X = 8, R = 3;
+  int causal = 0, norm = 0;  // meta "causal" / "norm" (0 gLN, 1 cLN): (0, 0) the shipped model, (1, 1) the streamable one
   float* dec_wt = nullptr;   // decoder_1d_1 weight transposed to [L][N]
   float* bn_st[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};  // eval BN (mean, rstd) [2][C]
 };
@@ -289,6 +291,7 @@ struct ws_engine {
   wsrt::Arena persist, work;
   long long n_launches = 0;
   long long long_windows = 0, long_forwards = 0;   // of the last ws_engine_separate_long
+  long long stream_state_bytes = 0;                // device state of the stream opened last (ws_engine_stream_open)
   long long cluster_fallbacks = 0;   // forwards in which a cluster recurrence timed out and the streaming kernels took over
   unsigned* cl_status = nullptr;     // sticky device word set by ws_lstm_fwd_cluster on a timeout
   // configuration shared by the plans
@@ -398,6 +401,26 @@ int tasnet_speaker(ws_engine* e, const float* enroll_wave, int R, int Te, float*
 int tasnet_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, const float* enroll_wave, int Te,
                   float* est);
 int tas_row_stats(ws_engine* e, const float* x, long long M, int C, float* st);
+struct TasGemm {
+  const float* A = nullptr;
+  long long lda = 0;
+  long long M = 0;
+  int K = 0;
+  const float* W = nullptr;
+  int ldw = 0, N = 0;
+  const float* bias = nullptr;
+  int act = 0;
+  float* C = nullptr;
+  long long ldc = 0;
+  const float* R = nullptr;                                       // residual, addressed like C
+  const float *stats = nullptr, *gamma = nullptr, *beta = nullptr; // norm-on-load
+  int st_div1 = 1;                                                 // rows per statistics pair (gLN: T', cLN: 1)
+  bool f32 = false;                                                // exact-fp32 products (the SpEx+ speaker encoder)
+  int a_div = kBig;                                                // frames view: row m -> (m / a_div) * a_s1 + (m % a_div) * lda
+  long long a_s1 = 0;
+};
+int tas_gemm(ws_engine* e, const TasGemm& t);
+inline bool tas_streamable(const ws_engine* e) { return e->arch == 1 && e->tas.causal && e->tas.norm == 1; }
 int tas_flat_stats(ws_engine* e, const float* x, int R, long long n, float* st);
 int prepare_dpccn(ws_engine* e);
 int dpccn_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est);

@@ -3,6 +3,7 @@
 //
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
 //                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
+//                 [--stream_ms 10]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -25,6 +26,10 @@
 // O, N window rows per forward, the estimates cross-faded on the device, the speaker encoder run once per line.  Memory
 // grows with N, not with the recording.  Scaling, output names and formats as above; works with --jobs and --dry_run; not
 // together with --batch N > 1 (a rectangle of whole utterances).  A mixture no longer than S is the whole-utterance forward.
+// --stream_ms M (causal cLN Conv-TasNet / SpEx+ models, ws_engine_info "streaming"): every line is fed to a stream
+// (ws_engine_stream_open / push / flush) in chunks of M milliseconds, as a live source would deliver it; the speaker encoder
+// runs once per line, at open.  Same files as the plain run: the streamed samples, then zeros where the plain run has its
+// zero tail.  Refused on a model that cannot stream, and together with --batch N > 1 or --chunk_seconds.
 // --dry_run validates the model file and the launch plan of every utterance without a GPU and writes nothing.
 // --raw_out additionally writes the unquantised estimates as <key>-spk{1,2}.f32 (float32, for parity checks).
 #include <stdio.h>
@@ -124,6 +129,9 @@ int main(int argc, char** argv) {
   const double overlap_s = args.has("overlap_seconds") ? atof(args.get("overlap_seconds", "0").c_str()) : chunk_s / 4;
   const int chunk_rows = atoi(args.get("chunk_rows", "8").c_str());
   const int window = static_cast<int>(chunk_s * sample_rate + 0.5), overlap = static_cast<int>(overlap_s * sample_rate + 0.5);
+  const bool streamed = args.has("stream_ms");
+  const double stream_ms = atof(args.get("stream_ms", "0").c_str());
+  const int stream_n = static_cast<int>(stream_ms * sample_rate / 1000.0 + 0.5);
   if (args.has("help")) {
     printf("usage: separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1]\n"
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
@@ -135,11 +143,16 @@ int main(int argc, char** argv) {
            "  --chunk_seconds S  long recordings: windows of S seconds through the separator, cross-faded; the speaker\n"
            "                     encoder runs once per line.  Not together with --batch N > 1\n"
            "  --overlap_seconds O  overlap of neighbouring windows, 0 <= O <= S / 2 (default S / 4)\n"
-           "  --chunk_rows N     window rows per forward (default 8): memory grows with N, not with the recording\n");
+           "  --chunk_rows N     window rows per forward (default 8): memory grows with N, not with the recording\n"
+           "  --stream_ms M      causal cLN Conv-TasNet / SpEx+ models: feed every line to a stream in chunks of M ms; same\n"
+           "                     files as the plain run.  Not together with --batch N > 1 or --chunk_seconds\n");
     return 0;
   }
   if (chunked && batch > 1) return die("--chunk_seconds and --batch " + std::to_string(batch) + " conflict: a batch is a rectangle of "
                                        "whole utterances, --chunk_seconds cuts one recording into windows (use --jobs for more lines at a time)");
+  if (streamed && (batch > 1 || chunked))
+    return die("--stream_ms conflicts with --batch N > 1 and --chunk_seconds: a stream takes one recording as it arrives");
+  if (streamed && stream_n < 1) return die("--stream_ms needs a positive chunk length");
   if (chunked && (chunk_s <= 0 || overlap_s < 0)) return die("--chunk_seconds needs a positive length and --overlap_seconds none below 0");
   if (args.has("sort_by_length") && batch > 1) {
     std::vector<size_t> count(waves.size()), order(waves.size());
@@ -174,6 +187,11 @@ int main(int argc, char** argv) {
     if (ws_engine_info(engine, "sample_rate") != sample_rate) {
       ws_engine_destroy(engine);
       return fail("model sample rate differs from --sample_rate");
+    }
+    if (streamed && ws_engine_info(engine, "streaming") != 1) {
+      ws_engine_destroy(engine);
+      return fail("--stream_ms: this model cannot stream (ws_engine_info \"streaming\" is not 1): streaming needs a causal cLN "
+                  "Conv-TasNet / SpEx+ container");
     }
     // --batch N > 1: group g = lines [g N, g N + N) in one ragged forward, two rows per line
     for (size_t g = batch > 1 ? next++ : ngroups; g < ngroups && !failed; g = next++) {
@@ -270,7 +288,38 @@ int main(int argc, char** argv) {
       std::vector<float> out(size_t(2) * n, 0.f);
       const auto t0 = std::chrono::steady_clock::now();
       int rc;
-      if (chunked) {
+      long long stream_launches = 0, stream_pushes = 0;
+      if (streamed) {
+        // the rows of ws_engine_forward_pcm16, pushed as they would arrive; what becomes final goes behind what came before
+        std::vector<float> enr(size_t(2) * n_enroll), chunk(size_t(2) * stream_n), got;
+        for (int i = 0; i < n_enroll; ++i) {
+          enr[i] = static_cast<float>(s1.samples[i]) / 32768.0f;
+          enr[size_t(n_enroll) + i] = static_cast<float>(s2.samples[i]) / 32768.0f;
+        }
+        const int L = static_cast<int>(ws_engine_info(engine, "L"));
+        const int cap = std::max(WS_STREAM_PUSH_CAP(stream_n, L), WS_STREAM_FLUSH_CAP);
+        got.resize(size_t(2) * cap);
+        ws_stream* st = nullptr;
+        rc = ws_engine_stream_open(engine, 2, enr.data(), WS_ENROLL_WAVE, n_enroll, 64, &st);
+        int done = 0;
+        auto take = [&](int m) {                                        // est [2][m] behind what came before
+          for (int k = 0; k < 2; ++k) memcpy(out.data() + size_t(k) * n + done, got.data() + size_t(k) * m, size_t(m) * 4);
+          done += m;
+        };
+        for (int pos = 0; rc == 0 && pos < n; pos += stream_n) {
+          const int c = std::min(stream_n, n - pos);
+          int m = 0;
+          for (int i = 0; i < c; ++i) chunk[i] = chunk[size_t(c) + i] = static_cast<float>(mix.samples[pos + i]) / 32768.0f;
+          if ((rc = ws_engine_stream_push(st, chunk.data(), c, got.data(), cap, &m)) == 0) take(m);
+          stream_launches += ws_engine_info(engine, "n_launches"), ++stream_pushes;
+        }
+        if (rc == 0) {
+          int m = 0;
+          if ((rc = ws_engine_stream_flush(st, got.data(), cap, &m)) == 0) take(m);
+          stream_launches += ws_engine_info(engine, "n_launches");
+        }
+        ws_engine_stream_close(st);
+      } else if (chunked) {
         // the rows of ws_engine_forward_pcm16, the mixture once: scaled to [-1, 1], one enrollment row per target speaker
         std::vector<float> m(n), enr(size_t(2) * n_enroll);
         for (int i = 0; i < n; ++i) m[i] = static_cast<float>(mix.samples[i]) / 32768.0f;
@@ -302,7 +351,11 @@ int main(int argc, char** argv) {
         }
       }
       std::lock_guard<std::mutex> l(io_mu);
-      if (chunked)
+      if (streamed)
+        printf("process: %s RTF: %.4f (%lld pushes of %d samples, %lld launches, %lld bytes of stream state)%s\n", w[0].c_str(),
+               ms / audio_ms, stream_pushes, stream_n, stream_launches, ws_engine_info(engine, "stream_state_bytes"),
+               dry ? " [dry run]" : "");
+      else if (chunked)
         printf("process: %s RTF: %.4f (%lld windows in %lld forwards: %lld launches, %lld MiB arena)%s\n", w[0].c_str(), ms / audio_ms,
                ws_engine_info(engine, "long_windows"), ws_engine_info(engine, "long_forwards"), ws_engine_info(engine, "n_launches"),
                ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");

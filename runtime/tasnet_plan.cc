@@ -1,6 +1,7 @@
 // =================================================================================================================
 // Conv-TasNet / SpEx+ (arch 1): the launch plan of wesep_amd/functional_tasnet.py in eval mode for the shipped
-// configuration -- MultiEncoder / MultiDecoder, gLN, non-causal, no skip connection, concatConv multi-fusion
+// configuration -- MultiEncoder / MultiDecoder, gLN, non-causal, no skip connection, concatConv multi-fusion -- and for its
+// streamable sibling, causal blocks with cLN (meta "causal" = 1, "norm" = 1; runtime/stream.cc feeds that one in chunks)
 // (convtasnet.py:162-219, separation.py:57-186, convs.py:41-160, encoder.py:66-114, decoder.py:66-114), fixed embeddings
 // or the SpEx+ speaker encoder on the enrollment waveform through the shared encoder (tasnet/speaker.py:47-64).
 // Only the first of the three decoder branches is computed: it is the estimate the reference's inference writes.
@@ -8,25 +9,6 @@
 #include "engine_internal.h"
 
 namespace wsrt {
-
-struct TasGemm {
-  const float* A = nullptr;
-  long long lda = 0;
-  long long M = 0;
-  int K = 0;
-  const float* W = nullptr;
-  int ldw = 0, N = 0;
-  const float* bias = nullptr;
-  int act = 0;
-  float* C = nullptr;
-  long long ldc = 0;
-  const float* R = nullptr;                                       // residual, addressed like C
-  const float *stats = nullptr, *gamma = nullptr, *beta = nullptr; // norm-on-load
-  int st_div1 = 1;                                                 // rows per statistics pair (gLN: T', cLN: 1)
-  bool f32 = false;                                                // exact-fp32 products (the SpEx+ speaker encoder)
-  int a_div = kBig;                                                // frames view: row m -> (m / a_div) * a_s1 + (m % a_div) * lda
-  long long a_s1 = 0;
-};
 
 int tas_gemm(ws_engine* e, const TasGemm& t) {
   ws_gemm_nt_args g = {};
@@ -105,6 +87,7 @@ int tas_encode(ws_engine* e, const float* wav, int R, int T, float* cat, float* 
 }
 
 // one TCN block (convs.py:41-160): out = x + sconv(gLN2(prelu2(dconv(gLN1(prelu1(conv1x1(x) + rb))))))
+// causal cLN containers: per-frame statistics (one pair per row of M, st_div 1) and every depthwise tap at or before t
 int tas_block(ws_engine* e, const std::string& pre, bool fuse, int dil, const float* x, const float* rb, int R, int Tp,
               float* out) {
   const int B = e->tas.B, H = e->tas.H, P = e->tas.P;
@@ -119,8 +102,9 @@ int tas_block(ws_engine* e, const std::string& pre, bool fuse, int dil, const fl
   float* c = a.alloc(size_t(M) * H);
   float* y1 = a.alloc(size_t(M) * H);
   float* z = a.alloc(size_t(M) * H);
-  float* st1 = a.alloc(size_t(R) * 2);
-  float* st2 = a.alloc(size_t(R) * 2);
+  const bool cln = e->tas.norm == 1;
+  float* st1 = a.alloc(size_t(cln ? M : R) * 2);
+  float* st2 = a.alloc(size_t(cln ? M : R) * 2);
   WS_PTR(c && y1 && z && st1 && st2);
   TasGemm g;
   g.A = x, g.lda = B, g.M = M, g.K = B, g.W = e->dev(pre + "conv1x1.weight"), g.ldw = fuse ? B + e->E : B, g.N = H;
@@ -128,6 +112,19 @@ int tas_block(ws_engine* e, const std::string& pre, bool fuse, int dil, const fl
   int rc = tas_gemm(e, g);
   if (rc != WS_OK) return rc;
   WS_RUN(e, ws_prelu_fwd(c, rb, e->dev(pre + n_p1), M, H, Tp, y1, s));
+  if (cln) {
+    if ((rc = tas_row_stats(e, y1, M, H, st1)) != WS_OK) return rc;
+    WS_RUN(e, ws_dwconv_ex_fwd(y1, st1, e->dev(n1 + "weight"), e->dev(n1 + "bias"), e->dev(dw + "weight"), e->dev(dw + "bias"), R,
+                               Tp, H, P, dil, 1, 1, z, s));
+    WS_RUN(e, ws_prelu_fwd(z, nullptr, e->dev(pre + n_p2), M, H, Tp, c, s));
+    if ((rc = tas_row_stats(e, c, M, H, st2)) != WS_OK) return rc;
+    TasGemm o;
+    o.A = c, o.lda = H, o.M = M, o.K = H, o.W = e->dev(outc + "weight"), o.ldw = H, o.N = B, o.bias = e->dev(outc + "bias");
+    o.C = out, o.ldc = B, o.R = x, o.stats = st2, o.gamma = e->dev(n2 + "weight"), o.beta = e->dev(n2 + "bias"), o.st_div1 = 1;
+    if ((rc = tas_gemm(e, o)) != WS_OK) return rc;
+    a.release(mk);
+    return WS_OK;
+  }
   if ((rc = tas_flat_stats(e, y1, R, (long long)Tp * H, st1)) != WS_OK) return rc;
   WS_RUN(e, ws_dwconv_ex_fwd(y1, st1, e->dev(n1 + "weight"), e->dev(n1 + "bias"), e->dev(dw + "weight"), e->dev(dw + "bias"), R,
                              Tp, H, P, dil, Tp, 0, z, s));
@@ -285,6 +282,12 @@ int prepare_tasnet(ws_engine* e) {
   e->tas.B = static_cast<int>(meta_or(e, "B", 128)), e->tas.H = static_cast<int>(meta_or(e, "H", 512));
   e->tas.P = static_cast<int>(meta_or(e, "P", 3)), e->tas.X = static_cast<int>(meta_or(e, "X", 8));
   e->tas.R = static_cast<int>(meta_or(e, "R", 3));
+  e->tas.causal = static_cast<int>(meta_or(e, "causal", 0)), e->tas.norm = static_cast<int>(meta_or(e, "norm", 0));
+  if (!((e->tas.causal == 0 && e->tas.norm == 0) || (e->tas.causal == 1 && e->tas.norm == 1))) {
+    set_err("engine: Conv-TasNet with causal = %d, norm = %d has no launch plan (non-causal gLN: 0, 0; causal cLN: 1, 1 -- gLN "
+            "takes its statistics over the whole utterance)", e->tas.causal, e->tas.norm);
+    return WS_ERR_INVALID;
+  }
   const int N = e->tas.N, L = e->tas.L, B = e->tas.B, H = e->tas.H, P = e->tas.P, E = e->E;
   if (N % 4 || B % 4 || H % 4 || E % 4 || L % 2 || L < 4 || L > 80 || P < 1 || P > 7 || e->tas.X < 1 || e->tas.R < 1) {
     set_err("engine: unsupported Conv-TasNet geometry (N %d, L %d, B %d, H %d, P %d, X %d, R %d, E %d)", N, L, B, H, P, e->tas.X,

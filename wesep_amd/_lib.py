@@ -309,6 +309,7 @@ _SIGS = {
     # streaming Conv-TasNet (stream.hip)
     "ws_dwconv_stream_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _ll, _i, _p, _p, _p]),
     "ws_ola_stream_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "ws_tcn_mid_stream_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_float, _ll, _i, _p, _p, _p, _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -121,8 +121,9 @@ def write_container(path, meta, state):
 
 def tasnet_meta(model):
     """Conv-TasNet / SpEx+ (arch 1): the runtime's launch plan covers the shipped configuration -- Multi encoder and
-    decoder, gLN, non-causal, no skip connection, concatConv multi-fusion -- with fixed embeddings or the SpEx+ speaker
-    encoder on the enrollment waveform.  Everything else is refused by name."""
+    decoder, gLN, non-causal, no skip connection, concatConv multi-fusion -- and its streamable sibling, causal blocks
+    with cLN (meta "causal": 1, "norm": 1; absent keys read as 0), with fixed embeddings or the SpEx+ speaker encoder on
+    the enrollment waveform.  Everything else is refused by name."""
     sep = model.separation
     first = sep.separation[0]
     problems = []
@@ -130,10 +131,14 @@ def tasnet_meta(model):
         problems.append(f"encoder / decoder type {model.encoder_type} / {model.decoder_type} (Multi only)")
     if sep.spk_fuse_type != "concatConv":
         problems.append(f"spk_fuse_type {sep.spk_fuse_type!r} (concatConv only)")
-    if model.norm_type != "gLN":
-        problems.append(f"norm {model.norm_type!r} (gLN only)")
-    if getattr(first, "causal", False):
-        problems.append("causal blocks")
+    causal = bool(getattr(first, "causal", False))
+    if causal and model.norm_type == "gLN":
+        problems.append("causal blocks with gLN (gLN takes its statistics over the whole utterance: a causal model needs "
+                        "cLN)")
+    elif causal and model.norm_type != "cLN":
+        problems.append(f"causal blocks with norm {model.norm_type!r} (causal needs cLN)")
+    elif not causal and model.norm_type != "gLN":
+        problems.append(f"norm {model.norm_type!r} on non-causal blocks (gLN only; cLN runs with causal=True)")
     if any(getattr(b, "skip_con", False) for m in sep.separation if hasattr(m, "separation") for b in m.separation):
         problems.append("skip connections")
     if model.joint_training and model.spk_feat:
@@ -150,6 +155,7 @@ def tasnet_meta(model):
         "spk_emb_dim": first.conv1x1.in_channels - enc.proj.out_channels,
         "use_spk_transform": int(not isinstance(model.spk_transform, torch.nn.Identity)),
         "joint_training": int(model.joint_training), "spk_feat": 0,
+        "causal": int(causal), "norm": int(model.norm_type == "cLN"),
     }
 
 

@@ -4,6 +4,8 @@
 // per frame.  All carried state is device memory owned by the caller; both kernels update it in the launch that uses it.
 // Both are built to give, over any chunking, bit for bit what dwconv_fwd_kernel(causal) / ola_fwd_kernel (tasnet.hip)
 // give over the whole sequence: same operand expression (tasnet_dw.h), same order of additions.  Plain C++, no atomics.
+// tcn_mid_stream_kernel is the whole middle of a causal cLN block (PReLU, statistics, the ring convolution, PReLU,
+// statistics) in one launch, for small chunks where the five launches it replaces cost more than their work.
 #include "common.h"
 #include "tasnet_dw.h"
 
@@ -96,7 +98,124 @@ __global__ __launch_bounds__(256) void ola_stream_kernel(const float* __restrict
   }
 }
 
+// The middle of a causal cLN block on one chunk, between its two GEMMs: PReLU, cLN statistics, the depthwise convolution
+// with its ring, PReLU, cLN statistics.  One workgroup per (row, chunk frame); thread i owns the channel quads i, i + NT, ...
+// of every frame it touches.  A tap inside the chunk is NOT read from the ring (another workgroup of this launch writes
+// it): the workgroup recomputes that frame's y1, statistics and xn from c -- a few KB of L2 hits per tap.  Every workgroup
+// has the same NT (a function of H alone) and walks a frame in the same order, so a frame's xn is the same bits whether its
+// own workgroup computes it (and writes it to the ring) or a later frame's does; a later chunk reads those bits back.
+// Statistics: the two-pass mean / variance of group_stats_kernel (norm.hip) with its per-thread and cross-wave order.
+// LDS (dynamic): y1 of the tap in hand [H], the accumulator / y2 [H], 16 floats for the cross-wave sums; a thread reads
+// back only the quads it wrote, so the barriers are those of ws_block_sum alone.  Nothing here waits on another workgroup.
+__global__ __launch_bounds__(256) void tcn_mid_stream_kernel(const float* __restrict__ c, const float* __restrict__ rb,
+                                                             const float* __restrict__ a1,
+                                                             const float* __restrict__ gamma1,
+                                                             const float* __restrict__ beta1,
+                                                             const float* __restrict__ wd, const float* __restrict__ bd,
+                                                             const float* __restrict__ a2, int Tc, int H, int P, int dil,
+                                                             float eps, long long t0, int base, int cap, float* ring,
+                                                             float* __restrict__ y2, float* __restrict__ st2) {
+  extern __shared__ __attribute__((aligned(16))) float tm_lds[];
+  f32x4* stage = reinterpret_cast<f32x4*>(tm_lds);
+  f32x4* accs = reinterpret_cast<f32x4*>(tm_lds + H);
+  float* red = tm_lds + 2 * H;
+  const long long f = blockIdx.x;
+  const int r = (int)(f / Tc), t = (int)(f - (long long)r * Tc);
+  const int c4n = H >> 2, nt = blockDim.x;
+  const float sl1 = a1[0], sl2 = a2[0];
+  float* rr = ring + (long long)r * cap * H;
+  for (int q = threadIdx.x; q < c4n; q += nt) accs[q] = *reinterpret_cast<const f32x4*>(bd + 4 * q);
+#pragma unroll 1
+  for (int p = 0; p < P; ++p) {
+    const int off = (P - 1 - p) * dil;
+    if (t0 + t - off < 0) continue;                       // before the start: no term, the ring is not read
+    if (off <= t) {                                       // a frame of this chunk: from c
+      const float* cr = c + (f - off) * H;
+      float s = 0.f;
+      for (int q = threadIdx.x; q < c4n; q += nt) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(cr + 4 * q);
+        if (rb) v += *reinterpret_cast<const f32x4*>(rb + (long long)r * H + 4 * q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : sl1 * v[j];
+        stage[q] = v;
+        s += (v[0] + v[1]) + (v[2] + v[3]);
+      }
+      const float mean = ws_block_sum(s, red) / (float)H;
+      float qs = 0.f;
+      for (int q = threadIdx.x; q < c4n; q += nt) {
+        const f32x4 d = stage[q] - mean;
+        qs += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+      }
+      const float rstd = 1.f / sqrtf(ws_block_sum(qs, red) / (float)H + eps);
+      int own = base + t;
+      own = own >= cap ? own - cap : own;
+      for (int q = threadIdx.x; q < c4n; q += nt) {
+        const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma1 + 4 * q), bt = *reinterpret_cast<const f32x4*>(beta1 + 4 * q);
+        const f32x4 xn = (stage[q] - mean) * rstd * gm + bt;
+        if (off == 0) *reinterpret_cast<f32x4*>(rr + (long long)own * H + 4 * q) = xn;
+        f32x4 acc = accs[q];
+        dw_tap(acc, wd, 4 * q, P, p, xn);
+        accs[q] = acc;
+      }
+    } else {                                              // an earlier chunk's frame: its slot (base + t - off in (-cap, cap))
+      int sl = base + t - off;
+      sl = sl < 0 ? sl + cap : (sl >= cap ? sl - cap : sl);
+      const float* rs = rr + (long long)sl * H;
+      for (int q = threadIdx.x; q < c4n; q += nt) {
+        const f32x4 xn = *reinterpret_cast<const f32x4*>(rs + 4 * q);
+        f32x4 acc = accs[q];
+        dw_tap(acc, wd, 4 * q, P, p, xn);
+        accs[q] = acc;
+      }
+    }
+  }
+  float s = 0.f;
+  for (int q = threadIdx.x; q < c4n; q += nt) {
+    f32x4 v = accs[q];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : sl2 * v[j];
+    accs[q] = v;
+    *reinterpret_cast<f32x4*>(y2 + f * H + 4 * q) = v;
+    s += (v[0] + v[1]) + (v[2] + v[3]);
+  }
+  const float mean = ws_block_sum(s, red) / (float)H;
+  float qs = 0.f;
+  for (int q = threadIdx.x; q < c4n; q += nt) {
+    const f32x4 d = accs[q] - mean;
+    qs += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+  }
+  const float var = ws_block_sum(qs, red) / (float)H;
+  if (threadIdx.x == 0) {
+    st2[2 * f] = mean;
+    st2[2 * f + 1] = 1.f / sqrtf(var + eps);
+  }
+}
+
 }  // namespace
+
+extern "C" int ws_tcn_mid_stream_fwd(const float* c, const float* rb, const float* a1, const float* gamma1,
+                                     const float* beta1, const float* wd, const float* bd, const float* a2, int R, int Tc,
+                                     int H, int P, int dil, float eps, long long t0, int cap, float* ring, float* y2,
+                                     float* st2, void* stream) {
+  WS_REQUIRE(c && a1 && gamma1 && beta1 && wd && bd && a2 && ring && y2 && st2, "ws_tcn_mid_stream_fwd: null pointer");
+  WS_REQUIRE(R > 0 && Tc > 0 && H > 0 && dil >= 1, "ws_tcn_mid_stream_fwd: bad geometry (R=%d, Tc=%d, H=%d, dil=%d)", R, Tc,
+             H, dil);
+  WS_REQUIRE(H % 4 == 0, "ws_tcn_mid_stream_fwd: H=%d is not a multiple of 4", H);
+  WS_REQUIRE(H <= WS_TCN_MID_MAXH, "ws_tcn_mid_stream_fwd: H=%d above %d (two rows of H floats are staged in LDS)", H,
+             WS_TCN_MID_MAXH);
+  WS_REQUIRE(P >= 1 && P <= TN_MAXP && (P & 1), "ws_tcn_mid_stream_fwd: P=%d (odd P <= %d)", P, TN_MAXP);
+  WS_REQUIRE(t0 >= 0, "ws_tcn_mid_stream_fwd: t0=%lld is negative", t0);
+  const long long need = (long long)(P - 1) * dil + Tc;
+  WS_REQUIRE(cap >= need, "ws_tcn_mid_stream_fwd: cap=%d is below (P - 1) * dil + Tc = %lld", cap, need);
+  WS_REQUIRE((long long)R * Tc < (1LL << 31), "ws_tcn_mid_stream_fwd: R * Tc reaches 2^31");
+  const long long n = (long long)R * Tc * H;
+  WS_REQUIRE(y2 + n <= c || c + n <= y2, "ws_tcn_mid_stream_fwd: y2 overlaps c");
+  const int nt = H / 4 >= 256 ? 256 : ((H / 4 + 63) / 64) * 64;
+  hipLaunchKernelGGL(tcn_mid_stream_kernel, dim3((unsigned)((long long)R * Tc)), dim3(nt),
+                     (size_t)(2 * H + 16) * sizeof(float), (hipStream_t)stream, c, rb, a1, gamma1, beta1, wd, bd, a2, Tc, H,
+                     P, dil, eps, t0, (int)(t0 % cap), cap, ring, y2, st2);
+  return ws_check_launch("ws_tcn_mid_stream_fwd");
+}
 
 extern "C" int ws_dwconv_stream_fwd(const float* x, const float* stats, const float* gamma, const float* beta,
                                     const float* w, const float* b, int R, int Tc, int C, int P, int dil, int st_div,

@@ -1690,6 +1690,25 @@ def ola_stream_fwd(frames, bias, R: int, Tc: int, Lk: int, hop: int, carry, est)
     _call("ws_ola_stream_fwd", _p(frames), _p(bias), R, Tc, Lk, hop, _p(carry), _p(est))
 
 
+def tcn_mid_stream_fwd(c, rb, a1, gamma1, beta1, wd, bd, a2, R: int, Tc: int, H: int, P: int, dil: int, eps: float, t0: int,
+                       ring, y2, st2):
+    """The middle of a causal cLN block on one chunk in one launch (prelu_fwd, group_stats, dwconv_stream_fwd, prelu_fwd,
+    group_stats): c [R*Tc, H] (read only) + rb [R, H] or None -> y2 [R*Tc, H] and its per-frame statistics st2 [R*Tc, 2];
+    ring [R, cap, H] as for dwconv_stream_fwd."""
+    for n, t in (("c", c), ("rb", rb), ("a1", a1), ("gamma1", gamma1), ("beta1", beta1), ("wd", wd), ("bd", bd), ("a2", a2),
+                 ("ring", ring), ("y2", y2), ("st2", st2)):
+        _chk(t, n)
+    if ring.dim() != 3 or ring.shape[0] != R or ring.shape[2] != H:
+        raise L.WesepHipError(f"ws_tcn_mid_stream_fwd: ring is {tuple(ring.shape)}, the call needs [{R}, cap, {H}]")
+    _chk_room(c, R * Tc * H, "ws_tcn_mid_stream_fwd", "c")
+    _chk_room(y2, R * Tc * H, "ws_tcn_mid_stream_fwd", "y2")
+    _chk_room(st2, R * Tc * 2, "ws_tcn_mid_stream_fwd", "st2")
+    if rb is not None:
+        _chk_room(rb, R * H, "ws_tcn_mid_stream_fwd", "rb")
+    _call("ws_tcn_mid_stream_fwd", _p(c), _p(rb), _p(a1), _p(gamma1), _p(beta1), _p(wd), _p(bd), _p(a2), R, Tc, H, P, dil,
+          float(eps), t0, ring.shape[1], _p(ring), _p(y2), _p(st2))
+
+
 # ---- DPCCN pieces (conv2d.hip) --------------------------------------------------------------------------
 IN_EPS = 1e-5  # nn.InstanceNorm{1,2}d default
 

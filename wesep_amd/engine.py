@@ -15,7 +15,9 @@ LIB_PATH = os.environ.get("WESEP_ENGINE_LIB") or os.path.join(
     os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "runtime", "libwesep_engine.so")
 SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", "ws_engine_destroy", "ws_engine_info",
            "ws_engine_separate", "ws_engine_separate_ragged", "ws_engine_forward_pcm16", "ws_engine_embed",
-           "ws_engine_separate_long")
+           "ws_engine_separate_long", "ws_engine_stream_open", "ws_engine_stream_push", "ws_engine_stream_flush",
+           "ws_engine_stream_reset", "ws_engine_stream_close")
+STREAM_FLUSH_CAP = 160  # WS_STREAM_FLUSH_CAP
 _lib = None
 
 
@@ -47,6 +49,16 @@ def lib():
         l.ws_engine_separate_long.restype = C.c_int
         l.ws_engine_separate_long.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                               C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        l.ws_engine_stream_open.restype = C.c_int
+        l.ws_engine_stream_open.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        l.ws_engine_stream_push.restype = C.c_int
+        l.ws_engine_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_stream_flush.restype = C.c_int
+        l.ws_engine_stream_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_stream_reset.restype = C.c_int
+        l.ws_engine_stream_reset.argtypes = [C.c_void_p]
+        l.ws_engine_stream_close.restype = None
+        l.ws_engine_stream_close.argtypes = [C.c_void_p]
         if l.ws_engine_abi_version() != ENGINE_ABI_VERSION:
             raise WesepHipError("libwesep_engine.so ABI version mismatch; rebuild")
         _lib = l
@@ -208,6 +220,11 @@ class Engine:
                                              int(max_rows), est.ctypes.data), "ws_engine_separate_long")
         return est
 
+    def stream(self, rows, enroll, kind, max_chunk_frames=64):
+        """A stream of `rows` rows on a causal cLN Conv-TasNet / SpEx+ container (info("streaming") == 1): enroll as in
+        separate(); the speaker stage runs once, here.  Close the stream before the engine."""
+        return EngineStream(self, rows, enroll, kind, max_chunk_frames)
+
     def forward_pcm16(self, mix, spk1, spk2):
         """int16 [n], int16 [n_enroll] x 2 -> float32 [2, n] in [-1, 1] (SeparateEngine::ForwardFunc)."""
         mix, spk1, spk2 = (np.ascontiguousarray(x, dtype=np.int16) for x in (mix, spk1, spk2))
@@ -217,3 +234,62 @@ class Engine:
         _check(lib().ws_engine_forward_pcm16(self._h, mix.ctypes.data, mix.shape[0], spk1.ctypes.data,
                                              spk2.ctypes.data, n_enroll, out.ctypes.data), "ws_engine_forward_pcm16")
         return out
+
+
+def stream_push_cap(n, L):
+    """WS_STREAM_PUSH_CAP: samples a row that a push of n samples can emit at most."""
+    return (n // (L // 2) + 1) * (L // 2)
+
+
+class EngineStream:
+    """ws_engine_stream_* (include/wesep_engine.h): audio in as it arrives, the samples that became final out.  The
+    concatenation of every push() and the flush() is the model-output part of Engine.separate's row."""
+
+    def __init__(self, engine, rows, enroll, kind, max_chunk_frames=64):
+        self._h, self._engine, self.rows = C.c_void_p(), engine, int(rows)      # (the engine must outlive the stream)
+        enroll = np.ascontiguousarray(enroll, dtype=np.float32)
+        if enroll.shape[0] != self.rows:
+            raise ValueError("one enrollment per stream row")
+        length = 0 if kind in (ENROLL_EMBEDDING, ENROLL_SPEAKER) else enroll.shape[1]
+        _quiesce_torch()
+        _check(lib().ws_engine_stream_open(engine._h, self.rows, enroll.ctypes.data, kind, length, int(max_chunk_frames),
+                                           C.byref(self._h)), "ws_engine_stream_open")
+        self._L = engine.info("L")
+
+    def _out(self, buf, m):
+        return buf[:self.rows * m].reshape(self.rows, m).copy()
+
+    def push(self, chunk, est_cap=None):
+        """chunk [rows, n], n >= 1 -> [rows, m] float32, the samples that became final (m = 0 while no frame is complete).
+        est_cap: samples a row the output buffer holds (default: what always suffices)."""
+        chunk = np.ascontiguousarray(chunk, dtype=np.float32)
+        if chunk.ndim != 2 or chunk.shape[0] != self.rows:
+            raise ValueError(f"EngineStream.push: chunk is {chunk.shape}, expected [{self.rows}, n >= 1]")
+        n = chunk.shape[1]
+        cap = stream_push_cap(n, self._L) if est_cap is None else int(est_cap)
+        buf, m = np.zeros(self.rows * max(cap, 1), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_stream_push(self._h, chunk.ctypes.data, n, buf.ctypes.data, cap, C.byref(m)), "ws_engine_stream_push")
+        return self._out(buf, m.value)
+
+    def flush(self, est_cap=STREAM_FLUSH_CAP):
+        """The end of the stream: the remaining frames on the zero-extended pending samples, then the overlap-add carry."""
+        buf, m = np.zeros(self.rows * max(int(est_cap), 1), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_stream_flush(self._h, buf.ctypes.data, int(est_cap), C.byref(m)), "ws_engine_stream_flush")
+        return self._out(buf, m.value)
+
+    def reset(self):
+        """Back to sample 0; the enrollment is kept."""
+        _check(lib().ws_engine_stream_reset(self._h), "ws_engine_stream_reset")
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
+            _lib.ws_engine_stream_close(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass

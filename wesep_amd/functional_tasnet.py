@@ -319,26 +319,39 @@ class ConvBlockFn(torch.autograd.Function):
         return grads
 
 
-def conv_block_stream(x, rb, geo, ring, t0, w1, b1, a1, g1, be1, wd, bd, a2, g2, be2, w3, b3, wsc=None, bsc=None):
+def conv_block_stream(x, rb, geo, ring, t0, w1, b1, a1, g1, be1, wd, bd, a2, g2, be2, w3, b3, wsc=None, bsc=None,
+                      fused=False):
     """ConvBlockFn.forward of a CAUSAL block on one chunk (inference only, no autograd): x [R*Tc, B] are the Tc frames
     that start at absolute frame t0, ring [R, cap, H] carries the normalised input of the depthwise convolution across
     chunks (dev.dwconv_stream_fwd; cap >= (P - 1) * dil + Tc).  The same launches as ConvBlockFn with the chunked
     depthwise kernel in place of dev.dwconv_fwd; everything else in the block is per frame.  geo = (R, Tc, norm, dil, bn)
     with norm 'cLN' (per-frame statistics) or 'BN' on its running statistics (bn = (rm1, rv1, rm2, rv2)): gLN's statistics
-    span the utterance and cannot be streamed.  Returns out, or (out, skip) with the skip branch's (wsc, bsc)."""
+    span the utterance and cannot be streamed.  Returns out, or (out, skip) with the skip branch's (wsc, bsc).
+    fused=True (cLN only): the five launches between the two GEMMs are one, dev.tcn_mid_stream_fwd."""
     _need_cuda(x, "ConvTasNet")
     R, Tc, norm, dil, bn = geo
     if norm not in ("cLN", "BN"):
         raise L.WesepHipError(f"conv_block_stream: norm {norm!r} needs statistics over the whole utterance")
+    if fused and norm != "cLN":
+        raise NotImplementedError("conv_block_stream: fused=True is built for cLN; norm='BN' runs the unfused launches")
     M, B = x.shape
     H, P = wd.shape[0], wd.shape[-1]
     x = x.contiguous()
     ldw = w1.shape[1]
     W1 = w1.reshape(H, ldw).contiguous()
     c = _gemm(x, M, B, W1, H, ldw=ldw, bias=None if rb is not None else b1)
+    g1f, be1f, g2f, be2f = (t.reshape(H).contiguous() for t in (g1, be1, g2, be2))
+    if fused:
+        y2, st2 = _empty(x.device, M, H), _empty(x.device, M, 2)
+        dev.tcn_mid_stream_fwd(c, rb.contiguous() if rb is not None else None, a1, g1f, be1f, wd.reshape(H, P).contiguous(),
+                               bd, a2, R, Tc, H, P, dil, LN_EPS, t0, ring, y2, st2)
+        nk = (st2, g2f, be2f, _stat_map(norm, Tc))
+        out = _gemm(y2, M, H, w3.reshape(B, H).contiguous(), B, bias=b3, R=x, norm=nk)
+        if wsc is None:
+            return out
+        return out, _gemm(y2, M, H, wsc.reshape(B, H).contiguous(), B, bias=bsc, norm=nk)
     y1 = _empty(x.device, M, H)
     dev.prelu_fwd(c, rb.contiguous() if rb is not None else None, a1, M, H, Tc, y1)
-    g1f, be1f, g2f, be2f = (t.reshape(H).contiguous() for t in (g1, be1, g2, be2))
     (st1, g1k, be1k, _, st_div), _ = _block_norm(y1, norm, R, Tc, H, g1f, be1f, bn and (bn[0], bn[1], False))
     z = _empty(x.device, M, H)
     dev.dwconv_stream_fwd(y1, st1, g1k, be1k, wd.reshape(H, P).contiguous(), bd, R, Tc, H, P, dil, st_div, t0, ring, z)

@@ -14,7 +14,10 @@ returned.  `flush` zero-extends the pending samples as the whole-utterance encod
 frames up to T' = (N - L) // s + 1 and returns the rest: (T' - 1) * s + L samples in all, the length of `model(x, emb)[0]`.
 
 Not built (refused by name at construction): non-causal blocks, gLN (its statistics span the utterance), the Deep ends
-(their dilated convolutions look ahead) and training mode.  All rows advance in lockstep."""
+(their dilated convolutions look ahead) and training mode.  All rows advance in lockstep.
+
+`fused=True` (cLN models) runs the five launches between a block's two GEMMs as one, `dev.tcn_mid_stream_fwd`: three C-ABI
+calls per block in place of seven.  The default issues the unfused launches."""
 import torch
 
 from . import _lib as L
@@ -26,7 +29,7 @@ from .modules.tasnet import Conv1DBlock, Conv1DBlock4Fuse, Separation, _FuseLaye
 
 
 class ConvTasNetStreamer:
-    def __init__(self, model, rows, max_chunk_frames=256):
+    def __init__(self, model, rows, max_chunk_frames=256, fused=False):
         from .models.convtasnet import ConvTasNet
         if not isinstance(model, ConvTasNet):
             raise TypeError(f"ConvTasNetStreamer: a ConvTasNet is needed, got {type(model).__name__}")
@@ -41,6 +44,10 @@ class ConvTasNetStreamer:
         blocks = [m for m in model.separation.modules() if isinstance(m, (Conv1DBlock, Conv1DBlock4Fuse))]
         if not all(b.causal for b in blocks):
             raise NotImplementedError("ConvTasNetStreamer: non-causal blocks look ahead; build the model with causal=True")
+        if fused and model.norm_type != "cLN":
+            raise NotImplementedError(f"ConvTasNetStreamer: fused=True is built for cLN blocks; this model's norm is "
+                                      f"{model.norm_type!r} (BN runs the unfused launches: fused=False)")
+        self.fused = bool(fused)
         if int(rows) < 1 or int(max_chunk_frames) < 1:
             raise ValueError(f"ConvTasNetStreamer: rows={rows}, max_chunk_frames={max_chunk_frames} must be positive")
         self.model, self.rows, self.max_chunk_frames = model, int(rows), int(max_chunk_frames)
@@ -258,8 +265,8 @@ class ConvTasNetStreamer:
         if fuse:
             return FT.conv_block_stream(x, self._rb[id(b)], g, ring, self._k, b.conv1x1.weight, b.conv1x1.bias,
                                         b.prelu1.weight, n1.weight, n1.bias, b.dconv.weight, b.dconv.bias, b.prelu2.weight,
-                                        n2.weight, n2.bias, b.sconv.weight, b.sconv.bias)
+                                        n2.weight, n2.bias, b.sconv.weight, b.sconv.bias, fused=self.fused)
         skip = (b.Sc_conv.weight, b.Sc_conv.bias) if b.skip_con else ()
         return FT.conv_block_stream(x, None, g, ring, self._k, b.conv1x1.weight, b.conv1x1.bias, b.PReLU_1.weight,
                                     n1.weight, n1.bias, b.dwconv.weight, b.dwconv.bias, b.PReLU_2.weight, n2.weight,
-                                    n2.bias, b.Output.weight, b.Output.bias, *skip)
+                                    n2.bias, b.Output.weight, b.Output.bias, *skip, fused=self.fused)
