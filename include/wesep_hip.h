@@ -611,7 +611,8 @@ typedef struct ws_bands {
 int ws_stft_bandsplit(const float* wav, int R, int T, const ws_bands* b, float* xbs, void* stream);
 /* Ragged batches (inference): row r holds lengths[r] valid samples, NFFT / 2 < lengths[r] <= T = the row pitch (device int
  * table; the callers that have the lengths on the host -- the engine, wesep_amd.dev -- refuse values outside that range,
- * the kernel clamps them so that no table entry can move a read out of its row).  The reflect padding turns at lengths[r];
+ * the kernel clamps them to [NFFT / 2 + 1, T], the range in which the reflected index stays inside the row, so that no
+ * table entry can move a read out of its row).  The reflect padding turns at lengths[r];
  * frames t >= 1 + lengths[r] / 128 are written as zeros; nothing behind lengths[r] is read.  The valid frames of a row are
  * bit for bit those of ws_stft_bandsplit on that row alone with T = lengths[r]. */
 int ws_stft_bandsplit_len(const float* wav, int R, int T, const int* lengths, const ws_bands* b, float* xbs, void* stream);
@@ -624,7 +625,9 @@ int ws_mask_istft_frames(const float* xbs, const float* mask3, int R, int Tf, co
 int ws_istft_ola(const float* frames, int R, int Tf, int T, float* wav, void* stream);
 /* Ragged batches (inference): only the frames t < 1 + lengths[r] / 128 of row r are added and counted in the window
  * envelope (the others are not read, so ws_mask_istft_frames runs over the rectangle unchanged); samples >= lengths[r]
- * are written as zeros.  lengths: device int table as in ws_stft_bandsplit_len. */
+ * are written as zeros.  lengths: the device int table of ws_stft_bandsplit_len; this kernel clamps an entry to [1, T]
+ * (nothing is reflected here: any value in that range keeps the last frame read, lengths[r] / 128, at most Tf - 1 and
+ * the samples inside the row); on a table that is valid for ws_stft_bandsplit_len the two clamps do nothing. */
 int ws_istft_ola_len(const float* frames, int R, int Tf, int T, const int* lengths, float* wav, void* stream);
 /* backward of the two calls above: dwav [R][T] -> dmask3 [R*Tf][4*F]                        */
 int ws_mask_istft_bwd(const float* dwav, const float* xbs, const float* mask3, int R, int Tf,

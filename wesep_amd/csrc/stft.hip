@@ -238,6 +238,8 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
        i += (long long)gridDim.x * blockDim.x) {
     const int r = (int)(i / T), pos = (int)(i - (long long)r * T);
     const int q = pos + NFFT / 2;
+    // (clamped to [1, T], not to ws_stft_bandsplit_len's [NFFT / 2 + 1, T]: nothing is reflected here, and any value in
+    // [1, T] keeps t_hi <= Tf - 1 and pos < T; the two agree on every table a caller may pass)
     const int Tr = lengths ? min(max(lengths[r], 1), T) : T;
     const int t_hi = min(q / HOP, lengths ? Tr / HOP : Tf - 1);
     const int t_lo = q >= NFFT ? (q - (NFFT - HOP)) / HOP : 0;
