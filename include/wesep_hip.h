@@ -810,8 +810,12 @@ int ws_lstm_fwd_fused(const ws_lstm_fused_args* a, void* stream);
  * wesep/models/bsrnn.py:9,217,352-356), channels-last [R][H][W][C] ------------------------------------------
  * conv2d(k x k, stride s, padding p, bias-free) = ws_im2col + ws_gemm_nt (K = k*k*C); input gradient =
  * ws_gemm_nt + ws_col2im (gather, deterministic); weight gradient = ws_gemm_tn on the patch matrix.
- * patches [R*Ho*Wo][ldp], column (ky*k + kx)*C + c; Ho = (H + 2p - k)/s + 1.  C == 1 or C % 4 == 0
- * (then ldp == k*k*C).  BatchNorm2d / ReLU / residual are the channels-last ws_bn_* / ws_prelu_* entry points. */
+ * patches [R*Ho*Wo][ldp], column (ky*k + kx)*C + c; Ho = (H + 2p - k)/s + 1.  C == 1 (ldp >= k*k; only the first k*k
+ * columns of a row are written, the padding [k*k, ldp) is left untouched) or C % 4 == 0 (then ldp == k*k*C and x, patches
+ * 16-byte aligned).  im2col is a copy: bit-exact, taps outside the image are exact zeros.  ws_col2im needs C % 4 == 0 (no
+ * C == 1 form) and 16-byte aligned dpatches / dx; a pixel that no patch covers (stride above k, or the tail behind the last
+ * whole stride when (H + 2p - k) % s != 0) is written as an exact zero.  ws_im2col / ws_col2im are ws_im2col_hw /
+ * ws_col2im_hw with sh = sw = s.  BatchNorm2d / ReLU / residual are the channels-last ws_bn_* / ws_prelu_* entry points. */
 int ws_im2col(const float* x, int R, int H, int W, int C, int k, int s, int p, long long ldp, float* patches,
               void* stream);
 int ws_col2im(const float* dpatches, int R, int H, int W, int C, int k, int s, int p, float* dx, void* stream);
@@ -860,8 +864,9 @@ int ws_mhastp_fwd_split(const float* x, const float* pack, int R, int F, int T, 
 int ws_mhastp_bwd_split(const float* x, const float* pack, const float* aux, const float* dout, int R, int F, int T,
                         int C, int Q, int H, int layers, int ds, int tsplit, float* dx, float* work, float* slab,
                         int nsplit, float* dpack, void* stream);
-/* y = act(x + rb[row / rows_per_r]) on [rows][C] (act 1 tanh, 3 sigmoid; rb NULL or [rows / rows_per_r][C]) and
- * dx = dy * act'(y) from the saved output: ECAPA's attention bottleneck (tanh) and SE gate (sigmoid).            */
+/* y = act(x + rb[row / rows_per_r]) on [rows][C] (act 1 tanh, 3 sigmoid; rb NULL or [ceil(rows / rows_per_r)][C]: the
+ * last bias row may serve fewer than rows_per_r rows) and dx = dy * act'(y) from the saved output (dx = dy (1 - y^2) or
+ * dy y (1 - y)): ECAPA's attention bottleneck (tanh) and SE gate (sigmoid).  Scalar accesses: any C, n and alignment. */
 int ws_rowbias_act_fwd(const float* x, const float* rb, long long rows, int C, int rows_per_r, int act, float* y,
                        void* stream);
 int ws_act_bwd(const float* y, const float* dy, long long n, int act, float* dx, void* stream);
@@ -890,12 +895,20 @@ int ws_im2col_hw(const float* x, int R, int H, int W, int C, int k, int sh, int 
                  float* patches, void* stream);
 int ws_col2im_hw(const float* dpatches, int R, int H, int W, int C, int k, int sh, int sw, int p, float* dx,
                  void* stream);
-/* nn.ELU: y = x > 0 ? x : expm1(x);  dx = dy * (x > 0 ? 1 : exp(x)) (dx may alias dy)                        */
+/* ALIGNMENT of the DPCCN / TF-GridNet entry points below: ws_elu_*, ws_inorm_apply / bwd_apply, ws_in_act_*, ws_avgpool_*,
+ * ws_bilinear_*, ws_scale_bf_fwd and ws_freq_linear_fwd (x, y) move 16 bytes per access -- every tensor pointer and every
+ * row stride (C, ldy, ldd, lddx; a column offset into a wider map likewise) must be a multiple of 4 floats from a 16-byte
+ * aligned base.  The entry points check C % 4 and the strides, not the pointers.  ws_inorm_finalize, ws_rowbias_act_fwd,
+ * ws_act_bwd, ws_scale_bf_bwd with its scalar kernel and ws_softmax_rows_* with theirs take any alignment.
+ * nn.ELU: y = x > 0 ? x : expm1(x);  dx = dy * (x > 0 ? 1 : exp(x)) (dx may alias dy);  n % 4 == 0.  x > 0 is a copy. */
 int ws_elu_fwd(const float* x, long long n, float* y, void* stream);
 int ws_elu_bwd(const float* x, const float* dy, long long n, float* dx, void* stream);
 /* InstanceNorm{1,2}d without affine over the P positions of each of G batch rows ([G*P][C] channels-last):
- * sums [G][2][C] = ws_chan_sums(g = x, x = x) -> stats [G][2][C] = (mean, rstd); y = (x - mean) * rstd;
- * backward with sums = ws_chan_sums(g = dy, x = y): dx = rstd * (dy - S0/P - y * S1/P)                       */
+ * sums [G][2][C] = ws_chan_sums(g = x, x = x) = (sum u, sum u^2) -> stats [G][2][C] = (mean, rstd) in ONE pass:
+ *   mean = S0 / P,  rstd = 1 / sqrt(max(S1 / P - mean^2, 0) + eps)     (fp32; the clamp absorbs the cancellation of a
+ *   constant group, whose rstd is then 1 / sqrt(eps); with |mean| >> std the variance carries ~ P * 2^-24 * mean^2 of error)
+ * y = (x - mean) * rstd;  backward with sums = ws_chan_sums(g = dy, x = y): dx = rstd * (dy - S0/P - y * S1/P), dx may
+ * alias dy.  ws_inorm_finalize: any C; apply / bwd_apply: C % 4 == 0, rows % P == 0 (rows = G * P).           */
 int ws_inorm_finalize(const float* sums, int G, int C, long long P, float eps, float* stats, void* stream);
 int ws_inorm_apply(const float* x, const float* stats, long long rows, int P, int C, float* y, void* stream);
 int ws_inorm_bwd_apply(const float* y, const float* dy, const float* stats, const float* sums, long long rows, int P,
@@ -967,7 +980,12 @@ int ws_conv3x3_wgrad(const ws_conv3x3_wgrad_args* a, void* stream);
  * of u = pre(x), to be reduced and finalised by ws_reduce_slabs + ws_inorm_finalize; backward: (sum d, sum d * n) with
  * n = (u - mean) * rstd and d = dy * (bit 1 ? ELU'(n) : 1).  ws_in_act_apply: y from x and the statistics (one pass).
  * ws_in_act_bwd_apply: dx = pre'(x) * rstd * (d - S0/P - n * S1/P) from x, dy, the statistics and the reduced sums
- * (dx may alias dy when both strides agree).  Only the pre-activation x has to be kept for the backward.  x is dense
+ * (dx may alias dy when both strides agree).  ws_in_act_sums writes EVERY element of the slab: split s owns the rows
+ * [s * per, min(P, (s + 1) * per)), per = ceil(P / nsplit), and a split that owns no row (nsplit does not divide P, or
+ * nsplit > P) leaves exact zeros; any nsplit >= 1 is legal and the reduced sums agree within rounding.  The backward sums need
+ * the statistics (stats NULL with dy is refused); flags outside 0..3 are refused.  ws_in_act_apply / bwd_apply write the
+ * columns [0, C) of every row of y / dx and nothing between C and the row stride.
+ * Only the pre-activation x has to be kept for the backward.  x is dense
  * [rows][C]; y (apply) has row stride ldy, dy (sums, bwd_apply) row stride ldd and dx row stride lddx -- 0 = C, else >= C and % 4: the
  * dense blocks write y into / read dy from a column range of their one wide feature map (no torch.cat, no slices). */
 int ws_in_act_sums(const float* x, const float* dy, long long ldd, const float* stats, int P, int G, int nsplit, int C,
@@ -976,27 +994,36 @@ int ws_in_act_apply(const float* x, const float* stats, long long rows, int P, i
                     void* stream);
 int ws_in_act_bwd_apply(const float* x, const float* dy, long long ldd, const float* stats, const float* sums, long long rows,
                         int P, int C, int flags, float* dx, long long lddx, void* stream);
-/* nn.AvgPool2d(sz) and its adjoint; nn.Upsample(size = (H, W), mode = "bilinear") (align_corners False) and its
- * adjoint (a gather over destination pixels)                                                                  */
+/* nn.AvgPool2d(sz) (stride sz, floor: H >= sz, W >= sz) and its adjoint: dx = dy / sz^2 on the covered pixels, EXACT zeros
+ * on the H % sz rows / W % sz columns the floor drops (all of dx is written).  nn.Upsample(size = (H, W), mode = "bilinear")
+ * (align_corners False: src = max((dst + 1/2) * h / H - 1/2, 0), taps floor(src) and min(floor(src) + 1, h - 1); any h, w,
+ * H, W >= 1, up- or downsampling) and its adjoint (a gather over destination pixels).  C % 4 == 0.              */
 int ws_avgpool_fwd(const float* x, int B, int H, int W, int C, int sz, float* y, void* stream);
 int ws_avgpool_bwd(const float* dy, int B, int H, int W, int C, int sz, float* dx, void* stream);
 int ws_bilinear_fwd(const float* x, int B, int h, int w, int H, int W, int C, float* y, void* stream);
-/* tmp: scratch of B * H * w * C floats (the adjoint runs as two separable passes: destination columns, then rows)   */
+/* tmp: scratch of B * H * w * C floats (the adjoint runs as two separable passes: destination columns, then rows): all of
+ * it is overwritten, nothing behind it; its contents afterwards are unspecified.                                       */
 int ws_bilinear_bwd(const float* dy, int B, int h, int w, int H, int W, int C, float* tmp, float* dx, void* stream);
 /* SpeakerFuseLayer multiply (mode 0) / additive (mode 1) on [B][T][F][C] with s [B][F] (speaker.py:102-121);
- * backward: dx, and ds [B][F] = sum over (t, c) of dy * x (mode 0) or dy (mode 1)                             */
+ * backward: dx (mode 1: a copy of dy), and ds [B][F] = sum over (t, c) of dy * x (mode 0) or dy (mode 1).  The forward needs
+ * C % 4 == 0.  The backward takes any C: C % 4 == 0, C <= 1024 and (C / 4) dividing 256 select the 16-byte kernel (C / 4
+ * threads per row, 256 / (C / 4) rows per pass, two passes in flight; x, dy, dx 16-byte aligned), every other C -- 6, 12,
+ * 1028 -- the scalar kernel, which has no alignment requirement.  One workgroup per (b, f): deterministic.      */
 int ws_scale_bf_fwd(const float* x, const float* s, int B, int T, int F, int C, int mode, float* y, void* stream);
 int ws_scale_bf_bwd(const float* x, const float* dy, const float* s, int B, int T, int F, int C, int mode, float* dx,
                     float* ds, void* stream);
 /* ABI v17: SpeakerFuseLayer 'concat' (speaker.py:95-101) on [B][T][F][C]: the Linear over the frequency axis of cat[x, e] --
  * y[b][t][f'][c] = sum_f W[f' * ldw + f] x[b][t][f][c] + rb[b][f'];  W: the first F columns of fc.linear.weight [F][F + E]
- * (ldw = F + E), rb [B][F] = We e + bias (ws_gemm_nt).  Exact fp32; F * C <= 16384.  Forward only: the native runtime's
+ * (ldw = F + E >= F; the columns [F, ldw) of W are not read), rb [B][F] = We e + bias (ws_gemm_nt).  Exact fp32; C % 4 == 0,
+ * F * C <= 16384 (the [F][C] tile of one (b, t) in 64 KB of LDS; more is refused).  Forward only: the native runtime's
  * form of the fusion (runtime/engine.cc); training composes it from GEMMs on a transposed view.                    */
 int ws_freq_linear_fwd(const float* x, const float* W, long long ldw, const float* rb, int B, int T, int F, int C, float* y,
                        void* stream);
 
 /* ---- TF-GridNet: everything but this row softmax is composed from the entry points
- * above (gridnet_block.py:212-213): y = softmax(scale * x) per row of n; dx = scale * y * (dy - sum(dy * y))   */
+ * above (gridnet_block.py:212-213): y = softmax(scale * x) per row of n (the maximum of scale * x is subtracted first);
+ * dx = scale * y * (dy - sum(dy * y)).  Any n >= 1 and any alignment: n <= 1024, n % 4 == 0 and 16-byte aligned x, y (y, dy,
+ * dx) select the one-pass 16-byte kernels, everything else the scalar ones; both give the same values within rounding.  */
 int ws_softmax_rows_fwd(const float* x, long long rows, int n, float scale, float* y, void* stream);
 int ws_softmax_rows_bwd(const float* y, const float* dy, long long rows, int n, float scale, float* dx, void* stream);
 

@@ -221,6 +221,23 @@ def elu_bwd(x, dy, dx):
     dx.copy_(torch.where(x > 0, dy, dy * torch.exp(x)))
 
 
+def inorm_finalize(sums, G, Cc, P, stats, eps=1e-5):
+    s = sums.reshape(G, 2, Cc)
+    mean = s[:, 0] / P
+    var = (s[:, 1] / P - mean * mean).clamp_min(0)
+    stats.reshape(G, 2, Cc)[:] = torch.stack([mean, 1.0 / torch.sqrt(var + eps)], 1)
+
+
+def inorm_apply(x, stats, rows, P, Cc, y):
+    st = stats.reshape(-1, 2, Cc)
+    y.reshape(-1, P, Cc)[:] = (x.reshape(-1, P, Cc) - st[:, 0:1]) * st[:, 1:2]
+
+
+def inorm_bwd_apply(y, dy, stats, sums, rows, P, Cc, dx):
+    st, sm = stats.reshape(-1, 2, Cc), sums.reshape(-1, 2, Cc)
+    dx.reshape(-1, P, Cc)[:] = st[:, 1:2] * (dy.reshape(-1, P, Cc) - sm[:, 0:1] / P - y.reshape(-1, P, Cc) * (sm[:, 1:2] / P))
+
+
 def inorm_fwd(x, G, P, Cc, y, eps=1e-5):
     xx = x.reshape(G, P, Cc)
     mean = xx.mean(1)
@@ -281,7 +298,7 @@ def bilinear_fwd(x, B, h, w, H, W, Cc, y):
     y.reshape(-1, Cc)[:] = _cl(F.interpolate(_nchw(x, B, h, w), size=(H, W), mode="bilinear"))
 
 
-def bilinear_bwd(dy, B, h, w, H, W, Cc, dx):
+def bilinear_bwd(dy, B, h, w, H, W, Cc, dx, tmp=None):
     xr = torch.zeros(B, Cc, h, w, requires_grad=True)
     with torch.enable_grad():
         F.interpolate(xr, size=(H, W), mode="bilinear").backward(_nchw(dy, B, H, W))
@@ -517,7 +534,61 @@ def _cols(t, rows, ld, off, Cc):
     return t.reshape(-1)[:rows * ld].reshape(rows, ld)[:, off:off + Cc] if ld else t.reshape(rows, Cc)
 
 
-def in_act_fwd(x, G, P, Cc, flags, y, eps=1e-5, y_ld=0, y_off=0):
+def _elud(v):
+    return torch.where(v > 0, torch.ones_like(v), torch.exp(v))
+
+
+def in_act_sums(x, dy, stats, G, P, Cc, flags, nsplit, slab, dy_ld=0, dy_off=0):
+    u = x.reshape(G, P, Cc)
+    if flags & 1:
+        u = F.elu(u)
+    if dy is None:
+        a, b = u, u * u
+    else:
+        st = stats.reshape(G, 2, Cc)
+        n = (u - st[:, 0:1]) * st[:, 1:2]
+        d = _cols(dy, G * P, dy_ld, dy_off, Cc).reshape(G, P, Cc)
+        a = d * _elud(n) if flags & 2 else d
+        b = a * n
+    out = slab.reshape(nsplit, G, 2, Cc)
+    out[:] = 0.0
+    per = -(-P // nsplit)
+    for s in range(nsplit):
+        lo, hi = s * per, min(P, (s + 1) * per)
+        if hi > lo:
+            out[s, :, 0], out[s, :, 1] = a[:, lo:hi].sum(1), b[:, lo:hi].sum(1)
+
+
+def in_act_apply(x, stats, rows, P, Cc, flags, y, y_ld=0, y_off=0):
+    st = stats.reshape(-1, 2, Cc)
+    u = x.reshape(-1, P, Cc)
+    if flags & 1:
+        u = F.elu(u)
+    n = (u - st[:, 0:1]) * st[:, 1:2]
+    _cols(y, rows, y_ld, y_off, Cc)[:] = (F.elu(n) if flags & 2 else n).reshape(rows, Cc)
+
+
+def in_act_bwd_apply(x, dy, stats, sums, rows, P, Cc, flags, dx, dy_ld=0, dy_off=0, dx_ld=0, dx_off=0):
+    st, sm = stats.reshape(-1, 2, Cc), sums.reshape(-1, 2, Cc)
+    xx = x.reshape(-1, P, Cc)
+    u = F.elu(xx) if flags & 1 else xx
+    n = (u - st[:, 0:1]) * st[:, 1:2]
+    d = _cols(dy, rows, dy_ld, dy_off, Cc).reshape(-1, P, Cc)
+    if flags & 2:
+        d = d * _elud(n)
+    r = st[:, 1:2] * (d - sm[:, 0:1] / P - n * (sm[:, 1:2] / P))
+    if flags & 1:
+        r = r * _elud(xx)
+    _cols(dx, rows, dx_ld, dx_off, Cc)[:] = r.reshape(rows, Cc)
+
+
+def freq_linear_fwd(x, W, ldw, rb, B, T, Fq, Cc, y):
+    Wm = W.reshape(-1)
+    Wm = torch.stack([Wm[f * ldw:f * ldw + Fq] for f in range(Fq)])
+    y.reshape(B, T, Fq, Cc)[:] = torch.einsum("gf,btfc->btgc", Wm, x.reshape(B, T, Fq, Cc)) + rb.reshape(B, 1, Fq, 1)
+
+
+def in_act_fwd(x, G, P, Cc, flags, y, eps=1e-5, y_ld=0, y_off=0, nsplit=None):
     u = x.reshape(G, P, Cc)
     if flags & 1:
         u = F.elu(u)
@@ -529,7 +600,7 @@ def in_act_fwd(x, G, P, Cc, flags, y, eps=1e-5, y_ld=0, y_off=0):
     return torch.stack([mean, rstd], 1)
 
 
-def in_act_bwd(x, dy, stats, G, P, Cc, flags, dx, dy_ld=0, dy_off=0, dx_ld=0, dx_off=0):
+def in_act_bwd(x, dy, stats, G, P, Cc, flags, dx, dy_ld=0, dy_off=0, dx_ld=0, dx_off=0, nsplit=None):
     xx, dd = x.reshape(G, P, Cc), _cols(dy, G * P, dy_ld, dy_off, Cc).reshape(G, P, Cc)
     u = F.elu(xx) if flags & 1 else xx
     mean, rstd = stats[:, 0][:, None], stats[:, 1][:, None]
@@ -792,7 +863,8 @@ EMULATED = [seg_sums, seg_scale, astp_fwd, astp_bwd, rowbias_act_fwd, act_bwd, c
             scale_bf_fwd, scale_bf_bwd, preemph_pad, ola_fwd, ola_bwd, total_sum, lstm_pack, lstm_fwd, lstm_bwd,
             group_stats, flat_stats, gn_bwd_reduce, norm_ab, norm_bwd_apply_cl, prelu_fwd, prelu_bwd, softmax_rows_fwd,
             softmax_rows_bwd, maskmul_fwd, maskmul_bwd, relu_mask, bn_stats, bn_prelu_fwd, bn_bwd, maxpool3_fwd, maxpool3_bwd,
-            bcast_rows, cross_entropy, im2col, col2im, tstp_fwd, tstp_bwd, power_spec, log_eps, rowln_ok, rowln_fwd, rowln_bwd, in_act_fwd, in_act_bwd, conv3x3, conv3x3_pack, conv3x3_pack_srcs, conv3x3_wgrad, conv3x3_wgrad_tiles, heads_ok, heads_fwd, heads_bwd]
+            bcast_rows, cross_entropy, im2col, col2im, tstp_fwd, tstp_bwd, power_spec, log_eps, rowln_ok, rowln_fwd, rowln_bwd, in_act_fwd, in_act_bwd,
+            inorm_finalize, inorm_apply, inorm_bwd_apply, in_act_sums, in_act_apply, in_act_bwd_apply, freq_linear_fwd, conv3x3, conv3x3_pack, conv3x3_pack_srcs, conv3x3_wgrad, conv3x3_wgrad_tiles, heads_ok, heads_fwd, heads_bwd]
 
 
 def install(monkeypatch):

@@ -1737,14 +1737,33 @@ def elu_bwd(x, dy, dx):
     _call("ws_elu_bwd", _p(x), _p(dy), x.numel(), _p(dx))
 
 
+def inorm_finalize(sums, G: int, Cc: int, P: int, stats, eps=IN_EPS):
+    """stats [G, 2, C] = (mean, 1 / sqrt(max(E[u^2] - mean^2, 0) + eps)) from sums [G, 2, C] = (sum u, sum u^2) over P positions."""
+    _chk(sums, "sums")
+    _chk(stats, "stats")
+    _call("ws_inorm_finalize", _p(sums), G, Cc, P, eps, _p(stats))
+
+
+def inorm_apply(x, stats, rows: int, P: int, Cc: int, y):
+    for n, t in (("x", x), ("stats", stats), ("y", y)):
+        _chk(t, n)
+    _call("ws_inorm_apply", _p(x), _p(stats), rows, P, Cc, _p(y))
+
+
+def inorm_bwd_apply(y, dy, stats, sums, rows: int, P: int, Cc: int, dx):
+    for n, t in (("y", y), ("dy", dy), ("stats", stats), ("sums", sums), ("dx", dx)):
+        _chk(t, n)
+    _call("ws_inorm_bwd_apply", _p(y), _p(dy), _p(stats), _p(sums), rows, P, Cc, _p(dx))
+
+
 def inorm_fwd(x, G: int, P: int, Cc: int, y, eps=IN_EPS):
     """y = InstanceNorm(x) over the P positions of each of G rows; returns stats [G, 2, C] = (mean, rstd)."""
     _chk(x, "x")
     _chk(y, "y")
     sums = chan_sums(x, x, None, 1, P, G, Cc)
     stats = torch.empty(G, 2, Cc, device=x.device, dtype=torch.float32)
-    _call("ws_inorm_finalize", _p(sums), G, Cc, P, eps, _p(stats))
-    _call("ws_inorm_apply", _p(x), _p(stats), G * P, P, Cc, _p(y))
+    inorm_finalize(sums, G, Cc, P, stats, eps)
+    inorm_apply(x, stats, G * P, P, Cc, y)
     return stats
 
 
@@ -1752,7 +1771,7 @@ def inorm_bwd(y, dy, stats, G: int, P: int, Cc: int, dx):
     for n, t in (("y", y), ("dy", dy), ("stats", stats), ("dx", dx)):
         _chk(t, n)
     sums = chan_sums(dy, y, None, 1, P, G, Cc)
-    _call("ws_inorm_bwd_apply", _p(y), _p(dy), _p(stats), _p(sums), G * P, P, Cc, _p(dx))
+    inorm_bwd_apply(y, dy, stats, sums, G * P, P, Cc, dx)
 
 
 def conv3x3_pack(W2, Cin: int, Cout: int):
@@ -1843,10 +1862,35 @@ def conv3x3_wgrad(*, G, ldg: int, X, ldx: int, B: int, H: int, Wd: int, Cin: int
 IN_ELU_PRE, IN_ELU_POST = 1, 2     # ws_in_act_* flags: y = IN(ELU(x)) / y = ELU(IN(x))
 
 
-def _in_act_sums(x, dy, stats, G: int, P: int, Cc: int, flags: int, dy_ld: int = 0, dy_off: int = 0):
-    nsplit = max(1, min(max(1, 1024 // G), P // 32))
-    slab = torch.empty(nsplit, G, 2, Cc, device=x.device, dtype=torch.float32)
+def in_act_nsplit(G: int, P: int) -> int:
+    return max(1, min(max(1, 1024 // G), P // 32))
+
+
+def in_act_sums(x, dy, stats, G: int, P: int, Cc: int, flags: int, nsplit: int, slab, dy_ld: int = 0, dy_off: int = 0):
+    """ws_in_act_sums: slab [nsplit, G, 2, C] = the partial sums of split s over rows [s * per, min(P, (s + 1) * per)),
+    per = ceil(P / nsplit), of every group (dy None: the forward sums)."""
+    for n, t in (("x", x), ("dy", dy), ("stats", stats), ("slab", slab)):
+        _chk(t, n)
     _call("ws_in_act_sums", _p(x), _p(dy, dy_off), dy_ld, _p(stats), P, G, nsplit, Cc, flags, _p(slab))
+
+
+def in_act_apply(x, stats, rows: int, P: int, Cc: int, flags: int, y, y_ld: int = 0, y_off: int = 0):
+    for n, t in (("x", x), ("stats", stats), ("y", y)):
+        _chk(t, n)
+    _call("ws_in_act_apply", _p(x), _p(stats), rows, P, Cc, flags, _p(y, y_off), y_ld)
+
+
+def in_act_bwd_apply(x, dy, stats, sums, rows: int, P: int, Cc: int, flags: int, dx, dy_ld: int = 0, dy_off: int = 0,
+                     dx_ld: int = 0, dx_off: int = 0):
+    for n, t in (("x", x), ("dy", dy), ("stats", stats), ("sums", sums), ("dx", dx)):
+        _chk(t, n)
+    _call("ws_in_act_bwd_apply", _p(x), _p(dy, dy_off), dy_ld, _p(stats), _p(sums), rows, P, Cc, flags, _p(dx, dx_off), dx_ld)
+
+
+def _in_act_sums(x, dy, stats, G: int, P: int, Cc: int, flags: int, dy_ld: int = 0, dy_off: int = 0, nsplit=None):
+    nsplit = in_act_nsplit(G, P) if nsplit is None else nsplit
+    slab = torch.empty(nsplit, G, 2, Cc, device=x.device, dtype=torch.float32)
+    in_act_sums(x, dy, stats, G, P, Cc, flags, nsplit, slab, dy_ld, dy_off)
     out = torch.empty(G, 2, Cc, device=x.device, dtype=torch.float32)
     reduce_slabs(slab, nsplit, G * 2 * Cc, G * 2 * Cc, out)
     return out
@@ -1860,29 +1904,30 @@ def _cols_ok(t, rows: int, ld: int, off: int, Cc: int, name: str):
         raise L.WesepHipError(f"{name}: expected {rows} x {Cc} elements")
 
 
-def in_act_fwd(x, G: int, P: int, Cc: int, flags: int, y, eps=IN_EPS, y_ld: int = 0, y_off: int = 0):
+def in_act_fwd(x, G: int, P: int, Cc: int, flags: int, y, eps=IN_EPS, y_ld: int = 0, y_off: int = 0, nsplit=None):
     """y = IN(ELU(x)) (flags IN_ELU_PRE) or ELU(IN(x)) (IN_ELU_POST) over the P positions of each of G rows, three
     passes; returns the statistics [G, 2, C] the backward needs (with x).  y_ld / y_off: write columns [y_off, y_off + Cc)
-    of the dense [G*P, y_ld] tensor y instead of a dense [G*P, Cc] one."""
+    of the dense [G*P, y_ld] tensor y instead of a dense [G*P, Cc] one.  nsplit: the row splits of the sums (None: the
+    default of in_act_nsplit)."""
     _chk(x, "x")
     _chk(y, "y")
     _cols_ok(y, G * P, y_ld, y_off, Cc, "in_act_fwd y")
-    sums = _in_act_sums(x, None, None, G, P, Cc, flags)
+    sums = _in_act_sums(x, None, None, G, P, Cc, flags, nsplit=nsplit)
     stats = torch.empty(G, 2, Cc, device=x.device, dtype=torch.float32)
-    _call("ws_inorm_finalize", _p(sums), G, Cc, P, eps, _p(stats))
-    _call("ws_in_act_apply", _p(x), _p(stats), G * P, P, Cc, flags, _p(y, y_off), y_ld)
+    inorm_finalize(sums, G, Cc, P, stats, eps)
+    in_act_apply(x, stats, G * P, P, Cc, flags, y, y_ld, y_off)
     return stats
 
 
 def in_act_bwd(x, dy, stats, G: int, P: int, Cc: int, flags: int, dx, dy_ld: int = 0, dy_off: int = 0, dx_ld: int = 0,
-               dx_off: int = 0):
+               dx_off: int = 0, nsplit=None):
     """dy_ld / dy_off: dy is columns [dy_off, dy_off + Cc) of a dense [G*P, dy_ld] tensor; dx_ld / dx_off likewise for dx."""
     for n, t in (("x", x), ("dy", dy), ("stats", stats), ("dx", dx)):
         _chk(t, n)
     _cols_ok(dy, G * P, dy_ld, dy_off, Cc, "in_act_bwd dy")
     _cols_ok(dx, G * P, dx_ld, dx_off, Cc, "in_act_bwd dx")
-    sums = _in_act_sums(x, dy, stats, G, P, Cc, flags, dy_ld, dy_off)
-    _call("ws_in_act_bwd_apply", _p(x), _p(dy, dy_off), dy_ld, _p(stats), _p(sums), G * P, P, Cc, flags, _p(dx, dx_off), dx_ld)
+    sums = _in_act_sums(x, dy, stats, G, P, Cc, flags, dy_ld, dy_off, nsplit=nsplit)
+    in_act_bwd_apply(x, dy, stats, sums, G * P, P, Cc, flags, dx, dy_ld, dy_off, dx_ld, dx_off)
 
 
 def avgpool_fwd(x, B: int, H: int, W: int, Cc: int, sz: int, y):
@@ -1903,10 +1948,15 @@ def bilinear_fwd(x, B: int, h: int, w: int, H: int, W: int, Cc: int, y):
     _call("ws_bilinear_fwd", _p(x), B, h, w, H, W, Cc, _p(y))
 
 
-def bilinear_bwd(dy, B: int, h: int, w: int, H: int, W: int, Cc: int, dx):
+def bilinear_bwd(dy, B: int, h: int, w: int, H: int, W: int, Cc: int, dx, tmp=None):
+    """tmp: B * H * w * Cc floats of scratch for the row pass of the separable adjoint (None: allocated here)."""
     _chk(dy, "dy")
     _chk(dx, "dx")
-    tmp = torch.empty(B * H * w * Cc, device=dy.device, dtype=torch.float32)      # row pass of the separable adjoint
+    _chk(tmp, "tmp")
+    if tmp is None:
+        tmp = torch.empty(B * H * w * Cc, device=dy.device, dtype=torch.float32)
+    elif tmp.numel() < B * H * w * Cc:
+        raise L.WesepHipError(f"bilinear_bwd tmp: {tmp.numel()} floats, the row pass needs {B * H * w * Cc}")
     _call("ws_bilinear_bwd", _p(dy), B, h, w, H, W, Cc, _p(tmp), _p(dx))
 
 
