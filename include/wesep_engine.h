@@ -54,7 +54,7 @@ void ws_engine_destroy(ws_engine* e);
  * target speaker and separator forwards of the last ws_engine_separate_long; 0 after any other call), "causal" / "norm"
  * (Conv-TasNet containers: 1 / 1 for causal blocks with cLN; absent, i.e. -1, in containers written before these keys, which
  * load as non-causal gLN), "streaming" (1: ws_engine_stream_open takes this container), "stream_state_bytes" (device state
- * of the stream opened last)}; unknown key -> -1. */
+ * of the stream or stream pool opened last)}; unknown key -> -1. */
 long long ws_engine_info(const ws_engine* e, const char* key);
 
 /* enrollment kinds */
@@ -165,6 +165,52 @@ int ws_engine_stream_push(ws_stream* s, const float* chunk, int n, float* est, i
 int ws_engine_stream_flush(ws_stream* s, float* est, int est_cap, int* n_out);
 int ws_engine_stream_reset(ws_stream* s);
 void ws_engine_stream_close(ws_stream* s);
+
+/* Stream pool (new symbols, engine ABI 2 unchanged): MANY independent streams on one engine -- calls that start at different
+ * times and deliver packets of different sizes -- through ONE launch chain per round.  A ws_stream's rows all sit at the same
+ * sample position; N of them pushed one after another cost N launch chains.  In a causal cLN model every frame depends on
+ * earlier frames of its own row only, and the two kernels that look across time take a per-row position, frame count and
+ * state slot (wesep_hip.h: ws_tcn_mid_stream_rows_fwd, ws_ola_stream_rows_fwd), so any set of streams shares one rectangle.
+ * Each slot is one stream with the emission rule, the outputs and the error bound of a ws_stream with rows = 1.
+ *
+ *   ws_engine_pool_open(e, slots, max_chunk_frames, &pool)  makes the state: ONE device allocation, freed at close, that no
+ *     push, attach or detach grows ("stream_state_bytes").  Per slot: per block a ring [(P - 1) dil + max_chunk_frames][H],
+ *     the overlap-add carry [L - s], the embedding after SpeakerTransform, the stacks' row biases; and one carry reset image.
+ *     The samples that have not completed a frame (fewer than 160 + s after a push) are kept on the HOST, per slot.
+ *   ws_engine_pool_attach(pool, enroll, enroll_kind, enroll_len, &slot)  takes the lowest free slot, runs the speaker stage
+ *     for this ONE enrollment (kinds as for ws_engine_stream_open with rows = 1), writes the slot's embedding and row biases
+ *     and puts it at sample 0 (carry = the decoder bias; the rings need no clearing).  A full pool is refused by name.
+ *   ws_engine_pool_push(pool, n_active, slots, chunks, n, est, est_cap, n_out)  one packet for each of n_active DISTINCT
+ *     attached slots: chunks[i] is n[i] >= 1 samples for slots[i]; the samples of that slot that became final go to est[i]
+ *     (est_cap[i] >= n_out[i]; WS_STREAM_PUSH_CAP(n[i], L) always suffices), their count to n_out[i] -- per slot the
+ *     emission rule of ws_engine_stream_push.  The work is cut into groups: a slot that still owes frames joins a group with
+ *     tc_i = min(frames owed, max_chunk_frames) of them, the group is the rectangle [A][Tc], A the slots in it, Tc = max tc_i,
+ *     staged zero-filled on the host and uploaded once with its three tables.  Frames t >= tc_i of a row are computed on
+ *     zeros by the GEMMs and consumed by nothing: the price of one rectangle, largest when one slot delivers a long packet
+ *     beside short ones.  A group is WS_POOL_GROUP_LAUNCHES(R, X) = 3 R X + 9 entry-point calls whatever A is (a ws_stream's
+ *     group without the pending-sample copy); "n_launches" after a push is that figure times its groups; a round in which
+ *     every slot owes at most max_chunk_frames frames is one group.  One host synchronisation per push.
+ *   ws_engine_pool_flush(pool, slot, est, est_cap, &n_out)  the end of ONE slot's stream, as ws_engine_stream_flush: the
+ *     remaining frames on the zero-extended pending samples (groups with A = 1), then the carry; at most
+ *     WS_STREAM_FLUSH_CAP samples.  The slot then takes no push or flush until it is detached.
+ *   ws_engine_pool_detach(pool, slot)  frees the slot for the next attach.    ws_engine_pool_close(pool)  before
+ *     ws_engine_destroy.
+ * What one slot returns does not depend on what the other slots of a push carry (NaN and inf included): no launch mixes
+ * rows.  All pointers are HOST pointers; callers serialise, as for every engine call.
+ * WS_ERR_INVALID with a message and nothing launched: a container that cannot stream (the text of ws_engine_stream_open),
+ * slots < 1, max_chunk_frames outside [1, 65536], slots x max_chunk_frames over the 2^31 guards of ws_engine_stream_open, a
+ * full pool, a slot of a push or flush that is not attached, was flushed, or is named twice, n[i] < 1, est_cap[i] below what
+ * the slot emits, a flush with fewer than L samples, a NULL pointer, and any call but detach and close after a push or flush
+ * that failed half way, until the slots that call named are detached. */
+#define WS_POOL_GROUP_LAUNCHES(R, X) (3 * (R) * (X) + 9)
+typedef struct ws_pool ws_pool;
+int ws_engine_pool_open(ws_engine* e, int slots, int max_chunk_frames, ws_pool** out);
+int ws_engine_pool_attach(ws_pool* p, const void* enroll, int enroll_kind, int enroll_len, int* slot);
+int ws_engine_pool_push(ws_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n, float* const* est,
+                        const int* est_cap, int* n_out);
+int ws_engine_pool_flush(ws_pool* p, int slot, float* est, int est_cap, int* n_out);
+int ws_engine_pool_detach(ws_pool* p, int slot);
+void ws_engine_pool_close(ws_pool* p);
 
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by

@@ -1182,6 +1182,38 @@ int ws_ola_stream_fwd(const float* frames, const float* bias, int R, int Tc, int
 int ws_tcn_mid_stream_fwd(const float* c, const float* rb, const float* a1, const float* gamma1, const float* beta1,
                           const float* wd, const float* bd, const float* a2, int R, int Tc, int H, int P, int dil,
                           float eps, long long t0, int cap, float* ring, float* y2, float* st2, void* stream);
+/* ---- stream pool (stream.hip; runtime/stream_pool.cc) -- new symbols, ABI 20 unchanged -------------------
+ * The two kernels above for MANY independent streams in one launch: every stream at its own position, with its own number
+ * of new frames.  Data rows are compact, state is addressed by slot: row i of the [A][Tc] rectangle belongs to the stream
+ * whose state is row slot[i] of the [nslots] state arrays.  Three DEVICE tables of A entries, one entry per row:
+ *   slot [A] int        0 <= slot[i] < nslots
+ *   t0   [A] long long  absolute index of the row's first frame in this launch
+ *   tc   [A] int        valid frames of the row in this launch, 0 <= tc[i] <= Tc
+ * As for every length table of this header, an entry can never move an access out of its buffer: an out-of-range slot or a
+ * negative t0 skips the row (it is treated as tc[i] = 0: its outputs are the zeros below, no state row is touched), tc is
+ * clamped to [0, Tc].  Distinct rows naming the same slot would race on its state: that is the caller's contract (the
+ * engine checks it on the host).  State rows of slots that no entry names are neither read nor written.
+ *   ws_tcn_mid_stream_rows_fwd  ws_tcn_mid_stream_fwd with c [A][Tc][H], rb [nslots][H] (read at slot[i]) or NULL, ring
+ *                   [nslots][cap][H], y2 [A][Tc][H], st2 [A][Tc][2].  One workgroup per (i, t), the same number of threads
+ *                   (a function of H alone), the same expressions in the same order: frame t < tc[i] of row i -- y2, st2
+ *                   and the ring slot it writes -- is bit for bit what ws_tcn_mid_stream_fwd(R = 1, Tc = tc[i], t0 = t0[i])
+ *                   gives on that row's c, rb[slot[i]] and ring row.  A tap inside the chunk is recomputed from c only for
+ *                   frames below tc[i]; everything earlier comes from the ring.  A frame t >= tc[i] gets exact zeros in y2
+ *                   and (0, 1) in st2 (a norm-on-load GEMM behind it stays finite) and writes no ring slot; c behind tc[i]
+ *                   is never read into a valid output (NaN included).  Contract: cap >= (P - 1) * dil + Tc.
+ *                   WS_ERR_INVALID before any launch: as ws_tcn_mid_stream_fwd, and A < 1, nslots < 1, a NULL table.
+ *   ws_ola_stream_rows_fwd  ws_ola_stream_fwd with frames [A][Tc][L], carry [nslots][L - hop], est [A][Tc * hop].  Row i
+ *                   emits the tc[i] * hop samples that become final after tc[i] frames, exact zeros behind them up to the
+ *                   row pitch Tc * hop, and leaves carry[slot[i]] as ws_ola_stream_fwd(R = 1, Tc = tc[i]) would -- the
+ *                   additions in ascending frame order, so bit for bit.  With tc[i] = 0 the carry row is neither read nor
+ *                   written.  frames behind tc[i] are not read.  WS_ERR_INVALID before any launch: as ws_ola_stream_fwd, and
+ *                   A < 1, nslots < 1, a NULL table. */
+int ws_tcn_mid_stream_rows_fwd(const float* c, const float* rb, const float* a1, const float* gamma1, const float* beta1,
+                               const float* wd, const float* bd, const float* a2, int A, int Tc, int H, int P, int dil,
+                               float eps, int nslots, const int* slot, const long long* t0, const int* tc, int cap,
+                               float* ring, float* y2, float* st2, void* stream);
+int ws_ola_stream_rows_fwd(const float* frames, const float* bias, int A, int Tc, int L, int hop, int nslots,
+                           const int* slot, const long long* t0, const int* tc, float* carry, float* est, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@
 //   gridnet_plan.cc  TF-GridNet (arch 3)
 //   longform.cc      ws_engine_separate_long: one long mixture as overlapping windows through the rectangular plans
 //   stream.cc        ws_engine_stream_*: causal cLN Conv-TasNet fed audio as it arrives, state carried on the device
+//   stream_pool.cc   ws_engine_pool_*: many such streams, each at its own position, through one launch chain per round
 // Everything here lives in namespace wsrt and is built with -fvisibility=hidden: the library exports the C ABI only
 // (WS_ENGINE_API).  Host code only: no kernels in the runtime.
 #ifndef WESEP_ENGINE_INTERNAL_H_
@@ -421,6 +422,19 @@ struct TasGemm {
 };
 int tas_gemm(ws_engine* e, const TasGemm& t);
 inline bool tas_streamable(const ws_engine* e) { return e->arch == 1 && e->tas.causal && e->tas.norm == 1; }
+// ---- what the solo stream (stream.cc) and the stream pool (stream_pool.cc) share ----
+struct StreamBlock {         // one causal cLN block: its weights, and where its carried state lives
+  const float *w1, *b1, *a1, *g1, *be1, *wd, *bd, *a2, *g2, *be2, *w3, *b3;
+  int ldw, dil, cap;
+  float* ring;               // [rows or slots][cap][H]
+  const float* rb;           // [rows or slots][H] = W_e e + b for the stack's first block, else NULL
+};
+struct StreamWeights {       // every weight pointer of a group of frames, resolved once
+  const float *enc_w[3], *enc_b[3], *ln_g, *ln_b, *proj_w, *proj_b, *mask_w, *mask_b, *dec_b;
+  std::vector<StreamBlock> blocks;
+};
+void resolve_stream_weights(const ws_engine* e, StreamWeights* w);   // blocks: weights, ldw and dil; the owner sets cap, ring, rb
+int refuse_not_streamable(const ws_engine* e, const char* who);      // WS_ERR_INVALID with the reason, by name
 int tas_flat_stats(ws_engine* e, const float* x, int R, long long n, float* st);
 int prepare_dpccn(ws_engine* e);
 int dpccn_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est);

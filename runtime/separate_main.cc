@@ -3,7 +3,7 @@
 //
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
 //                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
-//                 [--stream_ms 10]
+//                 [--stream_ms 10 [--stream_pool 4]]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -30,6 +30,11 @@
 // (ws_engine_stream_open / push / flush) in chunks of M milliseconds, as a live source would deliver it; the speaker encoder
 // runs once per line, at open.  Same files as the plain run: the streamed samples, then zeros where the plain run has its
 // zero tail.  Refused on a model that cannot stream, and together with --batch N > 1 or --chunk_seconds.
+// --stream_ms M --stream_pool N: N consecutive lines of the scp run CONCURRENTLY through one stream pool (ws_engine_pool_*, two
+// slots per line): every round feeds each live line its next M ms packet in ONE push -- one launch chain for all of them --
+// and a line that ends is flushed, its slots detached and re-attached to the next line, while the others are in mid-stream.
+// Output names and formats are those of --stream_ms alone.  --stream_pool without --stream_ms, or together with --batch N > 1
+// or --chunk_seconds, is refused.
 // --dry_run validates the model file and the launch plan of every utterance without a GPU and writes nothing.
 // --raw_out additionally writes the unquantised estimates as <key>-spk{1,2}.f32 (float32, for parity checks).
 #include <stdio.h>
@@ -132,10 +137,12 @@ int main(int argc, char** argv) {
   const bool streamed = args.has("stream_ms");
   const double stream_ms = atof(args.get("stream_ms", "0").c_str());
   const int stream_n = static_cast<int>(stream_ms * sample_rate / 1000.0 + 0.5);
+  const bool pooled = args.has("stream_pool");
+  const int pool_n = atoi(args.get("stream_pool", "0").c_str());
   if (args.has("help")) {
     printf("usage: separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1]\n"
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
-           "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]]\n"
+           "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]] [--stream_ms M [--stream_pool N]]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
@@ -145,11 +152,17 @@ int main(int argc, char** argv) {
            "  --overlap_seconds O  overlap of neighbouring windows, 0 <= O <= S / 2 (default S / 4)\n"
            "  --chunk_rows N     window rows per forward (default 8): memory grows with N, not with the recording\n"
            "  --stream_ms M      causal cLN Conv-TasNet / SpEx+ models: feed every line to a stream in chunks of M ms; same\n"
-           "                     files as the plain run.  Not together with --batch N > 1 or --chunk_seconds\n");
+           "                     files as the plain run.  Not together with --batch N > 1 or --chunk_seconds\n"
+           "  --stream_pool N    with --stream_ms M: N consecutive lines at a time through one stream pool, one push per round\n"
+           "                     of M ms packets; same files as --stream_ms alone\n");
     return 0;
   }
   if (chunked && batch > 1) return die("--chunk_seconds and --batch " + std::to_string(batch) + " conflict: a batch is a rectangle of "
                                        "whole utterances, --chunk_seconds cuts one recording into windows (use --jobs for more lines at a time)");
+  if (pooled && !streamed) return die("--stream_pool needs --stream_ms M: the pool is fed packets of M milliseconds");
+  if (pooled && (batch > 1 || chunked))
+    return die("--stream_pool conflicts with --batch N > 1 and --chunk_seconds: the pool's lines are streams, each fed as it arrives");
+  if (pooled && pool_n < 1) return die("--stream_pool needs a positive number of lines");
   if (streamed && (batch > 1 || chunked))
     return die("--stream_ms conflicts with --batch N > 1 and --chunk_seconds: a stream takes one recording as it arrives");
   if (streamed && stream_n < 1) return die("--stream_ms needs a positive chunk length");
@@ -192,6 +205,146 @@ int main(int argc, char** argv) {
       ws_engine_destroy(engine);
       return fail("--stream_ms: this model cannot stream (ws_engine_info \"streaming\" is not 1): streaming needs a causal cLN "
                   "Conv-TasNet / SpEx+ container");
+    }
+    // --stream_pool N: up to N lines in flight on one pool of 2 N slots; a lane takes the next line when its own ends
+    if (pooled) {
+      struct Lane {
+        bool live = false;
+        size_t line = 0;
+        wesep_rt::Wav mix;
+        std::vector<float> out, chunk;
+        int n = 0, pos = 0, done = 0, slot[2] = {-1, -1};
+        long long pushes = 0;
+        std::chrono::steady_clock::time_point t0;
+      };
+      const int L = static_cast<int>(ws_engine_info(engine, "L"));
+      const int cap = std::max(WS_STREAM_PUSH_CAP(stream_n, L), WS_STREAM_FLUSH_CAP);
+      ws_pool* pool = nullptr;
+      if (ws_engine_pool_open(engine, 2 * pool_n, 64, &pool) != 0) {
+        fail(std::string("--stream_pool: ") + ws_engine_last_error());
+        ws_engine_destroy(engine);
+        return;
+      }
+      std::vector<Lane> lanes(pool_n);
+      std::vector<std::vector<float>> got(size_t(2) * pool_n, std::vector<float>(cap));
+      bool ok = true;
+      long long rounds = 0, launches = 0;
+      double audio_ms = 0.0;
+      const auto pool_t0 = std::chrono::steady_clock::now();
+      auto start = [&](Lane& ln) {              // the next line of the scp into this lane: read it, attach its two enrollments
+        const size_t i = next++;
+        if (i >= waves.size() || failed) return;
+        const auto& w = waves[i];
+        wesep_rt::Wav s1, s2;
+        std::string err;
+        if (!wesep_rt::read_wav(w[1], &ln.mix, &err) || !wesep_rt::read_wav(w[2], &s1, &err) || !wesep_rt::read_wav(w[3], &s2, &err)) {
+          fail(err);
+          ok = false;
+          return;
+        }
+        if (ln.mix.sample_rate != sample_rate || s1.sample_rate != sample_rate || s2.sample_rate != sample_rate) {
+          fail(w[0] + ": sample rate is not " + std::to_string(sample_rate));
+          ok = false;
+          return;
+        }
+        ln.line = i, ln.n = static_cast<int>(ln.mix.samples.size()), ln.pos = ln.done = 0, ln.pushes = 0;
+        ln.out.assign(size_t(2) * ln.n, 0.f);
+        ln.t0 = std::chrono::steady_clock::now();
+        const int n_enroll = static_cast<int>(std::min(s1.samples.size(), s2.samples.size()));
+        std::vector<float> enr(n_enroll);
+        for (int k = 0; k < 2 && ok; ++k) {
+          const std::vector<int16_t>& src = k == 0 ? s1.samples : s2.samples;
+          for (int j = 0; j < n_enroll; ++j) enr[j] = static_cast<float>(src[j]) / 32768.0f;
+          if (ws_engine_pool_attach(pool, enr.data(), WS_ENROLL_WAVE, n_enroll, &ln.slot[k]) != 0) {
+            fail(w[0] + ": " + ws_engine_last_error());
+            ok = false;
+          }
+        }
+        ln.live = ok;
+      };
+      auto finish = [&](Lane& ln, int lane_id) {  // flush both slots, free them, write the line's files
+        const auto& w = waves[ln.line];
+        std::string err;
+        for (int k = 0; k < 2 && ok; ++k) {
+          int m = 0;
+          float* g = got[size_t(2) * lane_id + k].data();
+          if (ws_engine_pool_flush(pool, ln.slot[k], g, cap, &m) != 0 || ws_engine_pool_detach(pool, ln.slot[k]) != 0) {
+            fail(w[0] + ": " + ws_engine_last_error());
+            ok = false;
+            return;
+          }
+          launches += ws_engine_info(engine, "n_launches");
+          memcpy(ln.out.data() + size_t(k) * ln.n + ln.done, g, size_t(std::min(m, ln.n - ln.done)) * 4);
+        }
+        ln.live = false;
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ln.t0).count();
+        if (!dry && (!wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk1.wav", ln.out.data(), ln.n, sample_rate, &err) ||
+                     !wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk2.wav", ln.out.data() + ln.n, ln.n, sample_rate, &err))) {
+          fail(err);
+          ok = false;
+          return;
+        }
+        if (!dry && raw_out) {
+          for (int k = 0; k < 2; ++k) {
+            FILE* f = fopen((out_dir + "/" + w[0] + "-spk" + std::to_string(k + 1) + ".f32").c_str(), "wb");
+            if (!f || fwrite(ln.out.data() + size_t(k) * ln.n, 4, ln.n, f) != size_t(ln.n)) fail("cannot write raw output");
+            if (f) fclose(f);
+          }
+        }
+        std::lock_guard<std::mutex> l(io_mu);
+        printf("process: %s RTF: %.4f (pool of %d lines: %lld pushes of %d samples, %lld bytes of stream state)%s\n", w[0].c_str(),
+               ms / (1000.0 * ln.n / sample_rate), pool_n, ln.pushes, stream_n, ws_engine_info(engine, "stream_state_bytes"),
+               dry ? " [dry run]" : "");
+        audio_ms += 1000.0 * ln.n / sample_rate;
+      };
+      for (Lane& ln : lanes)
+        if (ok) start(ln);
+      while (ok && !failed) {
+        std::vector<int> slots, ns, caps, n_out;
+        std::vector<const float*> chunks;
+        std::vector<float*> ests;
+        for (int a = 0; a < pool_n; ++a) {
+          Lane& ln = lanes[a];
+          if (!ln.live) continue;
+          const int c = std::min(stream_n, ln.n - ln.pos);
+          ln.chunk.resize(c);
+          for (int j = 0; j < c; ++j) ln.chunk[j] = static_cast<float>(ln.mix.samples[ln.pos + j]) / 32768.0f;
+          for (int k = 0; k < 2; ++k) {
+            slots.push_back(ln.slot[k]), ns.push_back(c), caps.push_back(cap);
+            chunks.push_back(ln.chunk.data()), ests.push_back(got[size_t(2) * a + k].data());
+          }
+        }
+        if (slots.empty()) break;
+        n_out.assign(slots.size(), 0);
+        if (ws_engine_pool_push(pool, static_cast<int>(slots.size()), slots.data(), chunks.data(), ns.data(), ests.data(), caps.data(),
+                                n_out.data()) != 0) {
+          fail(std::string("--stream_pool: ") + ws_engine_last_error());
+          ok = false;
+          break;
+        }
+        launches += ws_engine_info(engine, "n_launches"), ++rounds;
+        size_t row = 0;
+        for (int a = 0; a < pool_n && ok; ++a) {
+          Lane& ln = lanes[a];
+          if (!ln.live) continue;
+          for (int k = 0; k < 2; ++k, ++row)
+            memcpy(ln.out.data() + size_t(k) * ln.n + ln.done, ests[row], size_t(n_out[row]) * 4);
+          ln.done += n_out[row - 1], ln.pos += ns[row - 1], ++ln.pushes;
+          if (ln.pos >= ln.n) {
+            finish(ln, a);
+            if (ok) start(ln);
+          }
+        }
+      }
+      ws_engine_pool_close(pool);
+      if (ok) {
+        std::lock_guard<std::mutex> l(io_mu);
+        printf("pool: %lld rounds, %lld launches\n", rounds, launches);
+        total_audio_ms += audio_ms;
+        total_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pool_t0).count();
+      }
+      ws_engine_destroy(engine);
+      return;
     }
     // --batch N > 1: group g = lines [g N, g N + N) in one ragged forward, two rows per line
     for (size_t g = batch > 1 ? next++ : ngroups; g < ngroups && !failed; g = next++) {

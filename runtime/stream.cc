@@ -17,24 +17,54 @@ namespace {
 
 constexpr int kLmax = 160;     // the longest window of the MultiEncoder (encoder.py:66-114)
 
-struct StreamBlock {
-  const float *w1, *b1, *a1, *g1, *be1, *wd, *bd, *a2, *g2, *be2, *w3, *b3;
-  int ldw, dil, cap;
-  float* ring;                 // [rows][cap][H]
-  const float* rb;             // [rows][H] = W_e e + b for the stack's first block, else NULL
-};
-
 }  // namespace
 
-struct ws_stream {
+namespace wsrt {
+
+int refuse_not_streamable(const ws_engine* e, const char* who) {
+  if (e->arch != 1)
+    set_err("%s: this container holds arch %d; streaming is built for causal cLN Conv-TasNet / SpEx+ (arch 1)", who, e->arch);
+  else
+    set_err("%s: this Conv-TasNet container is %s with %s; streaming needs causal blocks with cLN (gLN takes "
+            "its statistics over the whole utterance, non-causal blocks look ahead)", who, e->tas.causal ? "causal" : "non-causal",
+            e->tas.norm == 1 ? "cLN" : "gLN");
+  return WS_ERR_INVALID;
+}
+
+void resolve_stream_weights(const ws_engine* e, StreamWeights* w) {
+  const TasNet& t = e->tas;
+  const char* enc[3] = {"encoder.encoder_1d_short.", "encoder.encoder_1d_middle.", "encoder.encoder_1d_long."};
+  for (int i = 0; i < 3; ++i) w->enc_w[i] = e->dev(std::string(enc[i]) + "weight"), w->enc_b[i] = e->dev(std::string(enc[i]) + "bias");
+  w->ln_g = e->dev("encoder.ln.weight"), w->ln_b = e->dev("encoder.ln.bias");
+  w->proj_w = e->dev("encoder.proj.weight"), w->proj_b = e->dev("encoder.proj.bias");
+  w->mask_w = e->dev("decoder.mask1.weight"), w->mask_b = e->dev("decoder.mask1.bias"), w->dec_b = e->dev("decoder.decoder_1d_1.bias");
+  w->blocks.clear();
+  for (int r = 0; r < t.R; ++r)
+    for (int k = 0; k < t.X; ++k) {
+      const bool fuse = k == 0;
+      const std::string pre = fuse ? "separation.separation." + std::to_string(2 * r) + "."
+                                   : "separation.separation." + std::to_string(2 * r + 1) + ".separation." + std::to_string(k - 1) + ".";
+      const std::string n1 = pre + (fuse ? "lnorm1." : "norm_1."), n2 = pre + (fuse ? "lnorm2." : "norm_2.");
+      const std::string dw = pre + (fuse ? "dconv." : "dwconv."), outc = pre + (fuse ? "sconv." : "Output.");
+      StreamBlock b;
+      b.w1 = e->dev(pre + "conv1x1.weight"), b.b1 = e->dev(pre + "conv1x1.bias"), b.ldw = fuse ? t.B + e->E : t.B;
+      b.a1 = e->dev(pre + (fuse ? "prelu1.weight" : "PReLU_1.weight")), b.a2 = e->dev(pre + (fuse ? "prelu2.weight" : "PReLU_2.weight"));
+      b.g1 = e->dev(n1 + "weight"), b.be1 = e->dev(n1 + "bias"), b.g2 = e->dev(n2 + "weight"), b.be2 = e->dev(n2 + "bias");
+      b.wd = e->dev(dw + "weight"), b.bd = e->dev(dw + "bias"), b.w3 = e->dev(outc + "weight"), b.b3 = e->dev(outc + "bias");
+      b.dil = 1 << k, b.cap = 0, b.ring = nullptr, b.rb = nullptr;
+      w->blocks.push_back(b);
+    }
+}
+
+}  // namespace wsrt
+
+struct ws_stream : wsrt::StreamWeights {
   ws_engine* e = nullptr;
   int rows = 0, G = 0, pcap = 0;        // pcap: floats per row of a pending buffer, G * s + 160 rounded up to 4
   char* state = nullptr;                // the one allocation
   size_t state_bytes = 0;
-  std::vector<StreamBlock> blocks;
   std::vector<float*> rb;               // per stack [rows][H]
   float *carry = nullptr, *carry0 = nullptr, *emb = nullptr, *pend[2] = {nullptr, nullptr};
-  const float *enc_w[3], *enc_b[3], *ln_g, *ln_b, *proj_w, *proj_b, *mask_w, *mask_b, *dec_b;
   int cur = 0, npend = 0;
   long long n = 0, k = 0;               // samples pushed, frames run
   bool done = false, failed = false;
@@ -192,16 +222,7 @@ WS_ENGINE_API int ws_engine_stream_open(ws_engine* e, int rows, const void* enro
   int rc = check_engine(e, "ws_engine_stream_open");
   if (rc != WS_OK) return rc;
   if (out) *out = nullptr;
-  if (!tas_streamable(e)) {
-    if (e->arch != 1)
-      set_err("ws_engine_stream_open: this container holds arch %d; streaming is built for causal cLN Conv-TasNet / SpEx+ (arch 1)",
-              e->arch);
-    else
-      set_err("ws_engine_stream_open: this Conv-TasNet container is %s with %s; streaming needs causal blocks with cLN (gLN takes "
-              "its statistics over the whole utterance, non-causal blocks look ahead)", e->tas.causal ? "causal" : "non-causal",
-              e->tas.norm == 1 ? "cLN" : "gLN");
-    return WS_ERR_INVALID;
-  }
+  if (!tas_streamable(e)) return refuse_not_streamable(e, "ws_engine_stream_open");
   if (!enroll || !out || rows < 1 || max_chunk_frames < 1 || max_chunk_frames > 65536) {
     set_err("ws_engine_stream_open: bad arguments (rows=%d, max_chunk_frames=%d in [1, 65536], enroll %s, out %s)", rows,
             max_chunk_frames, enroll ? "given" : "NULL", out ? "given" : "NULL");
@@ -257,25 +278,11 @@ WS_ENGINE_API int ws_engine_stream_open(ws_engine* e, int rows, const void* enro
   st->carry = at(si++), st->carry0 = at(si++), st->pend[0] = at(si++), st->pend[1] = at(si++), st->emb = at(si++);
   for (int r = 0; r < t.R; ++r) st->rb.push_back(at(si++));
   // ---- weights, resolved once ----
-  const char* enc[3] = {"encoder.encoder_1d_short.", "encoder.encoder_1d_middle.", "encoder.encoder_1d_long."};
-  for (int i = 0; i < 3; ++i) st->enc_w[i] = e->dev(std::string(enc[i]) + "weight"), st->enc_b[i] = e->dev(std::string(enc[i]) + "bias");
-  st->ln_g = e->dev("encoder.ln.weight"), st->ln_b = e->dev("encoder.ln.bias");
-  st->proj_w = e->dev("encoder.proj.weight"), st->proj_b = e->dev("encoder.proj.bias");
-  st->mask_w = e->dev("decoder.mask1.weight"), st->mask_b = e->dev("decoder.mask1.bias"), st->dec_b = e->dev("decoder.decoder_1d_1.bias");
+  resolve_stream_weights(e, st);
   for (int r = 0; r < t.R; ++r)
     for (int k = 0; k < t.X; ++k) {
-      const bool fuse = k == 0;
-      const std::string pre = fuse ? "separation.separation." + std::to_string(2 * r) + "."
-                                   : "separation.separation." + std::to_string(2 * r + 1) + ".separation." + std::to_string(k - 1) + ".";
-      const std::string n1 = pre + (fuse ? "lnorm1." : "norm_1."), n2 = pre + (fuse ? "lnorm2." : "norm_2.");
-      const std::string dw = pre + (fuse ? "dconv." : "dwconv."), outc = pre + (fuse ? "sconv." : "Output.");
-      StreamBlock b;
-      b.w1 = e->dev(pre + "conv1x1.weight"), b.b1 = e->dev(pre + "conv1x1.bias"), b.ldw = fuse ? B + e->E : B;
-      b.a1 = e->dev(pre + (fuse ? "prelu1.weight" : "PReLU_1.weight")), b.a2 = e->dev(pre + (fuse ? "prelu2.weight" : "PReLU_2.weight"));
-      b.g1 = e->dev(n1 + "weight"), b.be1 = e->dev(n1 + "bias"), b.g2 = e->dev(n2 + "weight"), b.be2 = e->dev(n2 + "bias");
-      b.wd = e->dev(dw + "weight"), b.bd = e->dev(dw + "bias"), b.w3 = e->dev(outc + "weight"), b.b3 = e->dev(outc + "bias");
-      b.dil = 1 << k, b.cap = (t.P - 1) * b.dil + G, b.ring = at(size_t(r) * t.X + k), b.rb = fuse ? st->rb[r] : nullptr;
-      st->blocks.push_back(b);
+      StreamBlock& b = st->blocks[size_t(r) * t.X + k];
+      b.cap = (t.P - 1) * b.dil + G, b.ring = at(size_t(r) * t.X + k), b.rb = k == 0 ? st->rb[r] : nullptr;
     }
   // ---- the speaker stage, once: embedding, SpeakerTransform, the stacks' row biases W_e e + b ----
   Arena& a = e->work;

@@ -310,6 +310,10 @@ _SIGS = {
     "ws_dwconv_stream_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _ll, _i, _p, _p, _p]),
     "ws_ola_stream_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "ws_tcn_mid_stream_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_float, _ll, _i, _p, _p, _p, _p]),
+    # stream pool: the two kernels above with per-row (slot, t0, tc) device tables
+    "ws_tcn_mid_stream_rows_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p, _i, _p, _p,
+                                        _p, _p]),
+    "ws_ola_stream_rows_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

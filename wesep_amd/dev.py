@@ -1709,6 +1709,51 @@ def tcn_mid_stream_fwd(c, rb, a1, gamma1, beta1, wd, bd, a2, R: int, Tc: int, H:
           float(eps), t0, ring.shape[1], _p(ring), _p(y2), _p(st2))
 
 
+def _chk_rows_tables(who, A: int, slot, t0, tc):
+    """The per-row device tables of a stream-pool launch: slot int32 [A], t0 int64 [A], tc int32 [A]."""
+    for n, t, dt in (("slot", slot, torch.int32), ("t0", t0, torch.int64), ("tc", tc, torch.int32)):
+        _chk(t, n, dt)
+        if t is not None and t.numel() < A:
+            raise L.WesepHipError(f"{who}: {n} holds {t.numel()} entries, the call needs {A}")
+
+
+def tcn_mid_stream_rows_fwd(c, rb, a1, gamma1, beta1, wd, bd, a2, A: int, Tc: int, H: int, P: int, dil: int, eps: float,
+                            slot, t0, tc, ring, y2, st2):
+    """tcn_mid_stream_fwd for A independent streams in one launch: c [A*Tc, H], rb [nslots, H] or None, ring
+    [nslots, cap, H]; row i is the stream in state slot slot[i] (int32 [A]), at first frame t0[i] (int64 [A]), with tc[i]
+    (int32 [A]) valid frames; frames behind tc[i] come out as zeros in y2 and (0, 1) in st2."""
+    for n, t in (("c", c), ("rb", rb), ("a1", a1), ("gamma1", gamma1), ("beta1", beta1), ("wd", wd), ("bd", bd), ("a2", a2),
+                 ("ring", ring), ("y2", y2), ("st2", st2)):
+        _chk(t, n)
+    _chk_rows_tables("ws_tcn_mid_stream_rows_fwd", A, slot, t0, tc)
+    if ring.dim() != 3 or ring.shape[2] != H:
+        raise L.WesepHipError(f"ws_tcn_mid_stream_rows_fwd: ring is {tuple(ring.shape)}, the call needs [nslots, cap, {H}]")
+    nslots = ring.shape[0]
+    _chk_room(c, A * Tc * H, "ws_tcn_mid_stream_rows_fwd", "c")
+    _chk_room(y2, A * Tc * H, "ws_tcn_mid_stream_rows_fwd", "y2")
+    _chk_room(st2, A * Tc * 2, "ws_tcn_mid_stream_rows_fwd", "st2")
+    if rb is not None:
+        _chk_room(rb, nslots * H, "ws_tcn_mid_stream_rows_fwd", "rb")
+    _call("ws_tcn_mid_stream_rows_fwd", _p(c), _p(rb), _p(a1), _p(gamma1), _p(beta1), _p(wd), _p(bd), _p(a2), A, Tc, H, P, dil,
+          float(eps), nslots, _p(slot), _p(t0), _p(tc), ring.shape[1], _p(ring), _p(y2), _p(st2))
+
+
+def ola_stream_rows_fwd(frames, bias, A: int, Tc: int, Lk: int, hop: int, slot, t0, tc, carry, est):
+    """ola_stream_fwd for A independent streams in one launch: frames [A*Tc, L] -> est [A, Tc*hop] (tc[i]*hop final samples,
+    zeros behind them); carry [nslots, L - hop] is updated at row slot[i] as after tc[i] frames.  Tables as for
+    tcn_mid_stream_rows_fwd."""
+    for n, t in (("frames", frames), ("bias", bias), ("carry", carry), ("est", est)):
+        _chk(t, n)
+    _chk_rows_tables("ws_ola_stream_rows_fwd", A, slot, t0, tc)
+    if carry is None or carry.dim() != 2 or carry.shape[1] != Lk - hop:
+        raise L.WesepHipError(f"ws_ola_stream_rows_fwd: carry is {None if carry is None else tuple(carry.shape)}, the call "
+                              f"needs [nslots, {Lk - hop}]")
+    _chk_room(frames, A * Tc * Lk, "ws_ola_stream_rows_fwd", "frames")
+    _chk_room(est, A * Tc * hop, "ws_ola_stream_rows_fwd", "est")
+    _call("ws_ola_stream_rows_fwd", _p(frames), _p(bias), A, Tc, Lk, hop, carry.shape[0], _p(slot), _p(t0), _p(tc), _p(carry),
+          _p(est))
+
+
 # ---- DPCCN pieces (conv2d.hip) --------------------------------------------------------------------------
 IN_EPS = 1e-5  # nn.InstanceNorm{1,2}d default
 

@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("WESEP_ENGINE_LIB") or os.path.join(
 SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", "ws_engine_destroy", "ws_engine_info",
            "ws_engine_separate", "ws_engine_separate_ragged", "ws_engine_forward_pcm16", "ws_engine_embed",
            "ws_engine_separate_long", "ws_engine_stream_open", "ws_engine_stream_push", "ws_engine_stream_flush",
-           "ws_engine_stream_reset", "ws_engine_stream_close")
+           "ws_engine_stream_reset", "ws_engine_stream_close", "ws_engine_pool_open", "ws_engine_pool_attach",
+           "ws_engine_pool_push", "ws_engine_pool_flush", "ws_engine_pool_detach", "ws_engine_pool_close")
 STREAM_FLUSH_CAP = 160  # WS_STREAM_FLUSH_CAP
 _lib = None
 
@@ -59,6 +60,19 @@ def lib():
         l.ws_engine_stream_reset.argtypes = [C.c_void_p]
         l.ws_engine_stream_close.restype = None
         l.ws_engine_stream_close.argtypes = [C.c_void_p]
+        l.ws_engine_pool_open.restype = C.c_int
+        l.ws_engine_pool_open.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        l.ws_engine_pool_attach.restype = C.c_int
+        l.ws_engine_pool_attach.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_pool_push.restype = C.c_int
+        l.ws_engine_pool_push.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+        l.ws_engine_pool_flush.restype = C.c_int
+        l.ws_engine_pool_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_pool_detach.restype = C.c_int
+        l.ws_engine_pool_detach.argtypes = [C.c_void_p, C.c_int]
+        l.ws_engine_pool_close.restype = None
+        l.ws_engine_pool_close.argtypes = [C.c_void_p]
         if l.ws_engine_abi_version() != ENGINE_ABI_VERSION:
             raise WesepHipError("libwesep_engine.so ABI version mismatch; rebuild")
         _lib = l
@@ -225,6 +239,12 @@ class Engine:
         separate(); the speaker stage runs once, here.  Close the stream before the engine."""
         return EngineStream(self, rows, enroll, kind, max_chunk_frames)
 
+    def stream_pool(self, slots, max_chunk_frames=64):
+        """A pool of `slots` independent streams on a causal cLN Conv-TasNet / SpEx+ container: each slot at its own
+        position, packets of any size, one launch chain per push whatever the number of slots in it.  Close the pool before
+        the engine."""
+        return StreamPool(self, slots, max_chunk_frames)
+
     def forward_pcm16(self, mix, spk1, spk2):
         """int16 [n], int16 [n_enroll] x 2 -> float32 [2, n] in [-1, 1] (SeparateEngine::ForwardFunc)."""
         mix, spk1, spk2 = (np.ascontiguousarray(x, dtype=np.int16) for x in (mix, spk1, spk2))
@@ -286,6 +306,73 @@ class EngineStream:
     def close(self):
         if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
             _lib.ws_engine_stream_close(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+def pool_group_launches(R, X):
+    """WS_POOL_GROUP_LAUNCHES: entry-point calls of one group of a pool push, whatever the number of slots in it."""
+    return 3 * R * X + 9
+
+
+class StreamPool:
+    """ws_engine_pool_* (include/wesep_engine.h): many independent streams through one launch chain per push.  Every slot
+    is a stream of one row: the concatenation of what its pushes and its flush return is the model-output part of
+    Engine.separate's row on that slot's audio, whatever the other slots were fed in the meantime."""
+
+    def __init__(self, engine, slots, max_chunk_frames=64):
+        self._h, self._engine, self.slots = C.c_void_p(), engine, int(slots)    # (the engine must outlive the pool)
+        _quiesce_torch()
+        _check(lib().ws_engine_pool_open(engine._h, self.slots, int(max_chunk_frames), C.byref(self._h)), "ws_engine_pool_open")
+        self._L = engine.info("L")
+
+    def attach(self, enroll, kind):
+        """One enrollment -- [E] (ENROLL_EMBEDDING / ENROLL_SPEAKER) or [Tw] (ENROLL_WAVE) -- -> the slot it took.  The
+        speaker stage runs here, once."""
+        enroll = np.ascontiguousarray(enroll, dtype=np.float32).reshape(-1)
+        length = 0 if kind in (ENROLL_EMBEDDING, ENROLL_SPEAKER) else enroll.shape[0]
+        slot = C.c_int(-1)
+        _quiesce_torch()
+        _check(lib().ws_engine_pool_attach(self._h, enroll.ctypes.data, kind, length, C.byref(slot)), "ws_engine_pool_attach")
+        return slot.value
+
+    def push(self, chunks, est_cap=None):
+        """{slot: chunk [n_slot >= 1]} -> {slot: float32 [m_slot]}, the samples of each slot that became final (m = 0 while no
+        frame is complete).  est_cap: {slot: samples the output buffer holds} (default: what always suffices)."""
+        ids = list(chunks)
+        data = [np.ascontiguousarray(chunks[i], dtype=np.float32).reshape(-1) for i in ids]
+        n = np.array([x.shape[0] for x in data], dtype=np.int32)
+        caps = np.array([stream_push_cap(int(k), self._L) if est_cap is None else int(est_cap[i]) for i, k in zip(ids, n)],
+                        dtype=np.int32)
+        bufs = [np.zeros(max(int(c), 1), dtype=np.float32) for c in caps]
+        A = len(ids)
+        slots, m = np.array(ids, dtype=np.int32), np.zeros(max(A, 1), dtype=np.int32)
+        cp = (C.c_void_p * max(A, 1))(*[x.ctypes.data for x in data])
+        ep = (C.c_void_p * max(A, 1))(*[b.ctypes.data for b in bufs])
+        _quiesce_torch()
+        _check(lib().ws_engine_pool_push(self._h, A, slots.ctypes.data, C.cast(cp, C.c_void_p), n.ctypes.data,
+                                         C.cast(ep, C.c_void_p), caps.ctypes.data, m.ctypes.data), "ws_engine_pool_push")
+        return {i: b[:int(k)].copy() for i, b, k in zip(ids, bufs, m)}
+
+    def flush(self, slot, est_cap=STREAM_FLUSH_CAP):
+        """The end of one slot's stream: its remaining frames on the zero-extended pending samples, then the overlap-add carry."""
+        buf, m = np.zeros(max(int(est_cap), 1), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_pool_flush(self._h, int(slot), buf.ctypes.data, int(est_cap), C.byref(m)), "ws_engine_pool_flush")
+        return buf[:m.value].copy()
+
+    def detach(self, slot):
+        """Frees the slot for the next attach."""
+        _check(lib().ws_engine_pool_detach(self._h, int(slot)), "ws_engine_pool_detach")
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
+            _lib.ws_engine_pool_close(self._h)
         self._h = None
 
     def __del__(self):
