@@ -205,6 +205,23 @@ void ws_engine_stream_close(ws_stream* s);
 #define WS_POOL_GROUP_LAUNCHES(R, X) (3 * (R) * (X) + 9)
 typedef struct ws_pool ws_pool;
 int ws_engine_pool_open(ws_engine* e, int slots, int max_chunk_frames, ws_pool** out);
+/* The whole block as one call (new symbols, engine ABI 2 unchanged).  ws_engine_stream_open_ex / ws_engine_pool_open_ex are
+ * the two opens above with a `flags` word; flags = 0 IS the plain open (which calls the _ex form with 0), an unknown bit is
+ * WS_ERR_INVALID by name.  WS_STREAM_BLOCK_KERNEL: every block of a group is ONE entry-point call, ws_tcn_block_stream_fwd
+ * (stream) or ws_tcn_block_stream_rows_fwd (pool), in place of GEMM, fused middle, GEMM: a group is framing GEMMs, row
+ * statistics, projection, one call per block, mask GEMM, mask product, synthesis GEMM, overlap-add (and the pending copy of
+ * the solo stream) -- WS_STREAM_BLOCK_GROUP_LAUNCHES(R, X) = R X + 10 and WS_POOL_BLOCK_GROUP_LAUNCHES(R, X) = R X + 9
+ * entry-point calls.  The block kernel reduces every frame's products in one fixed order wherever the frame sits, so the
+ * separator's part of a flagged stream does not depend on the packet sizes, nor a flagged pool slot's on its neighbours.
+ * State layout, "stream_state_bytes", push, flush, reset, attach, detach, the one synchronisation per push, the dry run and
+ * every refusal are those of the plain opens.  Containers with B above WS_TCN_BLOCK_MAXB or H above WS_TCN_BLOCK_MAXH
+ * (wesep_hip.h) are refused by the kernel at the first push. */
+#define WS_STREAM_BLOCK_KERNEL 1
+#define WS_STREAM_BLOCK_GROUP_LAUNCHES(R, X) ((R) * (X) + 10)
+#define WS_POOL_BLOCK_GROUP_LAUNCHES(R, X) ((R) * (X) + 9)
+int ws_engine_stream_open_ex(ws_engine* e, int rows, const void* enroll, int enroll_kind, int enroll_len, int max_chunk_frames,
+                             unsigned flags, ws_stream** out);
+int ws_engine_pool_open_ex(ws_engine* e, int slots, int max_chunk_frames, unsigned flags, ws_pool** out);
 int ws_engine_pool_attach(ws_pool* p, const void* enroll, int enroll_kind, int enroll_len, int* slot);
 int ws_engine_pool_push(ws_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n, float* const* est,
                         const int* est_cap, int* n_out);

@@ -1215,6 +1215,52 @@ int ws_tcn_mid_stream_rows_fwd(const float* c, const float* rb, const float* a1,
 int ws_ola_stream_rows_fwd(const float* frames, const float* bias, int A, int Tc, int L, int hop, int nslots,
                            const int* slot, const long long* t0, const int* tc, float* carry, float* est, void* stream);
 
+/* ---- the whole block (stream_block.hip; DESIGN section 7, "The whole block") -- new symbols, ABI 20 unchanged ---------------
+ *   ws_tcn_block_stream_fwd  a whole causal cLN block on one chunk in ONE launch, in place of ws_gemm_nt, ws_tcn_mid_stream_fwd
+ *                   and ws_gemm_nt.  x [R][Tc][B] is the block input for the frames t0 .. t0 + Tc - 1, W1 [H][ldw1] is read in
+ *                   its first B columns only (the concatConv block passes ldw1 = B + E; its embedding half is the row bias
+ *                   rb [R][H]), W2 is [B][H], ring [R][cap][H] as for ws_tcn_mid_stream_fwd.  For row r, chunk frame t with
+ *                   absolute index a = t0 + t:
+ *                     c   = W1[:, :B] . x[r][t] + (rb ? rb[r] : b1)
+ *                     y1  = prelu(c, a1[0]);  (m1, s1) = mean, 1 / sqrt(biased var + eps) of y1 over H   (two passes)
+ *                     xn(a) = (y1 - m1) * s1 * gamma1 + beta1              -> ring[r][a % cap][:]
+ *                     z   = bd + sum_p wd[ch][p] * xn(a - (P - 1 - p) * dil),  ascending p, the tap rules of
+ *                           ws_dwconv_stream_fwd (a' < 0: no term and no read; 0 <= a' < t0: ring slot a' % cap; a' >= t0: a
+ *                           chunk frame, never taken from a ring slot that another workgroup of the launch writes)
+ *                     y2  = prelu(z, a2[0]);  (m2, s2) of y2 over H
+ *                     out[r][t] = x[r][t] + (b2 + W2 . ((y2 - m2) * s2 * gamma2 + beta2))
+ *                   One workgroup per row walks the row's frames in tiles of 8, in order; a weight pass is shared by a
+ *                   tile's frames; a tap before the tile is read from the ring, which holds what an earlier launch or this
+ *                   same workgroup wrote.  Each dot product of a frame is one fp32 accumulator started at 0 and advanced by
+ *                   fmaf in ascending k, the bias added last; statistics are reduced per thread (channels i, i + 256, ...),
+ *                   per wave, then over the four waves in ascending order.  So out[r][t] and the ring slot a frame leaves are
+ *                   the same BITS under any chunking of the sequence (one chunk with all of it included), any position of the
+ *                   frame in a chunk or tile, any R and whatever the other rows hold, and from run to run.  No atomics,
+ *                   nothing waits on another workgroup.  Contract: cap >= (P - 1) * dil + Tc.  out may not overlap x; x, the
+ *                   weights and rb are read only.  WS_ERR_INVALID before any launch: a NULL pointer other than rb and b1
+ *                   (exactly one of the two must be given), B % 4, H % 4 or ldw1 % 4 non-zero, ldw1 < B, H above
+ *                   WS_TCN_BLOCK_MAXH or B above WS_TCN_BLOCK_MAXB (8 (B + H) + 4192 floats of LDS per workgroup), P not odd
+ *                   or above 7, dil < 1, t0 < 0, cap below the bound, out overlapping x.
+ *   ws_tcn_block_stream_rows_fwd  the same for the rows of a stream pool, with the three device tables and the exact
+ *                   semantics of ws_tcn_mid_stream_rows_fwd: x [A][Tc][B], rb [nslots][H] (read at slot[i]) or NULL, ring
+ *                   [nslots][cap][H], out [A][Tc][B].  One workgroup per row i runs the solo form's body (one shared inline
+ *                   function) on (tc[i], t0[i], rb and ring row slot[i]): a valid frame and the ring slot it leaves are bit
+ *                   for bit those of ws_tcn_block_stream_fwd(R = 1, Tc = tc[i], t0 = t0[i]).  An out-of-range slot or a
+ *                   negative t0 is treated as tc[i] = 0, tc is clamped to [0, Tc]; frames t >= tc[i] write exact zeros to
+ *                   out and touch no state; x behind tc[i] is never read (NaN there reaches nothing).  WS_ERR_INVALID before
+ *                   any launch: as above (no t0 argument), and A < 1, nslots < 1, a NULL table. */
+#define WS_TCN_BLOCK_MAXH 768
+#define WS_TCN_BLOCK_MAXB 512
+int ws_tcn_block_stream_fwd(const float* x, const float* rb, const float* W1, int ldw1, const float* b1, const float* a1,
+                            const float* gamma1, const float* beta1, const float* wd, const float* bd, const float* a2,
+                            const float* gamma2, const float* beta2, const float* W2, const float* b2, int R, int Tc, int B,
+                            int H, int P, int dil, float eps, long long t0, int cap, float* ring, float* out, void* stream);
+int ws_tcn_block_stream_rows_fwd(const float* x, const float* rb, const float* W1, int ldw1, const float* b1, const float* a1,
+                                 const float* gamma1, const float* beta1, const float* wd, const float* bd, const float* a2,
+                                 const float* gamma2, const float* beta2, const float* W2, const float* b2, int A, int Tc,
+                                 int B, int H, int P, int dil, float eps, int nslots, const int* slot, const long long* t0,
+                                 const int* tc, int cap, float* ring, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

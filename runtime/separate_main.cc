@@ -3,7 +3,7 @@
 //
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
 //                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
-//                 [--stream_ms 10 [--stream_pool 4]]
+//                 [--stream_ms 10 [--stream_pool 4] [--stream_block]]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -35,6 +35,9 @@
 // and a line that ends is flushed, its slots detached and re-attached to the next line, while the others are in mid-stream.
 // Output names and formats are those of --stream_ms alone.  --stream_pool without --stream_ms, or together with --batch N > 1
 // or --chunk_seconds, is refused.
+// --stream_block (with --stream_ms, alone or with --stream_pool): the streams are opened with WS_STREAM_BLOCK_KERNEL -- every
+// block of the separator is one call, and a line's samples do not depend on the packet size or on the lines beside it.
+// Refused without --stream_ms.
 // --dry_run validates the model file and the launch plan of every utterance without a GPU and writes nothing.
 // --raw_out additionally writes the unquantised estimates as <key>-spk{1,2}.f32 (float32, for parity checks).
 #include <stdio.h>
@@ -139,10 +142,13 @@ int main(int argc, char** argv) {
   const int stream_n = static_cast<int>(stream_ms * sample_rate / 1000.0 + 0.5);
   const bool pooled = args.has("stream_pool");
   const int pool_n = atoi(args.get("stream_pool", "0").c_str());
+  const bool stream_block = args.has("stream_block");
+  const unsigned stream_flags = stream_block ? WS_STREAM_BLOCK_KERNEL : 0u;
   if (args.has("help")) {
     printf("usage: separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1]\n"
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
-           "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]] [--stream_ms M [--stream_pool N]]\n"
+           "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]]\n"
+           "                     [--stream_ms M [--stream_pool N] [--stream_block]]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
@@ -154,7 +160,9 @@ int main(int argc, char** argv) {
            "  --stream_ms M      causal cLN Conv-TasNet / SpEx+ models: feed every line to a stream in chunks of M ms; same\n"
            "                     files as the plain run.  Not together with --batch N > 1 or --chunk_seconds\n"
            "  --stream_pool N    with --stream_ms M: N consecutive lines at a time through one stream pool, one push per round\n"
-           "                     of M ms packets; same files as --stream_ms alone\n");
+           "                     of M ms packets; same files as --stream_ms alone\n"
+           "  --stream_block     with --stream_ms M: every block of the separator as one call (WS_STREAM_BLOCK_KERNEL); the\n"
+           "                     samples of a line then do not depend on the packet size or on the other lines of a pool\n");
     return 0;
   }
   if (chunked && batch > 1) return die("--chunk_seconds and --batch " + std::to_string(batch) + " conflict: a batch is a rectangle of "
@@ -163,6 +171,7 @@ int main(int argc, char** argv) {
   if (pooled && (batch > 1 || chunked))
     return die("--stream_pool conflicts with --batch N > 1 and --chunk_seconds: the pool's lines are streams, each fed as it arrives");
   if (pooled && pool_n < 1) return die("--stream_pool needs a positive number of lines");
+  if (stream_block && !streamed) return die("--stream_block needs --stream_ms M: it selects the block kernel of a stream or a stream pool");
   if (streamed && (batch > 1 || chunked))
     return die("--stream_ms conflicts with --batch N > 1 and --chunk_seconds: a stream takes one recording as it arrives");
   if (streamed && stream_n < 1) return die("--stream_ms needs a positive chunk length");
@@ -220,7 +229,7 @@ int main(int argc, char** argv) {
       const int L = static_cast<int>(ws_engine_info(engine, "L"));
       const int cap = std::max(WS_STREAM_PUSH_CAP(stream_n, L), WS_STREAM_FLUSH_CAP);
       ws_pool* pool = nullptr;
-      if (ws_engine_pool_open(engine, 2 * pool_n, 64, &pool) != 0) {
+      if (ws_engine_pool_open_ex(engine, 2 * pool_n, 64, stream_flags, &pool) != 0) {
         fail(std::string("--stream_pool: ") + ws_engine_last_error());
         ws_engine_destroy(engine);
         return;
@@ -453,7 +462,7 @@ int main(int argc, char** argv) {
         const int cap = std::max(WS_STREAM_PUSH_CAP(stream_n, L), WS_STREAM_FLUSH_CAP);
         got.resize(size_t(2) * cap);
         ws_stream* st = nullptr;
-        rc = ws_engine_stream_open(engine, 2, enr.data(), WS_ENROLL_WAVE, n_enroll, 64, &st);
+        rc = ws_engine_stream_open_ex(engine, 2, enr.data(), WS_ENROLL_WAVE, n_enroll, 64, stream_flags, &st);
         int done = 0;
         auto take = [&](int m) {                                        // est [2][m] behind what came before
           for (int k = 0; k < 2; ++k) memcpy(out.data() + size_t(k) * n + done, got.data() + size_t(k) * m, size_t(m) * 4);

@@ -7,7 +7,8 @@
 // from the engine's work arena under mark / release.  Every weight pointer is resolved once, at open.
 // Per group of at most max_chunk_frames frames: 3 framing GEMMs, row statistics, projection; per block GEMM, the fused
 // middle, GEMM; mask GEMM, mask product, synthesis GEMM, overlap-add; the copy that moves the unconsumed pending samples
-// to the other buffer -- 3 R X + 10 entry-point calls (WS_STREAM_GROUP_LAUNCHES).
+// to the other buffer -- 3 R X + 10 entry-point calls (WS_STREAM_GROUP_LAUNCHES).  A stream opened with
+// WS_STREAM_BLOCK_KERNEL runs every block as ONE call, ws_tcn_block_stream_fwd: R X + 10 (WS_STREAM_BLOCK_GROUP_LAUNCHES).
 // =================================================================================================================
 #include "engine_internal.h"
 
@@ -68,6 +69,7 @@ struct ws_stream : wsrt::StreamWeights {
   int cur = 0, npend = 0;
   long long n = 0, k = 0;               // samples pushed, frames run
   bool done = false, failed = false;
+  bool block_kernel = false;            // WS_STREAM_BLOCK_KERNEL: one call per block
 };
 
 namespace {
@@ -135,6 +137,12 @@ int run_group(ws_stream* st, int Tc, float* host_est, int host_pitch, int col) {
   }
   float *x = xa, *other = xb;
   for (const StreamBlock& b : st->blocks) {
+    if (st->block_kernel) {
+      WS_RUN(e, ws_tcn_block_stream_fwd(x, b.rb, b.w1, b.ldw, b.rb ? nullptr : b.b1, b.a1, b.g1, b.be1, b.wd, b.bd, b.a2, b.g2, b.be2,
+                                        b.w3, b.b3, R, Tc, B, H, P, b.dil, kLnEps, st->k, b.cap, b.ring, other, q));
+      std::swap(x, other);
+      continue;
+    }
     TasGemm g;
     g.A = x, g.lda = B, g.M = M, g.K = B, g.W = b.w1, g.ldw = b.ldw, g.N = H, g.bias = b.rb ? nullptr : b.b1, g.C = c, g.ldc = H;
     if ((rc = tas_gemm(e, g)) != WS_OK) return rc;
@@ -219,10 +227,19 @@ void free_stream(ws_stream* s) {
 
 WS_ENGINE_API int ws_engine_stream_open(ws_engine* e, int rows, const void* enroll, int enroll_kind, int enroll_len,
                                         int max_chunk_frames, ws_stream** out) {
+  return ws_engine_stream_open_ex(e, rows, enroll, enroll_kind, enroll_len, max_chunk_frames, 0, out);
+}
+
+WS_ENGINE_API int ws_engine_stream_open_ex(ws_engine* e, int rows, const void* enroll, int enroll_kind, int enroll_len,
+                                           int max_chunk_frames, unsigned flags, ws_stream** out) {
   int rc = check_engine(e, "ws_engine_stream_open");
   if (rc != WS_OK) return rc;
   if (out) *out = nullptr;
   if (!tas_streamable(e)) return refuse_not_streamable(e, "ws_engine_stream_open");
+  if (flags & ~unsigned(WS_STREAM_BLOCK_KERNEL)) {
+    set_err("ws_engine_stream_open_ex: unknown flag bits 0x%x (known: WS_STREAM_BLOCK_KERNEL = 1)", flags & ~unsigned(WS_STREAM_BLOCK_KERNEL));
+    return WS_ERR_INVALID;
+  }
   if (!enroll || !out || rows < 1 || max_chunk_frames < 1 || max_chunk_frames > 65536) {
     set_err("ws_engine_stream_open: bad arguments (rows=%d, max_chunk_frames=%d in [1, 65536], enroll %s, out %s)", rows,
             max_chunk_frames, enroll ? "given" : "NULL", out ? "given" : "NULL");
@@ -241,6 +258,7 @@ WS_ENGINE_API int ws_engine_stream_open(ws_engine* e, int rows, const void* enro
   e->n_launches = 0;
   ws_stream* st = new ws_stream();
   st->e = e, st->rows = rows, st->G = G, st->pcap = (G * s + kLmax + 3) / 4 * 4;
+  st->block_kernel = (flags & WS_STREAM_BLOCK_KERNEL) != 0;
   // ---- the state block: rings, carry (+ its reset image), two pending buffers, embedding, row biases; 256-byte slots ----
   const int nblocks = t.R * t.X;
   std::vector<size_t> off;

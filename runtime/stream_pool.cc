@@ -10,7 +10,9 @@
 // SpeakerTransform and the stacks' row biases; one carry reset image.  The samples that have not completed a frame live on
 // the HOST, per slot: a group's staging block is built there and uploaded once, so there is no pending-sample copy on the
 // device.  Per group: 3 framing GEMMs, row statistics, projection; per block GEMM, the fused middle, GEMM; mask GEMM, mask
-// product, synthesis GEMM, overlap-add -- 3 R X + 9 entry-point calls (WS_POOL_GROUP_LAUNCHES), whatever A is.
+// product, synthesis GEMM, overlap-add -- 3 R X + 9 entry-point calls (WS_POOL_GROUP_LAUNCHES), whatever A is.  A pool opened
+// with WS_STREAM_BLOCK_KERNEL runs every block as ONE call, ws_tcn_block_stream_rows_fwd: R X + 9
+// (WS_POOL_BLOCK_GROUP_LAUNCHES); a slot's samples are then the same bits whatever else shares its rectangle.
 // =================================================================================================================
 #include "engine_internal.h"
 
@@ -45,6 +47,7 @@ struct ws_pool : wsrt::StreamWeights {
   float *carry = nullptr, *carry0 = nullptr, *emb = nullptr;     // [nslots][L - s], [L - s], [nslots][E]
   std::vector<PoolSlot> slots;
   std::vector<PoolGroup> groups;        // of the call in hand
+  bool block_kernel = false;            // WS_STREAM_BLOCK_KERNEL: one call per block
 };
 
 namespace {
@@ -130,6 +133,13 @@ int run_group(ws_pool* p, PoolGroup& g) {
   }
   float *x = xa, *other = xb;
   for (const StreamBlock& b : p->blocks) {
+    if (p->block_kernel) {
+      WS_RUN(e, ws_tcn_block_stream_rows_fwd(x, b.rb, b.w1, b.ldw, b.rb ? nullptr : b.b1, b.a1, b.g1, b.be1, b.wd, b.bd, b.a2, b.g2,
+                                             b.be2, b.w3, b.b3, A, Tc, B, H, P, b.dil, kLnEps, p->nslots, d_slot, d_t0, d_tc, b.cap,
+                                             b.ring, other, q));
+      std::swap(x, other);
+      continue;
+    }
     TasGemm gm;
     gm.A = x, gm.lda = B, gm.M = M, gm.K = B, gm.W = b.w1, gm.ldw = b.ldw, gm.N = H, gm.bias = b.rb ? nullptr : b.b1, gm.C = c, gm.ldc = H;
     if ((rc = tas_gemm(e, gm)) != WS_OK) return rc;
@@ -210,10 +220,18 @@ void free_pool(ws_pool* p) {
 }  // namespace
 
 WS_ENGINE_API int ws_engine_pool_open(ws_engine* e, int slots, int max_chunk_frames, ws_pool** out) {
+  return ws_engine_pool_open_ex(e, slots, max_chunk_frames, 0, out);
+}
+
+WS_ENGINE_API int ws_engine_pool_open_ex(ws_engine* e, int slots, int max_chunk_frames, unsigned flags, ws_pool** out) {
   int rc = check_engine(e, "ws_engine_pool_open");
   if (rc != WS_OK) return rc;
   if (out) *out = nullptr;
   if (!tas_streamable(e)) return refuse_not_streamable(e, "ws_engine_pool_open");
+  if (flags & ~unsigned(WS_STREAM_BLOCK_KERNEL)) {
+    set_err("ws_engine_pool_open_ex: unknown flag bits 0x%x (known: WS_STREAM_BLOCK_KERNEL = 1)", flags & ~unsigned(WS_STREAM_BLOCK_KERNEL));
+    return WS_ERR_INVALID;
+  }
   if (!out) {
     set_err("ws_engine_pool_open: out is NULL");
     return WS_ERR_INVALID;
@@ -237,7 +255,7 @@ WS_ENGINE_API int ws_engine_pool_open(ws_engine* e, int slots, int max_chunk_fra
   e->long_windows = e->long_forwards = 0;
   e->n_launches = 0;
   ws_pool* p = new ws_pool();
-  p->e = e, p->nslots = slots, p->G = G;
+  p->e = e, p->nslots = slots, p->G = G, p->block_kernel = (flags & WS_STREAM_BLOCK_KERNEL) != 0;
   p->slots.resize(slots);
   // ---- the state block: rings, carry, its reset image, embedding, row biases; 256-byte aligned parts ----
   const int nblocks = t.R * t.X;

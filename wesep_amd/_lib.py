@@ -314,6 +314,10 @@ _SIGS = {
     "ws_tcn_mid_stream_rows_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p, _i, _p, _p,
                                         _p, _p]),
     "ws_ola_stream_rows_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    # the whole causal cLN block in one launch (stream_block.hip): solo and pool rows
+    "ws_tcn_block_stream_fwd": (_i, [_p, _p, _p, _i] + [_p] * 11 + [_i, _i, _i, _i, _i, _i, C.c_float, _ll, _i, _p, _p, _p]),
+    "ws_tcn_block_stream_rows_fwd": (_i, [_p, _p, _p, _i] + [_p] * 11 + [_i, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p, _i,
+                                          _p, _p, _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

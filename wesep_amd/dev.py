@@ -1738,6 +1738,59 @@ def tcn_mid_stream_rows_fwd(c, rb, a1, gamma1, beta1, wd, bd, a2, A: int, Tc: in
           float(eps), nslots, _p(slot), _p(t0), _p(tc), ring.shape[1], _p(ring), _p(y2), _p(st2))
 
 
+def _chk_block_stream(who, rows, x, rb, W1, b1, a1, gamma1, beta1, wd, bd, a2, gamma2, beta2, W2, b2, Tc, B, H, P, ring, out):
+    """Host-side checks shared by the two whole-block wrappers; rows: the rows of x / out.  Returns ldw1."""
+    for n, t in (("x", x), ("rb", rb), ("W1", W1), ("b1", b1), ("a1", a1), ("gamma1", gamma1), ("beta1", beta1), ("wd", wd),
+                 ("bd", bd), ("a2", a2), ("gamma2", gamma2), ("beta2", beta2), ("W2", W2), ("b2", b2), ("ring", ring),
+                 ("out", out)):
+        _chk(t, n)
+    if (rb is None) == (b1 is None):
+        raise L.WesepHipError(f"{who}: exactly one of rb (the row bias) and b1 must be given")
+    if W1 is None or W1.dim() != 2 or W1.shape[0] != H or W1.shape[1] < B:
+        raise L.WesepHipError(f"{who}: W1 is {None if W1 is None else tuple(W1.shape)}, the call needs [{H}, ldw1 >= {B}]")
+    if ring is None or ring.dim() != 3 or ring.shape[2] != H:
+        raise L.WesepHipError(f"{who}: ring is {None if ring is None else tuple(ring.shape)}, the call needs [rows, cap, {H}]")
+    _chk_room(x, rows * Tc * B, who, "x")
+    _chk_room(out, rows * Tc * B, who, "out")
+    _chk_room(W2, B * H, who, "W2")
+    _chk_room(wd, H * P, who, "wd")
+    for n, t, need in (("b1", b1, H), ("gamma1", gamma1, H), ("beta1", beta1, H), ("bd", bd, H), ("gamma2", gamma2, H),
+                       ("beta2", beta2, H), ("b2", b2, B), ("a1", a1, 1), ("a2", a2, 1)):
+        if t is not None:
+            _chk_room(t, need, who, n)
+    return W1.shape[1]
+
+
+def tcn_block_stream_fwd(x, rb, W1, b1, a1, gamma1, beta1, wd, bd, a2, gamma2, beta2, W2, b2, R: int, Tc: int, B: int, H: int,
+                         P: int, dil: int, eps: float, t0: int, ring, out):
+    """A whole causal cLN block on one chunk in ONE launch (GEMM, tcn_mid_stream_fwd, GEMM + residual): x [R*Tc, B] (read
+    only) -> out [R*Tc, B]; W1 [H, ldw1 >= B] is read in its first B columns, exactly one of rb [R, H] and b1 [H] is
+    given; W2 [B, H]; ring [R, cap, H] as for tcn_mid_stream_fwd.  A frame's output bits do not depend on the chunking."""
+    who = "ws_tcn_block_stream_fwd"
+    ldw1 = _chk_block_stream(who, R, x, rb, W1, b1, a1, gamma1, beta1, wd, bd, a2, gamma2, beta2, W2, b2, Tc, B, H, P, ring, out)
+    if ring.shape[0] != R:
+        raise L.WesepHipError(f"{who}: ring is {tuple(ring.shape)}, the call needs [{R}, cap, {H}]")
+    if rb is not None:
+        _chk_room(rb, R * H, who, "rb")
+    _call(who, _p(x), _p(rb), _p(W1), ldw1, _p(b1), _p(a1), _p(gamma1), _p(beta1), _p(wd), _p(bd), _p(a2), _p(gamma2),
+          _p(beta2), _p(W2), _p(b2), R, Tc, B, H, P, dil, float(eps), t0, ring.shape[1], _p(ring), _p(out))
+
+
+def tcn_block_stream_rows_fwd(x, rb, W1, b1, a1, gamma1, beta1, wd, bd, a2, gamma2, beta2, W2, b2, A: int, Tc: int, B: int,
+                              H: int, P: int, dil: int, eps: float, slot, t0, tc, ring, out):
+    """tcn_block_stream_fwd for A independent streams in one launch: x [A*Tc, B], rb [nslots, H] or None, ring
+    [nslots, cap, H]; tables as for tcn_mid_stream_rows_fwd; frames behind tc[i] come out as zeros."""
+    who = "ws_tcn_block_stream_rows_fwd"
+    ldw1 = _chk_block_stream(who, A, x, rb, W1, b1, a1, gamma1, beta1, wd, bd, a2, gamma2, beta2, W2, b2, Tc, B, H, P, ring, out)
+    _chk_rows_tables(who, A, slot, t0, tc)
+    nslots = ring.shape[0]
+    if rb is not None:
+        _chk_room(rb, nslots * H, who, "rb")
+    _call(who, _p(x), _p(rb), _p(W1), ldw1, _p(b1), _p(a1), _p(gamma1), _p(beta1), _p(wd), _p(bd), _p(a2), _p(gamma2),
+          _p(beta2), _p(W2), _p(b2), A, Tc, B, H, P, dil, float(eps), nslots, _p(slot), _p(t0), _p(tc), ring.shape[1],
+          _p(ring), _p(out))
+
+
 def ola_stream_rows_fwd(frames, bias, A: int, Tc: int, Lk: int, hop: int, slot, t0, tc, carry, est):
     """ola_stream_fwd for A independent streams in one launch: frames [A*Tc, L] -> est [A, Tc*hop] (tc[i]*hop final samples,
     zeros behind them); carry [nslots, L - hop] is updated at row slot[i] as after tc[i] frames.  Tables as for

@@ -17,8 +17,10 @@ SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", 
            "ws_engine_separate", "ws_engine_separate_ragged", "ws_engine_forward_pcm16", "ws_engine_embed",
            "ws_engine_separate_long", "ws_engine_stream_open", "ws_engine_stream_push", "ws_engine_stream_flush",
            "ws_engine_stream_reset", "ws_engine_stream_close", "ws_engine_pool_open", "ws_engine_pool_attach",
-           "ws_engine_pool_push", "ws_engine_pool_flush", "ws_engine_pool_detach", "ws_engine_pool_close")
+           "ws_engine_pool_push", "ws_engine_pool_flush", "ws_engine_pool_detach", "ws_engine_pool_close",
+           "ws_engine_stream_open_ex", "ws_engine_pool_open_ex")
 STREAM_FLUSH_CAP = 160  # WS_STREAM_FLUSH_CAP
+STREAM_BLOCK_KERNEL = 1  # WS_STREAM_BLOCK_KERNEL: every block of a stream / pool group as one entry-point call
 _lib = None
 
 
@@ -71,6 +73,11 @@ def lib():
         l.ws_engine_pool_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         l.ws_engine_pool_detach.restype = C.c_int
         l.ws_engine_pool_detach.argtypes = [C.c_void_p, C.c_int]
+        l.ws_engine_stream_open_ex.restype = C.c_int
+        l.ws_engine_stream_open_ex.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint,
+                                               C.POINTER(C.c_void_p)]
+        l.ws_engine_pool_open_ex.restype = C.c_int
+        l.ws_engine_pool_open_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_void_p)]
         l.ws_engine_pool_close.restype = None
         l.ws_engine_pool_close.argtypes = [C.c_void_p]
         if l.ws_engine_abi_version() != ENGINE_ABI_VERSION:
@@ -234,16 +241,17 @@ class Engine:
                                              int(max_rows), est.ctypes.data), "ws_engine_separate_long")
         return est
 
-    def stream(self, rows, enroll, kind, max_chunk_frames=64):
+    def stream(self, rows, enroll, kind, max_chunk_frames=64, block_kernel=False):
         """A stream of `rows` rows on a causal cLN Conv-TasNet / SpEx+ container (info("streaming") == 1): enroll as in
-        separate(); the speaker stage runs once, here.  Close the stream before the engine."""
-        return EngineStream(self, rows, enroll, kind, max_chunk_frames)
+        separate(); the speaker stage runs once, here.  Close the stream before the engine.  block_kernel=True
+        (WS_STREAM_BLOCK_KERNEL): every block is one entry-point call."""
+        return EngineStream(self, rows, enroll, kind, max_chunk_frames, flags=STREAM_BLOCK_KERNEL if block_kernel else 0)
 
-    def stream_pool(self, slots, max_chunk_frames=64):
+    def stream_pool(self, slots, max_chunk_frames=64, block_kernel=False):
         """A pool of `slots` independent streams on a causal cLN Conv-TasNet / SpEx+ container: each slot at its own
         position, packets of any size, one launch chain per push whatever the number of slots in it.  Close the pool before
-        the engine."""
-        return StreamPool(self, slots, max_chunk_frames)
+        the engine.  block_kernel=True (WS_STREAM_BLOCK_KERNEL): every block is one entry-point call."""
+        return StreamPool(self, slots, max_chunk_frames, flags=STREAM_BLOCK_KERNEL if block_kernel else 0)
 
     def forward_pcm16(self, mix, spk1, spk2):
         """int16 [n], int16 [n_enroll] x 2 -> float32 [2, n] in [-1, 1] (SeparateEngine::ForwardFunc)."""
@@ -265,15 +273,19 @@ class EngineStream:
     """ws_engine_stream_* (include/wesep_engine.h): audio in as it arrives, the samples that became final out.  The
     concatenation of every push() and the flush() is the model-output part of Engine.separate's row."""
 
-    def __init__(self, engine, rows, enroll, kind, max_chunk_frames=64):
+    def __init__(self, engine, rows, enroll, kind, max_chunk_frames=64, flags=0):
         self._h, self._engine, self.rows = C.c_void_p(), engine, int(rows)      # (the engine must outlive the stream)
         enroll = np.ascontiguousarray(enroll, dtype=np.float32)
         if enroll.shape[0] != self.rows:
             raise ValueError("one enrollment per stream row")
         length = 0 if kind in (ENROLL_EMBEDDING, ENROLL_SPEAKER) else enroll.shape[1]
         _quiesce_torch()
-        _check(lib().ws_engine_stream_open(engine._h, self.rows, enroll.ctypes.data, kind, length, int(max_chunk_frames),
-                                           C.byref(self._h)), "ws_engine_stream_open")
+        if flags:
+            _check(lib().ws_engine_stream_open_ex(engine._h, self.rows, enroll.ctypes.data, kind, length, int(max_chunk_frames),
+                                                  int(flags), C.byref(self._h)), "ws_engine_stream_open_ex")
+        else:
+            _check(lib().ws_engine_stream_open(engine._h, self.rows, enroll.ctypes.data, kind, length, int(max_chunk_frames),
+                                               C.byref(self._h)), "ws_engine_stream_open")
         self._L = engine.info("L")
 
     def _out(self, buf, m):
@@ -315,6 +327,16 @@ class EngineStream:
             pass
 
 
+def stream_block_group_launches(R, X):
+    """WS_STREAM_BLOCK_GROUP_LAUNCHES: entry-point calls of one group of a stream opened with block_kernel=True."""
+    return R * X + 10
+
+
+def pool_block_group_launches(R, X):
+    """WS_POOL_BLOCK_GROUP_LAUNCHES: entry-point calls of one group of a pool opened with block_kernel=True."""
+    return R * X + 9
+
+
 def pool_group_launches(R, X):
     """WS_POOL_GROUP_LAUNCHES: entry-point calls of one group of a pool push, whatever the number of slots in it."""
     return 3 * R * X + 9
@@ -325,10 +347,14 @@ class StreamPool:
     is a stream of one row: the concatenation of what its pushes and its flush return is the model-output part of
     Engine.separate's row on that slot's audio, whatever the other slots were fed in the meantime."""
 
-    def __init__(self, engine, slots, max_chunk_frames=64):
+    def __init__(self, engine, slots, max_chunk_frames=64, flags=0):
         self._h, self._engine, self.slots = C.c_void_p(), engine, int(slots)    # (the engine must outlive the pool)
         _quiesce_torch()
-        _check(lib().ws_engine_pool_open(engine._h, self.slots, int(max_chunk_frames), C.byref(self._h)), "ws_engine_pool_open")
+        if flags:
+            _check(lib().ws_engine_pool_open_ex(engine._h, self.slots, int(max_chunk_frames), int(flags), C.byref(self._h)),
+                   "ws_engine_pool_open_ex")
+        else:
+            _check(lib().ws_engine_pool_open(engine._h, self.slots, int(max_chunk_frames), C.byref(self._h)), "ws_engine_pool_open")
         self._L = engine.info("L")
 
     def attach(self, enroll, kind):

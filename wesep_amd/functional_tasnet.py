@@ -320,25 +320,39 @@ class ConvBlockFn(torch.autograd.Function):
 
 
 def conv_block_stream(x, rb, geo, ring, t0, w1, b1, a1, g1, be1, wd, bd, a2, g2, be2, w3, b3, wsc=None, bsc=None,
-                      fused=False):
+                      fused=False, block=False):
     """ConvBlockFn.forward of a CAUSAL block on one chunk (inference only, no autograd): x [R*Tc, B] are the Tc frames
     that start at absolute frame t0, ring [R, cap, H] carries the normalised input of the depthwise convolution across
     chunks (dev.dwconv_stream_fwd; cap >= (P - 1) * dil + Tc).  The same launches as ConvBlockFn with the chunked
     depthwise kernel in place of dev.dwconv_fwd; everything else in the block is per frame.  geo = (R, Tc, norm, dil, bn)
     with norm 'cLN' (per-frame statistics) or 'BN' on its running statistics (bn = (rm1, rv1, rm2, rv2)): gLN's statistics
     span the utterance and cannot be streamed.  Returns out, or (out, skip) with the skip branch's (wsc, bsc).
-    fused=True (cLN only): the five launches between the two GEMMs are one, dev.tcn_mid_stream_fwd."""
+    fused=True (cLN only): the five launches between the two GEMMs are one, dev.tcn_mid_stream_fwd.
+    block=True (cLN only, no skip branch): the whole block is ONE launch, dev.tcn_block_stream_fwd; a frame's output bits
+    then do not depend on the chunking."""
     _need_cuda(x, "ConvTasNet")
     R, Tc, norm, dil, bn = geo
     if norm not in ("cLN", "BN"):
         raise L.WesepHipError(f"conv_block_stream: norm {norm!r} needs statistics over the whole utterance")
     if fused and norm != "cLN":
         raise NotImplementedError("conv_block_stream: fused=True is built for cLN; norm='BN' runs the unfused launches")
+    if block and norm != "cLN":
+        raise NotImplementedError("conv_block_stream: block=True is built for cLN; norm='BN' runs the unfused launches")
+    if block and wsc is not None:
+        raise NotImplementedError("conv_block_stream: block=True has no skip-connection branch (wsc given); run the block "
+                                  "with fused=True or the unfused launches")
     M, B = x.shape
     H, P = wd.shape[0], wd.shape[-1]
     x = x.contiguous()
     ldw = w1.shape[1]
     W1 = w1.reshape(H, ldw).contiguous()
+    if block:
+        out = _empty(x.device, M, B)
+        dev.tcn_block_stream_fwd(x, rb.contiguous() if rb is not None else None, W1, None if rb is not None else b1, a1,
+                                 g1.reshape(H).contiguous(), be1.reshape(H).contiguous(), wd.reshape(H, P).contiguous(), bd,
+                                 a2, g2.reshape(H).contiguous(), be2.reshape(H).contiguous(), w3.reshape(B, H).contiguous(),
+                                 b3, R, Tc, B, H, P, dil, LN_EPS, t0, ring, out)
+        return out
     c = _gemm(x, M, B, W1, H, ldw=ldw, bias=None if rb is not None else b1)
     g1f, be1f, g2f, be2f = (t.reshape(H).contiguous() for t in (g1, be1, g2, be2))
     if fused:

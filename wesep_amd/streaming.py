@@ -17,7 +17,9 @@ Not built (refused by name at construction): non-causal blocks, gLN (its statist
 (their dilated convolutions look ahead) and training mode.  All rows advance in lockstep.
 
 `fused=True` (cLN models) runs the five launches between a block's two GEMMs as one, `dev.tcn_mid_stream_fwd`: three C-ABI
-calls per block in place of seven.  The default issues the unfused launches."""
+calls per block in place of seven.  `block=True` (cLN blocks without skip connections) runs the whole block as one,
+`dev.tcn_block_stream_fwd`: one call per block, and the estimate's bits no longer depend on how the audio was cut into
+packets.  The default issues the unfused launches."""
 import torch
 
 from . import _lib as L
@@ -29,7 +31,7 @@ from .modules.tasnet import Conv1DBlock, Conv1DBlock4Fuse, Separation, _FuseLaye
 
 
 class ConvTasNetStreamer:
-    def __init__(self, model, rows, max_chunk_frames=256, fused=False):
+    def __init__(self, model, rows, max_chunk_frames=256, fused=False, block=False):
         from .models.convtasnet import ConvTasNet
         if not isinstance(model, ConvTasNet):
             raise TypeError(f"ConvTasNetStreamer: a ConvTasNet is needed, got {type(model).__name__}")
@@ -48,6 +50,13 @@ class ConvTasNetStreamer:
             raise NotImplementedError(f"ConvTasNetStreamer: fused=True is built for cLN blocks; this model's norm is "
                                       f"{model.norm_type!r} (BN runs the unfused launches: fused=False)")
         self.fused = bool(fused)
+        if block and model.norm_type != "cLN":
+            raise NotImplementedError(f"ConvTasNetStreamer: block=True is built for cLN blocks; this model's norm is "
+                                      f"{model.norm_type!r} (BN runs the unfused launches: block=False)")
+        if block and any(getattr(b, "skip_con", False) for b in blocks):
+            raise NotImplementedError("ConvTasNetStreamer: block=True has no skip-connection branch; this model's blocks "
+                                      "have skip connections (skip_con=True): stream it with fused=True or the default")
+        self.block = bool(block)
         if int(rows) < 1 or int(max_chunk_frames) < 1:
             raise ValueError(f"ConvTasNetStreamer: rows={rows}, max_chunk_frames={max_chunk_frames} must be positive")
         self.model, self.rows, self.max_chunk_frames = model, int(rows), int(max_chunk_frames)
@@ -265,8 +274,9 @@ class ConvTasNetStreamer:
         if fuse:
             return FT.conv_block_stream(x, self._rb[id(b)], g, ring, self._k, b.conv1x1.weight, b.conv1x1.bias,
                                         b.prelu1.weight, n1.weight, n1.bias, b.dconv.weight, b.dconv.bias, b.prelu2.weight,
-                                        n2.weight, n2.bias, b.sconv.weight, b.sconv.bias, fused=self.fused)
+                                        n2.weight, n2.bias, b.sconv.weight, b.sconv.bias, fused=self.fused,
+                                        block=self.block)
         skip = (b.Sc_conv.weight, b.Sc_conv.bias) if b.skip_con else ()
         return FT.conv_block_stream(x, None, g, ring, self._k, b.conv1x1.weight, b.conv1x1.bias, b.PReLU_1.weight,
                                     n1.weight, n1.bias, b.dwconv.weight, b.dwconv.bias, b.PReLU_2.weight, n2.weight,
-                                    n2.bias, b.Output.weight, b.Output.bias, *skip, fused=self.fused)
+                                    n2.bias, b.Output.weight, b.Output.bias, *skip, fused=self.fused, block=self.block)
