@@ -229,6 +229,69 @@ int ws_engine_pool_flush(ws_pool* p, int slot, float* est, int est_cap, int* n_o
 int ws_engine_pool_detach(ws_pool* p, int slot);
 void ws_engine_pool_close(ws_pool* p);
 
+/* Sample rates (new symbols, engine ABI 2 unchanged): audio at the caller's rate.  Every call above takes audio at the
+ * container's "sample_rate" only; these put the device resampler of wesep_hip.h ("sample rates": the sinc_interp_hann design
+ * with lowpass_filter_width 6, rolloff 0.99; D = rate_in / gcd, U = rate_out / gcd, w = ceil(6 D / (0.99 min(D, U))),
+ * K = 2 w + D taps per output sample) in front of and behind them.  The tap tables come from ws_resample_taps and are kept on
+ * the device per (rate_in, rate_out).  All pointers are HOST pointers.  Refused by name before any launch: rates <= 0, U or D
+ * above 1024, K above 4096 (the kernel's limits and its own texts).
+ *
+ *   ws_engine_resample(e, x, R, n, rate_in, rate_out, y, y_cap, &n_out)  x [R][n] -> y [R][*n_out], *n_out = ceil(U n / D) <=
+ *     y_cap: one upload, one launch, one download; any container.  Dry run supported.
+ *   ws_engine_separate_rate(e, mix, R, T, sample_rate, enroll, enroll_kind, enroll_len, enroll_rate, est)  mix and est are
+ *     [R][T] at sample_rate; ALL four architectures.  (1) the mixture is resampled to the container's rate, T' = ceil(U T / D)
+ *     samples; (2) a WS_ENROLL_WAVE enrollment is resampled from enroll_rate; (3) ws_engine_separate runs as it is on [R][T'];
+ *     (4) the estimate is resampled back and cropped to T.  A step whose rates are equal does not run: "n_launches" is
+ *     ws_engine_separate's figure plus WS_SEPARATE_RATE_LAUNCHES(mixture resampled, enrollment resampled), and with sample_rate
+ *     and enroll_rate equal to the container's rate (or enroll_rate == 0: "the container's") the call IS ws_engine_separate:
+ *     same launches, same bits.  The estimate is bit for bit ws_engine_resample -> ws_engine_separate -> ws_engine_resample,
+ *     cropped.  Refused by name before any launch: an enroll_rate other than 0 or the container's with a kind that is not a
+ *     waveform, a T' below the architecture's minimum (its own message), rates outside the kernel's limits.
+ *
+ * Rate stream: a causal cLN Conv-TasNet stream (ws_engine_stream_*) whose pushes carry and return samples at sample_rate.
+ *   ws_engine_rate_stream_open(e, rows, enroll, enroll_kind, enroll_len, enroll_rate, max_chunk_frames, flags, sample_rate,
+ *     max_push, &s)  flags is the word of ws_engine_stream_open_ex, passed through; a waveform enrollment is resampled from
+ *     enroll_rate first.  Per push, all on the device: chunk H2D -> resampler A (sample_rate -> container) -> the solo
+ *     stream's pending buffer and group loop -> its estimates, written behind resampler B's history -> resampler B (container ->
+ *     sample_rate) -> one D2H; ONE host synchronisation.  A resampler's state is the last < K samples it took, kept in one
+ *     of two buffers used in turn (the launch that computes a step's outputs also moves the new history to the other one).
+ *     The four buffers and the two staging buffers (A's output, B's output) are one more slot of the stream's ONE state
+ *     allocation, sized at open from max_push; "stream_state_bytes" reports the sum and no push changes it.  A push above
+ *     max_push is taken in pieces.
+ *   Emission.  A resampler that has taken N samples has returned U max(0, floor((N - w) / D)) (its flush: the rest up to
+ *     ceil(U N / D)); the solo stream after M samples floor((M - 160) / s + 1) s.  A push returns B's emission on the solo
+ *     stream's emission on A's emission; the count is known before anything runs.  ws_engine_rate_stream_flush is A's flush,
+ *     the solo stream's rest and flush, then B's flush, cropped so that the total is at most the number of samples pushed:
+ *     min(N, ceil(U_B ((T' - 1) s + L) / D_B)), T' the frames of ceil(U_A N / D_A) samples.  The whole output is bit for bit
+ *     ws_engine_resample -> the plain stream with the same flags -> ws_engine_resample, cropped, in the separator's part to
+ *     what that stream guarantees (WS_STREAM_BLOCK_KERNEL: bit for bit under any packet sizes).  Added delay: A holds back
+ *     up to w_A + D_A - 1 input samples, B up to w_B + D_B - 1 of the container's, on top of the solo stream's 160 + s - 1.
+ *   ws_engine_rate_stream_push_cap(s, n)  samples a row that a push of n >= 1 samples can return at most, from any state;
+ *     n = 0: what the flush can return at most.
+ *   Launches: a push's piece is the solo stream's groups plus WS_RATE_STREAM_PIECE_LAUNCHES = 2, one call of
+ *     ws_resample_stream_fwd per resampler (a resampler that received nothing in the piece -- B before the first frame is
+ *     complete -- does not run).  The copies to and from the host are not counted.
+ *   With sample_rate equal to the container's rate a rate stream IS the plain stream: the calls forward to ws_engine_stream_*
+ *     (same launches, same bits, its caps and refusals).  Otherwise, WS_ERR_INVALID with a message and nothing launched: a
+ *     container that cannot stream, an unknown flag bit (the texts of ws_engine_stream_open_ex), rows < 1, max_push outside
+ *     [1, 2^24], an enroll_rate with a kind that is not a waveform, est_cap below what the call emits, a flush before L samples
+ *     at the container's rate, push or flush after a flush, n < 1, a NULL pointer.
+ * The stream pool is NOT rate-aware: its pending samples live on the host, and per-slot rates need rows forms of the
+ * resampler (per-row geometry, position and history slot), which do not exist yet. */
+#define WS_SEPARATE_RATE_LAUNCHES(mix_resampled, enroll_resampled) (2 * ((mix_resampled) != 0) + ((enroll_resampled) != 0))
+#define WS_RATE_STREAM_PIECE_LAUNCHES 2
+typedef struct ws_rate_stream ws_rate_stream;
+int ws_engine_resample(ws_engine* e, const float* x, int R, int n, int rate_in, int rate_out, float* y, int y_cap, int* n_out);
+int ws_engine_separate_rate(ws_engine* e, const float* mix, int R, int T, int sample_rate, const void* enroll, int enroll_kind,
+                            int enroll_len, int enroll_rate, float* est);
+int ws_engine_rate_stream_open(ws_engine* e, int rows, const void* enroll, int enroll_kind, int enroll_len, int enroll_rate,
+                               int max_chunk_frames, unsigned flags, int sample_rate, int max_push, ws_rate_stream** out);
+int ws_engine_rate_stream_push(ws_rate_stream* s, const float* chunk, int n, float* est, int est_cap, int* n_out);
+int ws_engine_rate_stream_flush(ws_rate_stream* s, float* est, int est_cap, int* n_out);
+int ws_engine_rate_stream_reset(ws_rate_stream* s);
+void ws_engine_rate_stream_close(ws_rate_stream* s);
+int ws_engine_rate_stream_push_cap(const ws_rate_stream* s, int n);
+
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by
  * 2^-15 before the model, separate_engine.cc:81-84, and its wav writer scales back, frontend/wav.h:245-253).

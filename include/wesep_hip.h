@@ -1261,6 +1261,50 @@ int ws_tcn_block_stream_rows_fwd(const float* x, const float* rb, const float* W
                                  int B, int H, int P, int dil, float eps, int nslots, const int* slot, const long long* t0,
                                  const int* tc, int cap, float* ring, float* out, void* stream);
 
+/* ---- sample rates (resample.hip; DESIGN section 7, "Sample rates") -- new symbols, ABI 20 unchanged -------------------------
+ * Polyphase windowed-sinc rate conversion: the published sinc_interp_hann design with lowpass_filter_width = 6 and
+ * rolloff = 0.99.  For rate_in -> rate_out: g = gcd, D = rate_in / g, U = rate_out / g, base = min(D, U) * 0.99,
+ * w = ceil(6 D / base), K = 2 w + D.  The tap table taps[p][k], p < U, k < K, is computed in double and rounded to float once:
+ *   t = clamp((-p / U + (k - w) / D) * base, -6, 6);   taps[p][k] = (t == 0 ? 1 : sin(pi t) / (pi t)) * cos^2(pi t / 12) * base / D
+ * and  y[q] = sum_{k < K} taps[q % U][k] * x[(q / U) * D + k - w]  for q < ceil(U n_in / D), x = 0 outside [0, n_in).
+ *   ws_resample_geom  (U, D, w, K) of a pair of rates.  Host code.
+ *   ws_resample_taps  the table, HOST float [U][K].  Host code in double; the ONE place the table is made (the engine and
+ *                   the Python binding both call it and upload the result).
+ *   ws_resample_fwd   the whole signal: x [R][ldx] with n_in >= 1 valid samples a row -> y [R][ldy], ceil(U n_in / D) samples
+ *                   a row; taps: the DEVICE copy of the table.  Nothing behind n_in is read (NaN included), nothing behind
+ *                   the last output is written.  Rows have any pitch.
+ *   ws_resample_stream_fwd  the same filter on a stream's buffer buf [R][ldb] = history | new samples, n_valid >= 1 valid
+ *                   samples a row.  Groups of U outputs are numbered from the buffer: group g reads buf[g D - lead + k],
+ *                   k < K -- lead (0 <= lead <= w) is the number of taps of group 0 that lie before buf[0], which is sample 0
+ *                   of the signal when lead > 0.  The call writes n_out outputs, starting at phase 0 of group g_first, to
+ *                   y [R][ldy].  final = 0: every tap of every output must fall on a valid sample (refused otherwise);
+ *                   final = 1: the signal ends at n_valid, taps behind it are skipped (the zero extension of the whole-signal
+ *                   form), and outputs past ceil(U (n_valid + lead - w) / D) are refused.  The same launch copies
+ *                   buf[r][hist_from .. hist_from + hist_len) to hist [R][ldh] (another buffer; hist_len = 0: none) -- the
+ *                   history of the next call; n_out = 0 with hist_len > 0 only moves the history.
+ * One thread owns one output sample of one row: ONE fp32 accumulator started at 0 and advanced by fmaf in ascending k over
+ * the taps that fall on valid samples -- a tap before sample 0 or behind the end is skipped, not multiplied.  Both forms run
+ * the same device function on buffer-relative int offsets; nothing depends on the grid, R, the chunk or the position.  So an
+ * output sample has the same BITS in the whole-signal call, under any chunking of the streaming call, alone or beside other
+ * rows, and from run to run.  No atomics.  The caller keeps 64-bit sample and group counters.
+ * Streaming emission rule (wesep_amd/resample.py StreamResampler, runtime/rate.cc): group g is final once g D + w + D <= N, so
+ * after N input samples U max(0, floor((N - w) / D)) outputs have been returned; the flush returns the rest up to
+ * ceil(U N / D).  The history a stream keeps is the input from max(0, G D - w) on, G the groups returned: fewer than K samples.
+ * A table of U K <= 2048 floats is staged in LDS per workgroup; a larger one (44.1 kHz, 22.05 kHz) is read from global
+ * memory through the caches.  WS_ERR_INVALID before any launch, by name: a NULL pointer, rates <= 0, U or D above
+ * WS_RESAMPLE_MAX_UD, K above WS_RESAMPLE_MAX_K, R outside [1, 65535], n_in / n_valid < 1, a row pitch below its row, offsets
+ * reaching 2^31, lead outside [0, w], a history range outside the valid samples or overlapping buf, outputs beyond what the
+ * valid samples allow. */
+#define WS_RESAMPLE_MAX_UD 1024
+#define WS_RESAMPLE_MAX_K 4096
+int ws_resample_geom(int rate_in, int rate_out, int* U, int* D, int* w, int* K);
+int ws_resample_taps(int rate_in, int rate_out, float* taps);
+int ws_resample_fwd(const float* x, long long ldx, int R, int n_in, int rate_in, int rate_out, const float* taps, float* y,
+                    long long ldy, void* stream);
+int ws_resample_stream_fwd(const float* buf, long long ldb, int R, int rate_in, int rate_out, const float* taps, int lead,
+                           int n_valid, int final, int g_first, int n_out, float* y, long long ldy, int hist_from, int hist_len,
+                           float* hist, long long ldh, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

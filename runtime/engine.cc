@@ -450,6 +450,7 @@ int check_enroll(ws_engine* e, int R, int enroll_kind, int enroll_len, const int
 }
 
 static std::mutex g_device_mutex[16];   // see ForwardTurn
+static thread_local int g_turn_depth[16];   // turns this thread holds per device: only the outermost one locks
 
 // Engines that share a GPU overlap on the device.  Round 2 serialised them here (one forward at a time per GPU)
 // because ws_gemm_b2p / the grouped ws_gemm_nt / ws_gemm_tn disturbed this plan's STFT / iSTFT kernels on another
@@ -463,7 +464,14 @@ ForwardTurn::ForwardTurn(ws_engine* e) : turn(g_device_mutex[e->device & 15], st
     rc = WS_ERR_LAUNCH;
     return;
   }
-  if (serialize) turn.lock();
+  if (serialize) {
+    nested = e->device & 15;
+    if (g_turn_depth[nested]++ == 0) turn.lock();
+  }
+}
+
+ForwardTurn::~ForwardTurn() {
+  if (nested >= 0) --g_turn_depth[nested];      // (the outermost turn of the thread owns the lock and releases it last)
 }
 
 // the speaker stage of every forward: host enrollment -> device emb [R][E], the encoder's embedding before SpeakerTransform

@@ -11,6 +11,7 @@
 //   longform.cc      ws_engine_separate_long: one long mixture as overlapping windows through the rectangular plans
 //   stream.cc        ws_engine_stream_*: causal cLN Conv-TasNet fed audio as it arrives, state carried on the device
 //   stream_pool.cc   ws_engine_pool_*: many such streams, each at its own position, through one launch chain per round
+//   rate.cc          audio at the caller's sample rate: ws_engine_resample, ws_engine_separate_rate, ws_engine_rate_stream_*
 // Everything here lives in namespace wsrt and is built with -fvisibility=hidden: the library exports the C ABI only
 // (WS_ENGINE_API).  Host code only: no kernels in the runtime.
 #ifndef WESEP_ENGINE_INTERNAL_H_
@@ -295,6 +296,7 @@ struct ws_engine {
   long long stream_state_bytes = 0;                // device state of the stream opened last (ws_engine_stream_open)
   long long cluster_fallbacks = 0;   // forwards in which a cluster recurrence timed out and the streaming kernels took over
   unsigned* cl_status = nullptr;     // sticky device word set by ws_lstm_fwd_cluster on a timeout
+  std::map<std::pair<int, int>, const float*> rs_taps;   // (rate_in, rate_out) -> device tap table (rate.cc), made on first use
   // configuration shared by the plans
   int arch = 0;                   // 0 pBSRNN, 1 Conv-TasNet, 2 DPCCN, 3 TF-GridNet
   int sr = 16000, E = 256, use_xform = 0, joint = 0;
@@ -364,7 +366,12 @@ int check_enroll(ws_engine* e, int R, int enroll_kind, int enroll_len, const int
 struct ForwardTurn {     // hipSetDevice + the opt-in one-forward-at-a-time lock (WS_ENGINE_SERIALIZE), held while it lives
   std::unique_lock<std::mutex> turn;
   int rc = WS_OK;
+  int nested = -1;       // the device whose per-thread depth this turn counts in: a turn taken while the calling thread holds
+                         // one for the same device (ws_engine_separate_rate around ws_engine_separate) does not lock again
   explicit ForwardTurn(ws_engine* e);
+  ~ForwardTurn();
+  ForwardTurn(const ForwardTurn&) = delete;
+  ForwardTurn& operator=(const ForwardTurn&) = delete;
 };
 int speaker_stage(ws_engine* e, const void* enroll, int enroll_kind, int R, int enroll_len, int Te, const int* enroll_lengths,
                   const int* te_row, float* d_emb);
@@ -436,6 +443,15 @@ struct StreamWeights {       // every weight pointer of a group of frames, resol
 void resolve_stream_weights(const ws_engine* e, StreamWeights* w);   // blocks: weights, ldw and dil; the owner sets cap, ring, rb
 int refuse_not_streamable(const ws_engine* e, const char* who);      // WS_ERR_INVALID with the reason, by name
 int tas_flat_stats(ws_engine* e, const float* x, int R, long long n, float* st);
+// ---- what a rate stream (rate.cc) needs of the solo stream (stream.cc) ----
+// extra_floats > 0: one more slot in the stream's state allocation (*extra), and chunks / estimates are DEVICE buffers
+int stream_open_impl(ws_engine* e, int rows, const void* enroll, int enroll_kind, int enroll_len, int max_chunk_frames,
+                     unsigned flags, size_t extra_floats, ws_stream** out, float** extra);
+// pitches in floats; est_pitch < 0: the emitted count (the plain stream).  A device-buffer stream takes no turn, does not reset
+// the launch counter and does not synchronise: its caller does, once
+int stream_push_impl(ws_stream* st, const float* chunk, long long chunk_pitch, int n, float* est, long long est_pitch, int est_cap,
+                     int* n_out);
+int stream_flush_impl(ws_stream* st, float* est, long long est_pitch, int est_cap, int* n_out);
 int prepare_dpccn(ws_engine* e);
 int dpccn_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est);
 int dp_conv_view(ws_engine* e, const float* x, int R, int H, int W, int Cin, int mode, int Wo, int sw, const float* Wm, int Cout,

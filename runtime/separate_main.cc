@@ -3,7 +3,7 @@
 //
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
 //                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
-//                 [--stream_ms 10 [--stream_pool 4] [--stream_block]]
+//                 [--stream_ms 10 [--stream_pool 4] [--stream_block]] [--resample]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -38,6 +38,13 @@
 // --stream_block (with --stream_ms, alone or with --stream_pool): the streams are opened with WS_STREAM_BLOCK_KERNEL -- every
 // block of the separator is one call, and a line's samples do not depend on the packet size or on the lines beside it.
 // Refused without --stream_ms.
+// --resample (off by default: without it a file at another rate than the model's fails with "sample rate is not ..."): the
+// mixture and the two enrollments may each have any sample rate within the resampler's limits (wesep_hip.h, "sample rates").
+// Plain, --batch and --chunk_seconds runs bring every file to the model's rate with ws_engine_resample, run as above (seconds
+// are seconds of audio) and bring the estimates back; --stream_ms feeds a rate stream (ws_engine_rate_stream_*) packets of M
+// ms at the mixture's own rate.  Outputs are written at the mixture's rate with the mixture's length.  Refused together
+// with --stream_pool (the pool is not rate-aware).  A --dry_run with --resample and an --output_dir writes the files too, all
+// zeros: their rate and length can be checked without a GPU.
 // --dry_run validates the model file and the launch plan of every utterance without a GPU and writes nothing.
 // --raw_out additionally writes the unquantised estimates as <key>-spk{1,2}.f32 (float32, for parity checks).
 #include <stdio.h>
@@ -144,11 +151,15 @@ int main(int argc, char** argv) {
   const int pool_n = atoi(args.get("stream_pool", "0").c_str());
   const bool stream_block = args.has("stream_block");
   const unsigned stream_flags = stream_block ? WS_STREAM_BLOCK_KERNEL : 0u;
+  const bool resample = args.has("resample");
+  // a dry run writes nothing -- except with --resample and an --output_dir: the (all-zero) files then show the rate and the
+  // length an output will have
+  const bool write_out = !dry || (resample && !out_dir.empty());
   if (args.has("help")) {
     printf("usage: separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1]\n"
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
            "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]]\n"
-           "                     [--stream_ms M [--stream_pool N] [--stream_block]]\n"
+           "                     [--stream_ms M [--stream_pool N] [--stream_block]] [--resample]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
@@ -162,7 +173,9 @@ int main(int argc, char** argv) {
            "  --stream_pool N    with --stream_ms M: N consecutive lines at a time through one stream pool, one push per round\n"
            "                     of M ms packets; same files as --stream_ms alone\n"
            "  --stream_block     with --stream_ms M: every block of the separator as one call (WS_STREAM_BLOCK_KERNEL); the\n"
-           "                     samples of a line then do not depend on the packet size or on the other lines of a pool\n");
+           "                     samples of a line then do not depend on the packet size or on the other lines of a pool\n"
+           "  --resample         take files at any sample rate: resample to the model's rate on the device and back; outputs\n"
+           "                     have the mixture's rate and length.  Not together with --stream_pool\n");
     return 0;
   }
   if (chunked && batch > 1) return die("--chunk_seconds and --batch " + std::to_string(batch) + " conflict: a batch is a rectangle of "
@@ -170,6 +183,9 @@ int main(int argc, char** argv) {
   if (pooled && !streamed) return die("--stream_pool needs --stream_ms M: the pool is fed packets of M milliseconds");
   if (pooled && (batch > 1 || chunked))
     return die("--stream_pool conflicts with --batch N > 1 and --chunk_seconds: the pool's lines are streams, each fed as it arrives");
+  if (pooled && resample)
+    return die("--resample conflicts with --stream_pool: the stream pool is not rate-aware (its pending samples live on the host); use "
+               "--stream_ms alone");
   if (pooled && pool_n < 1) return die("--stream_pool needs a positive number of lines");
   if (stream_block && !streamed) return die("--stream_block needs --stream_ms M: it selects the block kernel of a stream or a stream pool");
   if (streamed && (batch > 1 || chunked))
@@ -215,6 +231,34 @@ int main(int argc, char** argv) {
       return fail("--stream_ms: this model cannot stream (ws_engine_info \"streaming\" is not 1): streaming needs a causal cLN "
                   "Conv-TasNet / SpEx+ container");
     }
+    // --resample: PCM at `rate` as floats in [-1, 1] at the model's rate, and estimates [R][n_m] back as [R][n] at `rate`
+    auto to_model = [&](const std::vector<int16_t>& x, int rate, std::vector<float>* y) -> bool {
+      std::vector<float> f(x.size());
+      for (size_t i = 0; i < x.size(); ++i) f[i] = static_cast<float>(x[i]) / 32768.0f;
+      if (rate == sample_rate) {
+        y->swap(f);
+        return true;
+      }
+      const long long cap = rate > 0 ? (static_cast<long long>(f.size()) * sample_rate + rate - 1) / rate : 0;   // ceil(U n / D)
+      y->assign(static_cast<size_t>(std::max<long long>(cap, 1)), 0.f);
+      int m = 0;
+      if (ws_engine_resample(engine, f.data(), 1, static_cast<int>(f.size()), rate, sample_rate, y->data(), static_cast<int>(cap), &m) != 0)
+        return false;
+      y->resize(m);
+      return true;
+    };
+    auto from_model = [&](const float* rows, int R, int n_m, int rate, int n, float* out) -> bool {
+      if (rate == sample_rate) {
+        for (int r = 0; r < R; ++r) memcpy(out + size_t(r) * n, rows + size_t(r) * n_m, size_t(std::min(n, n_m)) * 4);
+        return true;
+      }
+      const long long cap = (static_cast<long long>(n_m) * rate + sample_rate - 1) / sample_rate;
+      std::vector<float> back(size_t(R) * cap);
+      int m = 0;
+      if (ws_engine_resample(engine, rows, R, n_m, sample_rate, rate, back.data(), static_cast<int>(cap), &m) != 0) return false;
+      for (int r = 0; r < R; ++r) memcpy(out + size_t(r) * n, back.data() + size_t(r) * m, size_t(std::min(n, m)) * 4);
+      return true;
+    };
     // --stream_pool N: up to N lines in flight on one pool of 2 N slots; a lane takes the next line when its own ends
     if (pooled) {
       struct Lane {
@@ -360,6 +404,7 @@ int main(int argc, char** argv) {
       const size_t i0 = g * batch, B = (i0 + batch <= waves.size() ? i0 + batch : waves.size()) - i0;
       std::vector<wesep_rt::Wav> mix(B), s1(B), s2(B);
       std::vector<int> lengths(2 * B), elens(2 * B);
+      std::vector<std::vector<float>> mix_f(B), e1_f(B), e2_f(B);     // --resample: the line's files at the model's rate
       std::string err;
       int T = 0, Te = 0;
       bool ok = true;
@@ -369,12 +414,17 @@ int main(int argc, char** argv) {
             !wesep_rt::read_wav(w[3], &s2[b], &err)) {
           fail(err);
           ok = false;
-        } else if (mix[b].sample_rate != sample_rate || s1[b].sample_rate != sample_rate || s2[b].sample_rate != sample_rate) {
+        } else if (!resample && (mix[b].sample_rate != sample_rate || s1[b].sample_rate != sample_rate || s2[b].sample_rate != sample_rate)) {
           fail(w[0] + ": sample rate is not " + std::to_string(sample_rate));
           ok = false;
+        } else if (resample && (!to_model(mix[b].samples, mix[b].sample_rate, &mix_f[b]) || !to_model(s1[b].samples, s1[b].sample_rate, &e1_f[b]) ||
+                                !to_model(s2[b].samples, s2[b].sample_rate, &e2_f[b]))) {
+          fail(w[0] + ": " + ws_engine_last_error());
+          ok = false;
         } else {
-          const int n = static_cast<int>(mix[b].samples.size());
-          const int ne = static_cast<int>(s1[b].samples.size() < s2[b].samples.size() ? s1[b].samples.size() : s2[b].samples.size());
+          const int n = static_cast<int>(resample ? mix_f[b].size() : mix[b].samples.size());
+          const int ne = static_cast<int>(resample ? std::min(e1_f[b].size(), e2_f[b].size())
+                                                   : std::min(s1[b].samples.size(), s2[b].samples.size()));
           lengths[2 * b] = lengths[2 * b + 1] = n;
           elens[2 * b] = elens[2 * b + 1] = ne;
           T = n > T ? n : T;
@@ -388,6 +438,11 @@ int main(int argc, char** argv) {
         for (int k = 0; k < 2; ++k) {
           float* mr = m.data() + (2 * b + k) * size_t(T);
           float* er = enr.data() + (2 * b + k) * size_t(Te);
+          if (resample) {
+            memcpy(mr, mix_f[b].data(), size_t(lengths[2 * b]) * 4);
+            memcpy(er, (k == 0 ? e1_f[b] : e2_f[b]).data(), size_t(elens[2 * b]) * 4);
+            continue;
+          }
           const std::vector<int16_t>& src = k == 0 ? s1[b].samples : s2[b].samples;
           for (int i = 0; i < lengths[2 * b]; ++i) mr[i] = static_cast<float>(mix[b].samples[i]) / 32768.0f;
           for (int i = 0; i < elens[2 * b]; ++i) er[i] = static_cast<float>(src[i]) / 32768.0f;
@@ -400,21 +455,36 @@ int main(int argc, char** argv) {
         break;
       }
       const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      const long long batch_launches = ws_engine_info(engine, "n_launches");
       double audio_ms = 0.0;
+      std::vector<float> back;
       for (size_t b = 0; b < B && ok; ++b) {
         const std::string& key = waves[i0 + b][0];
-        const int n = lengths[2 * b];
+        int n = lengths[2 * b], Tp = T, out_rate = sample_rate;
         const float* o = out.data() + 2 * b * size_t(T);
-        audio_ms += 1000.0 * n / sample_rate;
-        if (!dry && (!wesep_rt::write_wav(out_dir + "/" + key + "-spk1.wav", o, n, sample_rate, &err) ||
-                     !wesep_rt::write_wav(out_dir + "/" + key + "-spk2.wav", o + T, n, sample_rate, &err))) {
+        if (resample) {                   // the line's two estimates back at the mixture's rate and length
+          const int n_m = n;
+          std::vector<float> two(size_t(2) * n_m);
+          for (int k = 0; k < 2; ++k) memcpy(two.data() + size_t(k) * n_m, o + size_t(k) * T, size_t(n_m) * 4);
+          n = Tp = static_cast<int>(mix[b].samples.size()), out_rate = mix[b].sample_rate;
+          back.assign(size_t(2) * n, 0.f);
+          if (!from_model(two.data(), 2, n_m, out_rate, n, back.data())) {
+            fail(key + ": " + ws_engine_last_error());
+            ok = false;
+            break;
+          }
+          o = back.data();
+        }
+        audio_ms += 1000.0 * n / out_rate;
+        if (write_out && (!wesep_rt::write_wav(out_dir + "/" + key + "-spk1.wav", o, n, out_rate, &err) ||
+                     !wesep_rt::write_wav(out_dir + "/" + key + "-spk2.wav", o + Tp, n, out_rate, &err))) {
           fail(err);
           ok = false;
         }
         if (ok && !dry && raw_out) {
           for (int k = 0; k < 2; ++k) {
             FILE* f = fopen((out_dir + "/" + key + "-spk" + std::to_string(k + 1) + ".f32").c_str(), "wb");
-            if (!f || fwrite(o + size_t(k) * T, 4, n, f) != size_t(n)) fail("cannot write raw output");
+            if (!f || fwrite(o + size_t(k) * Tp, 4, n, f) != size_t(n)) fail("cannot write raw output");
             if (f) fclose(f);
           }
         }
@@ -423,7 +493,7 @@ int main(int argc, char** argv) {
       std::lock_guard<std::mutex> l(io_mu);
       for (size_t b = 0; b < B; ++b)
         printf("process: %s RTF: %.4f (batch of %zu: %lld launches, %lld MiB arena)%s\n", waves[i0 + b][0].c_str(), ms / audio_ms,
-               B, ws_engine_info(engine, "n_launches"), ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");
+               B, batch_launches, ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");
       if (ws_engine_info(engine, "cluster_fallbacks") > fallbacks_seen) {
         fallbacks_seen = ws_engine_info(engine, "cluster_fallbacks");
         printf("note: %s: a cluster recurrence timed out (GPU shared); recomputed by the streaming kernels\n",
@@ -441,17 +511,71 @@ int main(int argc, char** argv) {
         fail(err);
         break;
       }
-      if (mix.sample_rate != sample_rate || s1.sample_rate != sample_rate || s2.sample_rate != sample_rate) {
+      if (!resample && (mix.sample_rate != sample_rate || s1.sample_rate != sample_rate || s2.sample_rate != sample_rate)) {
         fail(w[0] + ": sample rate is not " + std::to_string(sample_rate));
         break;
       }
       const int n = static_cast<int>(mix.samples.size());
-      const int n_enroll = static_cast<int>(s1.samples.size() < s2.samples.size() ? s1.samples.size() : s2.samples.size());
+      const int out_rate = resample ? mix.sample_rate : sample_rate;      // outputs have the mixture's rate and length
+      int n_enroll = static_cast<int>(s1.samples.size() < s2.samples.size() ? s1.samples.size() : s2.samples.size());
       std::vector<float> out(size_t(2) * n, 0.f);
       const auto t0 = std::chrono::steady_clock::now();
       int rc;
-      long long stream_launches = 0, stream_pushes = 0;
-      if (streamed) {
+      long long stream_launches = 0, stream_pushes = 0, plain_launches = -1, long_w = 0, long_f = 0;
+      int stream_samples = stream_n;
+      if (resample) {
+        // every file at the model's rate (the enrollments cut to the shorter one there); a stream takes the mixture as it is
+        std::vector<float> mix_f, e1, e2;
+        rc = to_model(s1.samples, s1.sample_rate, &e1) && to_model(s2.samples, s2.sample_rate, &e2) &&
+                     (streamed || to_model(mix.samples, mix.sample_rate, &mix_f)) ? 0 : -1;
+        n_enroll = static_cast<int>(std::min(e1.size(), e2.size()));
+        std::vector<float> enr(size_t(2) * n_enroll);
+        if (rc == 0) {
+          memcpy(enr.data(), e1.data(), size_t(n_enroll) * 4);
+          memcpy(enr.data() + n_enroll, e2.data(), size_t(n_enroll) * 4);
+        }
+        const int n_m = static_cast<int>(mix_f.size());
+        if (rc == 0 && streamed) {
+          stream_samples = std::max(1, static_cast<int>(stream_ms * out_rate / 1000.0 + 0.5));
+          ws_rate_stream* rs = nullptr;
+          rc = ws_engine_rate_stream_open(engine, 2, enr.data(), WS_ENROLL_WAVE, n_enroll, 0, 64, stream_flags, out_rate, stream_samples, &rs);
+          const int cap = rc == 0 ? std::max(ws_engine_rate_stream_push_cap(rs, stream_samples), ws_engine_rate_stream_push_cap(rs, 0)) : 1;
+          std::vector<float> chunk(size_t(2) * stream_samples), got(size_t(2) * cap);
+          int done = 0;
+          auto take = [&](int m) {                                      // est [2][m] behind what came before; never past n
+            const int c = std::min(m, n - done);
+            for (int k = 0; k < 2; ++k) memcpy(out.data() + size_t(k) * n + done, got.data() + size_t(k) * m, size_t(c) * 4);
+            done += c;
+          };
+          for (int pos = 0; rc == 0 && pos < n; pos += stream_samples) {
+            const int c = std::min(stream_samples, n - pos);
+            int m = 0;
+            for (int i = 0; i < c; ++i) chunk[i] = chunk[size_t(c) + i] = static_cast<float>(mix.samples[pos + i]) / 32768.0f;
+            if ((rc = ws_engine_rate_stream_push(rs, chunk.data(), c, got.data(), cap, &m)) == 0) take(m);
+            stream_launches += ws_engine_info(engine, "n_launches"), ++stream_pushes;
+          }
+          if (rc == 0) {
+            int m = 0;
+            if ((rc = ws_engine_rate_stream_flush(rs, got.data(), cap, &m)) == 0) take(m);
+            stream_launches += ws_engine_info(engine, "n_launches");
+          }
+          ws_engine_rate_stream_close(rs);
+        } else if (rc == 0) {
+          std::vector<float> out_m(size_t(2) * n_m, 0.f);
+          if (chunked) {
+            rc = ws_engine_separate_long(engine, mix_f.data(), n_m, 2, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, window, overlap,
+                                         chunk_rows, out_m.data());
+          } else {                                                      // the rows of ws_engine_forward_pcm16: the mixture twice
+            std::vector<float> two(size_t(2) * n_m);
+            memcpy(two.data(), mix_f.data(), size_t(n_m) * 4);
+            memcpy(two.data() + n_m, mix_f.data(), size_t(n_m) * 4);
+            rc = ws_engine_separate(engine, two.data(), 2, n_m, enr.data(), WS_ENROLL_WAVE, n_enroll, out_m.data());
+          }
+          plain_launches = ws_engine_info(engine, "n_launches");       // (the resampling back resets the engine's counters)
+          long_w = ws_engine_info(engine, "long_windows"), long_f = ws_engine_info(engine, "long_forwards");
+          if (rc == 0 && !from_model(out_m.data(), 2, n_m, out_rate, n, out.data())) rc = -1;
+        }
+      } else if (streamed) {
         // the rows of ws_engine_forward_pcm16, pushed as they would arrive; what becomes final goes behind what came before
         std::vector<float> enr(size_t(2) * n_enroll), chunk(size_t(2) * stream_n), got;
         for (int i = 0; i < n_enroll; ++i) {
@@ -499,9 +623,9 @@ int main(int argc, char** argv) {
         break;
       }
       const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      const double audio_ms = 1000.0 * n / sample_rate;
-      if (!dry && (!wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk1.wav", out.data(), n, sample_rate, &err) ||
-                   !wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk2.wav", out.data() + n, n, sample_rate, &err))) {
+      const double audio_ms = 1000.0 * n / out_rate;
+      if (write_out && (!wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk1.wav", out.data(), n, out_rate, &err) ||
+                   !wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk2.wav", out.data() + n, n, out_rate, &err))) {
         fail(err);
         break;
       }
@@ -515,15 +639,17 @@ int main(int argc, char** argv) {
       std::lock_guard<std::mutex> l(io_mu);
       if (streamed)
         printf("process: %s RTF: %.4f (%lld pushes of %d samples, %lld launches, %lld bytes of stream state)%s\n", w[0].c_str(),
-               ms / audio_ms, stream_pushes, stream_n, stream_launches, ws_engine_info(engine, "stream_state_bytes"),
+               ms / audio_ms, stream_pushes, stream_samples, stream_launches, ws_engine_info(engine, "stream_state_bytes"),
                dry ? " [dry run]" : "");
       else if (chunked)
         printf("process: %s RTF: %.4f (%lld windows in %lld forwards: %lld launches, %lld MiB arena)%s\n", w[0].c_str(), ms / audio_ms,
-               ws_engine_info(engine, "long_windows"), ws_engine_info(engine, "long_forwards"), ws_engine_info(engine, "n_launches"),
+               plain_launches >= 0 ? long_w : ws_engine_info(engine, "long_windows"),
+               plain_launches >= 0 ? long_f : ws_engine_info(engine, "long_forwards"),
+               plain_launches >= 0 ? plain_launches : ws_engine_info(engine, "n_launches"),
                ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");
       else
         printf("process: %s RTF: %.4f (%lld launches, %lld MiB arena)%s\n", w[0].c_str(), ms / audio_ms,
-               ws_engine_info(engine, "n_launches"), ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");
+               plain_launches >= 0 ? plain_launches : ws_engine_info(engine, "n_launches"), ws_engine_info(engine, "arena_bytes") >> 20, dry ? " [dry run]" : "");
       if (ws_engine_info(engine, "cluster_fallbacks") > fallbacks_seen) {
         fallbacks_seen = ws_engine_info(engine, "cluster_fallbacks");
         printf("note: %s: a cluster recurrence timed out (GPU shared); recomputed by the streaming kernels\n", w[0].c_str());

@@ -10,6 +10,8 @@
 // to the other buffer -- 3 R X + 10 entry-point calls (WS_STREAM_GROUP_LAUNCHES).  A stream opened with
 // WS_STREAM_BLOCK_KERNEL runs every block as ONE call, ws_tcn_block_stream_fwd: R X + 10 (WS_STREAM_BLOCK_GROUP_LAUNCHES).
 // =================================================================================================================
+#include <optional>
+
 #include "engine_internal.h"
 
 using namespace wsrt;
@@ -70,6 +72,7 @@ struct ws_stream : wsrt::StreamWeights {
   long long n = 0, k = 0;               // samples pushed, frames run
   bool done = false, failed = false;
   bool block_kernel = false;            // WS_STREAM_BLOCK_KERNEL: one call per block
+  bool dev_io = false;                  // the inner stream of a rate stream (rate.cc): chunks and estimates are DEVICE buffers
 };
 
 namespace {
@@ -99,7 +102,8 @@ int zero_cols(ws_engine* e, float* p, int pitch, int from, int to, int rows) {
 }
 
 // frames [k, k + Tc) from the first (Tc - 1) s + 160 pending samples; est [rows][Tc s] goes to host columns [col, col + Tc s)
-int run_group(ws_stream* st, int Tc, float* host_est, int host_pitch, int col) {
+// (a rate stream's inner stream: est is a device buffer, the copy is device to device)
+int run_group(ws_stream* st, int Tc, float* host_est, long long host_pitch, int col) {
   ws_engine* e = st->e;
   const TasNet& t = e->tas;
   const int N = t.N, L = t.L, B = t.B, H = t.H, P = t.P, s = L / 2, R = st->rows;
@@ -164,8 +168,8 @@ int run_group(ws_stream* st, int Tc, float* host_est, int host_pitch, int col) {
     if ((rc = tas_gemm(e, d)) != WS_OK) return rc;
     WS_RUN(e, ws_ola_stream_fwd(fr, st->dec_b, R, Tc, L, s, st->carry, est, q));
   }
-  if ((rc = copy2d(e, host_est + col, size_t(host_pitch) * 4, est, size_t(Tc) * s * 4, size_t(Tc) * s * 4, R, hipMemcpyDeviceToHost,
-                   "device-to-host copy")) != WS_OK)
+  if ((rc = copy2d(e, host_est + col, size_t(host_pitch) * 4, est, size_t(Tc) * s * 4, size_t(Tc) * s * 4, R,
+                   st->dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, "device-to-host copy")) != WS_OK)
     return rc;
   // the unconsumed pending samples move to the OTHER buffer (no overlapping copy in place)
   const int keep = st->npend - Tc * s;
@@ -232,6 +236,13 @@ WS_ENGINE_API int ws_engine_stream_open(ws_engine* e, int rows, const void* enro
 
 WS_ENGINE_API int ws_engine_stream_open_ex(ws_engine* e, int rows, const void* enroll, int enroll_kind, int enroll_len,
                                            int max_chunk_frames, unsigned flags, ws_stream** out) {
+  return wsrt::stream_open_impl(e, rows, enroll, enroll_kind, enroll_len, max_chunk_frames, flags, 0, out, nullptr);
+}
+
+// extra_floats > 0: the state allocation gets one more slot of that many floats, returned in *extra, and the stream takes
+// and returns DEVICE buffers (stream_push_impl / stream_flush_impl): the inner stream of a rate stream (rate.cc)
+int wsrt::stream_open_impl(ws_engine* e, int rows, const void* enroll, int enroll_kind, int enroll_len, int max_chunk_frames,
+                           unsigned flags, size_t extra_floats, ws_stream** out, float** extra) {
   int rc = check_engine(e, "ws_engine_stream_open");
   if (rc != WS_OK) return rc;
   if (out) *out = nullptr;
@@ -275,6 +286,8 @@ WS_ENGINE_API int ws_engine_stream_open_ex(ws_engine* e, int rows, const void* e
   slot(size_t(rows) * st->pcap);
   slot(size_t(rows) * e->E);
   for (int r = 0; r < t.R; ++r) slot(size_t(rows) * H);
+  if (extra_floats) slot(extra_floats);
+  st->dev_io = extra_floats != 0;
   st->state_bytes = total;
   if (e->dry) {
     st->state = static_cast<char*>(malloc(total));
@@ -295,6 +308,7 @@ WS_ENGINE_API int ws_engine_stream_open_ex(ws_engine* e, int rows, const void* e
   size_t si = nblocks;
   st->carry = at(si++), st->carry0 = at(si++), st->pend[0] = at(si++), st->pend[1] = at(si++), st->emb = at(si++);
   for (int r = 0; r < t.R; ++r) st->rb.push_back(at(si++));
+  if (extra_floats) *extra = at(si++);
   // ---- weights, resolved once ----
   resolve_stream_weights(e, st);
   for (int r = 0; r < t.R; ++r)
@@ -337,6 +351,18 @@ WS_ENGINE_API int ws_engine_stream_open_ex(ws_engine* e, int rows, const void* e
 }
 
 WS_ENGINE_API int ws_engine_stream_push(ws_stream* st, const float* chunk, int n, float* est, int est_cap, int* n_out) {
+  if (st && st->dev_io) {
+    set_err("ws_engine_stream_push: this stream belongs to a rate stream; use ws_engine_rate_stream_push");
+    return WS_ERR_INVALID;
+  }
+  return wsrt::stream_push_impl(st, chunk, n, n, est, -1, est_cap, n_out);
+}
+
+// The plain stream (host chunk and est, est's row pitch is the emitted count: est_pitch < 0), or the inner stream of a rate
+// stream (dev_io: device chunk and est of the given pitches; the caller holds the turn, counts the launches over its whole
+// call and synchronises once, after its own last copy).
+int wsrt::stream_push_impl(ws_stream* st, const float* chunk, long long chunk_pitch, int n, float* est, long long est_pitch,
+                           int est_cap, int* n_out) {
   int rc = check_stream(st, "ws_engine_stream_push");
   if (rc != WS_OK) return rc;
   ws_engine* e = st->e;
@@ -357,32 +383,43 @@ WS_ENGINE_API int ws_engine_stream_push(ws_stream* st, const float* chunk, int n
             emit, est_cap, WS_STREAM_PUSH_CAP(n, L));
     return WS_ERR_INVALID;
   }
-  ForwardTurn turn(e);
-  if (turn.rc != WS_OK) return turn.rc;
+  const bool dev = st->dev_io;
+  std::optional<ForwardTurn> turn;      // (the caller of a device-buffer stream holds the turn)
+  if (!dev) turn.emplace(e);
+  if (turn && turn->rc != WS_OK) return turn->rc;
   e->long_windows = e->long_forwards = 0;
-  e->n_launches = 0;
+  if (!dev) e->n_launches = 0;
+  if (est_pitch < 0) est_pitch = emit;
   st->failed = true;                    // until the push is complete
   int off = 0, col = 0;
   while (off < n) {
     // at most G s + 159 pending samples: a piece completes at most G frames, one group (and fewer than 160 stay pending)
     const int take = std::min(n - off, st->G * s + kLmax - 1 - st->npend);
-    if ((rc = copy2d(e, st->pend[st->cur] + st->npend, size_t(st->pcap) * 4, chunk + off, size_t(n) * 4, size_t(take) * 4, R,
-                     hipMemcpyHostToDevice, "host-to-device copy")) != WS_OK)
+    if ((rc = copy2d(e, st->pend[st->cur] + st->npend, size_t(st->pcap) * 4, chunk + off, size_t(chunk_pitch) * 4, size_t(take) * 4, R,
+                     dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, "host-to-device copy")) != WS_OK)
       return rc;
     st->npend += take, off += take, st->n += take;
     while (st->npend >= kLmax) {
       const int Tc = std::min((st->npend - kLmax) / s + 1, st->G);
-      if ((rc = run_group(st, Tc, est, static_cast<int>(emit), col)) != WS_OK) return rc;
+      if ((rc = run_group(st, Tc, est, est_pitch, col)) != WS_OK) return rc;
       col += Tc * s;
     }
   }
-  if ((rc = sync_stream(e)) != WS_OK) return rc;     // the one host synchronisation of a push
+  if (!dev && (rc = sync_stream(e)) != WS_OK) return rc;     // the one host synchronisation of a push
   st->failed = false;
   *n_out = static_cast<int>(emit);
   return WS_OK;
 }
 
 WS_ENGINE_API int ws_engine_stream_flush(ws_stream* st, float* est, int est_cap, int* n_out) {
+  if (st && st->dev_io) {
+    set_err("ws_engine_stream_flush: this stream belongs to a rate stream; use ws_engine_rate_stream_flush");
+    return WS_ERR_INVALID;
+  }
+  return wsrt::stream_flush_impl(st, est, -1, est_cap, n_out);
+}
+
+int wsrt::stream_flush_impl(ws_stream* st, float* est, long long est_pitch, int est_cap, int* n_out) {
   int rc = check_stream(st, "ws_engine_stream_flush");
   if (rc != WS_OK) return rc;
   ws_engine* e = st->e;
@@ -402,10 +439,13 @@ WS_ENGINE_API int ws_engine_stream_flush(ws_stream* st, float* est, int est_cap,
             emit, est_cap, est && n_out ? "" : ", est or n_out is NULL", WS_STREAM_FLUSH_CAP);
     return WS_ERR_INVALID;
   }
-  ForwardTurn turn(e);
-  if (turn.rc != WS_OK) return turn.rc;
+  const bool dev = st->dev_io;
+  std::optional<ForwardTurn> turn;      // (the caller of a device-buffer stream holds the turn)
+  if (!dev) turn.emplace(e);
+  if (turn && turn->rc != WS_OK) return turn->rc;
   e->long_windows = e->long_forwards = 0;
-  e->n_launches = 0;
+  if (!dev) e->n_launches = 0;
+  if (est_pitch < 0) est_pitch = emit;
   st->failed = true;
   int col = 0;
   while (st->k < target) {
@@ -413,13 +453,13 @@ WS_ENGINE_API int ws_engine_stream_flush(ws_stream* st, float* est, int est_cap,
     if ((rc = zero_cols(e, st->pend[st->cur], st->pcap, st->npend, st->pcap, R)) != WS_OK) return rc;
     st->npend = st->pcap;
     const int Tc = static_cast<int>(std::min<long long>(target - st->k, st->G));
-    if ((rc = run_group(st, Tc, est, static_cast<int>(emit), col)) != WS_OK) return rc;
+    if ((rc = run_group(st, Tc, est, est_pitch, col)) != WS_OK) return rc;
     col += Tc * s;
   }
-  if ((rc = copy2d(e, est + col, size_t(emit) * 4, st->carry, size_t(L - s) * 4, size_t(L - s) * 4, R, hipMemcpyDeviceToHost,
-                   "device-to-host copy")) != WS_OK)
+  if ((rc = copy2d(e, est + col, size_t(est_pitch) * 4, st->carry, size_t(L - s) * 4, size_t(L - s) * 4, R,
+                   dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, "device-to-host copy")) != WS_OK)
     return rc;
-  if ((rc = sync_stream(e)) != WS_OK) return rc;
+  if (!dev && (rc = sync_stream(e)) != WS_OK) return rc;
   st->failed = false;
   st->done = true;
   *n_out = static_cast<int>(emit);

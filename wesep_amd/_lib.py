@@ -318,6 +318,11 @@ _SIGS = {
     "ws_tcn_block_stream_fwd": (_i, [_p, _p, _p, _i] + [_p] * 11 + [_i, _i, _i, _i, _i, _i, C.c_float, _ll, _i, _p, _p, _p]),
     "ws_tcn_block_stream_rows_fwd": (_i, [_p, _p, _p, _i] + [_p] * 11 + [_i, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p, _i,
                                           _p, _p, _p]),
+    # sample rates (resample.hip): geometry and tap table on the host, whole-signal and streaming kernels
+    "ws_resample_geom": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "ws_resample_taps": (_i, [_i, _i, _p]),
+    "ws_resample_fwd": (_i, [_p, _ll, _i, _i, _i, _i, _p, _p, _ll, _p]),
+    "ws_resample_stream_fwd": (_i, [_p, _ll, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _i, _i, _p, _ll, _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

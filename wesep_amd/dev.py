@@ -2162,3 +2162,57 @@ def softmax_rows_bwd(y, dy, rows: int, n: int, scale: float, dx):
     for nm, t in (("y", y), ("dy", dy), ("dx", dx)):
         _chk(t, nm)
     _call("ws_softmax_rows_bwd", _p(y), _p(dy), rows, n, scale, _p(dx))
+
+
+# ---- sample rates (resample.hip) ----
+def resample_geom(rate_in: int, rate_out: int):
+    """(U, D, w, K) of rate_in -> rate_out (ws_resample_geom; host code, no device call)."""
+    v = [C.c_int(0) for _ in range(4)]
+    L.check(L.lib().ws_resample_geom(int(rate_in), int(rate_out), *[C.byref(x) for x in v]), "ws_resample_geom")
+    return tuple(x.value for x in v)
+
+
+def resample_taps(rate_in: int, rate_out: int) -> np.ndarray:
+    """The tap table [U, K] float32 of rate_in -> rate_out (ws_resample_taps: computed in double on the host, rounded once)."""
+    U, _, _, K = resample_geom(rate_in, rate_out)
+    taps = np.zeros((U, K), dtype=np.float32)
+    L.check(L.lib().ws_resample_taps(int(rate_in), int(rate_out), taps.ctypes.data), "ws_resample_taps")
+    return taps
+
+
+def _rows_ok(t, R: int, n: int, who: str, name: str):
+    """t is [R, pitch] float32 on the device with unit stride along a row and at least n samples a row -> its pitch"""
+    if t.dim() != 2 or t.shape[0] != R or not t.is_cuda or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise L.WesepHipError(f"{who}: {name} must be a float32 CUDA tensor [{R}, n] with unit stride along a row")
+    if t.shape[1] < n:
+        raise L.WesepHipError(f"{who}: {name} holds {t.shape[1]} samples a row, the call needs {n}")
+    pitch = t.stride(0) if R > 1 else max(t.stride(0), t.shape[1])
+    if R > 1 and pitch < t.shape[1]:
+        raise L.WesepHipError(f"{who}: the rows of {name} overlap")
+    return pitch
+
+
+def resample_fwd(x, n_in: int, rate_in: int, rate_out: int, taps, y):
+    """x [R, >= n_in] (rows of any pitch) -> y [R, >= ceil(U n_in / D)]; taps: the device copy of resample_taps."""
+    _chk(taps, "taps")
+    R = x.shape[0]
+    U, D, _, K = resample_geom(rate_in, rate_out)
+    _chk_room(taps, U * K, "ws_resample_fwd", "taps")
+    ldx = _rows_ok(x, R, n_in, "ws_resample_fwd", "x")
+    ldy = _rows_ok(y, R, -(-U * n_in // D), "ws_resample_fwd", "y")
+    _call("ws_resample_fwd", _p(x), ldx, R, n_in, int(rate_in), int(rate_out), _p(taps), _p(y), ldy)
+
+
+def resample_stream_fwd(buf, rate_in: int, rate_out: int, taps, lead: int, n_valid: int, final: bool, g_first: int, n_out: int,
+                        y, hist_from: int = 0, hist_len: int = 0, hist=None):
+    """The streaming form on buf [R, >= n_valid] = history | new samples (include/wesep_hip.h, ws_resample_stream_fwd):
+    n_out outputs from phase 0 of group g_first to y [R, >= n_out]; buf[:, hist_from : hist_from + hist_len] to hist."""
+    _chk(taps, "taps")
+    R = buf.shape[0]
+    U, _, _, K = resample_geom(rate_in, rate_out)
+    _chk_room(taps, U * K, "ws_resample_stream_fwd", "taps")
+    ldb = _rows_ok(buf, R, n_valid, "ws_resample_stream_fwd", "buf")
+    ldy = _rows_ok(y, R, n_out, "ws_resample_stream_fwd", "y") if y is not None else 0
+    ldh = _rows_ok(hist, R, hist_len, "ws_resample_stream_fwd", "hist") if hist is not None else 0
+    _call("ws_resample_stream_fwd", _p(buf), ldb, R, int(rate_in), int(rate_out), _p(taps), int(lead), int(n_valid),
+          1 if final else 0, int(g_first), int(n_out), _p(y), ldy, int(hist_from), int(hist_len), _p(hist), ldh)

@@ -18,7 +18,9 @@ SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", 
            "ws_engine_separate_long", "ws_engine_stream_open", "ws_engine_stream_push", "ws_engine_stream_flush",
            "ws_engine_stream_reset", "ws_engine_stream_close", "ws_engine_pool_open", "ws_engine_pool_attach",
            "ws_engine_pool_push", "ws_engine_pool_flush", "ws_engine_pool_detach", "ws_engine_pool_close",
-           "ws_engine_stream_open_ex", "ws_engine_pool_open_ex")
+           "ws_engine_stream_open_ex", "ws_engine_pool_open_ex", "ws_engine_resample", "ws_engine_separate_rate",
+           "ws_engine_rate_stream_open", "ws_engine_rate_stream_push", "ws_engine_rate_stream_flush",
+           "ws_engine_rate_stream_reset", "ws_engine_rate_stream_close", "ws_engine_rate_stream_push_cap")
 STREAM_FLUSH_CAP = 160  # WS_STREAM_FLUSH_CAP
 STREAM_BLOCK_KERNEL = 1  # WS_STREAM_BLOCK_KERNEL: every block of a stream / pool group as one entry-point call
 _lib = None
@@ -80,6 +82,25 @@ def lib():
         l.ws_engine_pool_open_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_void_p)]
         l.ws_engine_pool_close.restype = None
         l.ws_engine_pool_close.argtypes = [C.c_void_p]
+        l.ws_engine_resample.restype = C.c_int
+        l.ws_engine_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                         C.POINTER(C.c_int)]
+        l.ws_engine_separate_rate.restype = C.c_int
+        l.ws_engine_separate_rate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                              C.c_int, C.c_void_p]
+        l.ws_engine_rate_stream_open.restype = C.c_int
+        l.ws_engine_rate_stream_open.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint,
+                                                 C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        l.ws_engine_rate_stream_push.restype = C.c_int
+        l.ws_engine_rate_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_rate_stream_flush.restype = C.c_int
+        l.ws_engine_rate_stream_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_rate_stream_reset.restype = C.c_int
+        l.ws_engine_rate_stream_reset.argtypes = [C.c_void_p]
+        l.ws_engine_rate_stream_close.restype = None
+        l.ws_engine_rate_stream_close.argtypes = [C.c_void_p]
+        l.ws_engine_rate_stream_push_cap.restype = C.c_int
+        l.ws_engine_rate_stream_push_cap.argtypes = [C.c_void_p, C.c_int]
         if l.ws_engine_abi_version() != ENGINE_ABI_VERSION:
             raise WesepHipError("libwesep_engine.so ABI version mismatch; rebuild")
         _lib = l
@@ -253,6 +274,43 @@ class Engine:
         the engine.  block_kernel=True (WS_STREAM_BLOCK_KERNEL): every block is one entry-point call."""
         return StreamPool(self, slots, max_chunk_frames, flags=STREAM_BLOCK_KERNEL if block_kernel else 0)
 
+    def resample(self, x, rate_in, rate_out):
+        """x [R, n] float32 at rate_in -> [R, ceil(U n / D)] float32 at rate_out (numpy, host): the device resampler of
+        wesep_amd.resample through the engine -- one upload, one launch, one download (ws_engine_resample)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise ValueError("Engine.resample: x is [R, n] with n >= 1")
+        R, n = x.shape
+        cap = -(-int(rate_out) * n // int(rate_in)) if rate_in > 0 and rate_out > 0 else 1      # ceil(U n / D); bad rates: refused below
+        y, m = np.zeros((R, max(cap, 1)), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_resample(self._h, x.ctypes.data, R, n, int(rate_in), int(rate_out), y.ctypes.data, cap, C.byref(m)),
+               "ws_engine_resample")
+        return y[:, :m.value]
+
+    def separate_rate(self, mix, enroll, kind, sample_rate, enroll_rate=0):
+        """separate() on audio at the caller's rate: mix [R, T] at sample_rate -> est [R, T] at sample_rate; an ENROLL_WAVE
+        enrollment is at enroll_rate (0: the container's).  Resample in, separate as it is, resample back and crop; with
+        every rate equal to the container's it IS separate() (ws_engine_separate_rate)."""
+        mix = np.ascontiguousarray(mix, dtype=np.float32)
+        enroll = np.ascontiguousarray(enroll, dtype=np.float32)
+        R, T = mix.shape
+        if enroll.shape[0] != R:
+            raise ValueError("one enrollment per mixture row")
+        est = np.zeros((R, T), dtype=np.float32)
+        length = 0 if kind in (ENROLL_EMBEDDING, ENROLL_SPEAKER) else enroll.shape[1]
+        _quiesce_torch()
+        _check(lib().ws_engine_separate_rate(self._h, mix.ctypes.data, R, T, int(sample_rate), enroll.ctypes.data, kind, length,
+                                             int(enroll_rate), est.ctypes.data), "ws_engine_separate_rate")
+        return est
+
+    def rate_stream(self, rows, enroll, kind, sample_rate, enroll_rate=0, max_chunk_frames=64, max_push=4800, block_kernel=False):
+        """stream() whose pushes carry and return samples at sample_rate: two stateful resamplers around the stream, all on
+        the device, one host synchronisation per push.  max_push: the samples a row the resamplers' buffers are sized for (a
+        longer push is taken in pieces).  Close the stream before the engine."""
+        return EngineRateStream(self, rows, enroll, kind, sample_rate, enroll_rate, max_chunk_frames, max_push,
+                                flags=STREAM_BLOCK_KERNEL if block_kernel else 0)
+
     def forward_pcm16(self, mix, spk1, spk2):
         """int16 [n], int16 [n_enroll] x 2 -> float32 [2, n] in [-1, 1] (SeparateEngine::ForwardFunc)."""
         mix, spk1, spk2 = (np.ascontiguousarray(x, dtype=np.int16) for x in (mix, spk1, spk2))
@@ -318,6 +376,74 @@ class EngineStream:
     def close(self):
         if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
             _lib.ws_engine_stream_close(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+RATE_STREAM_PIECE_LAUNCHES = 2      # WS_RATE_STREAM_PIECE_LAUNCHES: one ws_resample_stream_fwd per resampler that received samples
+
+
+def separate_rate_launches(mix_resampled, enroll_resampled):
+    """WS_SEPARATE_RATE_LAUNCHES: what ws_engine_separate_rate adds to ws_engine_separate's entry-point calls."""
+    return 2 * bool(mix_resampled) + bool(enroll_resampled)
+
+
+class EngineRateStream:
+    """ws_engine_rate_stream_* (include/wesep_engine.h): an EngineStream at the caller's sample rate.  The concatenation of
+    every push() and the flush() is Engine.resample -> EngineStream (same flags) -> Engine.resample, cropped to the samples
+    pushed."""
+
+    def __init__(self, engine, rows, enroll, kind, sample_rate, enroll_rate=0, max_chunk_frames=64, max_push=4800, flags=0):
+        self._h, self._engine, self.rows = C.c_void_p(), engine, int(rows)      # (the engine must outlive the stream)
+        enroll = np.ascontiguousarray(enroll, dtype=np.float32)
+        if enroll.shape[0] != self.rows:
+            raise ValueError("one enrollment per stream row")
+        length = 0 if kind in (ENROLL_EMBEDDING, ENROLL_SPEAKER) else enroll.shape[1]
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_stream_open(engine._h, self.rows, enroll.ctypes.data, kind, length, int(enroll_rate),
+                                                int(max_chunk_frames), int(flags), int(sample_rate), int(max_push),
+                                                C.byref(self._h)), "ws_engine_rate_stream_open")
+
+    def push_cap(self, n):
+        """samples a row that a push of n >= 1 samples returns at most (n = 0: the flush)."""
+        return int(lib().ws_engine_rate_stream_push_cap(self._h, int(n)))
+
+    def _out(self, buf, m):
+        return buf[:self.rows * m].reshape(self.rows, m).copy()
+
+    def push(self, chunk, est_cap=None):
+        """chunk [rows, n] at sample_rate, n >= 1 -> [rows, m] float32 at sample_rate, the samples that became final."""
+        chunk = np.ascontiguousarray(chunk, dtype=np.float32)
+        if chunk.ndim != 2 or chunk.shape[0] != self.rows:
+            raise ValueError(f"EngineRateStream.push: chunk is {chunk.shape}, expected [{self.rows}, n >= 1]")
+        n = chunk.shape[1]
+        cap = self.push_cap(n) if est_cap is None else int(est_cap)
+        buf, m = np.zeros(self.rows * max(cap, 1), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_stream_push(self._h, chunk.ctypes.data, n, buf.ctypes.data, cap, C.byref(m)),
+               "ws_engine_rate_stream_push")
+        return self._out(buf, m.value)
+
+    def flush(self, est_cap=None):
+        """The end of the stream: A's flush, the stream's rest and flush, B's flush; the total is at most the samples pushed."""
+        cap = self.push_cap(0) if est_cap is None else int(est_cap)
+        buf, m = np.zeros(self.rows * max(cap, 1), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_stream_flush(self._h, buf.ctypes.data, cap, C.byref(m)), "ws_engine_rate_stream_flush")
+        return self._out(buf, m.value)
+
+    def reset(self):
+        """Back to sample 0; the enrollment is kept."""
+        _check(lib().ws_engine_rate_stream_reset(self._h), "ws_engine_rate_stream_reset")
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
+            _lib.ws_engine_rate_stream_close(self._h)
         self._h = None
 
     def __del__(self):
