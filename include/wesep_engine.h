@@ -277,7 +277,7 @@ void ws_engine_pool_close(ws_pool* p);
  *     [1, 2^24], an enroll_rate with a kind that is not a waveform, est_cap below what the call emits, a flush before L samples
  *     at the container's rate, push or flush after a flush, n < 1, a NULL pointer.
  * The stream pool is NOT rate-aware: its pending samples live on the host, and per-slot rates need rows forms of the
- * resampler (per-row geometry, position and history slot), which do not exist yet. */
+ * resampler (per-row geometry, position and history slot): that pool is the rate pool below. */
 #define WS_SEPARATE_RATE_LAUNCHES(mix_resampled, enroll_resampled) (2 * ((mix_resampled) != 0) + ((enroll_resampled) != 0))
 #define WS_RATE_STREAM_PIECE_LAUNCHES 2
 typedef struct ws_rate_stream ws_rate_stream;
@@ -291,6 +291,55 @@ int ws_engine_rate_stream_flush(ws_rate_stream* s, float* est, int est_cap, int*
 int ws_engine_rate_stream_reset(ws_rate_stream* s);
 void ws_engine_rate_stream_close(ws_rate_stream* s);
 int ws_engine_rate_stream_push_cap(const ws_rate_stream* s, int n);
+
+/* Rate pool (new symbols, engine ABI 2 unchanged): the stream pool with a sample rate per slot -- calls at 8, 16 and 48 kHz in
+ * one push.  A slot is a rate stream of one row; one round carries one packet for any set of slots at any mix of rates, and the
+ * number of entry-point calls does not depend on how many slots or how many distinct rates the round holds.
+ *   ws_engine_rate_pool_open(e, slots, max_chunk_frames, flags, rates, n_rates, max_push, &pool)  rates [n_rates]: the sample
+ *     rates the pool will accept; the container's own is always accepted.  Every listed rate is validated in both directions
+ *     with the kernel's limits, by name, and every tap table is made and uploaded here.  max_push in [1, 2^24]: caller-rate
+ *     samples per slot per piece.  The state -- the pool's, two pending buffers and resampler B's two buffers per slot, the
+ *     output block, the tables -- is ONE device allocation sized from max_push and the worst listed geometry; it never grows
+ *     (ws_engine_info "stream_state_bytes", constant over attach, push, flush and detach).  flags: the word of
+ *     ws_engine_pool_open_ex.
+ *   ws_engine_rate_pool_attach(pool, enroll, enroll_kind, enroll_len, enroll_rate, sample_rate, &slot)  as ws_engine_pool_attach;
+ *     sample_rate must be one of the accepted rates (refused by name, the message lists them); a waveform enrollment at
+ *     enroll_rate != 0 is resampled first, as ws_engine_rate_stream_open does.
+ *   ws_engine_rate_pool_push(pool, n_active, slots, chunks, n, est, est_cap, n_out)  as ws_engine_pool_push with chunks and
+ *     estimates at each slot's own rate.  Entry i emits B's emission on the pool's emission on A's emission (known before
+ *     anything runs; est_cap[i] is checked before any launch; ws_engine_rate_pool_push_cap(pool, slot, n) always suffices).
+ *     A packet above max_push is taken in pieces, piece j of every slot that has one in round j: each slot sees the inner
+ *     pushes of a solo rate stream opened with the same max_push.  Per piece, all on the device: resampler A over all slots
+ *     (its history is caller samples and stays on the host; one staging block and the table are uploaded) -> the pool's
+ *     groups, each gathered from the slots' pending samples and scattered behind the slots' B histories by ws_rows_copy_fwd
+ *     -> one compaction copy of the pending samples -> resampler B over all slots -> one device-to-host copy of B's compact
+ *     block.  ONE host synchronisation per push.  A group is WS_RATE_POOL_GROUP_LAUNCHES(R, X) = WS_POOL_GROUP_LAUNCHES + 2
+ *     entry-point calls, a piece adds WS_RATE_POOL_PIECE_LAUNCHES = 3 (A, compaction, B; a step that has nothing to do in a
+ *     piece -- no frame complete yet -- does not run); with WS_STREAM_BLOCK_KERNEL the _BLOCK_ forms.
+ *   ws_engine_rate_pool_flush(pool, slot, est, est_cap, &n_out)  the end of ONE slot's stream: A's flush, the remaining frames,
+ *     the inner flush group and the overlap-add carry, B's steps, B's flush; the total is cropped to the samples pushed.
+ *   ws_engine_rate_pool_detach / _close  as the pool's.
+ * A slot at the container's rate runs the identity table (U = D = K = 1, the tap 1.0) through both resamplers: no delay, no
+ * filter; its samples are the plain pool's.  WS_ERR_INVALID with a message and nothing launched: the refusals of
+ * ws_engine_pool_* and ws_engine_rate_stream_* under this family's names (a container that cannot stream, an unknown flag
+ * bit, an enroll_rate with a kind that is not a waveform, a slot that is free, flushed or named twice, est_cap below the
+ * emission, a flush before L samples at the container's rate, a slot of a call that failed half way), slots outside
+ * [1, 65535], a rate outside the kernel's limits, an attach at a rate that was not listed. */
+#define WS_RATE_POOL_GROUP_LAUNCHES(R, X) (WS_POOL_GROUP_LAUNCHES(R, X) + 2)
+#define WS_RATE_POOL_BLOCK_GROUP_LAUNCHES(R, X) (WS_POOL_BLOCK_GROUP_LAUNCHES(R, X) + 2)
+#define WS_RATE_POOL_PIECE_LAUNCHES 3
+#define WS_RATE_POOL_BLOCK_PIECE_LAUNCHES 3
+typedef struct ws_rate_pool ws_rate_pool;
+int ws_engine_rate_pool_open(ws_engine* e, int slots, int max_chunk_frames, unsigned flags, const int* rates, int n_rates,
+                             int max_push, ws_rate_pool** out);
+int ws_engine_rate_pool_attach(ws_rate_pool* p, const void* enroll, int enroll_kind, int enroll_len, int enroll_rate,
+                               int sample_rate, int* slot);
+int ws_engine_rate_pool_push(ws_rate_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n,
+                             float* const* est, const int* est_cap, int* n_out);
+int ws_engine_rate_pool_push_cap(const ws_rate_pool* p, int slot, int n);
+int ws_engine_rate_pool_flush(ws_rate_pool* p, int slot, float* est, int est_cap, int* n_out);
+int ws_engine_rate_pool_detach(ws_rate_pool* p, int slot);
+void ws_engine_rate_pool_close(ws_rate_pool* p);
 
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by

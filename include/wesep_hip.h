@@ -1305,6 +1305,46 @@ int ws_resample_stream_fwd(const float* buf, long long ldb, int R, int rate_in, 
                            int n_valid, int final, int g_first, int n_out, float* y, long long ldy, int hist_from, int hist_len,
                            float* hist, long long ldh, void* stream);
 
+/* Rows forms (new symbols, ABI 20 unchanged): ONE launch for A rows that share nothing but the launch.
+ *   ws_resample_stream_rows_fwd  row i is ws_resample_stream_fwd with R = 1 on its own geometry, table, buffer, position,
+ *                   output range and history destination, all named by its descriptor rows[i]:
+ *                     buf + in_off    the row's `history | new samples`, n_valid valid ones
+ *                     taps + taps_off its table [U][K], any table that ws_resample_taps made, or the identity U = D = K = 1
+ *                                     with the one tap 1.0f (y = the input samples, bit for bit: the container's own rate)
+ *                     y + out_off     n_out outputs from phase 0 of group g_first
+ *                     hist + hist_off buf[in_off + hist_from .. + hist_len)
+ *                   with U, D, K explicit (w = (K - D) / 2) and lead, n_valid, final, g_first, n_out, hist_from, hist_len as
+ *                   in the solo call.  Offsets count floats into four arenas whose lengths are arguments.  The table comes
+ *                   twice: `rows`, a HOST pointer, is validated and sizes the grid; `d_rows` is a DEVICE pointer to the same
+ *                   bytes, uploaded by the caller on the same stream before the call (the convention of slot / t0 / tc above).
+ *                   Every row runs the device function of the two calls above, so its outputs and history are bit for bit
+ *                   what ws_resample_stream_fwd gives with R = 1 and the same arguments, whatever the other rows are.  Grid
+ *                   (max_i(nb_out_i + nb_hist_i), A); a workgroup beyond its row's count leaves before any barrier.  A row
+ *                   with U K <= 2048 stages its table in LDS (8 KB of dynamic LDS when any row does), another row of the
+ *                   same launch reads its table from global memory.  No atomics.  WS_ERR_INVALID before any launch, each
+ *                   with the row index: every check of ws_resample_stream_fwd, and U or D outside [1, WS_RESAMPLE_MAX_UD],
+ *                   K outside [1, WS_RESAMPLE_MAX_K], K < D, K - D odd, a range that leaves its arena, a y or hist range
+ *                   that overlaps any other range of the call (by address: the arenas may be parts of one allocation);
+ *                   A outside [1, 65535], a NULL pointer.
+ *   ws_rows_copy_fwd  row i: dst[dst_off + j] = src[src_off + j], j < len, then `fill` zeros behind them.  Pure data
+ *                   movement (a gather of per-slot samples into a rectangle, or the scatter back); the same two-table
+ *                   convention.  WS_ERR_INVALID before any launch, with the row index: len or fill negative or both 0, a range
+ *                   that leaves its arena, a dst range that overlaps any other range of the call. */
+typedef struct ws_resample_row {
+  long long in_off, taps_off, out_off, hist_off;
+  int U, D, K;
+  int lead, n_valid, final, g_first, n_out, hist_from, hist_len;
+} ws_resample_row;
+typedef struct ws_rows_copy_row {
+  long long src_off, dst_off;
+  int len, fill;
+} ws_rows_copy_row;
+int ws_resample_stream_rows_fwd(const ws_resample_row* rows, const ws_resample_row* d_rows, int A, const float* buf,
+                                long long n_buf, const float* taps, long long n_taps, float* y, long long n_y, float* hist,
+                                long long n_hist, void* stream);
+int ws_rows_copy_fwd(const ws_rows_copy_row* rows, const ws_rows_copy_row* d_rows, int A, const float* src, long long n_src,
+                     float* dst, long long n_dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

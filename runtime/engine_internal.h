@@ -12,6 +12,7 @@
 //   stream.cc        ws_engine_stream_*: causal cLN Conv-TasNet fed audio as it arrives, state carried on the device
 //   stream_pool.cc   ws_engine_pool_*: many such streams, each at its own position, through one launch chain per round
 //   rate.cc          audio at the caller's sample rate: ws_engine_resample, ws_engine_separate_rate, ws_engine_rate_stream_*
+//   rate_pool.cc     ws_engine_rate_pool_*: the stream pool with a sample rate per slot, on the rows forms of the resampler
 // Everything here lives in namespace wsrt and is built with -fvisibility=hidden: the library exports the C ABI only
 // (WS_ENGINE_API).  Host code only: no kernels in the runtime.
 #ifndef WESEP_ENGINE_INTERNAL_H_
@@ -452,6 +453,53 @@ int stream_open_impl(ws_engine* e, int rows, const void* enroll, int enroll_kind
 int stream_push_impl(ws_stream* st, const float* chunk, long long chunk_pitch, int n, float* est, long long est_pitch, int est_cap,
                      int* n_out);
 int stream_flush_impl(ws_stream* st, float* est, long long est_pitch, int est_cap, int* n_out);
+// ---- the stream pool's state (stream_pool.cc), and what a rate pool (rate_pool.cc) needs of it ----
+constexpr int kPoolLmax = 160;   // the longest window of the MultiEncoder (encoder.py:66-114)
+struct PoolSlot {
+  enum State { kFree, kAttached, kDone } state = kFree;
+  bool failed = false;         // a push or flush that named this slot ended half way
+  long long n = 0, k = 0;      // samples pushed, frames run
+  std::vector<float> pend;     // the samples from frame k's first one on (a rate pool keeps them on the device)
+};
+struct PoolGroup {             // host memory of one group, alive until the call's synchronisation
+  std::vector<float> stage, est;
+  std::vector<int> slot, tc, col;      // col: where the row's samples go in its caller's buffer
+  std::vector<long long> t0;
+  int Tc = 0;
+  // a group on DEVICE buffers (a rate pool): row i's pending samples are src_have[i] floats at state float src_off[i], its
+  // estimates go to state float dst_off[i]; the two ws_rows_copy_fwd tables stay alive here
+  std::vector<long long> src_off, dst_off;
+  std::vector<int> src_have;
+  std::vector<ws_rows_copy_row> gather, scatter;
+};
+}  // namespace wsrt
+
+struct ws_pool : wsrt::StreamWeights {
+  ws_engine* e = nullptr;
+  int nslots = 0, G = 0;
+  char* state = nullptr;                // the one allocation
+  size_t state_bytes = 0;
+  std::vector<float*> rb;               // per stack [nslots][H]
+  float *carry = nullptr, *carry0 = nullptr, *emb = nullptr;     // [nslots][L - s], [L - s], [nslots][E]
+  std::vector<wsrt::PoolSlot> slots;
+  std::vector<wsrt::PoolGroup> groups;  // of the call in hand
+  bool block_kernel = false;            // WS_STREAM_BLOCK_KERNEL: one call per block
+  bool device_io = false;               // a rate pool's: groups gather from and scatter to the state allocation
+};
+
+namespace wsrt {
+// who: the entry point's name in messages; extra_floats > 0: one more part of the ONE state allocation (*extra), and groups
+// run on device buffers (PoolGroup src_off / dst_off).  The caller holds no turn; attach takes the lowest free slot.
+int pool_open_impl(ws_engine* e, const char* who, int slots, int max_chunk_frames, unsigned flags, size_t extra_floats, ws_pool** out,
+                   float** extra);
+int pool_attach_impl(ws_pool* p, const char* who, const void* enroll, int enroll_kind, int enroll_len, int* slot);
+int pool_run_group(ws_pool* p, PoolGroup& g);
+int pool_check(const ws_pool* p, const char* who);
+void pool_free(ws_pool* p);
+// ---- what a rate pool needs of rate.cc: x [R][n] (host) at rate_in -> y [R][*n_out] (host) at rate_out, the kernel's limits and
+// the sizes refused by name as `who`; the caller holds the turn
+int resample_host_rows(ws_engine* e, const char* who, const float* x, int R, int n, int rate_in, int rate_out, std::vector<float>* y,
+                       int* n_out);
 int prepare_dpccn(ws_engine* e);
 int dpccn_device(ws_engine* e, const float* wav, int R, int T, const float* emb_in, float* est);
 int dp_conv_view(ws_engine* e, const float* x, int R, int H, int W, int Cin, int mode, int Wo, int sw, const float* Wm, int Cout,

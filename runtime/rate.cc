@@ -80,6 +80,16 @@ int check_resample_sizes(const char* who, const Geom& g, int R, int n) {
 
 }  // namespace
 
+int wsrt::resample_host_rows(ws_engine* e, const char* who, const float* x, int R, int n, int rate_in, int rate_out, std::vector<float>* y,
+                             int* n_out) {
+  Geom g;
+  int rc;
+  if ((rc = rate_geom(who, rate_in, rate_out, &g)) != WS_OK || (rc = check_resample_sizes(who, g, R, n)) != WS_OK) return rc;
+  *n_out = static_cast<int>(rs_len(g, n));
+  y->resize(size_t(R) * *n_out);
+  return resample_rows(e, x, R, n, rate_in, rate_out, g, y->data());
+}
+
 WS_ENGINE_API int ws_engine_resample(ws_engine* e, const float* x, int R, int n, int rate_in, int rate_out, float* y, int y_cap,
                                      int* n_out) {
   int rc = check_engine(e, "ws_engine_resample");

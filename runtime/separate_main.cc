@@ -3,7 +3,7 @@
 //
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
 //                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
-//                 [--stream_ms 10 [--stream_pool 4] [--stream_block]] [--resample]
+//                 [--stream_ms 10 [--stream_pool 4 | --rate_pool 4] [--stream_block]] [--resample]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -43,7 +43,9 @@
 // Plain, --batch and --chunk_seconds runs bring every file to the model's rate with ws_engine_resample, run as above (seconds
 // are seconds of audio) and bring the estimates back; --stream_ms feeds a rate stream (ws_engine_rate_stream_*) packets of M
 // ms at the mixture's own rate.  Outputs are written at the mixture's rate with the mixture's length.  Refused together
-// with --stream_pool (the pool is not rate-aware).  A --dry_run with --resample and an --output_dir writes the files too, all
+// with --stream_pool (the pool is not rate-aware; --rate_pool N is: N lines at a time through ws_engine_rate_pool_*, every line
+// at its own file's rate, packets of M ms at that rate, outputs at the mixture's rate and length; refused with --stream_pool,
+// --batch N > 1 and --chunk_seconds).  A --dry_run with --resample and an --output_dir writes the files too, all
 // zeros: their rate and length can be checked without a GPU.
 // --dry_run validates the model file and the launch plan of every utterance without a GPU and writes nothing.
 // --raw_out additionally writes the unquantised estimates as <key>-spk{1,2}.f32 (float32, for parity checks).
@@ -152,14 +154,16 @@ int main(int argc, char** argv) {
   const bool stream_block = args.has("stream_block");
   const unsigned stream_flags = stream_block ? WS_STREAM_BLOCK_KERNEL : 0u;
   const bool resample = args.has("resample");
+  const bool rate_pooled = args.has("rate_pool");
+  const int rate_pool_n = atoi(args.get("rate_pool", "0").c_str());
   // a dry run writes nothing -- except with --resample and an --output_dir: the (all-zero) files then show the rate and the
   // length an output will have
-  const bool write_out = !dry || (resample && !out_dir.empty());
+  const bool write_out = !dry || ((resample || rate_pooled) && !out_dir.empty());
   if (args.has("help")) {
     printf("usage: separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1]\n"
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
            "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]]\n"
-           "                     [--stream_ms M [--stream_pool N] [--stream_block]] [--resample]\n"
+           "                     [--stream_ms M [--stream_pool N | --rate_pool N] [--stream_block]] [--resample]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
@@ -175,7 +179,9 @@ int main(int argc, char** argv) {
            "  --stream_block     with --stream_ms M: every block of the separator as one call (WS_STREAM_BLOCK_KERNEL); the\n"
            "                     samples of a line then do not depend on the packet size or on the other lines of a pool\n"
            "  --resample         take files at any sample rate: resample to the model's rate on the device and back; outputs\n"
-           "                     have the mixture's rate and length.  Not together with --stream_pool\n");
+           "                     have the mixture's rate and length.  Not together with --stream_pool\n"
+           "  --rate_pool N      with --stream_ms M: N consecutive lines at a time through one rate pool, every line at its own\n"
+           "                     file's sample rate (packets of M ms at that rate); outputs have the mixture's rate and length\n");
     return 0;
   }
   if (chunked && batch > 1) return die("--chunk_seconds and --batch " + std::to_string(batch) + " conflict: a batch is a rectangle of "
@@ -185,7 +191,12 @@ int main(int argc, char** argv) {
     return die("--stream_pool conflicts with --batch N > 1 and --chunk_seconds: the pool's lines are streams, each fed as it arrives");
   if (pooled && resample)
     return die("--resample conflicts with --stream_pool: the stream pool is not rate-aware (its pending samples live on the host); use "
-               "--stream_ms alone");
+               "--stream_ms alone, or --rate_pool N for lines at their own rates through one pool");
+  if (rate_pooled && !streamed) return die("--rate_pool needs --stream_ms M: the pool is fed packets of M milliseconds");
+  if (rate_pooled && pooled) return die("--rate_pool conflicts with --stream_pool: one pool per run; --rate_pool takes lines at any rate");
+  if (rate_pooled && (batch > 1 || chunked))
+    return die("--rate_pool conflicts with --batch N > 1 and --chunk_seconds: the pool's lines are streams, each fed as it arrives");
+  if (rate_pooled && rate_pool_n < 1) return die("--rate_pool needs a positive number of lines");
   if (pooled && pool_n < 1) return die("--stream_pool needs a positive number of lines");
   if (stream_block && !streamed) return die("--stream_block needs --stream_ms M: it selects the block kernel of a stream or a stream pool");
   if (streamed && (batch > 1 || chunked))
@@ -259,6 +270,163 @@ int main(int argc, char** argv) {
       for (int r = 0; r < R; ++r) memcpy(out + size_t(r) * n, back.data() + size_t(r) * m, size_t(std::min(n, m)) * 4);
       return true;
     };
+    // --rate_pool N: as --stream_pool N, every line at its own file's rate through one rate pool (ws_engine_rate_pool_*); the
+    // accepted rates are those of the scp's mixtures, read before the pool is opened; outputs have the mixture's rate and length
+    if (rate_pooled) {
+      struct Lane {
+        bool live = false;
+        size_t line = 0;
+        wesep_rt::Wav mix;
+        std::vector<float> out, chunk;
+        int n = 0, pos = 0, done = 0, packet = 0, slot[2] = {-1, -1};
+        long long pushes = 0;
+        std::chrono::steady_clock::time_point t0;
+      };
+      std::vector<int> rates;
+      int max_packet = 1;
+      for (const auto& w : waves) {
+        wesep_rt::Wav hdr;
+        std::string err;
+        if (!wesep_rt::read_wav(w[1], &hdr, &err)) {
+          fail(err);
+          ws_engine_destroy(engine);
+          return;
+        }
+        if (std::find(rates.begin(), rates.end(), hdr.sample_rate) == rates.end()) rates.push_back(hdr.sample_rate);
+        max_packet = std::max(max_packet, static_cast<int>(stream_ms * hdr.sample_rate / 1000.0 + 0.5));
+      }
+      ws_rate_pool* pool = nullptr;
+      if (ws_engine_rate_pool_open(engine, 2 * rate_pool_n, 64, stream_flags, rates.data(), static_cast<int>(rates.size()), max_packet, &pool) != 0) {
+        fail(std::string("--rate_pool: ") + ws_engine_last_error());
+        ws_engine_destroy(engine);
+        return;
+      }
+      std::vector<Lane> lanes(rate_pool_n);
+      std::vector<std::vector<float>> got(size_t(2) * rate_pool_n);
+      bool ok = true;
+      long long rounds = 0, launches = 0;
+      double audio_ms = 0.0;
+      const auto pool_t0 = std::chrono::steady_clock::now();
+      auto start = [&](Lane& ln, int lane_id) {   // the next line into this lane: its enrollments at the model's rate, two slots at its rate
+        const size_t i = next++;
+        if (i >= waves.size() || failed) return;
+        const auto& w = waves[i];
+        wesep_rt::Wav s1, s2;
+        std::string err;
+        if (!wesep_rt::read_wav(w[1], &ln.mix, &err) || !wesep_rt::read_wav(w[2], &s1, &err) || !wesep_rt::read_wav(w[3], &s2, &err)) {
+          fail(err);
+          ok = false;
+          return;
+        }
+        const int rate = ln.mix.sample_rate;
+        ln.line = i, ln.n = static_cast<int>(ln.mix.samples.size()), ln.pos = ln.done = 0, ln.pushes = 0;
+        ln.packet = std::max(1, static_cast<int>(stream_ms * rate / 1000.0 + 0.5));
+        ln.out.assign(size_t(2) * ln.n, 0.f);
+        ln.t0 = std::chrono::steady_clock::now();
+        std::vector<float> e[2];
+        if (!to_model(s1.samples, s1.sample_rate, &e[0]) || !to_model(s2.samples, s2.sample_rate, &e[1])) {
+          fail(w[0] + ": " + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        const int n_enroll = static_cast<int>(std::min(e[0].size(), e[1].size()));
+        for (int k = 0; k < 2 && ok; ++k) {
+          if (ws_engine_rate_pool_attach(pool, e[k].data(), WS_ENROLL_WAVE, n_enroll, 0, rate, &ln.slot[k]) != 0) {
+            fail(w[0] + ": " + ws_engine_last_error());
+            ok = false;
+            return;
+          }
+          const int cap = std::max(ws_engine_rate_pool_push_cap(pool, ln.slot[k], ln.packet), ws_engine_rate_pool_push_cap(pool, ln.slot[k], 0));
+          got[size_t(2) * lane_id + k].assign(size_t(std::max(cap, 1)), 0.f);
+        }
+        ln.live = ok;
+      };
+      auto finish = [&](Lane& ln, int lane_id) {  // flush both slots, free them, write the line's files at the mixture's rate
+        const auto& w = waves[ln.line];
+        const int rate = ln.mix.sample_rate;
+        std::string err;
+        for (int k = 0; k < 2 && ok; ++k) {
+          int m = 0;
+          std::vector<float>& g = got[size_t(2) * lane_id + k];
+          if (ws_engine_rate_pool_flush(pool, ln.slot[k], g.data(), static_cast<int>(g.size()), &m) != 0 ||
+              ws_engine_rate_pool_detach(pool, ln.slot[k]) != 0) {
+            fail(w[0] + ": " + ws_engine_last_error());
+            ok = false;
+            return;
+          }
+          launches += ws_engine_info(engine, "n_launches");
+          memcpy(ln.out.data() + size_t(k) * ln.n + ln.done, g.data(), size_t(std::max(0, std::min(m, ln.n - ln.done))) * 4);
+        }
+        ln.live = false;
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ln.t0).count();
+        if (write_out && (!wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk1.wav", ln.out.data(), ln.n, rate, &err) ||
+                          !wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk2.wav", ln.out.data() + ln.n, ln.n, rate, &err))) {
+          fail(err);
+          ok = false;
+          return;
+        }
+        if (write_out && raw_out) {
+          for (int k = 0; k < 2; ++k) {
+            FILE* f = fopen((out_dir + "/" + w[0] + "-spk" + std::to_string(k + 1) + ".f32").c_str(), "wb");
+            if (!f || fwrite(ln.out.data() + size_t(k) * ln.n, 4, ln.n, f) != size_t(ln.n)) fail("cannot write raw output");
+            if (f) fclose(f);
+          }
+        }
+        std::lock_guard<std::mutex> l(io_mu);
+        printf("process: %s RTF: %.4f (rate pool of %d lines: %lld pushes of %d samples at %d Hz, %lld bytes of stream state)%s\n", w[0].c_str(),
+               ms / (1000.0 * ln.n / rate), rate_pool_n, ln.pushes, ln.packet, rate, ws_engine_info(engine, "stream_state_bytes"),
+               dry ? " [dry run]" : "");
+        audio_ms += 1000.0 * ln.n / rate;
+      };
+      for (int a = 0; a < rate_pool_n; ++a)
+        if (ok) start(lanes[a], a);
+      while (ok && !failed) {
+        std::vector<int> slots, ns, caps, n_out;
+        std::vector<const float*> chunks;
+        std::vector<float*> ests;
+        for (int a = 0; a < rate_pool_n; ++a) {
+          Lane& ln = lanes[a];
+          if (!ln.live) continue;
+          const int c = std::min(ln.packet, ln.n - ln.pos);
+          ln.chunk.resize(c);
+          for (int j = 0; j < c; ++j) ln.chunk[j] = static_cast<float>(ln.mix.samples[ln.pos + j]) / 32768.0f;
+          for (int k = 0; k < 2; ++k) {
+            slots.push_back(ln.slot[k]), ns.push_back(c), caps.push_back(static_cast<int>(got[size_t(2) * a + k].size()));
+            chunks.push_back(ln.chunk.data()), ests.push_back(got[size_t(2) * a + k].data());
+          }
+        }
+        if (slots.empty()) break;
+        n_out.assign(slots.size(), 0);
+        if (ws_engine_rate_pool_push(pool, static_cast<int>(slots.size()), slots.data(), chunks.data(), ns.data(), ests.data(), caps.data(),
+                                     n_out.data()) != 0) {
+          fail(std::string("--rate_pool: ") + ws_engine_last_error());
+          ok = false;
+          break;
+        }
+        launches += ws_engine_info(engine, "n_launches"), ++rounds;
+        size_t row = 0;
+        for (int a = 0; a < rate_pool_n && ok; ++a) {
+          Lane& ln = lanes[a];
+          if (!ln.live) continue;
+          for (int k = 0; k < 2; ++k, ++row)
+            memcpy(ln.out.data() + size_t(k) * ln.n + ln.done, ests[row], size_t(std::max(0, std::min(n_out[row], ln.n - ln.done))) * 4);
+          ln.done += std::min(n_out[row - 1], ln.n - ln.done), ln.pos += ns[row - 1], ++ln.pushes;
+          if (ln.pos >= ln.n) {
+            finish(ln, a);
+            if (ok) start(ln, a);
+          }
+        }
+      }
+      ws_engine_rate_pool_close(pool);
+      if (ok) {
+        std::lock_guard<std::mutex> l(io_mu);
+        printf("rate pool: %lld rounds, %lld launches\n", rounds, launches);
+        total_audio_ms += audio_ms;
+        total_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pool_t0).count();
+      }
+      ws_engine_destroy(engine);
+      return;
+    }
     // --stream_pool N: up to N lines in flight on one pool of 2 N slots; a lane takes the next line when its own ends
     if (pooled) {
       struct Lane {

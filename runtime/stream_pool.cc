@@ -13,6 +13,9 @@
 // product, synthesis GEMM, overlap-add -- 3 R X + 9 entry-point calls (WS_POOL_GROUP_LAUNCHES), whatever A is.  A pool opened
 // with WS_STREAM_BLOCK_KERNEL runs every block as ONE call, ws_tcn_block_stream_rows_fwd: R X + 9
 // (WS_POOL_BLOCK_GROUP_LAUNCHES); a slot's samples are then the same bits whatever else shares its rectangle.
+// A rate pool (rate_pool.cc) opens, attaches and runs its groups through the same functions (pool_open_impl, pool_attach_impl,
+// pool_run_group): its pending samples and its estimates' destination live in one more part of the state allocation, so a
+// group gathers its rectangle and scatters its estimates with ws_rows_copy_fwd in place of the upload and the download.
 // =================================================================================================================
 #include "engine_internal.h"
 
@@ -20,37 +23,7 @@ using namespace wsrt;
 
 namespace {
 
-constexpr int kLmax = 160;     // the longest window of the MultiEncoder (encoder.py:66-114)
-
-struct PoolSlot {
-  enum State { kFree, kAttached, kDone } state = kFree;
-  bool failed = false;         // a push or flush that named this slot ended half way
-  long long n = 0, k = 0;      // samples pushed, frames run
-  std::vector<float> pend;     // the samples from frame k's first one on
-};
-
-struct PoolGroup {             // host memory of one group, alive until the call's synchronisation
-  std::vector<float> stage, est;
-  std::vector<int> slot, tc, col;      // col: where the row's samples go in its caller's buffer
-  std::vector<long long> t0;
-  int Tc = 0;
-};
-
-}  // namespace
-
-struct ws_pool : wsrt::StreamWeights {
-  ws_engine* e = nullptr;
-  int nslots = 0, G = 0;
-  char* state = nullptr;                // the one allocation
-  size_t state_bytes = 0;
-  std::vector<float*> rb;               // per stack [nslots][H]
-  float *carry = nullptr, *carry0 = nullptr, *emb = nullptr;     // [nslots][L - s], [L - s], [nslots][E]
-  std::vector<PoolSlot> slots;
-  std::vector<PoolGroup> groups;        // of the call in hand
-  bool block_kernel = false;            // WS_STREAM_BLOCK_KERNEL: one call per block
-};
-
-namespace {
+constexpr int kLmax = kPoolLmax;
 
 int async_copy(ws_engine* e, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* what) {
   if (bytes == 0) return WS_OK;
@@ -83,20 +56,23 @@ int run_group(ws_pool* p, PoolGroup& g) {
   const int pitch = (Tc - 1) * s + kLmax;
   const long long M = (long long)A * Tc;
   void* q = e->stream;
-  g.stage.assign(size_t(A) * pitch, 0.f);
+  const bool dio = p->device_io;
+  if (!dio) g.stage.assign(size_t(A) * pitch, 0.f);
   g.t0.resize(A);
   for (int i = 0; i < A; ++i) {
     const PoolSlot& sl = p->slots[g.slot[i]];
     const size_t want = size_t(g.tc[i] - 1) * s + kLmax;
-    memcpy(g.stage.data() + size_t(i) * pitch, sl.pend.data(), std::min(want, sl.pend.size()) * 4);
+    if (!dio) memcpy(g.stage.data() + size_t(i) * pitch, sl.pend.data(), std::min(want, sl.pend.size()) * 4);
     g.t0[i] = sl.k;
   }
-  g.est.assign(size_t(A) * Tc * s, 0.f);
+  if (!dio) g.est.assign(size_t(A) * Tc * s, 0.f);
   Arena& a = e->work;
   const Arena::Mark mk = a.mark();
   float* x0 = a.alloc(size_t(A) * pitch);
   // the three tables in one block: t0 (8-byte entries) first, then slot and tc
   char* tab = reinterpret_cast<char*>(a.alloc(size_t(A) * 4));
+  ws_rows_copy_row* d_rows = dio ? reinterpret_cast<ws_rows_copy_row*>(a.alloc(size_t(A) * 2 * sizeof(ws_rows_copy_row) / 4)) : nullptr;
+  WS_PTR(!dio || d_rows);
   float* cat = a.alloc(size_t(M) * 3 * N);
   float* st0 = a.alloc(size_t(M) * 2);
   float* xa = a.alloc(size_t(M) * B);
@@ -113,7 +89,23 @@ int run_group(ws_pool* p, PoolGroup& g) {
   int* d_slot = reinterpret_cast<int*>(tab + size_t(A) * 8);
   int* d_tc = d_slot + A;
   int rc;
-  if ((rc = async_copy(e, x0, g.stage.data(), g.stage.size() * 4, hipMemcpyHostToDevice, "host-to-device copy")) != WS_OK) return rc;
+  float* const state = reinterpret_cast<float*>(p->state);
+  const long long state_floats = static_cast<long long>(p->state_bytes / 4);
+  if (dio) {
+    // the rectangle is gathered from the slots' pending samples on the device, zeros behind them (the staging block's zero fill);
+    // the estimates are scattered behind each slot's destination: two table-driven copies in place of the upload and download
+    g.gather.resize(A), g.scatter.resize(A);
+    for (int i = 0; i < A; ++i) {
+      const int want = (g.tc[i] - 1) * s + kLmax, len = std::min(want, g.src_have[i]);
+      g.gather[i] = ws_rows_copy_row{g.src_off[i], (long long)i * pitch, len, pitch - len};
+      g.scatter[i] = ws_rows_copy_row{(long long)i * Tc * s, g.dst_off[i], g.tc[i] * s, 0};
+    }
+    if ((rc = async_copy(e, d_rows, g.gather.data(), size_t(A) * sizeof(ws_rows_copy_row), hipMemcpyHostToDevice, "table upload")) != WS_OK) return rc;
+    if ((rc = async_copy(e, d_rows + A, g.scatter.data(), size_t(A) * sizeof(ws_rows_copy_row), hipMemcpyHostToDevice, "table upload")) != WS_OK) return rc;
+    WS_RUN(e, ws_rows_copy_fwd(g.gather.data(), d_rows, A, state, state_floats, x0, (long long)A * pitch, q));
+  } else if ((rc = async_copy(e, x0, g.stage.data(), g.stage.size() * 4, hipMemcpyHostToDevice, "host-to-device copy")) != WS_OK) {
+    return rc;
+  }
   if ((rc = async_copy(e, d_t0, g.t0.data(), size_t(A) * 8, hipMemcpyHostToDevice, "table upload")) != WS_OK) return rc;
   if ((rc = async_copy(e, d_slot, g.slot.data(), size_t(A) * 4, hipMemcpyHostToDevice, "table upload")) != WS_OK) return rc;
   if ((rc = async_copy(e, d_tc, g.tc.data(), size_t(A) * 4, hipMemcpyHostToDevice, "table upload")) != WS_OK) return rc;
@@ -161,7 +153,11 @@ int run_group(ws_pool* p, PoolGroup& g) {
     if ((rc = tas_gemm(e, d)) != WS_OK) return rc;
     WS_RUN(e, ws_ola_stream_rows_fwd(fr, p->dec_b, A, Tc, L, s, p->nslots, d_slot, d_t0, d_tc, p->carry, est, q));
   }
-  if ((rc = async_copy(e, g.est.data(), est, g.est.size() * 4, hipMemcpyDeviceToHost, "device-to-host copy")) != WS_OK) return rc;
+  if (dio) {
+    WS_RUN(e, ws_rows_copy_fwd(g.scatter.data(), d_rows + A, A, est, (long long)A * Tc * s, state, state_floats, q));
+  } else if ((rc = async_copy(e, g.est.data(), est, g.est.size() * 4, hipMemcpyDeviceToHost, "device-to-host copy")) != WS_OK) {
+    return rc;
+  }
   for (int i = 0; i < A; ++i) {
     PoolSlot& sl = p->slots[g.slot[i]];
     const size_t used = std::min(size_t(g.tc[i]) * s, sl.pend.size());
@@ -224,30 +220,35 @@ WS_ENGINE_API int ws_engine_pool_open(ws_engine* e, int slots, int max_chunk_fra
 }
 
 WS_ENGINE_API int ws_engine_pool_open_ex(ws_engine* e, int slots, int max_chunk_frames, unsigned flags, ws_pool** out) {
-  int rc = check_engine(e, "ws_engine_pool_open");
+  return pool_open_impl(e, "ws_engine_pool_open", slots, max_chunk_frames, flags, 0, out, nullptr);
+}
+
+int wsrt::pool_open_impl(ws_engine* e, const char* who, int slots, int max_chunk_frames, unsigned flags, size_t extra_floats, ws_pool** out,
+                         float** extra) {
+  int rc = check_engine(e, who);
   if (rc != WS_OK) return rc;
   if (out) *out = nullptr;
-  if (!tas_streamable(e)) return refuse_not_streamable(e, "ws_engine_pool_open");
+  if (!tas_streamable(e)) return refuse_not_streamable(e, who);
   if (flags & ~unsigned(WS_STREAM_BLOCK_KERNEL)) {
-    set_err("ws_engine_pool_open_ex: unknown flag bits 0x%x (known: WS_STREAM_BLOCK_KERNEL = 1)", flags & ~unsigned(WS_STREAM_BLOCK_KERNEL));
+    set_err("%s%s: unknown flag bits 0x%x (known: WS_STREAM_BLOCK_KERNEL = 1)", who, extra_floats ? "" : "_ex", flags & ~unsigned(WS_STREAM_BLOCK_KERNEL));
     return WS_ERR_INVALID;
   }
   if (!out) {
-    set_err("ws_engine_pool_open: out is NULL");
+    set_err("%s: out is NULL", who);
     return WS_ERR_INVALID;
   }
   if (slots < 1) {
-    set_err("ws_engine_pool_open: slots=%d, a pool has at least one", slots);
+    set_err("%s: slots=%d, a pool has at least one", who, slots);
     return WS_ERR_INVALID;
   }
   if (max_chunk_frames < 1 || max_chunk_frames > 65536) {
-    set_err("ws_engine_pool_open: max_chunk_frames=%d is outside [1, 65536]", max_chunk_frames);
+    set_err("%s: max_chunk_frames=%d is outside [1, 65536]", who, max_chunk_frames);
     return WS_ERR_INVALID;
   }
   const TasNet& t = e->tas;
   const int L = t.L, s = L / 2, H = t.H, G = max_chunk_frames;
   if ((long long)slots * G * 3 * t.N > 0x7fffffffLL || (long long)slots * ((long long)(t.P - 1) * (1 << (t.X - 1)) + G) * H > 0x7fffffffLL) {
-    set_err("ws_engine_pool_open: slots=%d with max_chunk_frames=%d reaches 2^31 elements in one buffer", slots, G);
+    set_err("%s: slots=%d with max_chunk_frames=%d reaches 2^31 elements in one buffer", who, slots, G);
     return WS_ERR_INVALID;
   }
   ForwardTurn turn(e);
@@ -271,6 +272,8 @@ WS_ENGINE_API int ws_engine_pool_open_ex(ws_engine* e, int slots, int max_chunk_
   part(size_t(L - s));
   part(size_t(slots) * e->E);
   for (int r = 0; r < t.R; ++r) part(size_t(slots) * H);
+  if (extra_floats) part(extra_floats);
+  p->device_io = extra_floats != 0;
   p->state_bytes = total;
   if (e->dry) {
     p->state = static_cast<char*>(malloc(total));
@@ -278,7 +281,7 @@ WS_ENGINE_API int ws_engine_pool_open_ex(ws_engine* e, int slots, int max_chunk_
     p->state = nullptr;
   }
   if (!p->state) {
-    set_err("ws_engine_pool_open: device allocation of %zu bytes failed", total);
+    set_err("%s: device allocation of %zu bytes failed", who, total);
     free_pool(p);
     return WS_ERR_LAUNCH;
   }
@@ -291,6 +294,7 @@ WS_ENGINE_API int ws_engine_pool_open_ex(ws_engine* e, int slots, int max_chunk_
   size_t si = nblocks;
   p->carry = at(si++), p->carry0 = at(si++), p->emb = at(si++);
   for (int r = 0; r < t.R; ++r) p->rb.push_back(at(si++));
+  if (extra_floats && extra) *extra = at(si++);
   resolve_stream_weights(e, p);
   for (int r = 0; r < t.R; ++r)
     for (int k = 0; k < t.X; ++k) {
@@ -308,18 +312,22 @@ WS_ENGINE_API int ws_engine_pool_open_ex(ws_engine* e, int slots, int max_chunk_
 }
 
 WS_ENGINE_API int ws_engine_pool_attach(ws_pool* p, const void* enroll, int enroll_kind, int enroll_len, int* slot) {
-  int rc = check_pool(p, "ws_engine_pool_attach");
+  return pool_attach_impl(p, "ws_engine_pool_attach", enroll, enroll_kind, enroll_len, slot);
+}
+
+int wsrt::pool_attach_impl(ws_pool* p, const char* who, const void* enroll, int enroll_kind, int enroll_len, int* slot) {
+  int rc = check_pool(p, who);
   if (rc != WS_OK) return rc;
   ws_engine* e = p->e;
   if (!enroll || !slot) {
-    set_err("ws_engine_pool_attach: bad arguments (enroll %s, slot %s)", enroll ? "given" : "NULL", slot ? "given" : "NULL");
+    set_err("%s: bad arguments (enroll %s, slot %s)", who, enroll ? "given" : "NULL", slot ? "given" : "NULL");
     return WS_ERR_INVALID;
   }
   if ((rc = tasnet_check_enroll(e, enroll_kind, enroll_len)) != WS_OK) return rc;
   int id = 0;
   while (id < p->nslots && p->slots[id].state != PoolSlot::kFree) ++id;
   if (id == p->nslots) {
-    set_err("ws_engine_pool_attach: the pool is full: all %d slots are attached (detach one, or open a larger pool)", p->nslots);
+    set_err("%s: the pool is full: all %d slots are attached (detach one, or open a larger pool)", who, p->nslots);
     return WS_ERR_INVALID;
   }
   const TasNet& t = e->tas;
@@ -493,3 +501,8 @@ WS_ENGINE_API void ws_engine_pool_close(ws_pool* p) {
   }
   free_pool(p);
 }
+
+// ---- for the rate pool (rate_pool.cc) ----
+int wsrt::pool_run_group(ws_pool* p, PoolGroup& g) { return run_group(p, g); }
+int wsrt::pool_check(const ws_pool* p, const char* who) { return check_pool(p, who); }
+void wsrt::pool_free(ws_pool* p) { free_pool(p); }

@@ -323,7 +323,16 @@ _SIGS = {
     "ws_resample_taps": (_i, [_i, _i, _p]),
     "ws_resample_fwd": (_i, [_p, _ll, _i, _i, _i, _i, _p, _p, _ll, _p]),
     "ws_resample_stream_fwd": (_i, [_p, _ll, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _i, _i, _p, _ll, _p]),
+    # rows forms: (host table, device table, A), then the arenas with their lengths in floats
+    "ws_resample_stream_rows_fwd": (_i, [_p, _p, _i, _p, _ll, _p, _ll, _p, _ll, _p, _ll, _p]),
+    "ws_rows_copy_fwd": (_i, [_p, _p, _i, _p, _ll, _p, _ll, _p]),
 }
+
+# the descriptors of the rows forms (include/wesep_hip.h: ws_resample_row, ws_rows_copy_row), field for field
+RESAMPLE_ROW = np.dtype([("in_off", "<i8"), ("taps_off", "<i8"), ("out_off", "<i8"), ("hist_off", "<i8"), ("U", "<i4"), ("D", "<i4"),
+                         ("K", "<i4"), ("lead", "<i4"), ("n_valid", "<i4"), ("final", "<i4"), ("g_first", "<i4"), ("n_out", "<i4"),
+                         ("hist_from", "<i4"), ("hist_len", "<i4")])
+ROWS_COPY_ROW = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("fill", "<i4")])
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None

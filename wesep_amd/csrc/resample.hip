@@ -16,6 +16,13 @@
 // 22.05k against 16k: 300 - 575 KB) does not fit and stays in global memory: lane q walks row q % U of the table
 // front to back, so every 64-byte line it fetches serves its next 16 taps from the vector cache, and the table is shared by
 // all workgroups through L2.  The two paths read the same floats in the same order.  Plain C++, no packed FP32.
+//
+// Rows forms (below the solo launch): ws_resample_stream_rows_fwd runs A rows, each with its own geometry, table, buffer,
+// position and destinations, through the same resample_one in one launch; ws_rows_copy_fwd is table-driven data movement.
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
 #include "common.h"
 
 namespace {
@@ -105,7 +112,170 @@ int rs_launch(const char* who, const float* buf, long long ldb, int R, const RsG
   return ws_check_launch(who);
 }
 
+// ---- rows forms: one launch for A rows, each with its own geometry, table, buffer, position and destinations -----------
+// grid (max_i(nb_out_i + nb_hist_i), A): workgroup (b, i) reads row i's descriptor (the same address in every lane) and
+// leaves before any barrier when b is beyond the row's own count -- blockIdx and the descriptor only, so the exit, the
+// history / output split and the choice of tap staging are workgroup-uniform.  Outputs run resample_one as above.
+__global__ __launch_bounds__(256) void resample_rows_kernel(const ws_resample_row* __restrict__ rows, const float* __restrict__ buf,
+                                                            const float* __restrict__ taps, float* __restrict__ y,
+                                                            float* __restrict__ hist) {
+  extern __shared__ float s_taps[];
+  const ws_resample_row r = rows[blockIdx.y];
+  const int nb_out = (r.n_out + 255) / 256, nb_hist = (r.hist_len + 255) / 256;
+  const int b = (int)blockIdx.x;
+  if (b >= nb_out + nb_hist) return;
+  const float* row = buf + r.in_off;
+  if (b >= nb_out) {
+    const int i = (b - nb_out) * 256 + (int)threadIdx.x;
+    if (i < r.hist_len) hist[r.hist_off + i] = row[r.hist_from + i];
+    return;
+  }
+  const float* tg = taps + r.taps_off;
+  const bool lds = r.U * r.K <= RS_LDS_TAPS;
+  if (lds) {
+    for (int i = threadIdx.x; i < r.U * r.K; i += 256) s_taps[i] = tg[i];
+    __syncthreads();
+  }
+  const int i = b * 256 + (int)threadIdx.x;
+  if (i >= r.n_out) return;
+  const int q = r.g_first * r.U + i;
+  const int grp = q / r.U, p = q - grp * r.U;
+  if (lds)
+    y[r.out_off + i] = resample_one(row, s_taps + p * r.K, r.D, r.K, r.lead, r.n_valid, grp);
+  else
+    y[r.out_off + i] = resample_one(row, tg + p * r.K, r.D, r.K, r.lead, r.n_valid, grp);
+}
+
+// grid (max_i nb_i, A): row i copies len floats and writes fill zeros behind them
+__global__ __launch_bounds__(256) void rows_copy_kernel(const ws_rows_copy_row* __restrict__ rows, const float* __restrict__ src,
+                                                        float* __restrict__ dst) {
+  const ws_rows_copy_row r = rows[blockIdx.y];
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < r.len)
+    dst[r.dst_off + i] = src[r.src_off + i];
+  else if (i < (long long)r.len + r.fill)
+    dst[r.dst_off + i] = 0.f;
+}
+
+// Address ranges of one rows call: a written range may meet no other range of the call, read or written (another
+// workgroup of the launch owns it).  Ranges that are only read may share.
+struct RsSpan {
+  uintptr_t lo, hi;
+  int row;
+  bool write;
+  const char* name;
+};
+
+int rs_spans_disjoint(const char* who, std::vector<RsSpan>& v) {
+  std::sort(v.begin(), v.end(), [](const RsSpan& a, const RsSpan& b) { return a.lo < b.lo; });
+  const RsSpan *far_r = nullptr, *far_w = nullptr;      // the read / written range that ends last so far
+  for (const RsSpan& x : v) {
+    const RsSpan* hit = far_w && x.lo < far_w->hi ? far_w : (x.write && far_r && x.lo < far_r->hi ? far_r : nullptr);
+    WS_REQUIRE(!hit, "%s: row %d: its %s range overlaps the %s range of row %d", who, x.row, x.name, hit->name, hit->row);
+    const RsSpan*& far = x.write ? far_w : far_r;
+    if (!far || x.hi > far->hi) far = &x;
+  }
+  return WS_OK;
+}
+
 }  // namespace
+
+extern "C" int ws_resample_stream_rows_fwd(const ws_resample_row* rows, const ws_resample_row* d_rows, int A, const float* buf,
+                                           long long n_buf, const float* taps, long long n_taps, float* y, long long n_y,
+                                           float* hist, long long n_hist, void* stream) {
+  const char* who = "ws_resample_stream_rows_fwd";
+  WS_REQUIRE(rows && d_rows && buf && taps, "%s: rows, d_rows, buf or taps is NULL", who);
+  WS_REQUIRE(A > 0 && A <= 65535, "%s: A=%d is outside [1, 65535]", who, A);
+  WS_REQUIRE(n_buf >= 0 && n_taps >= 0 && n_y >= 0 && n_hist >= 0, "%s: an arena length is negative (buf %lld, taps %lld, y %lld, hist %lld)",
+             who, n_buf, n_taps, n_y, n_hist);
+  std::vector<RsSpan> spans;
+  spans.reserve((size_t)A * 4);
+  int nb_max = 0;
+  bool any_lds = false;
+  for (int i = 0; i < A; ++i) {
+    const ws_resample_row& r = rows[i];
+    WS_REQUIRE(r.U >= 1 && r.D >= 1 && r.U <= RS_MAX_UD && r.D <= RS_MAX_UD, "%s: row %d: U=%d, D=%d; U and D lie in [1, %d]", who, i, r.U, r.D,
+               RS_MAX_UD);
+    WS_REQUIRE(r.K >= 1 && r.K <= RS_MAX_K, "%s: row %d: K=%d taps per output sample; K lies in [1, %d]", who, i, r.K, RS_MAX_K);
+    WS_REQUIRE(r.K >= r.D, "%s: row %d: K=%d is below D=%d", who, i, r.K, r.D);
+    WS_REQUIRE((r.K - r.D) % 2 == 0, "%s: row %d: K - D = %d is odd (K = 2 w + D)", who, i, r.K - r.D);
+    const int w = (r.K - r.D) / 2;
+    WS_REQUIRE(y || r.n_out == 0, "%s: row %d: y is NULL with n_out=%d", who, i, r.n_out);
+    WS_REQUIRE(hist || r.hist_len == 0, "%s: row %d: hist is NULL with hist_len=%d", who, i, r.hist_len);
+    WS_REQUIRE(r.n_valid > 0 && r.n_out >= 0 && r.hist_len >= 0 && r.n_out + (long long)r.hist_len > 0,
+               "%s: row %d: bad sizes (n_valid=%d >= 1, n_out=%d, hist_len=%d, one of them positive)", who, i, r.n_valid, r.n_out, r.hist_len);
+    WS_REQUIRE(r.lead >= 0 && r.lead <= w && r.g_first >= 0, "%s: row %d: lead=%d outside [0, w=%d] or g_first=%d negative", who, i, r.lead, w,
+               r.g_first);
+    WS_REQUIRE(r.in_off >= 0 && r.in_off <= n_buf - r.n_valid, "%s: row %d: buf [%lld, %lld + %d) leaves the arena of %lld floats", who, i,
+               r.in_off, r.in_off, r.n_valid, n_buf);
+    WS_REQUIRE(r.taps_off >= 0 && r.taps_off <= n_taps - (long long)r.U * r.K, "%s: row %d: taps [%lld, %lld + %d * %d) leaves the arena of %lld floats",
+               who, i, r.taps_off, r.taps_off, r.U, r.K, n_taps);
+    WS_REQUIRE(r.n_out == 0 || (r.out_off >= 0 && r.out_off <= n_y - r.n_out), "%s: row %d: y [%lld, %lld + %d) leaves the arena of %lld floats", who,
+               i, r.out_off, r.out_off, r.n_out, n_y);
+    WS_REQUIRE(r.hist_len == 0 || (r.hist_off >= 0 && r.hist_off <= n_hist - r.hist_len),
+               "%s: row %d: hist [%lld, %lld + %d) leaves the arena of %lld floats", who, i, r.hist_off, r.hist_off, r.hist_len, n_hist);
+    WS_REQUIRE(r.hist_from >= 0 && (long long)r.hist_from + r.hist_len <= r.n_valid, "%s: row %d: history [%d, %d + %d) leaves the %d valid samples",
+               who, i, r.hist_from, r.hist_from, r.hist_len, r.n_valid);
+    const long long q_end = (long long)r.g_first * r.U + r.n_out;
+    WS_REQUIRE(q_end + r.U + 256 < (1LL << 31) && (q_end / r.U + 2) * r.D + r.K < (1LL << 31) && (long long)r.n_valid + r.K + 256 < (1LL << 31),
+               "%s: row %d: offsets reach 2^31 (g_first=%d, n_out=%d, n_valid=%d)", who, i, r.g_first, r.n_out, r.n_valid);
+    if (r.n_out > 0) {
+      if (r.final) {
+        const long long span = (long long)r.n_valid + r.lead - w;
+        const long long allowed = span > 0 ? ((long long)r.U * span + r.D - 1) / r.D : 0;
+        WS_REQUIRE(q_end <= allowed, "%s: row %d: outputs up to %lld asked, the %d valid samples end the signal at output %lld", who, i, q_end,
+                   r.n_valid, allowed);
+      } else {
+        const long long last_grp = (q_end - 1) / r.U;
+        WS_REQUIRE(last_grp * r.D - r.lead + r.K <= r.n_valid,
+                   "%s: row %d: outputs up to %lld need %lld valid samples, %d are given and the end is not final", who, i, q_end,
+                   last_grp * r.D - r.lead + r.K, r.n_valid);
+      }
+    }
+    const auto span = [i](const float* p, long long off, long long n, bool wr, const char* name) {
+      return RsSpan{reinterpret_cast<uintptr_t>(p + off), reinterpret_cast<uintptr_t>(p + off + n), i, wr, name};
+    };
+    spans.push_back(span(buf, r.in_off, r.n_valid, false, "buf"));
+    spans.push_back(span(taps, r.taps_off, (long long)r.U * r.K, false, "taps"));
+    if (r.n_out > 0) spans.push_back(span(y, r.out_off, r.n_out, true, "y"));
+    if (r.hist_len > 0) spans.push_back(span(hist, r.hist_off, r.hist_len, true, "hist"));
+    nb_max = std::max(nb_max, (r.n_out + 255) / 256 + (r.hist_len + 255) / 256);
+    any_lds = any_lds || r.U * r.K <= RS_LDS_TAPS;
+  }
+  const int rc = rs_spans_disjoint(who, spans);
+  if (rc != WS_OK) return rc;
+  hipLaunchKernelGGL(resample_rows_kernel, dim3((unsigned)nb_max, (unsigned)A), dim3(256), any_lds ? RS_LDS_TAPS * sizeof(float) : 0,
+                     (hipStream_t)stream, d_rows, buf, taps, y, hist);
+  return ws_check_launch(who);
+}
+
+extern "C" int ws_rows_copy_fwd(const ws_rows_copy_row* rows, const ws_rows_copy_row* d_rows, int A, const float* src, long long n_src,
+                                float* dst, long long n_dst, void* stream) {
+  const char* who = "ws_rows_copy_fwd";
+  WS_REQUIRE(rows && d_rows && src && dst, "%s: rows, d_rows, src or dst is NULL", who);
+  WS_REQUIRE(A > 0 && A <= 65535, "%s: A=%d is outside [1, 65535]", who, A);
+  WS_REQUIRE(n_src >= 0 && n_dst >= 0, "%s: an arena length is negative (src %lld, dst %lld)", who, n_src, n_dst);
+  std::vector<RsSpan> spans;
+  spans.reserve((size_t)A * 2);
+  long long nb_max = 0;
+  for (int i = 0; i < A; ++i) {
+    const ws_rows_copy_row& r = rows[i];
+    WS_REQUIRE(r.len >= 0 && r.fill >= 0 && (long long)r.len + r.fill > 0 && (long long)r.len + r.fill + 256 < (1LL << 31),
+               "%s: row %d: bad sizes (len=%d >= 0, fill=%d >= 0, one of them positive, their sum below 2^31)", who, i, r.len, r.fill);
+    WS_REQUIRE(r.len == 0 || (r.src_off >= 0 && r.src_off <= n_src - r.len), "%s: row %d: src [%lld, %lld + %d) leaves the arena of %lld floats", who,
+               i, r.src_off, r.src_off, r.len, n_src);
+    WS_REQUIRE(r.dst_off >= 0 && r.dst_off <= n_dst - ((long long)r.len + r.fill),
+               "%s: row %d: dst [%lld, %lld + %d + %d) leaves the arena of %lld floats", who, i, r.dst_off, r.dst_off, r.len, r.fill, n_dst);
+    if (r.len > 0)
+      spans.push_back(RsSpan{reinterpret_cast<uintptr_t>(src + r.src_off), reinterpret_cast<uintptr_t>(src + r.src_off + r.len), i, false, "src"});
+    spans.push_back(RsSpan{reinterpret_cast<uintptr_t>(dst + r.dst_off), reinterpret_cast<uintptr_t>(dst + r.dst_off + r.len + r.fill), i, true, "dst"});
+    nb_max = std::max(nb_max, ((long long)r.len + r.fill + 255) / 256);
+  }
+  const int rc = rs_spans_disjoint(who, spans);
+  if (rc != WS_OK) return rc;
+  hipLaunchKernelGGL(rows_copy_kernel, dim3((unsigned)nb_max, (unsigned)A), dim3(256), 0, (hipStream_t)stream, d_rows, src, dst);
+  return ws_check_launch(who);
+}
 
 extern "C" int ws_resample_geom(int rate_in, int rate_out, int* U, int* D, int* w, int* K) {
   WS_REQUIRE(U && D && w && K, "ws_resample_geom: U, D, w or K is NULL");

@@ -2216,3 +2216,69 @@ def resample_stream_fwd(buf, rate_in: int, rate_out: int, taps, lead: int, n_val
     ldh = _rows_ok(hist, R, hist_len, "ws_resample_stream_fwd", "hist") if hist is not None else 0
     _call("ws_resample_stream_fwd", _p(buf), ldb, R, int(rate_in), int(rate_out), _p(taps), int(lead), int(n_valid),
           1 if final else 0, int(g_first), int(n_out), _p(y), ldy, int(hist_from), int(hist_len), _p(hist), ldh)
+
+
+def _rows_table(rows, dtype, who: str) -> np.ndarray:
+    """The descriptor table of a rows form: a list of dicts (a field left out is 0), or a structured array that is taken as
+    it is.  ONE array: the call reads its bytes on the host and uploads the same bytes."""
+    if isinstance(rows, np.ndarray):
+        if rows.dtype != dtype or rows.ndim != 1 or not rows.flags.c_contiguous:
+            raise L.WesepHipError(f"{who}: the table must be a contiguous 1-D array of {dtype.names}")
+        return rows
+    tab = np.zeros(len(rows), dtype=dtype)
+    for i, r in enumerate(rows):
+        unknown = set(r) - set(dtype.names)
+        if unknown:
+            raise L.WesepHipError(f"{who}: row {i} has unknown fields {sorted(unknown)}")
+        for k, v in r.items():
+            tab[i][k] = int(v)
+    return tab
+
+
+def resample_rows_table(rows) -> np.ndarray:
+    """ws_resample_row [A] (include/wesep_hip.h) from dicts with the fields in_off, taps_off, out_off, hist_off, U, D, K, lead,
+    n_valid, final, g_first, n_out, hist_from, hist_len."""
+    return _rows_table(rows, L.RESAMPLE_ROW, "ws_resample_stream_rows_fwd")
+
+
+def rows_copy_table(rows) -> np.ndarray:
+    """ws_rows_copy_row [A] from dicts with the fields src_off, dst_off, len, fill."""
+    return _rows_table(rows, L.ROWS_COPY_ROW, "ws_rows_copy_fwd")
+
+
+def _arena(t, who: str, name: str) -> int:
+    """a 1-D contiguous float32 CUDA tensor (or None) -> its length in floats"""
+    if t is None:
+        return 0
+    _chk(t, f"{who}: {name}")
+    if t.dim() != 1:
+        raise L.WesepHipError(f"{who}: {name} is an arena: a 1-D tensor, got {tuple(t.shape)}")
+    return t.numel()
+
+
+def resample_stream_rows_fwd(rows, buf, taps, y, hist=None):
+    """ws_resample_stream_rows_fwd: ONE launch for the rows of `rows` (resample_rows_table, or the dicts it takes); buf, taps,
+    y, hist: the four arenas, 1-D float32 on one device.  The host table and the device table are the same numpy array; the
+    upload goes on the current stream, in front of the launch.  Returns the device table (alive until the launch has run)."""
+    who = "ws_resample_stream_rows_fwd"
+    tab = resample_rows_table(rows)
+    lens = [_arena(t, who, nm) for nm, t in (("buf", buf), ("taps", taps), ("y", y), ("hist", hist))]
+    if buf is None or taps is None:
+        raise L.WesepHipError(f"{who}: buf and taps must be given")
+    d_tab = L.upload_struct_array(tab, buf.device)
+    _call(who, C.c_void_p(tab.ctypes.data), C.c_void_p(d_tab.data_ptr()), len(tab), _p(buf), lens[0], _p(taps), lens[1], _p(y), lens[2],
+          _p(hist), lens[3])
+    return d_tab
+
+
+def rows_copy_fwd(rows, src, dst):
+    """ws_rows_copy_fwd: row i copies src[src_off : src_off + len] to dst[dst_off :] and writes `fill` zeros behind it; src and
+    dst are arenas as above.  Returns the device table."""
+    who = "ws_rows_copy_fwd"
+    tab = rows_copy_table(rows)
+    n_src, n_dst = _arena(src, who, "src"), _arena(dst, who, "dst")
+    if src is None or dst is None:
+        raise L.WesepHipError(f"{who}: src and dst must be given")
+    d_tab = L.upload_struct_array(tab, src.device)
+    _call(who, C.c_void_p(tab.ctypes.data), C.c_void_p(d_tab.data_ptr()), len(tab), _p(src), n_src, _p(dst), n_dst)
+    return d_tab

@@ -20,7 +20,9 @@ SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", 
            "ws_engine_pool_push", "ws_engine_pool_flush", "ws_engine_pool_detach", "ws_engine_pool_close",
            "ws_engine_stream_open_ex", "ws_engine_pool_open_ex", "ws_engine_resample", "ws_engine_separate_rate",
            "ws_engine_rate_stream_open", "ws_engine_rate_stream_push", "ws_engine_rate_stream_flush",
-           "ws_engine_rate_stream_reset", "ws_engine_rate_stream_close", "ws_engine_rate_stream_push_cap")
+           "ws_engine_rate_stream_reset", "ws_engine_rate_stream_close", "ws_engine_rate_stream_push_cap",
+           "ws_engine_rate_pool_open", "ws_engine_rate_pool_attach", "ws_engine_rate_pool_push", "ws_engine_rate_pool_push_cap",
+           "ws_engine_rate_pool_flush", "ws_engine_rate_pool_detach", "ws_engine_rate_pool_close")
 STREAM_FLUSH_CAP = 160  # WS_STREAM_FLUSH_CAP
 STREAM_BLOCK_KERNEL = 1  # WS_STREAM_BLOCK_KERNEL: every block of a stream / pool group as one entry-point call
 _lib = None
@@ -101,6 +103,21 @@ def lib():
         l.ws_engine_rate_stream_close.argtypes = [C.c_void_p]
         l.ws_engine_rate_stream_push_cap.restype = C.c_int
         l.ws_engine_rate_stream_push_cap.argtypes = [C.c_void_p, C.c_int]
+        l.ws_engine_rate_pool_open.restype = C.c_int
+        l.ws_engine_rate_pool_open.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        l.ws_engine_rate_pool_attach.restype = C.c_int
+        l.ws_engine_rate_pool_attach.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_rate_pool_push.restype = C.c_int
+        l.ws_engine_rate_pool_push.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+        l.ws_engine_rate_pool_push_cap.restype = C.c_int
+        l.ws_engine_rate_pool_push_cap.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        l.ws_engine_rate_pool_flush.restype = C.c_int
+        l.ws_engine_rate_pool_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_rate_pool_detach.restype = C.c_int
+        l.ws_engine_rate_pool_detach.argtypes = [C.c_void_p, C.c_int]
+        l.ws_engine_rate_pool_close.restype = None
+        l.ws_engine_rate_pool_close.argtypes = [C.c_void_p]
         if l.ws_engine_abi_version() != ENGINE_ABI_VERSION:
             raise WesepHipError("libwesep_engine.so ABI version mismatch; rebuild")
         _lib = l
@@ -303,6 +320,11 @@ class Engine:
         _check(lib().ws_engine_separate_rate(self._h, mix.ctypes.data, R, T, int(sample_rate), enroll.ctypes.data, kind, length,
                                              int(enroll_rate), est.ctypes.data), "ws_engine_separate_rate")
         return est
+
+    def rate_pool(self, slots, rates, max_chunk_frames=64, max_push=4800, block_kernel=False):
+        """A stream pool whose slots have their own sample rates (`rates`: the rates it will accept; the container's own always
+        is): one launch chain per push whatever the number of slots and distinct rates in it.  Close it before the engine."""
+        return RatePool(self, slots, rates, max_chunk_frames, max_push, flags=STREAM_BLOCK_KERNEL if block_kernel else 0)
 
     def rate_stream(self, rows, enroll, kind, sample_rate, enroll_rate=0, max_chunk_frames=64, max_push=4800, block_kernel=False):
         """stream() whose pushes carry and return samples at sample_rate: two stateful resamplers around the stream, all on
@@ -525,6 +547,87 @@ class StreamPool:
     def close(self):
         if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
             _lib.ws_engine_pool_close(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+RATE_POOL_PIECE_LAUNCHES = 3        # WS_RATE_POOL_PIECE_LAUNCHES: resampler A, the pending samples' compaction, resampler B
+RATE_POOL_BLOCK_PIECE_LAUNCHES = 3  # WS_RATE_POOL_BLOCK_PIECE_LAUNCHES
+
+
+def rate_pool_group_launches(R, X):
+    """WS_RATE_POOL_GROUP_LAUNCHES: a pool group, its gather and its scatter -- whatever the slots and rates in it."""
+    return pool_group_launches(R, X) + 2
+
+
+def rate_pool_block_group_launches(R, X):
+    """WS_RATE_POOL_BLOCK_GROUP_LAUNCHES: the same for a pool opened with block_kernel=True."""
+    return pool_block_group_launches(R, X) + 2
+
+
+class RatePool:
+    """ws_engine_rate_pool_* (include/wesep_engine.h): a StreamPool whose slots carry and return audio at their own sample
+    rates.  Every slot is an EngineRateStream of one row: the concatenation of what its pushes and its flush return is what
+    that stream returns for the same packets, whatever the other slots, their rates and their audio were."""
+
+    def __init__(self, engine, slots, rates, max_chunk_frames=64, max_push=4800, flags=0):
+        self._h, self._engine, self.slots = C.c_void_p(), engine, int(slots)    # (the engine must outlive the pool)
+        rates = np.ascontiguousarray(list(rates), dtype=np.int32)
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_pool_open(engine._h, self.slots, int(max_chunk_frames), int(flags), rates.ctypes.data, len(rates),
+                                              int(max_push), C.byref(self._h)), "ws_engine_rate_pool_open")
+
+    def attach(self, enroll, kind, sample_rate, enroll_rate=0):
+        """One enrollment -- [E] (ENROLL_EMBEDDING / ENROLL_SPEAKER) or [Tw] (ENROLL_WAVE, at enroll_rate or the container's)
+        -- and the rate of the slot's audio -> the slot it took."""
+        enroll = np.ascontiguousarray(enroll, dtype=np.float32).reshape(-1)
+        length = 0 if kind in (ENROLL_EMBEDDING, ENROLL_SPEAKER) else enroll.shape[0]
+        slot = C.c_int(-1)
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_pool_attach(self._h, enroll.ctypes.data, kind, length, int(enroll_rate), int(sample_rate),
+                                                C.byref(slot)), "ws_engine_rate_pool_attach")
+        return slot.value
+
+    def push_cap(self, slot, n):
+        """samples that a push of n >= 1 samples to `slot` returns at most (n = 0: the flush)."""
+        return int(lib().ws_engine_rate_pool_push_cap(self._h, int(slot), int(n)))
+
+    def push(self, chunks, est_cap=None):
+        """{slot: chunk [n_slot >= 1] at the slot's rate} -> {slot: float32 [m_slot]} at the slot's rate."""
+        ids = list(chunks)
+        data = [np.ascontiguousarray(chunks[i], dtype=np.float32).reshape(-1) for i in ids]
+        n = np.array([x.shape[0] for x in data], dtype=np.int32)
+        caps = np.array([self.push_cap(i, int(k)) if est_cap is None else int(est_cap[i]) for i, k in zip(ids, n)], dtype=np.int32)
+        bufs = [np.zeros(max(int(c), 1), dtype=np.float32) for c in caps]
+        A = len(ids)
+        slots, m = np.array(ids, dtype=np.int32), np.zeros(max(A, 1), dtype=np.int32)
+        cp = (C.c_void_p * max(A, 1))(*[x.ctypes.data for x in data])
+        ep = (C.c_void_p * max(A, 1))(*[b.ctypes.data for b in bufs])
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_pool_push(self._h, A, slots.ctypes.data, C.cast(cp, C.c_void_p), n.ctypes.data,
+                                              C.cast(ep, C.c_void_p), caps.ctypes.data, m.ctypes.data), "ws_engine_rate_pool_push")
+        return {i: b[:int(k)].copy() for i, b, k in zip(ids, bufs, m)}
+
+    def flush(self, slot, est_cap=None):
+        """The end of one slot's stream; the slot's total is at most the samples pushed to it."""
+        cap = self.push_cap(slot, 0) if est_cap is None else int(est_cap)
+        buf, m = np.zeros(max(cap, 1), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_pool_flush(self._h, int(slot), buf.ctypes.data, cap, C.byref(m)), "ws_engine_rate_pool_flush")
+        return buf[:m.value].copy()
+
+    def detach(self, slot):
+        """Frees the slot for the next attach, at any accepted rate."""
+        _check(lib().ws_engine_rate_pool_detach(self._h, int(slot)), "ws_engine_rate_pool_detach")
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
+            _lib.ws_engine_rate_pool_close(self._h)
         self._h = None
 
     def __del__(self):

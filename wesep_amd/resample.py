@@ -3,6 +3,7 @@
 The filter is the published sinc_interp_hann design with lowpass_filter_width = 6 and rolloff = 0.99, as a polyphase table
 made once on the host in double (ws_resample_taps).  One output sample is one dot product reduced in one fixed order, so a
 stream's output is bit for bit the whole-signal result whatever the packet sizes."""
+import numpy as np
 import torch
 
 from . import dev
@@ -113,3 +114,118 @@ class StreamResampler:
         if self.n_in == 0:
             return torch.empty(self.rows, 0, device=self.taps.device, dtype=torch.float32)
         return self._step(None, True)
+
+
+def step_plan(geom, n_in, groups, h, n_new, final):
+    """The arguments of one streaming step, from the counters alone (the rule of StreamResampler._step and runtime/rate.cc):
+    (lead, n_valid, n_out, hist_from, hist_len, groups after the step) for n_new samples behind a history of h."""
+    U, D, w, _ = geom
+    N = n_in + n_new
+    a0 = max(0, groups * D - w)
+    lead = max(0, w - groups * D)
+    if final:
+        return lead, h + n_new, -(-U * N // D) - groups * U, 0, 0, groups
+    g_new = max(0, (N - w) // D)
+    hist_from = max(0, g_new * D - w) - a0
+    return lead, h + n_new, (g_new - groups) * U, hist_from, N - a0 - hist_from, g_new
+
+
+class StreamResamplerRows:
+    """Many StreamResamplers with one row each, every row at its own pair of rates, in ONE launch per round
+    (ws_resample_stream_rows_fwd).  pairs[i] = (rate_in, rate_out) of row i; a row with rate_in == rate_out runs the identity
+    table U = D = K = 1 (no delay, no filter: its outputs are its inputs).  Per row the bookkeeping of StreamResampler; the
+    histories of all rows live in one arena, two buffers [K_i - 1 + max_push] a row used in turn, and the tables of the
+    distinct pairs in another.  A row's outputs are bit for bit those of StreamResampler(1, *pairs[i], max_push) fed the same
+    chunks, whatever the other rows are and carry.  A chunk above max_push is taken in pieces: round j carries piece j of every
+    row that has one."""
+
+    def __init__(self, pairs, max_push=4800, device="cuda"):
+        self.pairs, self.max_push = [(int(a), int(b)) for a, b in pairs], int(max_push)
+        if not self.pairs or self.max_push < 1:
+            raise ValueError("StreamResamplerRows: at least one row and max_push >= 1")
+        device = torch.device(device)
+        tables, self.geom, self._taps_off, off = [], [], [], {}
+        for pair in self.pairs:
+            ident = pair[0] == pair[1]
+            self.geom.append((1, 1, 0, 1) if ident else geometry(*pair))
+            key = "identity" if ident else pair
+            if key not in off:
+                off[key] = sum(t.size for t in tables)
+                tables.append(np.ones(1, dtype=np.float32) if ident else dev.resample_taps(*pair).reshape(-1))
+            self._taps_off.append(off[key])
+        self.taps = torch.from_numpy(np.concatenate(tables)).to(device)
+        self._ld = [g[3] - 1 + self.max_push for g in self.geom]
+        self._base = [2 * sum(self._ld[:i]) for i in range(len(self.pairs))]
+        self.buf = torch.zeros(2 * sum(self._ld), device=device, dtype=torch.float32)
+        self.launches = 0
+        self._st = [None] * len(self.pairs)
+        for i in range(len(self.pairs)):
+            self.reset(i)
+
+    def reset(self, row):
+        self._st[row] = dict(cur=0, h=0, n_in=0, groups=0, done=False)
+
+    def _at(self, row, which):
+        return self._base[row] + which * self._ld[row]
+
+    def history(self, row):
+        """[h] (a view): the input samples row `row` keeps, h < K"""
+        st = self._st[row]
+        o = self._at(row, st["cur"])
+        return self.buf[o:o + st["h"]]
+
+    def _round(self, pieces, final):
+        """pieces: {row: [n] tensor} (final: {row: None}) -> {row: [m] tensor}"""
+        plan, n_y = [], 0
+        for row, piece in pieces.items():
+            st, n = self._st[row], 0 if piece is None else piece.shape[0]
+            o = self._at(row, st["cur"])
+            if n:
+                self.buf[o + st["h"]:o + st["h"] + n] = piece
+            lead, n_valid, n_out, hist_from, hist_len, g_new = step_plan(self.geom[row], st["n_in"], st["groups"], st["h"], n, final)
+            plan.append((row, n_y, n_out, hist_len, g_new, n))
+            if n_out or hist_len:
+                U, D, _, K = self.geom[row]
+                plan[-1] += (dict(in_off=o, taps_off=self._taps_off[row], out_off=n_y, hist_off=self._at(row, 1 - st["cur"]), U=U, D=D,
+                                  K=K, lead=lead, n_valid=n_valid, final=int(final), n_out=n_out, hist_from=hist_from,
+                                  hist_len=hist_len),)
+            n_y += n_out
+        y = torch.empty(n_y, device=self.buf.device, dtype=torch.float32)
+        table = [p[6] for p in plan if len(p) == 7]
+        if table:
+            dev.resample_stream_rows_fwd(table, self.buf, self.taps, y, self.buf)
+            self.launches += 1
+        out = {}
+        for p in plan:
+            row, y_off, n_out, hist_len, g_new, n = p[:6]
+            st = self._st[row]
+            if not final and len(p) == 7:
+                st["cur"], st["h"], st["groups"] = 1 - st["cur"], hist_len, g_new
+            st["n_in"] += n
+            out[row] = y[y_off:y_off + n_out]
+        return out
+
+    def push(self, chunks):
+        """chunks: {row: [n >= 1] tensor on the device} -> {row: [m] tensor}, the samples that became final (m may be 0)."""
+        for row, c in chunks.items():
+            if self._st[row]["done"]:
+                raise ValueError(f"StreamResamplerRows.push: row {row} was flushed (reset({row}) starts another)")
+            if c.dim() != 1 or c.shape[0] < 1:
+                raise ValueError(f"StreamResamplerRows.push: the chunk of row {row} is {tuple(c.shape)}, expected [n >= 1]")
+        outs = {row: [] for row in chunks}
+        for j in range(max(-(-c.shape[0] // self.max_push) for c in chunks.values())):
+            lo = j * self.max_push
+            got = self._round({row: c[lo:lo + self.max_push] for row, c in chunks.items() if c.shape[0] > lo}, False)
+            for row, y in got.items():
+                outs[row].append(y)
+        return {row: ys[0] if len(ys) == 1 else torch.cat(ys) for row, ys in outs.items()}
+
+    def flush(self, rows):
+        """The end of the signal of every row in `rows`, in one launch: {row: the outputs up to ceil(U N / D)}."""
+        for row in rows:
+            if self._st[row]["done"]:
+                raise ValueError(f"StreamResamplerRows.flush: row {row} was flushed already")
+            self._st[row]["done"] = True
+        out = self._round({row: None for row in rows if self._st[row]["n_in"]}, True)
+        empty = torch.empty(0, device=self.buf.device, dtype=torch.float32)
+        return {row: out.get(row, empty) for row in rows}
