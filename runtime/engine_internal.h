@@ -9,10 +9,14 @@
 //   dpccn_plan.cc    DPCCN (arch 2)
 //   gridnet_plan.cc  TF-GridNet (arch 3)
 //   longform.cc      ws_engine_separate_long: one long mixture as overlapping windows through the rectangular plans
-//   stream.cc        ws_engine_stream_*: causal cLN Conv-TasNet fed audio as it arrives, state carried on the device
-//   stream_pool.cc   ws_engine_pool_*: many such streams, each at its own position, through one launch chain per round
+//   stream.cc        what every streaming front end shares -- the launch chain of a group of frames (stream_chain), the state
+//                    block (StreamCore) and the speaker stage of a stream (stream_enroll) -- and ws_engine_stream_*: causal
+//                    cLN Conv-TasNet fed audio as it arrives, state carried on the device
+//   stream_pool.cc   ws_engine_pool_*: many such streams, each at its own position, through one launch chain per round; the
+//                    slot checks of both pools
 //   rate.cc          audio at the caller's sample rate: ws_engine_resample, ws_engine_separate_rate, ws_engine_rate_stream_*
 //   rate_pool.cc     ws_engine_rate_pool_*: the stream pool with a sample rate per slot, on the rows forms of the resampler
+// The emission rule of all four (Geom, plan_step, plain_emitted, ...) and their copy / synchronise helpers are below.
 // Everything here lives in namespace wsrt and is built with -fvisibility=hidden: the library exports the C ABI only
 // (WS_ENGINE_API).  Host code only: no kernels in the runtime.
 #ifndef WESEP_ENGINE_INTERNAL_H_
@@ -148,6 +152,15 @@ struct Arena {
     chunks.clear();
     reset();
   }
+};
+
+struct ArenaScope {         // what is allocated while it lives goes back to the arena on every path out
+  Arena& a;
+  const Arena::Mark mk;
+  explicit ArenaScope(Arena& arena) : a(arena), mk(arena.mark()) {}
+  ~ArenaScope() { a.release(mk); }
+  ArenaScope(const ArenaScope&) = delete;
+  ArenaScope& operator=(const ArenaScope&) = delete;
 };
 
 struct RnnPrep {            // one ResRNN (bsrnn.py:26-46) or TF-GridNet BLSTM, everything the forward needs, device pointers
@@ -430,20 +443,131 @@ struct TasGemm {
 };
 int tas_gemm(ws_engine* e, const TasGemm& t);
 inline bool tas_streamable(const ws_engine* e) { return e->arch == 1 && e->tas.causal && e->tas.norm == 1; }
-// ---- what the solo stream (stream.cc) and the stream pool (stream_pool.cc) share ----
+// ---- what the streaming front ends (stream.cc, stream_pool.cc, rate.cc, rate_pool.cc) share ----
 struct StreamBlock {         // one causal cLN block: its weights, and where its carried state lives
   const float *w1, *b1, *a1, *g1, *be1, *wd, *bd, *a2, *g2, *be2, *w3, *b3;
   int ldw, dil, cap;
-  float* ring;               // [rows or slots][cap][H]
-  const float* rb;           // [rows or slots][H] = W_e e + b for the stack's first block, else NULL
+  float* ring;               // [rows][cap][H]
+  const float* rb;           // [rows][H] = W_e e + b for the stack's first block, else NULL
 };
 struct StreamWeights {       // every weight pointer of a group of frames, resolved once
   const float *enc_w[3], *enc_b[3], *ln_g, *ln_b, *proj_w, *proj_b, *mask_w, *mask_b, *dec_b;
   std::vector<StreamBlock> blocks;
 };
-void resolve_stream_weights(const ws_engine* e, StreamWeights* w);   // blocks: weights, ldw and dil; the owner sets cap, ring, rb
 int refuse_not_streamable(const ws_engine* e, const char* who);      // WS_ERR_INVALID with the reason, by name
 int tas_flat_stats(ws_engine* e, const float* x, int R, long long n, float* st);
+// The state block of a solo stream or a pool: ONE allocation made at open.  rows: the rows of a stream, the slots of a pool.
+struct StreamCore : StreamWeights {
+  ws_engine* e = nullptr;
+  int rows = 0, G = 0;
+  char* state = nullptr;
+  size_t state_bytes = 0;
+  std::vector<float*> rb;               // per stack [rows][H]
+  float *carry = nullptr, *carry0 = nullptr, *emb = nullptr;     // [rows][L - s], the carry's reset image, [rows][E]
+  bool block_kernel = false;            // WS_STREAM_BLOCK_KERNEL: one call per block
+};
+// rows x max_chunk_frames against 2^31 elements in one buffer; noun: "rows" or "slots"
+int stream_core_check(const ws_engine* e, const char* who, const char* noun, int rows, int G);
+// Lays out and allocates the state -- the rings per block, `parts` (floats each, the owner's), the row biases per stack,
+// `extra_floats` if any; 256-byte aligned, in that order -- fills it with NaN under WS_ENGINE_POISON, resolves the weights and
+// wires cap / ring / rb into the blocks.  at: the addresses of `parts`, then of the extra part.
+int stream_core_open(StreamCore* c, const char* who, ws_engine* e, int rows, int G, unsigned flags, const std::vector<size_t>& parts,
+                     size_t extra_floats, std::vector<float*>* at);
+void stream_core_free(StreamCore* c);
+// The speaker stage for rows [row0, row0 + n): embedding, SpeakerTransform, copy into emb, the stacks' row biases W_e e + b
+int stream_enroll(StreamCore* c, const char* who, const void* enroll, int enroll_kind, int enroll_len, int row0, int n);
+struct ChainRows {           // how the two time-crossing kernels address their rows
+  int rows = 0, Tc = 0;
+  long long t0 = 0;          // solo form: every row at frame t0, state row = rectangle row
+  int nslots = 0;            // rows form (d_slot != nullptr): per-row (slot, t0, tc) device tables
+  const int *d_slot = nullptr, *d_tc = nullptr;
+  const long long* d_t0 = nullptr;
+};
+// The launch chain of one group of frames over the rectangle x0 [rows][pitch]: 3 framing GEMMs, row statistics, projection; per
+// block GEMM, the fused middle, GEMM (or the block kernel); mask GEMM, mask product, synthesis GEMM, overlap-add.  Its
+// activations and *est [rows][Tc s] come from the work arena: the caller holds an ArenaScope.
+int stream_chain(ws_engine* e, const StreamWeights& w, bool block_kernel, const float* x0, long long pitch, const ChainRows& r,
+                 float* carry, float** est);
+
+// ---- the emission rule ----
+constexpr int kEncLmax = 160;    // the longest window of the MultiEncoder (encoder.py:66-114)
+struct Geom {                    // one direction of the resampler (ws_resample_geom)
+  int U = 1, D = 1, w = 0, K = 1;
+};
+inline long long rs_len(const Geom& g, long long n) { return ((long long)g.U * n + g.D - 1) / g.D; }                   // whole signal
+inline long long rs_emitted(const Geom& g, long long n) { return n > g.w ? (long long)g.U * ((n - g.w) / g.D) : 0; }    // streamed so far
+// frames of a stream that n samples complete: while it runs (the longest window must fit), and at its flush (zero-extended)
+inline long long plain_frames(long long n, int L, bool flush = false) {
+  return flush ? (n - L) / (L / 2) + 1 : (n >= kEncLmax ? (n - kEncLmax) / (L / 2) + 1 : 0);
+}
+inline long long plain_emitted(long long n, int L) { return plain_frames(n, L) * (L / 2); }
+inline long long plain_total(long long n, int L) { return ((n - L) / (L / 2)) * (L / 2) + L; }
+struct Step {
+  int lead = 0, n_valid = 0, n_out = 0, hist_from = 0, hist_len = 0;
+  long long g_new = 0;
+};
+// the arguments of one streaming resampler step from the counters: n_new samples behind a history of h; a final step keeps none
+inline Step plan_step(const Geom& g, long long n_in, long long groups, int h, int n_new, bool final) {
+  Step s;
+  const long long N = n_in + n_new;
+  const long long a0 = std::max<long long>(0, groups * g.D - g.w);
+  s.lead = static_cast<int>(std::max<long long>(0, g.w - groups * g.D));
+  s.n_valid = h + n_new;
+  s.g_new = groups;
+  if (final) {
+    s.n_out = static_cast<int>(rs_len(g, N) - groups * g.U);
+  } else {
+    s.g_new = N > g.w ? (N - g.w) / g.D : 0;
+    s.n_out = static_cast<int>((s.g_new - groups) * g.U);
+    s.hist_from = static_cast<int>(std::max<long long>(0, s.g_new * g.D - g.w) - a0);
+    s.hist_len = s.n_valid - s.hist_from;
+  }
+  return s;
+}
+// what a push of n >= 1 samples at the caller's rate returns at most (n = 0: the flush), through a (in) and b (back)
+inline int rate_push_cap(const Geom& a, const Geom& b, int L, int n) {
+  const int hop = L / 2;
+  if (n == 0) {      // the flush: what A still owes (its history is below K), the inner stream's rest, what B still owes
+    const long long ma = ((long long)a.K / a.D + 1) * a.U;
+    const long long mm = (ma / hop + 1) * hop + WS_STREAM_FLUSH_CAP;
+    return static_cast<int>(std::min<long long>(0x7fffffff, ((mm + b.K) / b.D + 2) * b.U));
+  }
+  // A returns whole groups: at most n / D + 1 of them; the inner stream whole frames; B whole groups again
+  const long long ma = ((long long)n / a.D + 1) * a.U;
+  const long long mm = (ma / hop + 1) * hop;
+  return static_cast<int>(std::min<long long>(0x7fffffff, (mm / b.D + 1) * b.U));
+}
+
+// ---- copies and the synchronisation of a streaming call, on the engine's stream; who / what: the message of a failure.
+// Dry run: nothing was computed, so a caller's buffer (device to host) stays untouched; every other copy is a memcpy (dry
+// "device" memory is malloc'd).  height == 1 with both pitches 0: a 1-D copy
+inline int copy_async(ws_engine* e, const char* who, const char* what, void* dst, size_t dpitch, const void* src, size_t spitch,
+                      size_t width, size_t height, hipMemcpyKind kind) {
+  if (width == 0 || height == 0) return WS_OK;
+  const bool flat = height == 1 && dpitch == 0 && spitch == 0;
+  if (e->dry) {
+    for (size_t r = 0; kind != hipMemcpyDeviceToHost && r < height; ++r)
+      memcpy(static_cast<char*>(dst) + r * dpitch, static_cast<const char*>(src) + r * spitch, width);
+    return WS_OK;
+  }
+  if ((flat ? hipMemcpyAsync(dst, src, width, kind, e->stream)
+            : hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, kind, e->stream)) != hipSuccess) {
+    set_err("%s: %s failed", who, what);
+    return WS_ERR_LAUNCH;
+  }
+  return WS_OK;
+}
+inline int copy_async(ws_engine* e, const char* who, const char* what, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+  return copy_async(e, who, what, dst, 0, src, 0, bytes, 1, kind);
+}
+inline int sync_stream(ws_engine* e, const char* who) {
+  if (!e->dry && hipStreamSynchronize(e->stream) != hipSuccess) {
+    set_err("%s: the device reported an error", who);
+    return WS_ERR_LAUNCH;
+  }
+  return WS_OK;
+}
+
 // ---- what a rate stream (rate.cc) needs of the solo stream (stream.cc) ----
 // extra_floats > 0: one more slot in the stream's state allocation (*extra), and chunks / estimates are DEVICE buffers
 int stream_open_impl(ws_engine* e, int rows, const void* enroll, int enroll_kind, int enroll_len, int max_chunk_frames,
@@ -454,7 +578,6 @@ int stream_push_impl(ws_stream* st, const float* chunk, long long chunk_pitch, i
                      int* n_out);
 int stream_flush_impl(ws_stream* st, float* est, long long est_pitch, int est_cap, int* n_out);
 // ---- the stream pool's state (stream_pool.cc), and what a rate pool (rate_pool.cc) needs of it ----
-constexpr int kPoolLmax = 160;   // the longest window of the MultiEncoder (encoder.py:66-114)
 struct PoolSlot {
   enum State { kFree, kAttached, kDone } state = kFree;
   bool failed = false;         // a push or flush that named this slot ended half way
@@ -474,16 +597,9 @@ struct PoolGroup {             // host memory of one group, alive until the call
 };
 }  // namespace wsrt
 
-struct ws_pool : wsrt::StreamWeights {
-  ws_engine* e = nullptr;
-  int nslots = 0, G = 0;
-  char* state = nullptr;                // the one allocation
-  size_t state_bytes = 0;
-  std::vector<float*> rb;               // per stack [nslots][H]
-  float *carry = nullptr, *carry0 = nullptr, *emb = nullptr;     // [nslots][L - s], [L - s], [nslots][E]
+struct ws_pool : wsrt::StreamCore {     // rows: the slots; carry0 is one row [L - s]
   std::vector<wsrt::PoolSlot> slots;
   std::vector<wsrt::PoolGroup> groups;  // of the call in hand
-  bool block_kernel = false;            // WS_STREAM_BLOCK_KERNEL: one call per block
   bool device_io = false;               // a rate pool's: groups gather from and scatter to the state allocation
 };
 
@@ -496,6 +612,13 @@ int pool_attach_impl(ws_pool* p, const char* who, const void* enroll, int enroll
 int pool_run_group(ws_pool* p, PoolGroup& g);
 int pool_check(const ws_pool* p, const char* who);
 void pool_free(ws_pool* p);
+// the slot checks of a push, a flush and a detach, for both pools: the argument arrays; entry i (slot id, n samples at chunk:
+// attached, not flushed, named once -- seen [slots] -- a packet); the slot of a flush or a detach
+int pool_check_push_args(const char* who, int n_active, const void* slots, const void* chunks, const void* n, const void* est,
+                         const void* est_cap, const void* n_out);
+int pool_check_entry(const ws_pool* p, const char* who, std::vector<char>& seen, int i, int id, int n, const float* chunk);
+int pool_check_slot(const ws_pool* p, const char* who, int slot, bool flush);
+int pool_detach_impl(ws_pool* p, const char* who, int slot);   // p NULL: refused as a null pool
 // ---- what a rate pool needs of rate.cc: x [R][n] (host) at rate_in -> y [R][*n_out] (host) at rate_out, the kernel's limits and
 // the sizes refused by name as `who`; the caller holds the turn
 int resample_host_rows(ws_engine* e, const char* who, const float* x, int R, int n, int rate_in, int rate_out, std::vector<float>* y,

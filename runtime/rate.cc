@@ -9,6 +9,8 @@
 //                            one host synchronisation per push.  The resamplers' histories and staging buffers are one more
 //                            slot of the stream's ONE state allocation.
 // Tap tables are made by ws_resample_taps (the one place) and kept on the device per (rate_in, rate_out).
+// The emission rule -- Geom, rs_len, rs_emitted, plan_step, plain_emitted, rate_push_cap -- is engine_internal.h's, shared with
+// the rate pool (rate_pool.cc); copies and the synchronisation are its copy_async / sync_stream.
 // =================================================================================================================
 #include <memory>
 
@@ -18,10 +20,6 @@ using namespace wsrt;
 
 namespace {
 
-struct Geom {
-  int U = 1, D = 1, w = 0, K = 1;
-};
-
 // the kernel's limits, by name, before any launch
 int rate_geom(const char* who, int rate_in, int rate_out, Geom* g) {
   if (ws_resample_geom(rate_in, rate_out, &g->U, &g->D, &g->w, &g->K) != WS_OK) {
@@ -30,10 +28,6 @@ int rate_geom(const char* who, int rate_in, int rate_out, Geom* g) {
   }
   return WS_OK;
 }
-
-long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
-long long rs_len(const Geom& g, long long n) { return ceil_div((long long)g.U * n, g.D); }                       // whole signal
-long long rs_emitted(const Geom& g, long long n) { return n > g.w ? (long long)g.U * ((n - g.w) / g.D) : 0; }    // streamed so far
 
 int rate_taps(ws_engine* e, int rate_in, int rate_out, const Geom& g, const float** out) {
   auto it = e->rs_taps.find({rate_in, rate_out});
@@ -57,11 +51,7 @@ int resample_rows(ws_engine* e, const float* x, int R, int n, int rate_in, int r
   const float* taps = nullptr;
   int rc = rate_taps(e, rate_in, rate_out, g, &taps);
   if (rc != WS_OK) return rc;
-  struct Scope {              // the two transient buffers go back to the arena on every path
-    Arena& a;
-    const Arena::Mark mk;
-    ~Scope() { a.release(mk); }
-  } scope{e->work, e->work.mark()};
+  ArenaScope scope(e->work);      // the two transient buffers go back to the arena on every path
   float* dx = e->work.alloc(size_t(R) * n);
   float* dy = e->work.alloc(size_t(R) * n_out);
   WS_PTR(dx && dy);
@@ -214,42 +204,19 @@ namespace {
 // buffer.  Nothing runs when nothing arrived and nothing is owed.
 int rs_step(ws_rate_stream* s, Resampler& r, int n_new, bool final, float* y, long long ldy, int* n_out) {
   ws_engine* e = s->e;
-  const Geom& g = r.g;
-  const long long N = r.n + n_new;
-  const long long a0 = std::max<long long>(0, r.groups * g.D - g.w);
-  const int lead = static_cast<int>(std::max<long long>(0, g.w - r.groups * g.D));
-  const int n_valid = r.h + n_new;
-  long long g_new = r.groups, outs;
-  int hist_from = 0, hist_len = 0;
-  if (final) {
-    outs = rs_len(g, N) - r.groups * g.U;
-  } else {
-    g_new = N > g.w ? (N - g.w) / g.D : 0;
-    outs = (g_new - r.groups) * g.U;
-    hist_from = static_cast<int>(std::max<long long>(0, g_new * g.D - g.w) - a0);
-    hist_len = n_valid - hist_from;
-  }
-  *n_out = static_cast<int>(outs);
-  r.n = N;
-  if (n_valid == 0 || (n_new == 0 && !final)) return WS_OK;
-  WS_RUN(e, ws_resample_stream_fwd(r.buf[r.cur], r.ld, s->rows, r.rate_in, r.rate_out, r.taps, lead, n_valid, final ? 1 : 0, 0,
-                                   static_cast<int>(outs), outs ? y : nullptr, ldy, hist_from, hist_len,
-                                   hist_len ? r.buf[1 - r.cur] : nullptr, r.ld, e->stream));
-  if (!final) r.cur ^= 1, r.h = hist_len, r.groups = g_new;
+  const Step p = plan_step(r.g, r.n, r.groups, r.h, n_new, final);
+  *n_out = p.n_out;
+  r.n += n_new;
+  if (p.n_valid == 0 || (n_new == 0 && !final)) return WS_OK;
+  WS_RUN(e, ws_resample_stream_fwd(r.buf[r.cur], r.ld, s->rows, r.rate_in, r.rate_out, r.taps, p.lead, p.n_valid, final ? 1 : 0, 0, p.n_out,
+                                   p.n_out ? y : nullptr, ldy, p.hist_from, p.hist_len, p.hist_len ? r.buf[1 - r.cur] : nullptr, r.ld,
+                                   e->stream));
+  if (!final) r.cur ^= 1, r.h = p.hist_len, r.groups = p.g_new;
   return WS_OK;
 }
 
-int rs_copy2d(ws_engine* e, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind) {
-  if (width == 0 || height == 0 || e->dry) return WS_OK;
-  if (hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, kind, e->stream) != hipSuccess) {
-    set_err("ws_engine_rate_stream: a copy between host and device failed");
-    return WS_ERR_LAUNCH;
-  }
-  return WS_OK;
-}
-
-long long plain_emitted(long long n, int L) { return n >= 160 ? ((n - 160) / (L / 2) + 1) * (L / 2) : 0; }
-long long plain_total(long long n, int L) { return ((n - L) / (L / 2)) * (L / 2) + L; }
+constexpr const char* kWho = "ws_engine_rate_stream";
+constexpr const char* kCopy = "a copy between host and device";
 
 int check_rate_stream(const ws_rate_stream* s, const char* who) {
   if (!s || !s->e || !s->inner) {
@@ -269,8 +236,8 @@ int b_step(ws_rate_stream* s, int m, bool final, float* est, long long pitch, lo
   int nb = 0, rc;
   if ((rc = rs_step(s, s->B, m, final, s->b_out, s->b_cap, &nb)) != WS_OK) return rc;
   const long long take = std::min<long long>(nb, pitch - *col);
-  if ((rc = rs_copy2d(s->e, est + *col, size_t(pitch) * 4, s->b_out, size_t(s->b_cap) * 4, size_t(take) * 4, s->rows,
-                      hipMemcpyDeviceToHost)) != WS_OK)
+  if ((rc = copy_async(s->e, kWho, kCopy, est + *col, size_t(pitch) * 4, s->b_out, size_t(s->b_cap) * 4, size_t(take) * 4, s->rows,
+                       hipMemcpyDeviceToHost)) != WS_OK)
     return rc;
   *col += take;
   return WS_OK;
@@ -362,18 +329,9 @@ WS_ENGINE_API int ws_engine_rate_stream_open(ws_engine* e, int rows, const void*
 
 WS_ENGINE_API int ws_engine_rate_stream_push_cap(const ws_rate_stream* s, int n) {
   if (!s || !s->e || n < 0) return -1;
-  const int L = s->e->tas.L, hop = L / 2;
+  const int L = s->e->tas.L;
   if (s->plain) return n == 0 ? WS_STREAM_FLUSH_CAP : WS_STREAM_PUSH_CAP(n, L);
-  const Geom &a = s->A.g, &b = s->B.g;
-  if (n == 0) {      // the flush: what A still owes (its history is below K), the inner stream's rest, what B still owes
-    const long long ma = ((long long)a.K / a.D + 1) * a.U;
-    const long long mm = (ma / hop + 1) * hop + WS_STREAM_FLUSH_CAP;
-    return static_cast<int>(std::min<long long>(0x7fffffff, ((mm + b.K) / b.D + 2) * b.U));
-  }
-  // A returns whole groups: at most n / D + 1 of them; the inner stream whole frames; B whole groups again
-  const long long ma = ((long long)n / a.D + 1) * a.U;
-  const long long mm = (ma / hop + 1) * hop;
-  return static_cast<int>(std::min<long long>(0x7fffffff, (mm / b.D + 1) * b.U));
+  return rate_push_cap(s->A.g, s->B.g, L, n);
 }
 
 WS_ENGINE_API int ws_engine_rate_stream_push(ws_rate_stream* s, const float* chunk, int n, float* est, int est_cap, int* n_out) {
@@ -406,8 +364,8 @@ WS_ENGINE_API int ws_engine_rate_stream_push(ws_rate_stream* s, const float* chu
   for (int off = 0; off < n;) {
     const int take = std::min(n - off, s->max_push);
     Resampler& A = s->A;
-    if ((rc = rs_copy2d(e, A.buf[A.cur] + A.h, size_t(A.ld) * 4, chunk + off, size_t(n) * 4, size_t(take) * 4, s->rows,
-                        hipMemcpyHostToDevice)) != WS_OK)
+    if ((rc = copy_async(e, kWho, kCopy, A.buf[A.cur] + A.h, size_t(A.ld) * 4, chunk + off, size_t(n) * 4, size_t(take) * 4, s->rows,
+                         hipMemcpyHostToDevice)) != WS_OK)
       return rc;
     off += take;
     int na = 0, m = 0;
@@ -418,10 +376,7 @@ WS_ENGINE_API int ws_engine_rate_stream_push(ws_rate_stream* s, const float* chu
     }
     if ((rc = b_step(s, m, false, est, emit, &col)) != WS_OK) return rc;
   }
-  if (!e->dry && hipStreamSynchronize(e->stream) != hipSuccess) {      // the one host synchronisation of a push
-    set_err("ws_engine_rate_stream_push: the device reported an error");
-    return WS_ERR_LAUNCH;
-  }
+  if ((rc = sync_stream(e, "ws_engine_rate_stream_push")) != WS_OK) return rc;      // the one host synchronisation of a push
   if (col != emit) {
     set_err("ws_engine_rate_stream_push: internal error: %lld samples were produced where the rule says %lld", col, emit);
     return WS_ERR_LAUNCH;
@@ -472,10 +427,7 @@ WS_ENGINE_API int ws_engine_rate_stream_flush(ws_rate_stream* s, float* est, int
   if ((rc = stream_flush_impl(s->inner, B.buf[B.cur] + B.h, B.ld, s->m_cap, &m)) != WS_OK) return rc;   // ... and flush
   if ((rc = b_step(s, m, false, est, emit, &col)) != WS_OK) return rc;
   if ((rc = b_step(s, 0, true, est, emit, &col)) != WS_OK) return rc;                       // B's flush, cropped
-  if (!e->dry && hipStreamSynchronize(e->stream) != hipSuccess) {
-    set_err("ws_engine_rate_stream_flush: the device reported an error");
-    return WS_ERR_LAUNCH;
-  }
+  if ((rc = sync_stream(e, "ws_engine_rate_stream_flush")) != WS_OK) return rc;
   if (col != emit) {
     set_err("ws_engine_rate_stream_flush: internal error: %lld samples were produced where the rule says %lld", col, emit);
     return WS_ERR_LAUNCH;

@@ -1,7 +1,8 @@
 // =================================================================================================================
 // ws_engine_rate_pool_*: the stream pool (stream_pool.cc) with a sample rate per slot.  One round carries one packet for any
 // set of slots at any mix of rates through ONE launch chain per piece:
-//   host: per slot A's emission, the frames owed, B's emission (the formulas of rate.cc), est_cap checked before any launch
+//   host: per slot A's emission, the frames owed, B's emission (the emission rule of engine_internal.h, the rate stream's too),
+//         est_cap checked before any launch; the slots checked by the plain pool's helpers (pool_check_*)
 //   A     one ws_resample_stream_rows_fwd over all slots of the piece: caller rate -> the container's.  A's history is caller
 //         samples, which the host has: it stays on the HOST; the staging block [A][history | new] is uploaded once with the
 //         table.  A's outputs land behind each slot's pending samples, which live in the state allocation
@@ -23,47 +24,11 @@ using namespace wsrt;
 
 namespace {
 
-constexpr int kLmax = kPoolLmax;
-
-struct Geom {
-  int U = 1, D = 1, w = 0, K = 1;
-};
-
 struct Rate {                // one accepted sample rate: caller -> container (a) and back (b); tables at state floats
   int rate = 0;
   Geom a, b;
   long long a_taps = 0, b_taps = 0;
 };
-
-long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
-long long rs_len(const Geom& g, long long n) { return ceil_div((long long)g.U * n, g.D); }
-long long rs_emitted(const Geom& g, long long n) { return n > g.w ? (long long)g.U * ((n - g.w) / g.D) : 0; }
-long long plain_emitted(long long n, int L) { return n >= kLmax ? ((n - kLmax) / (L / 2) + 1) * (L / 2) : 0; }
-long long plain_total(long long n, int L) { return ((n - L) / (L / 2)) * (L / 2) + L; }
-
-struct Step {
-  int lead = 0, n_valid = 0, n_out = 0, hist_from = 0, hist_len = 0;
-  long long g_new = 0;
-};
-
-// the arguments of one streaming step from the counters (rate.cc rs_step): n_new samples behind a history of h
-Step plan_step(const Geom& g, long long n_in, long long groups, int h, int n_new, bool final) {
-  Step s;
-  const long long N = n_in + n_new;
-  const long long a0 = std::max<long long>(0, groups * g.D - g.w);
-  s.lead = static_cast<int>(std::max<long long>(0, g.w - groups * g.D));
-  s.n_valid = h + n_new;
-  s.g_new = groups;
-  if (final) {
-    s.n_out = static_cast<int>(rs_len(g, N) - groups * g.U);
-  } else {
-    s.g_new = N > g.w ? (N - g.w) / g.D : 0;
-    s.n_out = static_cast<int>((s.g_new - groups) * g.U);
-    s.hist_from = static_cast<int>(std::max<long long>(0, s.g_new * g.D - g.w) - a0);
-    s.hist_len = s.n_valid - s.hist_from;
-  }
-  return s;
-}
 
 struct RateSlot {
   int ri = -1;                        // its rate, an index into ws_rate_pool::rates
@@ -113,22 +78,7 @@ struct ws_rate_pool {
 
 namespace {
 
-int rp_copy(ws_engine* e, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* what) {
-  if (bytes == 0 || e->dry) return WS_OK;
-  if (hipMemcpyAsync(dst, src, bytes, kind, e->stream) != hipSuccess) {
-    set_err("ws_engine_rate_pool: %s failed", what);
-    return WS_ERR_LAUNCH;
-  }
-  return WS_OK;
-}
-
-int rp_sync(ws_engine* e) {
-  if (!e->dry && hipStreamSynchronize(e->stream) != hipSuccess) {
-    set_err("ws_engine_rate_pool: the device reported an error");
-    return WS_ERR_LAUNCH;
-  }
-  return WS_OK;
-}
+constexpr const char* kWho = "ws_engine_rate_pool";
 
 // the table goes up behind everything the launch reads; `buf` is the staging block (A) or the state (B)
 int rows_launch(ws_rate_pool* rp, const float* buf, long long n_buf, bool with_hist) {
@@ -138,7 +88,7 @@ int rows_launch(ws_rate_pool* rp, const float* buf, long long n_buf, bool with_h
   ws_resample_row* d_tab = reinterpret_cast<ws_resample_row*>(e->work.alloc(size_t(A) * sizeof(ws_resample_row) / 4));
   WS_PTR(d_tab);
   int rc;
-  if ((rc = rp_copy(e, d_tab, tab.data(), size_t(A) * sizeof(ws_resample_row), hipMemcpyHostToDevice, "table upload")) != WS_OK) return rc;
+  if ((rc = copy_async(e, kWho, "table upload", d_tab, tab.data(), size_t(A) * sizeof(ws_resample_row), hipMemcpyHostToDevice)) != WS_OK) return rc;
   WS_RUN(e, ws_resample_stream_rows_fwd(tab.data(), d_tab, A, buf, n_buf, rp->state, rp->state_floats, rp->state, rp->state_floats,
                                         with_hist ? rp->state : nullptr, with_hist ? rp->state_floats : 0, e->stream));
   return WS_OK;
@@ -178,7 +128,7 @@ int a_step(ws_rate_pool* rp, std::vector<PieceRow>& rows, bool final) {
   float* d_stage = e->work.alloc(stage.size());
   WS_PTR(d_stage);
   int rc;
-  if ((rc = rp_copy(e, d_stage, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, "host-to-device copy")) != WS_OK) return rc;
+  if ((rc = copy_async(e, kWho, "host-to-device copy", d_stage, stage.data(), stage.size() * 4, hipMemcpyHostToDevice)) != WS_OK) return rc;
   return rows_launch(rp, d_stage, static_cast<long long>(stage.size()), false);
 }
 
@@ -192,8 +142,7 @@ int run_frames(ws_rate_pool* rp, std::vector<PieceRow>& rows, bool flush) {
     const RateSlot& sl = rp->slots[rows[r].slot];
     PoolSlot& isl = p->slots[rows[r].slot];
     const long long nm = sl.n_model;
-    const long long target = flush ? (nm - L) / s + 1 : (nm >= kLmax ? (nm - kLmax) / s + 1 : 0);
-    owed[r] = target - isl.k;
+    owed[r] = plain_frames(nm, L, flush) - isl.k;
     isl.n = nm;
   }
   int rc;
@@ -234,7 +183,7 @@ int compact(ws_rate_pool* rp, std::vector<PieceRow>& rows) {
   ws_rows_copy_row* d_tab = reinterpret_cast<ws_rows_copy_row*>(e->work.alloc(size_t(A) * sizeof(ws_rows_copy_row) / 4));
   WS_PTR(d_tab);
   int rc;
-  if ((rc = rp_copy(e, d_tab, tab.data(), size_t(A) * sizeof(ws_rows_copy_row), hipMemcpyHostToDevice, "table upload")) != WS_OK) return rc;
+  if ((rc = copy_async(e, kWho, "table upload", d_tab, tab.data(), size_t(A) * sizeof(ws_rows_copy_row), hipMemcpyHostToDevice)) != WS_OK) return rc;
   WS_RUN(e, ws_rows_copy_fwd(tab.data(), d_tab, A, rp->state, rp->state_floats, rp->state, rp->state_floats, e->stream));
   return WS_OK;
 }
@@ -267,7 +216,7 @@ int b_step(ws_rate_pool* rp, std::vector<PieceRow>& rows, bool final) {
   int rc;
   if ((rc = rows_launch(rp, rp->state, rp->state_floats, true)) != WS_OK) return rc;
   rec.host.assign(size_t(off), 0.f);
-  return rp_copy(e, rec.host.data(), rp->state + rp->bout0, size_t(off) * 4, hipMemcpyDeviceToHost, "device-to-host copy");
+  return copy_async(e, kWho, "device-to-host copy", rec.host.data(), rp->state + rp->bout0, size_t(off) * 4, hipMemcpyDeviceToHost);
 }
 
 // after the synchronisation: B's blocks to the callers' buffers, in order, cropped to what each entry emits
@@ -289,18 +238,7 @@ int check_rate_pool(const ws_rate_pool* rp, const char* who) {
   return pool_check(rp->inner, who);
 }
 
-int push_cap_of(const ws_rate_pool* rp, const Rate& rt, int n) {
-  const int L = rp->e->tas.L, hop = L / 2;
-  const Geom &a = rt.a, &b = rt.b;
-  if (n == 0) {
-    const long long ma = ((long long)a.K / a.D + 1) * a.U;
-    const long long mm = (ma / hop + 1) * hop + WS_STREAM_FLUSH_CAP;
-    return static_cast<int>(std::min<long long>(0x7fffffff, ((mm + b.K) / b.D + 2) * b.U));
-  }
-  const long long ma = ((long long)n / a.D + 1) * a.U;
-  const long long mm = (ma / hop + 1) * hop;
-  return static_cast<int>(std::min<long long>(0x7fffffff, (mm / b.D + 1) * b.U));
-}
+int push_cap_of(const ws_rate_pool* rp, const Rate& rt, int n) { return rate_push_cap(rt.a, rt.b, rp->e->tas.L, n); }
 
 std::string rates_text(const ws_rate_pool* rp) {
   std::string s;
@@ -357,7 +295,7 @@ WS_ENGINE_API int ws_engine_rate_pool_open(ws_engine* e, int slots, int max_chun
     r.a_taps = taps, taps += (long long)r.a.U * r.a.K;
     r.b_taps = taps, taps += (long long)r.b.U * r.b.K;
   }
-  const long long pend_cap = (kLmax + s + a_cap + 3) / 4 * 4;
+  const long long pend_cap = (kEncLmax + s + a_cap + 3) / 4 * 4;
   const long long m_cap = (pend_cap / s + 1) * s + L;
   long long b_ld = 0, b_cap = 0;
   for (const Rate& r : rp->rates) {
@@ -467,32 +405,13 @@ WS_ENGINE_API int ws_engine_rate_pool_push(ws_rate_pool* rp, int n_active, const
   ws_engine* e = rp->e;
   ws_pool* p = rp->inner;
   const int L = e->tas.L;
-  if (n_active < 1 || !slots || !chunks || !n || !est || !est_cap || !n_out) {
-    set_err("%s: bad arguments (n_active=%d >= 1%s)", who, n_active, slots && chunks && n && est && est_cap && n_out ? "" : ", a NULL array");
-    return WS_ERR_INVALID;
-  }
-  std::vector<char> seen(p->nslots, 0);
+  if ((rc = pool_check_push_args(who, n_active, slots, chunks, n, est, est_cap, n_out)) != WS_OK) return rc;
+  std::vector<char> seen(p->rows, 0);
   std::vector<long long> emit(n_active), col(n_active, 0);
   int pieces = 0;
   for (int i = 0; i < n_active; ++i) {
     const int id = slots[i];
-    if (id < 0 || id >= p->nslots || p->slots[id].state == PoolSlot::kFree) {
-      set_err("%s: slot %d (entry %d) is not attached (the pool has %d slots)", who, id, i, p->nslots);
-      return WS_ERR_INVALID;
-    }
-    if (p->slots[id].state == PoolSlot::kDone) {
-      set_err("%s: slot %d (entry %d) was flushed (detach it, then attach the next stream)", who, id, i);
-      return WS_ERR_INVALID;
-    }
-    if (seen[id]) {
-      set_err("%s: slot %d is named twice (entry %d): one packet a slot in a push", who, id, i);
-      return WS_ERR_INVALID;
-    }
-    seen[id] = 1;
-    if (n[i] < 1 || !chunks[i]) {
-      set_err("%s: entry %d (slot %d): n=%d >= 1, chunk %s", who, i, id, n[i], chunks[i] ? "given" : "NULL");
-      return WS_ERR_INVALID;
-    }
+    if ((rc = pool_check_entry(p, who, seen, i, id, n[i], chunks[i])) != WS_OK) return rc;
     const RateSlot& sl = rp->slots[id];
     const Rate& rt = rp->rates[sl.ri];
     emit[i] = rs_emitted(rt.b, plain_emitted(rs_emitted(rt.a, sl.n + n[i]), L)) - sl.returned;
@@ -509,7 +428,7 @@ WS_ENGINE_API int ws_engine_rate_pool_push(ws_rate_pool* rp, int n_active, const
   e->n_launches = 0;
   for (int i = 0; i < n_active; ++i) p->slots[slots[i]].failed = true;      // until the push is complete
   rp->clear_call();
-  const Arena::Mark mk = e->work.mark();
+  ArenaScope scope(e->work);
   for (int j = 0; j < pieces && rc == WS_OK; ++j) {
     std::vector<PieceRow> rows;
     for (int i = 0; i < n_active; ++i) {
@@ -524,8 +443,7 @@ WS_ENGINE_API int ws_engine_rate_pool_push(ws_rate_pool* rp, int n_active, const
     if ((rc = compact(rp, rows)) != WS_OK) break;
     rc = b_step(rp, rows, false);
   }
-  if (rc == WS_OK) rc = rp_sync(e);                 // the one host synchronisation of a push
-  e->work.release(mk);
+  if (rc == WS_OK) rc = sync_stream(e, kWho);                 // the one host synchronisation of a push
   if (rc != WS_OK) return rc;
   deliver(rp, est, emit, col);
   rp->clear_call();
@@ -550,17 +468,10 @@ WS_ENGINE_API int ws_engine_rate_pool_flush(ws_rate_pool* rp, int slot, float* e
   ws_engine* e = rp->e;
   ws_pool* p = rp->inner;
   const int L = e->tas.L, s = L / 2;
-  if (slot < 0 || slot >= p->nslots || p->slots[slot].state == PoolSlot::kFree) {
-    set_err("%s: slot %d is not attached (the pool has %d slots)", who, slot, p->nslots);
-    return WS_ERR_INVALID;
-  }
+  if ((rc = pool_check_slot(p, who, slot, true)) != WS_OK) return rc;
   PoolSlot& isl = p->slots[slot];
   RateSlot& sl = rp->slots[slot];
   const Rate& rt = rp->rates[sl.ri];
-  if (isl.state == PoolSlot::kDone) {
-    set_err("%s: slot %d was flushed already (detach it, then attach the next stream)", who, slot);
-    return WS_ERR_INVALID;
-  }
   const long long n_model = rs_len(rt.a, sl.n);
   if (n_model < L) {
     set_err("%s: slot %d: %lld samples were pushed, %lld at the container's rate, fewer than the encoder window L = %d", who, slot, sl.n, n_model,
@@ -580,7 +491,7 @@ WS_ENGINE_API int ws_engine_rate_pool_flush(ws_rate_pool* rp, int slot, float* e
   e->n_launches = 0;
   isl.failed = true;
   rp->clear_call();
-  const Arena::Mark mk = e->work.mark();
+  ArenaScope scope(e->work);
   std::vector<PieceRow> rows(1);
   rows[0].slot = slot;
   do {
@@ -597,7 +508,7 @@ WS_ENGINE_API int ws_engine_rate_pool_flush(ws_rate_pool* rp, int slot, float* e
         rc = WS_ERR_LAUNCH;
         break;
       }
-      if ((rc = rp_copy(e, d_tab, rp->ctabs.back().data(), sizeof(ws_rows_copy_row), hipMemcpyHostToDevice, "table upload")) != WS_OK) break;
+      if ((rc = copy_async(e, kWho, "table upload", d_tab, rp->ctabs.back().data(), sizeof(ws_rows_copy_row), hipMemcpyHostToDevice)) != WS_OK) break;
       const int crc = ws_rows_copy_fwd(rp->ctabs.back().data(), d_tab, 1, rp->state, rp->state_floats, rp->state, rp->state_floats, e->stream);
       if (!passes(e, crc, "ws_rows_copy_fwd")) {
         rc = crc ? crc : WS_ERR_LAUNCH;
@@ -608,8 +519,7 @@ WS_ENGINE_API int ws_engine_rate_pool_flush(ws_rate_pool* rp, int slot, float* e
     if ((rc = b_step(rp, rows, false)) != WS_OK) break;
     rc = b_step(rp, rows, true);                                       // B's flush, cropped below
   } while (false);
-  if (rc == WS_OK) rc = rp_sync(e);
-  e->work.release(mk);
+  if (rc == WS_OK) rc = sync_stream(e, kWho);
   if (rc != WS_OK) return rc;
   float* const ests[1] = {est};
   deliver(rp, ests, emit, col);
@@ -627,19 +537,9 @@ WS_ENGINE_API int ws_engine_rate_pool_flush(ws_rate_pool* rp, int slot, float* e
 }
 
 WS_ENGINE_API int ws_engine_rate_pool_detach(ws_rate_pool* rp, int slot) {
-  const char* who = "ws_engine_rate_pool_detach";
-  if (!rp || !rp->e || !rp->inner) {
-    set_err("%s: null pool", who);
-    return WS_ERR_INVALID;
-  }
-  ws_pool* p = rp->inner;
-  if (slot < 0 || slot >= p->nslots || p->slots[slot].state == PoolSlot::kFree) {
-    set_err("%s: slot %d is not attached (the pool has %d slots)", who, slot, p->nslots);
-    return WS_ERR_INVALID;
-  }
-  p->slots[slot] = PoolSlot();          // free, and no longer the slot of a half-finished call
-  rp->slots[slot] = RateSlot();
-  return WS_OK;
+  const int rc = pool_detach_impl(rp && rp->e ? rp->inner : nullptr, "ws_engine_rate_pool_detach", slot);
+  if (rc == WS_OK) rp->slots[slot] = RateSlot();
+  return rc;
 }
 
 WS_ENGINE_API void ws_engine_rate_pool_close(ws_rate_pool* rp) {

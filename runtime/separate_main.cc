@@ -57,6 +57,7 @@
 #include <atomic>
 #include <chrono>
 #include <fstream>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <sstream>
@@ -270,9 +271,11 @@ int main(int argc, char** argv) {
       for (int r = 0; r < R; ++r) memcpy(out + size_t(r) * n, back.data() + size_t(r) * m, size_t(std::min(n, m)) * 4);
       return true;
     };
-    // --rate_pool N: as --stream_pool N, every line at its own file's rate through one rate pool (ws_engine_rate_pool_*); the
-    // accepted rates are those of the scp's mixtures, read before the pool is opened; outputs have the mixture's rate and length
-    if (rate_pooled) {
+    // --stream_pool N: up to N lines in flight on one pool of 2 N slots; a lane takes the next line when its own ends.
+    // --rate_pool N: the same through one rate pool (ws_engine_rate_pool_*), every line at its own file's rate; the accepted rates
+    // are those of the scp's mixtures, read before the pool is opened; outputs have the mixture's rate and length.
+    // One lane driver for both: PoolDriver holds what they differ in.
+    if (pooled || rate_pooled) {
       struct Lane {
         bool live = false;
         size_t line = 0;
@@ -282,32 +285,73 @@ int main(int argc, char** argv) {
         long long pushes = 0;
         std::chrono::steady_clock::time_point t0;
       };
-      std::vector<int> rates;
-      int max_packet = 1;
-      for (const auto& w : waves) {
-        wesep_rt::Wav hdr;
-        std::string err;
-        if (!wesep_rt::read_wav(w[1], &hdr, &err)) {
-          fail(err);
+      struct PoolDriver {
+        const char *flag, *name;          // in messages; in the printed lines
+        int lanes = 0;
+        bool any_rate = false;            // every line at its own file's rate; else every file must be at --sample_rate
+        bool writes = false;              // the line's files are written
+        std::function<int(const float* enroll, int n_enroll, int rate, int* slot)> attach;
+        std::function<int(int n_active, const int* slots, const float* const* chunks, const int* n, float* const* est, const int* est_cap,
+                          int* n_out)> push;
+        std::function<int(int slot, float* est, int est_cap, int* n_out)> flush;
+        std::function<int(int slot)> detach;
+        std::function<int(int slot, int packet)> cap;     // samples a push of `packet` samples or the flush returns at most
+        std::function<void()> close;
+      } d;
+      ws_pool* pool = nullptr;
+      ws_rate_pool* rpool = nullptr;
+      if (rate_pooled) {
+        std::vector<int> rates;
+        int max_packet = 1;
+        for (const auto& w : waves) {
+          wesep_rt::Wav hdr;
+          std::string err;
+          if (!wesep_rt::read_wav(w[1], &hdr, &err)) {
+            fail(err);
+            ws_engine_destroy(engine);
+            return;
+          }
+          if (std::find(rates.begin(), rates.end(), hdr.sample_rate) == rates.end()) rates.push_back(hdr.sample_rate);
+          max_packet = std::max(max_packet, static_cast<int>(stream_ms * hdr.sample_rate / 1000.0 + 0.5));
+        }
+        d.flag = "--rate_pool", d.name = "rate pool", d.lanes = rate_pool_n, d.any_rate = true, d.writes = write_out;
+        if (ws_engine_rate_pool_open(engine, 2 * rate_pool_n, 64, stream_flags, rates.data(), static_cast<int>(rates.size()), max_packet, &rpool) != 0) {
+          fail(std::string("--rate_pool: ") + ws_engine_last_error());
           ws_engine_destroy(engine);
           return;
         }
-        if (std::find(rates.begin(), rates.end(), hdr.sample_rate) == rates.end()) rates.push_back(hdr.sample_rate);
-        max_packet = std::max(max_packet, static_cast<int>(stream_ms * hdr.sample_rate / 1000.0 + 0.5));
+        d.attach = [&](const float* e, int ne, int rate, int* slot) { return ws_engine_rate_pool_attach(rpool, e, WS_ENROLL_WAVE, ne, 0, rate, slot); };
+        d.push = [&](int na, const int* sl, const float* const* ch, const int* n, float* const* est, const int* cap, int* m) {
+          return ws_engine_rate_pool_push(rpool, na, sl, ch, n, est, cap, m);
+        };
+        d.flush = [&](int slot, float* est, int cap, int* m) { return ws_engine_rate_pool_flush(rpool, slot, est, cap, m); };
+        d.detach = [&](int slot) { return ws_engine_rate_pool_detach(rpool, slot); };
+        d.cap = [&](int slot, int packet) { return std::max(ws_engine_rate_pool_push_cap(rpool, slot, packet), ws_engine_rate_pool_push_cap(rpool, slot, 0)); };
+        d.close = [&] { ws_engine_rate_pool_close(rpool); };
+      } else {
+        d.flag = "--stream_pool", d.name = "pool", d.lanes = pool_n, d.any_rate = false, d.writes = !dry;
+        if (ws_engine_pool_open_ex(engine, 2 * pool_n, 64, stream_flags, &pool) != 0) {
+          fail(std::string("--stream_pool: ") + ws_engine_last_error());
+          ws_engine_destroy(engine);
+          return;
+        }
+        const int L = static_cast<int>(ws_engine_info(engine, "L"));
+        d.attach = [&](const float* e, int ne, int, int* slot) { return ws_engine_pool_attach(pool, e, WS_ENROLL_WAVE, ne, slot); };
+        d.push = [&](int na, const int* sl, const float* const* ch, const int* n, float* const* est, const int* cap, int* m) {
+          return ws_engine_pool_push(pool, na, sl, ch, n, est, cap, m);
+        };
+        d.flush = [&](int slot, float* est, int cap, int* m) { return ws_engine_pool_flush(pool, slot, est, cap, m); };
+        d.detach = [&](int slot) { return ws_engine_pool_detach(pool, slot); };
+        d.cap = [L](int, int packet) { return std::max(WS_STREAM_PUSH_CAP(packet, L), WS_STREAM_FLUSH_CAP); };
+        d.close = [&] { ws_engine_pool_close(pool); };
       }
-      ws_rate_pool* pool = nullptr;
-      if (ws_engine_rate_pool_open(engine, 2 * rate_pool_n, 64, stream_flags, rates.data(), static_cast<int>(rates.size()), max_packet, &pool) != 0) {
-        fail(std::string("--rate_pool: ") + ws_engine_last_error());
-        ws_engine_destroy(engine);
-        return;
-      }
-      std::vector<Lane> lanes(rate_pool_n);
-      std::vector<std::vector<float>> got(size_t(2) * rate_pool_n);
+      std::vector<Lane> lanes(d.lanes);
+      std::vector<std::vector<float>> got(size_t(2) * d.lanes);
       bool ok = true;
       long long rounds = 0, launches = 0;
       double audio_ms = 0.0;
       const auto pool_t0 = std::chrono::steady_clock::now();
-      auto start = [&](Lane& ln, int lane_id) {   // the next line into this lane: its enrollments at the model's rate, two slots at its rate
+      auto start = [&](Lane& ln, int lane_id) {   // the next line of the scp into this lane: read it, attach its two enrollments
         const size_t i = next++;
         if (i >= waves.size() || failed) return;
         const auto& w = waves[i];
@@ -318,28 +362,32 @@ int main(int argc, char** argv) {
           ok = false;
           return;
         }
+        if (!d.any_rate && (ln.mix.sample_rate != sample_rate || s1.sample_rate != sample_rate || s2.sample_rate != sample_rate)) {
+          fail(w[0] + ": sample rate is not " + std::to_string(sample_rate));
+          ok = false;
+          return;
+        }
         const int rate = ln.mix.sample_rate;
         ln.line = i, ln.n = static_cast<int>(ln.mix.samples.size()), ln.pos = ln.done = 0, ln.pushes = 0;
-        ln.packet = std::max(1, static_cast<int>(stream_ms * rate / 1000.0 + 0.5));
+        ln.packet = std::max(1, static_cast<int>(stream_ms * rate / 1000.0 + 0.5));      // M ms at the line's rate
         ln.out.assign(size_t(2) * ln.n, 0.f);
         ln.t0 = std::chrono::steady_clock::now();
-        std::vector<float> e[2];
+        std::vector<float> e[2];               // the enrollments at the model's rate, cut to the shorter one
         if (!to_model(s1.samples, s1.sample_rate, &e[0]) || !to_model(s2.samples, s2.sample_rate, &e[1])) {
           fail(w[0] + ": " + ws_engine_last_error());
           ok = false;
           return;
         }
         const int n_enroll = static_cast<int>(std::min(e[0].size(), e[1].size()));
-        for (int k = 0; k < 2 && ok; ++k) {
-          if (ws_engine_rate_pool_attach(pool, e[k].data(), WS_ENROLL_WAVE, n_enroll, 0, rate, &ln.slot[k]) != 0) {
+        for (int k = 0; k < 2; ++k) {
+          if (d.attach(e[k].data(), n_enroll, rate, &ln.slot[k]) != 0) {
             fail(w[0] + ": " + ws_engine_last_error());
             ok = false;
             return;
           }
-          const int cap = std::max(ws_engine_rate_pool_push_cap(pool, ln.slot[k], ln.packet), ws_engine_rate_pool_push_cap(pool, ln.slot[k], 0));
-          got[size_t(2) * lane_id + k].assign(size_t(std::max(cap, 1)), 0.f);
+          got[size_t(2) * lane_id + k].assign(size_t(std::max(d.cap(ln.slot[k], ln.packet), 1)), 0.f);
         }
-        ln.live = ok;
+        ln.live = true;
       };
       auto finish = [&](Lane& ln, int lane_id) {  // flush both slots, free them, write the line's files at the mixture's rate
         const auto& w = waves[ln.line];
@@ -348,8 +396,7 @@ int main(int argc, char** argv) {
         for (int k = 0; k < 2 && ok; ++k) {
           int m = 0;
           std::vector<float>& g = got[size_t(2) * lane_id + k];
-          if (ws_engine_rate_pool_flush(pool, ln.slot[k], g.data(), static_cast<int>(g.size()), &m) != 0 ||
-              ws_engine_rate_pool_detach(pool, ln.slot[k]) != 0) {
+          if (d.flush(ln.slot[k], g.data(), static_cast<int>(g.size()), &m) != 0 || d.detach(ln.slot[k]) != 0) {
             fail(w[0] + ": " + ws_engine_last_error());
             ok = false;
             return;
@@ -359,32 +406,33 @@ int main(int argc, char** argv) {
         }
         ln.live = false;
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ln.t0).count();
-        if (write_out && (!wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk1.wav", ln.out.data(), ln.n, rate, &err) ||
-                          !wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk2.wav", ln.out.data() + ln.n, ln.n, rate, &err))) {
+        if (d.writes && (!wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk1.wav", ln.out.data(), ln.n, rate, &err) ||
+                         !wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk2.wav", ln.out.data() + ln.n, ln.n, rate, &err))) {
           fail(err);
           ok = false;
           return;
         }
-        if (write_out && raw_out) {
+        if (d.writes && raw_out) {
           for (int k = 0; k < 2; ++k) {
             FILE* f = fopen((out_dir + "/" + w[0] + "-spk" + std::to_string(k + 1) + ".f32").c_str(), "wb");
             if (!f || fwrite(ln.out.data() + size_t(k) * ln.n, 4, ln.n, f) != size_t(ln.n)) fail("cannot write raw output");
             if (f) fclose(f);
           }
         }
+        const std::string at = d.any_rate ? " at " + std::to_string(rate) + " Hz" : "";
         std::lock_guard<std::mutex> l(io_mu);
-        printf("process: %s RTF: %.4f (rate pool of %d lines: %lld pushes of %d samples at %d Hz, %lld bytes of stream state)%s\n", w[0].c_str(),
-               ms / (1000.0 * ln.n / rate), rate_pool_n, ln.pushes, ln.packet, rate, ws_engine_info(engine, "stream_state_bytes"),
+        printf("process: %s RTF: %.4f (%s of %d lines: %lld pushes of %d samples%s, %lld bytes of stream state)%s\n", w[0].c_str(),
+               ms / (1000.0 * ln.n / rate), d.name, d.lanes, ln.pushes, ln.packet, at.c_str(), ws_engine_info(engine, "stream_state_bytes"),
                dry ? " [dry run]" : "");
         audio_ms += 1000.0 * ln.n / rate;
       };
-      for (int a = 0; a < rate_pool_n; ++a)
+      for (int a = 0; a < d.lanes; ++a)
         if (ok) start(lanes[a], a);
       while (ok && !failed) {
         std::vector<int> slots, ns, caps, n_out;
         std::vector<const float*> chunks;
         std::vector<float*> ests;
-        for (int a = 0; a < rate_pool_n; ++a) {
+        for (int a = 0; a < d.lanes; ++a) {
           Lane& ln = lanes[a];
           if (!ln.live) continue;
           const int c = std::min(ln.packet, ln.n - ln.pos);
@@ -397,15 +445,14 @@ int main(int argc, char** argv) {
         }
         if (slots.empty()) break;
         n_out.assign(slots.size(), 0);
-        if (ws_engine_rate_pool_push(pool, static_cast<int>(slots.size()), slots.data(), chunks.data(), ns.data(), ests.data(), caps.data(),
-                                     n_out.data()) != 0) {
-          fail(std::string("--rate_pool: ") + ws_engine_last_error());
+        if (d.push(static_cast<int>(slots.size()), slots.data(), chunks.data(), ns.data(), ests.data(), caps.data(), n_out.data()) != 0) {
+          fail(std::string(d.flag) + ": " + ws_engine_last_error());
           ok = false;
           break;
         }
         launches += ws_engine_info(engine, "n_launches"), ++rounds;
         size_t row = 0;
-        for (int a = 0; a < rate_pool_n && ok; ++a) {
+        for (int a = 0; a < d.lanes && ok; ++a) {
           Lane& ln = lanes[a];
           if (!ln.live) continue;
           for (int k = 0; k < 2; ++k, ++row)
@@ -417,150 +464,10 @@ int main(int argc, char** argv) {
           }
         }
       }
-      ws_engine_rate_pool_close(pool);
+      d.close();
       if (ok) {
         std::lock_guard<std::mutex> l(io_mu);
-        printf("rate pool: %lld rounds, %lld launches\n", rounds, launches);
-        total_audio_ms += audio_ms;
-        total_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pool_t0).count();
-      }
-      ws_engine_destroy(engine);
-      return;
-    }
-    // --stream_pool N: up to N lines in flight on one pool of 2 N slots; a lane takes the next line when its own ends
-    if (pooled) {
-      struct Lane {
-        bool live = false;
-        size_t line = 0;
-        wesep_rt::Wav mix;
-        std::vector<float> out, chunk;
-        int n = 0, pos = 0, done = 0, slot[2] = {-1, -1};
-        long long pushes = 0;
-        std::chrono::steady_clock::time_point t0;
-      };
-      const int L = static_cast<int>(ws_engine_info(engine, "L"));
-      const int cap = std::max(WS_STREAM_PUSH_CAP(stream_n, L), WS_STREAM_FLUSH_CAP);
-      ws_pool* pool = nullptr;
-      if (ws_engine_pool_open_ex(engine, 2 * pool_n, 64, stream_flags, &pool) != 0) {
-        fail(std::string("--stream_pool: ") + ws_engine_last_error());
-        ws_engine_destroy(engine);
-        return;
-      }
-      std::vector<Lane> lanes(pool_n);
-      std::vector<std::vector<float>> got(size_t(2) * pool_n, std::vector<float>(cap));
-      bool ok = true;
-      long long rounds = 0, launches = 0;
-      double audio_ms = 0.0;
-      const auto pool_t0 = std::chrono::steady_clock::now();
-      auto start = [&](Lane& ln) {              // the next line of the scp into this lane: read it, attach its two enrollments
-        const size_t i = next++;
-        if (i >= waves.size() || failed) return;
-        const auto& w = waves[i];
-        wesep_rt::Wav s1, s2;
-        std::string err;
-        if (!wesep_rt::read_wav(w[1], &ln.mix, &err) || !wesep_rt::read_wav(w[2], &s1, &err) || !wesep_rt::read_wav(w[3], &s2, &err)) {
-          fail(err);
-          ok = false;
-          return;
-        }
-        if (ln.mix.sample_rate != sample_rate || s1.sample_rate != sample_rate || s2.sample_rate != sample_rate) {
-          fail(w[0] + ": sample rate is not " + std::to_string(sample_rate));
-          ok = false;
-          return;
-        }
-        ln.line = i, ln.n = static_cast<int>(ln.mix.samples.size()), ln.pos = ln.done = 0, ln.pushes = 0;
-        ln.out.assign(size_t(2) * ln.n, 0.f);
-        ln.t0 = std::chrono::steady_clock::now();
-        const int n_enroll = static_cast<int>(std::min(s1.samples.size(), s2.samples.size()));
-        std::vector<float> enr(n_enroll);
-        for (int k = 0; k < 2 && ok; ++k) {
-          const std::vector<int16_t>& src = k == 0 ? s1.samples : s2.samples;
-          for (int j = 0; j < n_enroll; ++j) enr[j] = static_cast<float>(src[j]) / 32768.0f;
-          if (ws_engine_pool_attach(pool, enr.data(), WS_ENROLL_WAVE, n_enroll, &ln.slot[k]) != 0) {
-            fail(w[0] + ": " + ws_engine_last_error());
-            ok = false;
-          }
-        }
-        ln.live = ok;
-      };
-      auto finish = [&](Lane& ln, int lane_id) {  // flush both slots, free them, write the line's files
-        const auto& w = waves[ln.line];
-        std::string err;
-        for (int k = 0; k < 2 && ok; ++k) {
-          int m = 0;
-          float* g = got[size_t(2) * lane_id + k].data();
-          if (ws_engine_pool_flush(pool, ln.slot[k], g, cap, &m) != 0 || ws_engine_pool_detach(pool, ln.slot[k]) != 0) {
-            fail(w[0] + ": " + ws_engine_last_error());
-            ok = false;
-            return;
-          }
-          launches += ws_engine_info(engine, "n_launches");
-          memcpy(ln.out.data() + size_t(k) * ln.n + ln.done, g, size_t(std::min(m, ln.n - ln.done)) * 4);
-        }
-        ln.live = false;
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ln.t0).count();
-        if (!dry && (!wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk1.wav", ln.out.data(), ln.n, sample_rate, &err) ||
-                     !wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk2.wav", ln.out.data() + ln.n, ln.n, sample_rate, &err))) {
-          fail(err);
-          ok = false;
-          return;
-        }
-        if (!dry && raw_out) {
-          for (int k = 0; k < 2; ++k) {
-            FILE* f = fopen((out_dir + "/" + w[0] + "-spk" + std::to_string(k + 1) + ".f32").c_str(), "wb");
-            if (!f || fwrite(ln.out.data() + size_t(k) * ln.n, 4, ln.n, f) != size_t(ln.n)) fail("cannot write raw output");
-            if (f) fclose(f);
-          }
-        }
-        std::lock_guard<std::mutex> l(io_mu);
-        printf("process: %s RTF: %.4f (pool of %d lines: %lld pushes of %d samples, %lld bytes of stream state)%s\n", w[0].c_str(),
-               ms / (1000.0 * ln.n / sample_rate), pool_n, ln.pushes, stream_n, ws_engine_info(engine, "stream_state_bytes"),
-               dry ? " [dry run]" : "");
-        audio_ms += 1000.0 * ln.n / sample_rate;
-      };
-      for (Lane& ln : lanes)
-        if (ok) start(ln);
-      while (ok && !failed) {
-        std::vector<int> slots, ns, caps, n_out;
-        std::vector<const float*> chunks;
-        std::vector<float*> ests;
-        for (int a = 0; a < pool_n; ++a) {
-          Lane& ln = lanes[a];
-          if (!ln.live) continue;
-          const int c = std::min(stream_n, ln.n - ln.pos);
-          ln.chunk.resize(c);
-          for (int j = 0; j < c; ++j) ln.chunk[j] = static_cast<float>(ln.mix.samples[ln.pos + j]) / 32768.0f;
-          for (int k = 0; k < 2; ++k) {
-            slots.push_back(ln.slot[k]), ns.push_back(c), caps.push_back(cap);
-            chunks.push_back(ln.chunk.data()), ests.push_back(got[size_t(2) * a + k].data());
-          }
-        }
-        if (slots.empty()) break;
-        n_out.assign(slots.size(), 0);
-        if (ws_engine_pool_push(pool, static_cast<int>(slots.size()), slots.data(), chunks.data(), ns.data(), ests.data(), caps.data(),
-                                n_out.data()) != 0) {
-          fail(std::string("--stream_pool: ") + ws_engine_last_error());
-          ok = false;
-          break;
-        }
-        launches += ws_engine_info(engine, "n_launches"), ++rounds;
-        size_t row = 0;
-        for (int a = 0; a < pool_n && ok; ++a) {
-          Lane& ln = lanes[a];
-          if (!ln.live) continue;
-          for (int k = 0; k < 2; ++k, ++row)
-            memcpy(ln.out.data() + size_t(k) * ln.n + ln.done, ests[row], size_t(n_out[row]) * 4);
-          ln.done += n_out[row - 1], ln.pos += ns[row - 1], ++ln.pushes;
-          if (ln.pos >= ln.n) {
-            finish(ln, a);
-            if (ok) start(ln);
-          }
-        }
-      }
-      ws_engine_pool_close(pool);
-      if (ok) {
-        std::lock_guard<std::mutex> l(io_mu);
-        printf("pool: %lld rounds, %lld launches\n", rounds, launches);
+        printf("%s: %lld rounds, %lld launches\n", d.name, rounds, launches);
         total_audio_ms += audio_ms;
         total_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pool_t0).count();
       }

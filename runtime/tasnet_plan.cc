@@ -51,7 +51,7 @@ int tas_flat_stats(ws_engine* e, const float* x, int R, long long n, float* st) 
 // e [M][B] = proj(LayerNorm(cat)); M = R * T', T' = (T - L) / stride + 1
 int tas_encode(ws_engine* e, const float* wav, int R, int T, float* cat, float* feat) {
   const int N = e->tas.N, L = e->tas.L, B = e->tas.B, stride = L / 2;
-  const int Ls[3] = {L, 80, 160};
+  const int Ls[3] = {L, 80, kEncLmax};
   const char* names[3] = {"encoder.encoder_1d_short.", "encoder.encoder_1d_middle.", "encoder.encoder_1d_long."};
   const int Tp = (T - L) / stride + 1;
   const long long M = (long long)R * Tp;
@@ -300,7 +300,7 @@ int prepare_tasnet(ws_engine* e) {
   }
   e->dw = upload(e, e->persist, e->hw.data(), e->hw.size());
   WS_PTR(e->dw);
-  const int Ls[3] = {L, 80, 160};
+  const int Ls[3] = {L, 80, kEncLmax};
   const char* enc[3] = {"encoder.encoder_1d_short.", "encoder.encoder_1d_middle.", "encoder.encoder_1d_long."};
   for (int i = 0; i < 3; ++i)
     if (!require(e, std::string(enc[i]) + "weight", {N, 1, Ls[i]}) || !require(e, std::string(enc[i]) + "bias", {N}))
@@ -368,7 +368,7 @@ int prepare_tasnet(ws_engine* e) {
 // the argument checks of a Conv-TasNet forward, shared by ws_engine_separate and ws_engine_separate_long
 int tasnet_check_rows(ws_engine* e, bool ptrs, int R, int T) {
   const int L = e->tas.L, stride = L / 2;
-  if (!ptrs || R < 1 || T < 160 || (long long)R * ((T - L) / stride + 1) * 3 * e->tas.N > 0x7fffffffLL) {
+  if (!ptrs || R < 1 || T < kEncLmax || (long long)R * ((T - L) / stride + 1) * 3 * e->tas.N > 0x7fffffffLL) {
     set_err("ws_engine_separate: bad arguments (R=%d, T=%d; Conv-TasNet needs T >= 160)", R, T);
     return WS_ERR_INVALID;
   }
