@@ -341,6 +341,48 @@ int ws_engine_rate_pool_flush(ws_rate_pool* p, int slot, float* est, int est_cap
 int ws_engine_rate_pool_detach(ws_rate_pool* p, int slot);
 void ws_engine_rate_pool_close(ws_rate_pool* p);
 
+/* ---- live windows (runtime/live.cc; DESIGN sections 7 and 11b) -- new symbols, WS_ENGINE_ABI_VERSION 2 unchanged ----------
+ * ws_engine_separate_long for audio that arrives: ANY container (pBSRNN, Conv-TasNet, DPCCN, TF-GridNet; nothing here needs a
+ * causal model), one mixture, K target speakers, pushes of any size.  S = window, O = overlap, H = S - O, N = samples pushed.
+ *   windows run      Wr(N) = N < S ? 0 : 1 + (N - S) / H: window w starts at w H and runs once w H + S samples exist
+ *   samples emitted  E(N) = max(Wr - 1, 0) H: the samples before the start of the newest window run.  Every later window,
+ *                    regular or end-aligned, starts behind it, so every window covering an emitted sample has run, with its
+ *                    tail ramp.  LATENCY: a sample comes out S .. S + H samples after it went in -- the price of not knowing
+ *                    where the recording ends (the end-aligned last window may reach back to the newest window's start)
+ *   flush            n = N is final: if (n - S) % H != 0 one more window runs at n - S (no tail ramp); n < S is the one short
+ *                    row of ws_engine_separate_long's W == 1 branch, with the architecture's own lower bound on T -- a refusal
+ *                    launches nothing and leaves the state as it was, so a later push goes on.  Then [E, n) comes out.
+ * open makes exactly the checks of ws_engine_separate_long (its messages), runs the speaker stage ONCE over the K enrollments
+ * (or copies fixed embeddings / WS_ENROLL_SPEAKER) and makes ONE device allocation, ws_engine_info "live_state_bytes", a
+ * function of (K, S, O, max_rows): a ring [K][cap][S] of window estimates, cap = g_max + 3, g_max = max(1, max_rows / K); the
+ * ring of TF-GridNet's per-window factors; a group's samples, rows and embeddings.  Pending samples (fewer than S + H between
+ * pushes) stay on the host.  K > max_rows: a window's K rows go in several forwards, as in ws_engine_separate_long.
+ * push: est [K][est_cap], *n_out samples a target.  If no window became complete: *n_out = 0, NO launch, NO synchronisation.
+ * Otherwise per group of at most g_max new windows (cut where the ring wraps): one upload of its span, ws_window_rows, the
+ * rectangular plan on its rows in forwards of at most max_rows rows, the estimates into the ring, ws_xfade_stream_fwd on what
+ * became final; then one device-to-host copy and one synchronisation.  ws_engine_info "n_launches" after a push or flush:
+ *     sum over its groups of (the forwards' rectangular counts + WS_LIVE_GROUP_LAUNCHES(K, max_rows)) + 1
+ * -- per group ws_window_rows, the copy into the ring where a forward's rows span several targets (K > 1 and max_rows > 1;
+ * otherwise the plan writes into the ring itself) and ws_xfade_stream_fwd; + 1: the copy to the host.  A flush runs at most
+ * one group.  Nothing of it depends on N.  "live_windows": windows run since open / reset; "live_groups": groups of the last
+ * push or flush.  The engine's work arena is used under a scope and never reset; other calls on the engine between two
+ * pushes do not disturb the handle.  A push or flush after a flush is refused until ws_engine_live_reset (back to sample 0,
+ * enrollments kept).  Dry-run engines take every call.
+ * PARITY: the concatenated output equals ws_engine_separate_long(mix, n, K, ..., window, overlap, max_rows)
+ *   - to the rounding of forwards over other row counts (groups form differently);
+ *   - bit for bit when both run one row per forward (max_rows = 1), whatever the packet sizes;
+ *   - a flush alone with n <= window, K <= max_rows is ws_engine_separate on [K][n], bit for bit. */
+typedef struct ws_live ws_live;
+#define WS_LIVE_PUSH_CAP(n, H) (((n) / (H) + 1) * (H))
+#define WS_LIVE_FLUSH_CAP(S, O) (2 * (S) - (O))
+#define WS_LIVE_GROUP_LAUNCHES(K, max_rows) (2 + ((K) > 1 && (max_rows) > 1))
+int ws_engine_live_open(ws_engine* e, int K, const void* enroll, int enroll_kind, int enroll_len, const int* enroll_lengths,
+                        int window, int overlap, int max_rows, ws_live** out);
+int ws_engine_live_push(ws_live* s, const float* chunk, int n, float* est, int est_cap, int* n_out);
+int ws_engine_live_flush(ws_live* s, float* est, int est_cap, int* n_out);
+int ws_engine_live_reset(ws_live* s);
+void ws_engine_live_close(ws_live* s);
+
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by
  * 2^-15 before the model, separate_engine.cc:81-84, and its wav writer scales back, frontend/wav.h:245-253).

@@ -1135,6 +1135,25 @@ int ws_heads_merge_fwd(const float* ov, int nh, int R, long long P, int cp, floa
 int ws_window_rows(const float* x, int n, int W, int S, int H, int reps, const float* scale, float* rows, void* stream);
 int ws_xfade_ola(const float* y, int K, int W, int S, int O, int n, const float* scale, float* out, void* stream);
 
+/* Live windows (longform.hip; runtime/live.cc) -- a new symbol, ABI 20 unchanged.  ws_xfade_ola over the absolute
+ * sample positions [i0, i0 + count) of a recording whose windows arrive one by one:
+ *   ring [K][cap][S]   window w's estimate in slot w % cap;  scale_ring [cap] or NULL: its factor, in the same slot
+ *   windows_run        the regular windows 0 .. windows_run - 1 (start w H) have been written
+ *   final == 0         no last window exists yet: every covering window is regular with its tail ramp, no end-aligned term is
+ *                      added, and the range must end at or before (windows_run - 1) H -- the start of the newest window, behind
+ *                      which every later window, regular or end-aligned, starts.  W and n are ignored
+ *   final != 0         the layout of ws_xfade_ola for (n, S, O) with its W windows, all run (windows_run == W): the end-aligned
+ *                      last window sits in slot (W - 1) % cap; n < S is the one short window of L = n samples in slot 0
+ *   out [K][ld_out]    out[k][i - i0], ld_out >= count
+ * The per-sample arithmetic is the body ws_xfade_ola inlines (same weights, ascending w, num / den), so the concatenated
+ * ranges equal ws_xfade_ola on the same estimates bit for bit.  One thread per output sample, 64-bit window and sample indices,
+ * no atomics; a slot is read only for a window that covers the sample.  WS_ERR_INVALID before any launch: NULL ring / out, O
+ * outside [0, S / 2], count < 0 (count == 0 launches nothing), a range past the windows run unless final, a final (W, n) that
+ * is not the layout or not all run, and a cap that does not hold the windows the range reads (they must be among the newest
+ * cap). */
+int ws_xfade_stream_fwd(const float* ring, int K, int cap, int S, int O, const float* scale_ring, long long i0, long long count,
+                        long long windows_run, int final, long long W, long long n, float* out, long long ld_out, void* stream);
+
 /* ---- streaming Conv-TasNet (stream.hip; wesep_amd/streaming.py) -- new symbols, ABI 20 unchanged --------
  * The two kernels of a causal Conv-TasNet that look across time, in a chunked form with state carried on the device.
  *   ws_dwconv_stream_fwd  ws_dwconv_ex_fwd(causal = 1) on one chunk of Tc frames whose first frame has absolute index t0.

@@ -355,6 +355,11 @@ WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   // 1: ws_engine_stream_open takes this container (causal cLN Conv-TasNet / SpEx+); the state bytes of the stream opened last
   if (k == "streaming") return tas_streamable(e) ? 1 : 0;
   if (k == "stream_state_bytes") return e->stream_state_bytes;
+  // the live handle opened last: its one device allocation; the handle that ran last: windows since its open / reset, groups of
+  // its last call
+  if (k == "live_state_bytes") return e->live_state_bytes;
+  if (k == "live_windows") return e->live_windows;
+  if (k == "live_groups") return e->live_groups;
   auto it = e->meta.find(k);
   return it == e->meta.end() ? -1 : it->second;
 }

@@ -9,6 +9,7 @@
 //   dpccn_plan.cc    DPCCN (arch 2)
 //   gridnet_plan.cc  TF-GridNet (arch 3)
 //   longform.cc      ws_engine_separate_long: one long mixture as overlapping windows through the rectangular plans
+//   live.cc          ws_engine_live_*: the windows of ws_engine_separate_long run as their samples arrive, any architecture
 //   stream.cc        what every streaming front end shares -- the launch chain of a group of frames (stream_chain), the state
 //                    block (StreamCore) and the speaker stage of a stream (stream_enroll) -- and ws_engine_stream_*: causal
 //                    cLN Conv-TasNet fed audio as it arrives, state carried on the device
@@ -307,6 +308,8 @@ struct ws_engine {
   wsrt::Arena persist, work;
   long long n_launches = 0;
   long long long_windows = 0, long_forwards = 0;   // of the last ws_engine_separate_long
+  long long live_state_bytes = 0;                  // device state of the live handle opened last (ws_engine_live_open)
+  long long live_windows = 0, live_groups = 0;     // windows run since that handle's open / reset; groups of its last call
   long long stream_state_bytes = 0;                // device state of the stream opened last (ws_engine_stream_open)
   long long cluster_fallbacks = 0;   // forwards in which a cluster recurrence timed out and the streaming kernels took over
   unsigned* cl_status = nullptr;     // sticky device word set by ws_lstm_fwd_cluster on a timeout
@@ -396,6 +399,9 @@ int separate_impl(ws_engine* e, const float* mix, int R, int T, const int* lengt
                   int enroll_len, const int* enroll_lengths, float* est);
 int separate_long(ws_engine* e, const float* mix, int n, int K, const void* enroll, int enroll_kind, int enroll_len,
                   const int* enroll_lengths, int window, int overlap, int max_rows, float* est);
+int long_check_window(ws_engine* e, int window, int overlap, int max_rows);
+int long_check_group(ws_engine* e, int G, int L, int K, int enroll_kind, int enroll_len, const int* enroll_lengths, int* Te,
+                     std::vector<int>* te_row);
 
 // ---- speaker stage (speaker.cc) ----
 int read_speaker_meta(ws_engine* e);

@@ -16,14 +16,10 @@
 
 namespace wsrt {
 
-int separate_long(ws_engine* e, const float* mix, int n, int K, const void* enroll, int enroll_kind, int enroll_len,
-                  const int* enroll_lengths, int window, int overlap, int max_rows, float* est) {
-  int rc = check_engine(e, "ws_engine_separate_long");
-  if (rc != WS_OK) return rc;
-  if (!mix || !enroll || !est || n < 1 || K < 1) {
-    set_err("ws_engine_separate_long: bad arguments (n=%d, K=%d)", n, K);
-    return WS_ERR_INVALID;
-  }
+// What ws_engine_separate_long demands of (window, overlap, max_rows), with its messages; ws_engine_live_open (live.cc) makes
+// the same checks
+int long_check_window(ws_engine* e, int window, int overlap, int max_rows) {
+  int rc;
   if (max_rows < 1) {
     set_err("ws_engine_separate_long: max_rows = %d (at least one row per forward)", max_rows);
     return WS_ERR_INVALID;
@@ -45,6 +41,31 @@ int separate_long(ws_engine* e, const float* mix, int n, int K, const void* enro
       return WS_ERR_INVALID;
     }
   }
+  return WS_OK;
+}
+
+// ... and of a group of G rows of L samples and the K enrollments
+int long_check_group(ws_engine* e, int G, int L, int K, int enroll_kind, int enroll_len, const int* enroll_lengths, int* Te,
+                     std::vector<int>* te_row) {
+  int rc;
+  if ((rc = check_rows(e, true, G, L)) != WS_OK) return rc;       // the group's geometry against the plan's 2^31 guards
+  if (enroll_lengths && e->arch != 0 && e->arch != 3) {
+    set_err("ws_engine_separate_long: per-row enrollment lengths are built for pBSRNN (arch 0) and TF-GridNet (arch 3) only; "
+            "this container holds arch %d", e->arch);
+    return WS_ERR_INVALID;
+  }
+  return check_enroll(e, K, enroll_kind, enroll_len, enroll_lengths, Te, te_row);
+}
+
+int separate_long(ws_engine* e, const float* mix, int n, int K, const void* enroll, int enroll_kind, int enroll_len,
+                  const int* enroll_lengths, int window, int overlap, int max_rows, float* est) {
+  int rc = check_engine(e, "ws_engine_separate_long");
+  if (rc != WS_OK) return rc;
+  if (!mix || !enroll || !est || n < 1 || K < 1) {
+    set_err("ws_engine_separate_long: bad arguments (n=%d, K=%d)", n, K);
+    return WS_ERR_INVALID;
+  }
+  if ((rc = long_check_window(e, window, overlap, max_rows)) != WS_OK) return rc;
   const int H = window - overlap;
   const long long W64 = n <= window ? 1 : 1 + ((long long)n - window + H - 1) / H, rows64 = W64 * K;
   if (rows64 > 0x7fffffffLL) {
@@ -61,15 +82,9 @@ int separate_long(ws_engine* e, const float* mix, int n, int K, const void* enro
     return WS_OK;
   }
   const int G = rows < max_rows ? rows : max_rows;
-  if ((rc = check_rows(e, true, G, L)) != WS_OK) return rc;       // the group's geometry against the plan's 2^31 guards
-  if (enroll_lengths && e->arch != 0 && e->arch != 3) {
-    set_err("ws_engine_separate_long: per-row enrollment lengths are built for pBSRNN (arch 0) and TF-GridNet (arch 3) only; "
-            "this container holds arch %d", e->arch);
-    return WS_ERR_INVALID;
-  }
   int Te = enroll_len;
   std::vector<int> te_row;
-  if ((rc = check_enroll(e, K, enroll_kind, enroll_len, enroll_lengths, &Te, &te_row)) != WS_OK) return rc;
+  if ((rc = long_check_group(e, G, L, K, enroll_kind, enroll_len, enroll_lengths, &Te, &te_row)) != WS_OK) return rc;
 
   ForwardTurn turn(e);
   if (turn.rc != WS_OK) return turn.rc;

@@ -4,6 +4,7 @@
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
 //                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
 //                 [--stream_ms 10 [--stream_pool 4 | --rate_pool 4] [--stream_block]] [--resample]
+//                 [--live_ms 100 --chunk_seconds 4]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -26,6 +27,12 @@
 // O, N window rows per forward, the estimates cross-faded on the device, the speaker encoder run once per line.  Memory
 // grows with N, not with the recording.  Scaling, output names and formats as above; works with --jobs and --dry_run; not
 // together with --batch N > 1 (a rectangle of whole utterances).  A mixture no longer than S is the whole-utterance forward.
+// --live_ms M (with --chunk_seconds S; any model): the same windows, run as their samples arrive -- every line is fed to a
+// live handle (ws_engine_live_open / push / flush) in packets of M milliseconds at the model's rate, as a capture device would
+// deliver it; --overlap_seconds and --chunk_rows apply.  A sample comes out S .. S + (S - O) seconds of audio after it went in.
+// Names, scaling and formats are those of the --chunk_seconds run, and with --chunk_rows 1 so are the samples, bit for bit.
+// Works with --jobs, --dry_run and --resample (the files are brought to the model's rate around the handle, as for
+// --chunk_seconds).  Refused without --chunk_seconds, and together with --batch N > 1, --stream_ms and the pools.
 // --stream_ms M (causal cLN Conv-TasNet / SpEx+ models, ws_engine_info "streaming"): every line is fed to a stream
 // (ws_engine_stream_open / push / flush) in chunks of M milliseconds, as a live source would deliver it; the speaker encoder
 // runs once per line, at open.  Same files as the plain run: the streamed samples, then zeros where the plain run has its
@@ -155,6 +162,9 @@ int main(int argc, char** argv) {
   const bool stream_block = args.has("stream_block");
   const unsigned stream_flags = stream_block ? WS_STREAM_BLOCK_KERNEL : 0u;
   const bool resample = args.has("resample");
+  const bool live = args.has("live_ms");
+  const double live_ms = atof(args.get("live_ms", "0").c_str());
+  const int live_n = static_cast<int>(live_ms * sample_rate / 1000.0 + 0.5);
   const bool rate_pooled = args.has("rate_pool");
   const int rate_pool_n = atoi(args.get("rate_pool", "0").c_str());
   // a dry run writes nothing -- except with --resample and an --output_dir: the (all-zero) files then show the rate and the
@@ -165,6 +175,7 @@ int main(int argc, char** argv) {
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
            "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]]\n"
            "                     [--stream_ms M [--stream_pool N | --rate_pool N] [--stream_block]] [--resample]\n"
+           "                     [--live_ms M --chunk_seconds S]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
@@ -173,6 +184,9 @@ int main(int argc, char** argv) {
            "                     encoder runs once per line.  Not together with --batch N > 1\n"
            "  --overlap_seconds O  overlap of neighbouring windows, 0 <= O <= S / 2 (default S / 4)\n"
            "  --chunk_rows N     window rows per forward (default 8): memory grows with N, not with the recording\n"
+           "  --live_ms M        with --chunk_seconds S, any model: feed every line to a live handle in packets of M ms; the\n"
+           "                     windows run as their samples arrive (latency S .. 2 S - O seconds); same files as the\n"
+           "                     --chunk_seconds run.  Not together with --batch N > 1, --stream_ms or a pool\n"
            "  --stream_ms M      causal cLN Conv-TasNet / SpEx+ models: feed every line to a stream in chunks of M ms; same\n"
            "                     files as the plain run.  Not together with --batch N > 1 or --chunk_seconds\n"
            "  --stream_pool N    with --stream_ms M: N consecutive lines at a time through one stream pool, one push per round\n"
@@ -185,6 +199,11 @@ int main(int argc, char** argv) {
            "                     file's sample rate (packets of M ms at that rate); outputs have the mixture's rate and length\n");
     return 0;
   }
+  if (live && !chunked) return die("--live_ms needs --chunk_seconds S: a live handle runs the windows of S seconds as their samples arrive");
+  if (live && (batch > 1 || streamed || pooled || rate_pooled))
+    return die("--live_ms conflicts with --batch N > 1, --stream_ms, --stream_pool and --rate_pool: a live handle takes one recording as "
+               "it arrives, on any model, through the windows of --chunk_seconds");
+  if (live && live_n < 1) return die("--live_ms needs a positive packet length");
   if (chunked && batch > 1) return die("--chunk_seconds and --batch " + std::to_string(batch) + " conflict: a batch is a rectangle of "
                                        "whole utterances, --chunk_seconds cuts one recording into windows (use --jobs for more lines at a time)");
   if (pooled && !streamed) return die("--stream_pool needs --stream_ms M: the pool is fed packets of M milliseconds");
@@ -243,6 +262,33 @@ int main(int argc, char** argv) {
       return fail("--stream_ms: this model cannot stream (ws_engine_info \"streaming\" is not 1): streaming needs a causal cLN "
                   "Conv-TasNet / SpEx+ container");
     }
+    // --live_ms: mix [n] at the model's rate through a live handle in packets of live_n samples -> est [2][n]
+    long long live_pushes = 0, live_launches = 0, live_windows = 0, live_groups = 0;
+    auto run_live = [&](const float* mix, int n, const float* enr, int n_enroll, float* est) -> int {
+      live_pushes = live_launches = live_windows = live_groups = 0;
+      ws_live* lv = nullptr;
+      int rc = ws_engine_live_open(engine, 2, enr, WS_ENROLL_WAVE, n_enroll, nullptr, window, overlap, chunk_rows, &lv);
+      if (rc != 0) return rc;
+      const int cap = std::max(WS_LIVE_PUSH_CAP(live_n, window - overlap), WS_LIVE_FLUSH_CAP(window, overlap));
+      std::vector<float> got(size_t(2) * cap);
+      int done = 0;
+      auto take = [&](int m) {                                          // est [2][cap], m samples each, behind what came before
+        for (int k = 0; k < 2; ++k) memcpy(est + size_t(k) * n + done, got.data() + size_t(k) * cap, size_t(m) * 4);
+        done += m;
+        live_launches += ws_engine_info(engine, "n_launches"), live_groups += ws_engine_info(engine, "live_groups");
+      };
+      for (int pos = 0; rc == 0 && pos < n; pos += live_n, ++live_pushes) {
+        int m = 0;
+        if ((rc = ws_engine_live_push(lv, mix + pos, std::min(live_n, n - pos), got.data(), cap, &m)) == 0) take(m);
+      }
+      if (rc == 0) {
+        int m = 0;
+        if ((rc = ws_engine_live_flush(lv, got.data(), cap, &m)) == 0) take(m);
+      }
+      live_windows = ws_engine_info(engine, "live_windows");
+      ws_engine_live_close(lv);
+      return rc;
+    };
     // --resample: PCM at `rate` as floats in [-1, 1] at the model's rate, and estimates [R][n_m] back as [R][n] at `rate`
     auto to_model = [&](const std::vector<int16_t>& x, int rate, std::vector<float>* y) -> bool {
       std::vector<float> f(x.size());
@@ -637,7 +683,9 @@ int main(int argc, char** argv) {
           ws_engine_rate_stream_close(rs);
         } else if (rc == 0) {
           std::vector<float> out_m(size_t(2) * n_m, 0.f);
-          if (chunked) {
+          if (live) {
+            rc = run_live(mix_f.data(), n_m, enr.data(), n_enroll, out_m.data());
+          } else if (chunked) {
             rc = ws_engine_separate_long(engine, mix_f.data(), n_m, 2, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, window, overlap,
                                          chunk_rows, out_m.data());
           } else {                                                      // the rows of ws_engine_forward_pcm16: the mixture twice
@@ -688,8 +736,9 @@ int main(int argc, char** argv) {
           enr[i] = static_cast<float>(s1.samples[i]) / 32768.0f;
           enr[size_t(n_enroll) + i] = static_cast<float>(s2.samples[i]) / 32768.0f;
         }
-        rc = ws_engine_separate_long(engine, m.data(), n, 2, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, window, overlap,
-                                     chunk_rows, out.data());
+        rc = live ? run_live(m.data(), n, enr.data(), n_enroll, out.data())
+                  : ws_engine_separate_long(engine, m.data(), n, 2, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, window, overlap,
+                                            chunk_rows, out.data());
       } else {
         rc = ws_engine_forward_pcm16(engine, mix.samples.data(), n, s1.samples.data(), s2.samples.data(), n_enroll, out.data());
       }
@@ -716,6 +765,10 @@ int main(int argc, char** argv) {
         printf("process: %s RTF: %.4f (%lld pushes of %d samples, %lld launches, %lld bytes of stream state)%s\n", w[0].c_str(),
                ms / audio_ms, stream_pushes, stream_samples, stream_launches, ws_engine_info(engine, "stream_state_bytes"),
                dry ? " [dry run]" : "");
+      else if (live)
+        printf("process: %s RTF: %.4f (%lld pushes of %d samples: %lld windows in %lld groups, %lld launches, %lld bytes of live state)%s\n",
+               w[0].c_str(), ms / audio_ms, live_pushes, live_n, live_windows, live_groups, live_launches,
+               ws_engine_info(engine, "live_state_bytes"), dry ? " [dry run]" : "");
       else if (chunked)
         printf("process: %s RTF: %.4f (%lld windows in %lld forwards: %lld launches, %lld MiB arena)%s\n", w[0].c_str(), ms / audio_ms,
                plain_launches >= 0 ? long_w : ws_engine_info(engine, "long_windows"),

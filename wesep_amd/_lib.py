@@ -306,6 +306,7 @@ _SIGS = {
     # long recordings (longform.hip)
     "ws_window_rows": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "ws_xfade_ola": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ws_xfade_stream_fwd": (_i, [_p, _i, _i, _i, _i, _p, _ll, _ll, _ll, _i, _ll, _ll, _p, _ll, _p]),
     # streaming Conv-TasNet (stream.hip)
     "ws_dwconv_stream_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _ll, _i, _p, _p, _p]),
     "ws_ola_stream_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),

@@ -1663,6 +1663,21 @@ def xfade_ola(y, K: int, W: int, S: int, O: int, n: int, out, scale=None):
     _call("ws_xfade_ola", _p(y), K, W, S, O, n, _p(scale), _p(out))
 
 
+def xfade_stream_fwd(ring, K: int, cap: int, S: int, O: int, i0: int, count: int, windows_run: int, out, ld_out: int,
+                     final=None, scale_ring=None):
+    """ws_xfade_ola over the positions [i0, i0 + count), windows read from ring [K][cap][S] (window w in slot w % cap);
+    final = (W, n) at a flush, None while the recording runs.  out [K][ld_out]."""
+    for nm, t in (("ring", ring), ("out", out), ("scale_ring", scale_ring)):
+        _chk(t, nm)
+    _chk_room(ring, K * cap * S, "ws_xfade_stream_fwd", "ring")
+    _chk_room(out, (K - 1) * ld_out + count, "ws_xfade_stream_fwd", "out")
+    if scale_ring is not None:
+        _chk_room(scale_ring, cap, "ws_xfade_stream_fwd", "scale_ring")
+    W, n = final if final is not None else (0, 0)
+    _call("ws_xfade_stream_fwd", _p(ring), K, cap, S, O, _p(scale_ring), i0, count, windows_run, int(final is not None), W, n,
+          _p(out), ld_out)
+
+
 # ---- streaming Conv-TasNet (stream.hip; wesep_amd/streaming.py) ---------------------------------------------------
 def dwconv_stream_fwd(x, stats, gamma, beta, w, b, R: int, Tc: int, Cc: int, P: int, dil: int, st_div: int, t0: int,
                       ring, y):

@@ -22,7 +22,8 @@ SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", 
            "ws_engine_rate_stream_open", "ws_engine_rate_stream_push", "ws_engine_rate_stream_flush",
            "ws_engine_rate_stream_reset", "ws_engine_rate_stream_close", "ws_engine_rate_stream_push_cap",
            "ws_engine_rate_pool_open", "ws_engine_rate_pool_attach", "ws_engine_rate_pool_push", "ws_engine_rate_pool_push_cap",
-           "ws_engine_rate_pool_flush", "ws_engine_rate_pool_detach", "ws_engine_rate_pool_close")
+           "ws_engine_rate_pool_flush", "ws_engine_rate_pool_detach", "ws_engine_rate_pool_close",
+           "ws_engine_live_open", "ws_engine_live_push", "ws_engine_live_flush", "ws_engine_live_reset", "ws_engine_live_close")
 STREAM_FLUSH_CAP = 160  # WS_STREAM_FLUSH_CAP
 STREAM_BLOCK_KERNEL = 1  # WS_STREAM_BLOCK_KERNEL: every block of a stream / pool group as one entry-point call
 _lib = None
@@ -118,6 +119,17 @@ def lib():
         l.ws_engine_rate_pool_detach.argtypes = [C.c_void_p, C.c_int]
         l.ws_engine_rate_pool_close.restype = None
         l.ws_engine_rate_pool_close.argtypes = [C.c_void_p]
+        l.ws_engine_live_open.restype = C.c_int
+        l.ws_engine_live_open.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_void_p)]
+        l.ws_engine_live_push.restype = C.c_int
+        l.ws_engine_live_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_live_flush.restype = C.c_int
+        l.ws_engine_live_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_live_reset.restype = C.c_int
+        l.ws_engine_live_reset.argtypes = [C.c_void_p]
+        l.ws_engine_live_close.restype = None
+        l.ws_engine_live_close.argtypes = [C.c_void_p]
         if l.ws_engine_abi_version() != ENGINE_ABI_VERSION:
             raise WesepHipError("libwesep_engine.so ABI version mismatch; rebuild")
         _lib = l
@@ -279,6 +291,14 @@ class Engine:
                                              int(max_rows), est.ctypes.data), "ws_engine_separate_long")
         return est
 
+    def live(self, enrolls, kind, window, overlap, max_rows=8):
+        """A live handle on ANY container: separate_long's windows run as their samples arrive.  enrolls as in
+        separate_long() (K of them); the speaker stage runs once, here.  push() takes packets of any size and returns the
+        samples that became final, flush() the rest; their concatenation is separate_long(mix, enrolls, kind, window,
+        overlap, max_rows) -- bit for bit with max_rows = 1.  Latency: window .. window + hop samples.  Close the handle
+        before the engine."""
+        return EngineLive(self, enrolls, kind, window, overlap, max_rows)
+
     def stream(self, rows, enroll, kind, max_chunk_frames=64, block_kernel=False):
         """A stream of `rows` rows on a causal cLN Conv-TasNet / SpEx+ container (info("streaming") == 1): enroll as in
         separate(); the speaker stage runs once, here.  Close the stream before the engine.  block_kernel=True
@@ -398,6 +418,71 @@ class EngineStream:
     def close(self):
         if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
             _lib.ws_engine_stream_close(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+def live_push_cap(n, H):
+    """WS_LIVE_PUSH_CAP: samples a target that a live push of n samples can emit at most (H = window - overlap)."""
+    return (n // H + 1) * H
+
+
+def live_flush_cap(S, O):
+    """WS_LIVE_FLUSH_CAP: samples a target that a live flush can emit at most."""
+    return 2 * S - O
+
+
+def live_group_launches(K, max_rows):
+    """WS_LIVE_GROUP_LAUNCHES: what a group of windows adds to its forwards' entry-point calls."""
+    return 2 + (1 if K > 1 and max_rows > 1 else 0)
+
+
+class EngineLive:
+    """ws_engine_live_* (include/wesep_engine.h): one mixture in as it arrives, K targets out.  The concatenation of every
+    push() and the flush() is Engine.separate_long on the concatenated input."""
+
+    def __init__(self, engine, enrolls, kind, window, overlap, max_rows=8):
+        self._h, self._engine = C.c_void_p(), engine      # (the engine must outlive the handle)
+        enroll, pitch, lengths = _enroll_rows(enrolls, kind, None)
+        self.K, self.window, self.overlap, self.max_rows = enroll.shape[0], int(window), int(overlap), int(max_rows)
+        _quiesce_torch()
+        _check(lib().ws_engine_live_open(engine._h, self.K, enroll.ctypes.data, kind, pitch,
+                                         None if lengths is None else lengths.ctypes.data, self.window, self.overlap,
+                                         self.max_rows, C.byref(self._h)), "ws_engine_live_open")
+
+    def push(self, chunk, est_cap=None):
+        """chunk [n], n >= 1 -> [K, m] float32, the samples that became final (m = 0 while no window became complete).
+        est_cap: samples a target the output buffer holds (default: what always suffices)."""
+        chunk = np.ascontiguousarray(chunk, dtype=np.float32)
+        if chunk.ndim != 1:
+            raise ValueError(f"EngineLive.push: chunk is {chunk.shape}, expected [n >= 1]")
+        n = chunk.shape[0]
+        cap = live_push_cap(n, self.window - self.overlap) if est_cap is None else int(est_cap)
+        buf, m = np.zeros((self.K, max(cap, 1)), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_live_push(self._h, chunk.ctypes.data, n, buf.ctypes.data, cap, C.byref(m)), "ws_engine_live_push")
+        return buf[:, :m.value].copy()
+
+    def flush(self, est_cap=None):
+        """The end of the recording: the end-aligned last window if one is due, then every sample not yet out."""
+        cap = live_flush_cap(self.window, self.overlap) if est_cap is None else int(est_cap)
+        buf, m = np.zeros((self.K, max(cap, 1)), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_live_flush(self._h, buf.ctypes.data, cap, C.byref(m)), "ws_engine_live_flush")
+        return buf[:, :m.value].copy()
+
+    def reset(self):
+        """Back to sample 0; the enrollments are kept."""
+        _check(lib().ws_engine_live_reset(self._h), "ws_engine_live_reset")
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
+            _lib.ws_engine_live_close(self._h)
         self._h = None
 
     def __del__(self):
