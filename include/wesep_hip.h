@@ -275,7 +275,10 @@ typedef struct ws_lstm_args {
                             weights streamed per wave and step (the arithmetic of ws_lstm_pair_args.rfmt = 2).  3 (ABI v20):
                             the same pack and stream with the lo term on v_mfma_scale_f32_32x32x64_f8f6f4 (the codes as A
                             operands of K = 64 against e4m3 of d(gates) / 256): four fp16 MFMAs + one FP8 MFMA per 64 gate
-                            columns instead of eight fp16 MFMAs; not with `dxn`                                          */
+                            columns instead of eight fp16 MFMAs; not with `dxn`.
+                            ws_lstm_fwd (which reads nothing else of this field), blocked-layout modes: WS_LSTM_FWD_H2P (16) =
+                            hcat leaves as two fp16 planes (H2P, below) instead of BLS pairs -- what a launch that stands behind
+                            ws_lstm_fwd_cluster2 with rfmt bit 1 has to leave                                              */
   const unsigned* amax;  /* WS_GATES_H2F, backward: max |dhcat| of this launch as float bits (see WS_GATES_H2F) */
   /* ABI v19 (three trailing fields, zero = every earlier behaviour), ws_lstm_bwd with rfmt = 2 only: d(normalised input) of
    * the ResRNN computed INSIDE the BPTT from the d(gates) image its recurrent product reads anyway (autograd's d(input) of
@@ -326,6 +329,7 @@ typedef struct ws_lstm_args {
 #define WS_LSTM_BF16X3_BLK16 5 /* as 4 with 16-sequence workgroups (two per tile): for views with too few
                                   sequences to fill the chip with 32-sequence workgroups         */
 #define WS_LSTM_H 256
+#define WS_LSTM_FWD_H2P 16 /* ws_lstm_args.rfmt of a forward launch: hcat as two fp16 planes */
 #define WS_LSTM_PACK_FLOATS (2 * 4 * WS_LSTM_H * WS_LSTM_H) /* per pass, both directions */
 /* Packs weight_hh_l0 / _reverse [4H][H] into MFMA fragment order for the fwd and bwd pass
  * (fp32 for WS_LSTM_F32_*, bf16 hi/lo pairs for WS_LSTM_BF16X3; same byte size).           */
@@ -398,8 +402,9 @@ typedef struct ws_lstm_cluster2_args {
   int nseq, L;
   int dbg, rfmt;        /* rfmt (ABI v20, the former pad_: 0 = every earlier behaviour): 1 = the lo term of the recurrent product on
                            v_mfma_scale_f32_32x32x64_f8f6f4 (e4m3 codes of 256 w - hi, one exponent per wave, against e4m3 of h): four
-                           fp16 MFMAs + one FP8 MFMA per 64 columns instead of eight fp16 MFMAs                        */
-  float* dbg_buf;       /* dbg 2048: L * 2 * 8 64-bit cycle stamps of cluster 0 / member 0 (tools/r05_recur_probe.py) */
+                           fp16 MFMAs + one FP8 MFMA per 64 columns instead of eight fp16 MFMAs.  Bit 1 (value 2): hcat leaves as
+                           two fp16 planes (H2P, below) instead of BLS pairs                                             */
+  float* dbg_buf;      /* dbg 2048: L * 2 * 8 64-bit cycle stamps of cluster 0 / member 0 (tools/r05_recur_probe.py) */
 } ws_lstm_cluster2_args;
 int ws_lstm_fwd_cluster2(const ws_lstm_cluster2_args* a, void* stream);
 /* BPTT over the same clusters (reduce-scatter of partial dh each step): gates holds the activated
@@ -481,6 +486,11 @@ int ws_lstm_cat_ih(const float* wih_f, const float* wih_r, const float* bih_f, c
  * Producers have both terms at hand (they feed them to their own MFMAs); consumers (ws_gemm_b2p's A, all operands
  * of ws_gemm_tnb, xn of ws_lstm_fwd_fused) rebuild fragments with byte permutes instead of converting again -- the
  * products are bit-identical to splitting an fp32 copy.  Pre-activations / activated gates, cbuf and dhcat stay fp32.
+ * Two-plane fp16 storage H2P of hcat (training with WS_GATES_H2F; selected per producer: ws_lstm_fused_args.hfmt bit 3,
+ * ws_lstm_cluster2_args.rfmt bit 1, ws_lstm_args.rfmt = WS_LSTM_FWD_H2P): the same pointer and the same nblk * 32 * 2H * 4 bytes
+ * hold two BLH(2H) planes of nblk blocks each -- first hi = fp16(h), then lo = fp16(h - hi), both round to nearest even; value =
+ * hi + lo, >= 21 significant bits down to fp16's subnormal floor (|h| < 1).  The hi plane alone is the fp16 A operand of
+ * ws_gemm_tnb (a_fmt = 1) and the G operand of ws_gemm_tnb_h16; ws_gemm_b2p reads both planes (a_fmt = 4).
  * ws_seqmap maps a slot to its position (row) in the plain Z-layout tensors:
  *   pos = (seq / sq_div) * sq_s1 + (seq % sq_div) * sq_s2 + step * step_rows.              */
 typedef struct ws_seqmap {
@@ -557,7 +567,10 @@ typedef struct ws_gemm_b2p_args {
   int a_fmt, pad_;   /* ABI v15: 0 = A holds BLS pairs (BL(K)); 1 = A holds bf16 elements (BLH(K)): d(gates) of WS_GATES_H2;
                         2 = A holds scaled fp16 elements (BLH(K)): d(gates) of WS_GATES_H2F, scale from `amax`; Wpack
                         is then a ws_pack_w_f16 pack.  3 (ABI v20): as 2 with the lo term of the product on
-                        v_mfma_scale_f32_32x32x64_f8f6f4 (Wpack from ws_pack_w_f16f8; e4m3 of A / 256 built in registers) */
+                        v_mfma_scale_f32_32x32x64_f8f6f4 (Wpack from ws_pack_w_f16f8; e4m3 of A / 256 built in registers).
+                        4: A holds h as two fp16 planes (H2P, above: hi at A, lo nblk blocks of BLH(K) behind it), Wpack is a
+                        ws_pack_w_f16 pack: hi w_hi + hi w_lo + lo w_hi on the fp16 MFMA (the dropped lo w_lo is 2^-22 of the
+                        product); no amax, no a16_out                                                                    */
   const unsigned* amax;
   void* a16_out;     /* optional (ABI v16, a_fmt 0 only: any other a_fmt with a16_out is refused): the A operand once more as
                         fp16(hi + lo) elements in BLH(K), padded slots included -- every block is read by exactly one wave
@@ -596,6 +609,17 @@ typedef struct ws_gemm_tnb_args {
                         per block instead of 56 (the kernel is bound by the CU's global-load issue rate)                */
 } ws_gemm_tnb_args;
 int ws_gemm_tnb(const ws_gemm_tnb_args* a, void* stream);
+/* dW_proj^T = h^T dout on the fp16 hi plane of h (H2P storage, above; a new symbol of ABI v20, the same argument struct):
+ *   slab[split][g][a] = sum G[(b,i)][g_off + g] * A0[(b,i)][a0_off + a],  aslab[split][a] = column sums of A0 (optional).
+ * G holds fp16 elements in BLH(g_width) -- the hi plane, used as it is --, A0 BLS pairs in BL(a0_width) with exactly 128 columns
+ * and no shift; no A1, no bslab, g_fmt = a_fmt = 0, amax REQUIRED: both bf16 terms of A0 are lifted into fp16 by the power of two
+ * S = 2^(WS_DGATES_EXP - floor(log2 max|d(hcat)|)) that `amax` defines (the scale of WS_GATES_H2F) -- exact for every term whose
+ * scaled magnitude is a normal fp16 number, rounded to nearest (at most 2^-25 / S off) in fp16's subnormals -- and a product is
+ * two fp16 MFMAs; slab and aslab come out unscaled.  Precondition: |A0| S <= 65504, i.e. max |A0| < 2^7 max |d(hcat)| (A0 is
+ * the gradient whose projection d(hcat) is; a projection weight of nearly zero breaks it: amax = 0 gives S = 1).  Beyond it the
+ * lifted term is +-Inf and the slab non-finite -- like an overflowing d(gates) of WS_GATES_H2F it reaches ws_grad_norms' guard
+ * and the step is skipped and counted, never a silently clipped gradient.  Splits as ws_gemm_tnb.                        */
+int ws_gemm_tnb_h16(const ws_gemm_tnb_args* a, void* stream);
 
 /* ---- STFT / iSTFT (torch.stft / torch.istft at bsrnn.py:309-316, 382-389) ---------------
  * n_fft = 512, hop = 128, periodic Hann, center + reflect pad.  Band-split spectrogram
@@ -792,7 +816,9 @@ typedef struct ws_lstm_fused_args {
                            (the wait of rounds 3-5).  Bit 2 (ABI v20; with bit 0: hfmt = 5): the lo term of that product on
                            v_mfma_scale_f32_32x32x64_f8f6f4 -- the residuals 256 w - hi as e4m3 codes with one exponent per
                            fragment against an e4m3 image of h: four fp16 MFMAs + one FP8 MFMA (K = 64, twice the rate) per
-                           recurrent k-step instead of eight; wpack from ws_lstm_pack_fused_h8 (64- and 32-sequence kernels)  */
+                           recurrent k-step instead of eight; wpack from ws_lstm_pack_fused_h8 (64- and 32-sequence kernels).
+                           Bit 3 (value 8, with bit 0): hcat leaves as two fp16 planes (H2P, above) instead of BLS pairs; gates
+                           and cbuf are bit-identical to the launch without it                                              */
 } ws_lstm_fused_args;
 #define WS_LSTM_FUSED_PACK_FLOATS (2 * 8 * 24 * 4 * 2 * 64 * 4)
 int ws_lstm_pack_fused(const float* wih_f, const float* wih_r, const float* whh_f, const float* whh_r,

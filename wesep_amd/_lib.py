@@ -29,6 +29,7 @@ def dgates_scale(amax_bits: int) -> float:
 
 
 LSTM_F32_MT1, LSTM_F32_MT2, LSTM_BF16X3, LSTM_BF16X3_BLK, LSTM_BF16X3_BLK16 = 1, 2, 3, 4, 5
+LSTM_FWD_H2P = 16          # WS_LSTM_FWD_H2P: ws_lstm_args.rfmt of a forward launch that leaves hcat as two fp16 planes
 LSTM_PACK_FLOATS = 2 * 4 * LSTM_H * LSTM_H
 
 _p = C.c_void_p
@@ -202,6 +203,7 @@ _SIGS = {
     "ws_gemm_p2b_len": (_i, [C.POINTER(GemmP2BArgs), _p, _i, _p]),
     "ws_gemm_b2p": (_i, [C.POINTER(GemmB2PArgs), _p]),
     "ws_gemm_tnb": (_i, [C.POINTER(GemmTNBArgs), _p]),
+    "ws_gemm_tnb_h16": (_i, [C.POINTER(GemmTNBArgs), _p]),
     "ws_stft_bandsplit": (_i, [_p, _i, _i, C.POINTER(Bands), _p, _p]),
     "ws_stft_bandsplit_len": (_i, [_p, _i, _i, _p, C.POINTER(Bands), _p, _p]),
     "ws_mask_istft_frames": (_i, [_p, _p, _i, _i, C.POINTER(Bands), _p, _p]),

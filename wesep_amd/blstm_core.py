@@ -398,8 +398,9 @@ class WeightPacks:
     weights change).  kinds: cat (wcat, bcat) | whh (contiguous W_hh pair) | hh (fwd, bwd recurrence packs of mode
     `lmode`) | hh8 / wx8 (streaming BPTT's FP8 packs) | hhp / hhp16 (pair-BPTT pack; hhp16 in the plan's `pair_rf` format) |
     fused* ([W_ih | W_hh] stream of lstm_fused.hip) | wih / wihT* (p2b x-projection, b2p d(xn)) | pw (contiguous proj.weight) |
-    proj / projT (b2p projection, p2b d(hcat)).  An object, not a pair of closures that name each other: a caller whose cache
-    lives for one forward / backward pair (TF-GridNet) gets its packs back when ctx dies, not when the cycle collector runs."""
+    proj / proj16 / projT (b2p projection, the same as fp16 hi / lo for h in fp16 planes, p2b d(hcat)).  An object, not a pair
+    of closures that name each other: a caller whose cache lives for one forward / backward pair (TF-GridNet) gets its packs
+    back when ctx dies, not when the cycle collector runs."""
 
     def __init__(self, cache, sig, lmode, pair_rf, wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r, proj_w):
         self.cache, self.sig, self.lmode, self.pair_rf = cache, sig, lmode, pair_rf
@@ -455,9 +456,9 @@ class WeightPacks:
             return out
         if kind == "pw":
             return proj_w.contiguous()
-        if kind == "proj":
+        if kind in ("proj", "proj16"):      # proj16: fp16 hi / lo of 256 w (ws_pack_w_f16): the projection over h as fp16 planes
             out = _empty(d, N * 2 * H)
-            dev.pack_w(W("pw"), N, 2 * H, 2 * H, out, order=1)
+            dev.pack_w(W("pw"), N, 2 * H, 2 * H, out, order=1, f16=kind == "proj16")
             return out
         if kind == "projT":
             out = _empty(d, 2 * H * N)
@@ -488,6 +489,7 @@ class BlstmPlan(NamedTuple):
     band_rfmt: int      # streaming BPTT's recurrent product (band_rfmt); 0 when another kernel runs
     band_dx: bool       # the streaming BPTT writes d(xn) itself (band_dx)
     a_fmt: int          # a_fmt of the d(xn) GEMM over d(gates) (dxn_fmt)
+    h2p: bool = False   # h leaves the recurrence as two fp16 planes: one buffer serves projection and weight gradients (dev.h2p_on)
 
 
 _WIHT_KIND = {0: "wihT", 1: "wihT", 2: "wihT16", 3: "wihT8"}     # BlstmPlan.a_fmt -> pack of W_ih^T for the d(xn) GEMM
@@ -516,10 +518,15 @@ def make_plan(seq, device, grad, gn_geo=None, ragged=False) -> BlstmPlan:
         fwd = "stream"
     g_fmt = {L.GATES_H2: 1, L.GATES_H2F: 2}.get(gfmt, 0)
     brf = band_rfmt(gfmt, lmode) if grad and bptt == "stream" else 0
+    a16 = gfmt == L.GATES_H2F and grad and tnb_a16()
+    # the planes replace the pair wherever the fp16 copies exist (a backward follows: inference and the ragged branches keep the
+    # pair); the fused forward writes them from its fp16-h kernels only
+    h2p = (a16 and dev.h2p_on(device) and not ragged and fwd in ("fused", "cluster2", "stream")
+           and (fwd != "fused" or bool(dev.lstm_fused_hfmt(gfmt) & 1)))
     return BlstmPlan(
         nb=dev.bl_num_blocks(seq), lmode=lmode, cluster=cluster, fwd=fwd, bptt=bptt, grad=grad, gfmt=gfmt, g_fmt=g_fmt,
-        a16=gfmt == L.GATES_H2F and grad and tnb_a16(), pair_rfmt=pair_rfmt(gfmt) if grad and bptt == "pair" else 0,
-        band_rfmt=brf, band_dx=bool(brf) and gn_geo is not None and band_dx(brf, seq, gn_geo), a_fmt=dxn_fmt(g_fmt))
+        a16=a16, pair_rfmt=pair_rfmt(gfmt) if grad and bptt == "pair" else 0,
+        band_rfmt=brf, band_dx=bool(brf) and gn_geo is not None and band_dx(brf, seq, gn_geo), a_fmt=dxn_fmt(g_fmt), h2p=h2p)
 
 
 def consume_once(ctx, who):
@@ -538,7 +545,8 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
     """out = res + Linear(BLSTM(x')) over the rows of the sequence map `seq`; x [rows, 128] plain, x' = x, or GroupNorm(x) with
     norm = dict(stats=, gamma=, beta=, stat_map=) (applied by ws_gemm_p2b on the way into BL).  W: the pack provider
     (WeightPacks).  Returns (out, saved): saved = (gates, cbuf, hcat, xn, hcat16) for ctx.save_for_backward -- xn is its
-    fp16 copy when plan.a16 (the backward never reads the split-pair xn again), hcat16 is None without it.
+    fp16 copy when plan.a16 (the backward never reads the split-pair xn again), hcat16 is None without it and with plan.h2p
+    (hcat then holds h as two fp16 planes and the copy is its first half: one tensor for h).
     steps (ragged batches, inference): (int32 device table, div) -- sequence s has table[s // div] valid steps; the
     pre-activations behind them are exact zeros, so the reverse direction reaches a sequence's last valid step with zero
     state (plan from make_plan(ragged=True); a branch that was not taught lengths refuses them)."""
@@ -562,7 +570,11 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
     # (profiles/r06_side_stream_tax.md: the clock follows the load): one MFMA per product instead of three on the side stream
     # is 263.6 -> 248.7 ms per step at config 5's per-GPU shape (two runs each, one box), 123 -> 131 GB
     xn16 = _empty(d, dev.blh_floats(nb, N)) if plan.a16 else None
-    hcat16 = _empty(d, dev.blh_floats(nb, 2 * H)) if plan.a16 else None
+    # plan.h2p: no twin -- `hcat` itself holds h as two fp16 planes (wesep_hip.h, H2P) and its first half IS that copy; the
+    # projection then reads 4 bytes per element and writes none, where it read 4 and wrote 2, and dW_proj reads 2 instead of 4
+    h2p = plan.h2p
+    planes = dict(h2p=True) if h2p else {}      # (the recurrences' keyword for it)
+    hcat16 = _empty(d, dev.blh_floats(nb, 2 * H)) if plan.a16 and not h2p else None
     if plan.fwd == "fused":
         # many short sequences (pBSRNN's band view, TF-GridNet's intra-frame path): the recurrence computes x W_ih^T itself
         # from the normalised input (BL(128)): the 16E-byte pre-activation buffer is never written and read back
@@ -570,7 +582,7 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
         dev.gemm_p2b(A=x, lda=N, sm=seq, Wpack=None, N=0, C_out=None, A_bl=xn, A_bl16=xn16, **norm)
         hf = dev.lstm_fused_hfmt(gfmt)
         dev.lstm_fwd_fused(gates, cbuf, hcat, xn, W("fused8" if hf & 4 else "fused16" if hf else "fused"), bcat, seq, gfmt=gfmt,
-                           hfmt=hf)
+                           hfmt=hf | (8 if h2p else 0))
     elif plan.fwd == "cluster2":
         # few long sequences (time view, inter-frame path), 2-byte formats (round 5): the cluster kernel computes x W_ih^T
         # itself from the normalised input (lstm_cluster2.hip) -- ws_gemm_p2b only normalises / relays (reads E, writes E
@@ -584,10 +596,10 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
         # (profiles/r05_tfg_cfg5_precision_split.txt); the input keeps its split pair since.  WESEP_LSTM_CLUSTER2=0 selects
         # the round-4 cluster kernel on fp32 pre-activations
         dev.gemm_p2b(A=x, lda=N, sm=seq, Wpack=None, N=0, C_out=None, A_bl=xn, A_bl16=xn16, **norm)
-        tw = dev.lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whf, whr, seq, dbg=_cluster_dbg())
+        tw = dev.lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whf, whr, seq, dbg=_cluster_dbg(), **planes)
         pre = dev.fallback_scratch(d, nb * 32 * 2 * G4)       # (untouched after a clean launch; one buffer per stream)
         dev.gemm_p2b(A=x, lda=N, sm=seq, Wpack=W("wih"), N=2 * G4, C_out=pre, bias=bcat, run_if=tw, **norm)
-        dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, run_if=tw, gfmt=gfmt, gates_in=pre)
+        dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, run_if=tw, gfmt=gfmt, gates_in=pre, **planes)
         del pre
     else:
         # pre-activations: in `gates` itself with the fp32 format (one buffer, three lives); with the 2-byte formats a
@@ -595,6 +607,7 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
         pre = _empty(d, nb, 32 * 2 * G4) if h2 else gates
         xproj = dict(A=x, lda=N, sm=seq, Wpack=W("wih"), N=2 * G4, C_out=pre, bias=bcat, A_bl=xn, A_bl16=xn16, **norm, **lens)
         rec = dict(gfmt=gfmt, gates_in=pre) if h2 else {}
+        # (the round-4 cluster kernel writes pairs only: make_plan never sets h2p for it)
         dev.gemm_p2b(**xproj)
         if _h2_probe() & 768 and not torch.cuda.is_available():
             # NUMERICS PROBE (CPU emulation only): the time view's pre-activations in 2 bytes -- fp16 (bit 256) / bf16 (512)
@@ -609,10 +622,13 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
                 dev.gemm_p2b(run_if=tw, **xproj)
             dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, run_if=tw, **rec)
         else:
-            dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, **rec)
+            dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, **planes, **rec)
         del pre
     out = torch.empty_like(res)
-    dev.gemm_b2p(A=hcat, K=2 * H, sm=seq, Wpack=W("proj"), C_out=out, ldc=N, bias=bias, R=res, a16_out=hcat16)
+    if h2p:     # both planes against the fp16 hi / lo pack of 256 w: three fp16 MFMAs per product, no copy written
+        dev.gemm_b2p(A=hcat, K=2 * H, sm=seq, Wpack=W("proj16"), C_out=out, ldc=N, bias=bias, R=res, a_fmt=4)
+    else:
+        dev.gemm_b2p(A=hcat, K=2 * H, sm=seq, Wpack=W("proj"), C_out=out, ldc=N, bias=bias, R=res, a16_out=hcat16)
     if _h2_probe() and not h2:
         if _h2_probe() & 1:
             _probe_round(gates, "f16")
@@ -707,12 +723,15 @@ def blstm_bptt(plan, W, gates, cbuf, hcat, dout, seq, release):
     return dg, dout_bl, amax, dxn2
 
 
-def weight_grads(gates, xn, hcat, dout_bl, seq, nb, g_fmt=0, amax=None, hcat16=None):
+def weight_grads(gates, xn, hcat, dout_bl, seq, nb, g_fmt=0, amax=None, hcat16=None, h2p=False):
     """[dW_ih | dW_hh | db] of both directions in one pass over each direction's dgates, and
     dW_proj / db_proj; launched on the current stream.  Returns them in nn.LSTM parameter order: [dW_ih_f, dW_hh_f, db_f,
     db_f (clone), dW_ih_r, dW_hh_r, db_r, db_r (clone), dW_proj, db_proj].  hcat16 given: `xn` and it are the fp16 copies in
-    BLH (ws_gemm_tnb a_fmt = 1; g_fmt 2 only)."""
+    BLH (ws_gemm_tnb a_fmt = 1; g_fmt 2 only).  h2p: `hcat` holds h as two fp16 planes; its hi plane is that copy and the
+    operand of dW_proj too (ws_gemm_tnb_h16)."""
     d = gates.device
+    if h2p:
+        hcat16 = dev.h2p_hi(hcat, nb)
     a_fmt = 1 if hcat16 is not None else 0
     if _h2_probe() & 192 and not torch.cuda.is_available() and not a_fmt:
         # NUMERICS PROBE (CPU emulation only: plain fp32 buffers): the A operand [xn | h] of the weight-gradient GEMMs at
@@ -731,8 +750,12 @@ def weight_grads(gates, xn, hcat, dout_bl, seq, nb, g_fmt=0, amax=None, hcat16=N
     # dW_proj^T [2H][N] = hcat^T dout (hcat as the streamed-once operand), db_proj = colsum(dout)
     ns, bps = dev.tnb_splits(nb, (2 * H) // 128)
     slab, aslab = _empty(d, ns, 2 * H * N), _empty(d, ns, N)
-    dev.gemm_tnb(G=hcat, g_width=2 * H, g_off=0, g_cols=2 * H, A0=dout_bl, a0_width=N, a0_off=0, a0_cols=N,
-                 nblk=nb, L_=seq.L, slab=slab, nsplit=ns, blocks_per_split=bps, aslab=aslab)
+    if h2p:     # fp16(h) against the stored pairs of dout lifted into fp16 by this backward's scale: two fp16 MFMAs per product
+        dev.gemm_tnb_h16(G=hcat16, g_width=2 * H, g_off=0, g_cols=2 * H, A0=dout_bl, a0_width=N, a0_off=0, nblk=nb, L_=seq.L,
+                         slab=slab, nsplit=ns, blocks_per_split=bps, amax=amax, aslab=aslab)
+    else:
+        dev.gemm_tnb(G=hcat, g_width=2 * H, g_off=0, g_cols=2 * H, A0=dout_bl, a0_width=N, a0_off=0, a0_cols=N,
+                     nblk=nb, L_=seq.L, slab=slab, nsplit=ns, blocks_per_split=bps, aslab=aslab)
     dproj_w = _reduce_new(slab, ns, 2 * H * N, (2 * H, N)).t().contiguous()
     dproj_b = _reduce_new(aslab, ns, N, (N,))
     ns, bps = dev.tnb_splits(nb, G4 // 128)
@@ -758,12 +781,12 @@ def blstm_weight_grads(plan, dg, xn, hcat, dout_bl, amax, hcat16, seq, box, orde
     box, records its event and keeps its operands valid (keep_for_side); Nones are returned and the carrier delivers.
     order: which of weight_grads' ten the caller's weight arguments take, in the order of those arguments."""
     if box is None:
-        wg = weight_grads(dg, xn, hcat, dout_bl, seq, plan.nb, plan.g_fmt, amax, hcat16)
+        wg = weight_grads(dg, xn, hcat, dout_bl, seq, plan.nb, plan.g_fmt, amax, hcat16, h2p=plan.h2p)
         return [wg[i] for i in order]
     prod = torch.cuda.current_stream()
 
     def job(side):
-        wg = weight_grads(dg, xn, hcat, dout_bl, seq, plan.nb, plan.g_fmt, amax, hcat16)
+        wg = weight_grads(dg, xn, hcat, dout_bl, seq, plan.nb, plan.g_fmt, amax, hcat16, h2p=plan.h2p)
         box.grads = [wg[i] for i in order]
         box.event = torch.cuda.Event()
         box.event.record(side)

@@ -400,11 +400,15 @@ extern "C" int ws_gemm_p2b_len(const ws_gemm_p2b_args* a, const int* steps, int 
 // A16 = 3 (a_fmt = 3, ABI v20): a_fmt 2 with the lo term on v_mfma_scale_f32_32x32x64_f8f6f4 -- Wpack from ws_pack_w_f16f8 (24 KB
 // per stage through LDS instead of 32), the A operand of the term = e4m3 of the stage's four fp16 fragments / 256, converted in
 // registers: per stage and column tile four fp16 MFMAs + one FP8 MFMA (K = 64, twice the rate) instead of eight.
+// A16 = 4 (a_fmt = 4): A holds h as two fp16 planes (H2P, wesep_hip.h: the hi plane at A, the lo plane nblk blocks of BLH(K) behind
+// it) and Wpack is the ws_pack_w_f16 pack: a_hi w_hi + a_hi w_lo + a_lo w_hi on v_mfma_f32_32x32x16_f16 -- the dropped term
+// a_lo w_lo is 2^-22 of the product --, the cells ARE the fragments, the epilogue multiplies by 1 / 256.  No amax, no a16_out
+// (the hi plane is that copy).  Activations half a stage ahead like a_fmt 0 (the same 16 registers in flight).
 // (launch bounds: the SECOND number is hipcc's minimum of waves per SIMD, not workgroups per CU.  With "2" (rounds 1-5) the kernel took
 //  129 .. 168 registers -- three waves per SIMD, i.e. ONE 512-thread workgroup per CU where 66 KB of LDS allow two.  Round 6: "4" =
 //  128 registers; a_fmt 2 fits as it was (0.69 -> 0.58 ms per launch alone, 4.5 ms per training step: profiles/r06_c28_*), the
 //  other formats once the weight stages go to LDS without a register stop and a_fmt 0's activations are requested half a stage
-//  ahead -- no spills in any of the four.)
+//  ahead -- no spills in any of the four; nor in a_fmt 4: 118 registers.)
 template <int A16>
 __global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args p) {
   __shared__ __attribute__((aligned(16))) u32x4 wl[2][2048];
@@ -428,7 +432,8 @@ __global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args
   constexpr int SU = A16 == 3 ? 1536 : 2048, NQ = SU / 512;    // 16-byte units of a weight stage; per thread
   const int* wsc = reinterpret_cast<const int*>(reinterpret_cast<const unsigned char*>(p.Wpack) + (long long)nstage * 24576);
   int sc_n = A16 == 3 ? wsc[0] : 0;                            // A16 = 3: the four fragment exponents of the next stage
-  const float inv_s = A16 >= 2 ? ws_dgates_scale_inv(*p.amax) * (1.f / WS_PACK16_SCALE) : 1.f;
+  const float inv_s = A16 == 4 ? 1.f / WS_PACK16_SCALE : A16 >= 2 ? ws_dgates_scale_inv(*p.amax) * (1.f / WS_PACK16_SCALE) : 1.f;
+  const long long lo_plane = (long long)nblk * 32 * K;   // A16 = 4: 2-byte elements between the hi and the lo plane
   const aelem* ab = reinterpret_cast<const aelem*>(p.A) + (long long)bb * 32 * K + i * 4 + 2 * half * 128;
   // weight stages: global -> LDS without a register stop (buffer_load ... lds: lane l of a wave lands at base + 16 l) -- the
   // 12 / 16 registers a stage used to wait in are what keeps the other formats from a second workgroup per CU
@@ -442,15 +447,18 @@ __global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args
   };
   // activations: requested one stage ahead -- the 16-byte cells of a_fmt 0 half a stage ahead (two k-steps: 16 registers in flight
   // instead of 32, with the stage's 32 the difference between one and two workgroups per CU)
-  constexpr int HS = A16 == 0 ? 2 : 1, KH = 4 / HS;   // halves per stage; k-steps per half
-  acell an[2 * KH];
+  constexpr int HS = (A16 == 0 || A16 == 4) ? 2 : 1, KH = 4 / HS;   // halves per stage; k-steps per half
+  constexpr int NP = A16 == 4 ? 2 : 1;                               // planes of A (A16 = 4: cells [plane][2 * KH])
+  acell an[NP * 2 * KH];
   auto load_a = [&](int st, int hs) {
     const aelem* a2 = ab + ((long long)st * 16 + hs * KH * 4) * 128;  // 16 quads per stage
 #pragma unroll
-    for (int ks = 0; ks < KH; ++ks) {
-      an[2 * ks] = *reinterpret_cast<const acell*>(a2 + (4 * ks) * 128);
-      an[2 * ks + 1] = *reinterpret_cast<const acell*>(a2 + (4 * ks + 1) * 128);
-    }
+    for (int pl = 0; pl < NP; ++pl)
+#pragma unroll
+      for (int ks = 0; ks < KH; ++ks) {
+        an[pl * 2 * KH + 2 * ks] = *reinterpret_cast<const acell*>(a2 + pl * lo_plane + (4 * ks) * 128);
+        an[pl * 2 * KH + 2 * ks + 1] = *reinterpret_cast<const acell*>(a2 + pl * lo_plane + (4 * ks + 1) * 128);
+      }
   };
   wstage(0, 0);
   load_a(0, 0);
@@ -469,9 +477,9 @@ __global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args
     v8i a8;   // A16 = 3: e4m3 of the stage's A fragments / 256
 #pragma unroll
     for (int hs = 0; hs < HS; ++hs) {
-    acell ac[2 * KH];
+    acell ac[NP * 2 * KH];
 #pragma unroll
-    for (int q = 0; q < 2 * KH; ++q) ac[q] = an[q];
+    for (int q = 0; q < NP * 2 * KH; ++q) ac[q] = an[q];
     if (hs == 0 && st + 1 < nstage) {
       wstage(st + 1, cur ^ 1);     // (the other buffer: last read one stage ago, behind that stage's barrier)
       if constexpr (A16 == 3) sc_n = wsc[st + 1];
@@ -510,6 +518,20 @@ __global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args
           acc[1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, frag(1), acc[1], 0, 0, 0, 127 + 8, 1, sc);
           acc[2] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, frag(2), acc[2], 0, 0, 0, 127 + 8, 2, sc);
           acc[3] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, frag(3), acc[3], 0, 0, 0, 127 + 8, 3, sc);
+        }
+        continue;
+      } else if constexpr (A16 == 4) {
+        const u32x2 c0 = __builtin_bit_cast(u32x2, ac[2 * ksl]), c1 = __builtin_bit_cast(u32x2, ac[2 * ksl + 1]);
+        const u32x2 l0 = __builtin_bit_cast(u32x2, ac[2 * KH + 2 * ksl]), l1 = __builtin_bit_cast(u32x2, ac[2 * KH + 2 * ksl + 1]);
+        const f16x8 a_hi = __builtin_bit_cast(f16x8, u32x4{c0[0], c0[1], c1[0], c1[1]});
+        const f16x8 a_lo = __builtin_bit_cast(f16x8, u32x4{l0[0], l0[1], l1[0], l1[1]});
+        const u32x4* wt = &wl[cur][ks * 512 + lane];  // [nt][part][lane]
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+          const f16x8 w_hi = __builtin_bit_cast(f16x8, wt[(nt * 2) * 64]);
+          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, w_hi, acc[nt], 0, 0, 0);
+          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, __builtin_bit_cast(f16x8, wt[(nt * 2 + 1) * 64]), acc[nt], 0, 0, 0);
+          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, w_hi, acc[nt], 0, 0, 0);
         }
         continue;
       } else if constexpr (A16 == 2) {
@@ -598,7 +620,8 @@ __global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args
 extern "C" int ws_gemm_b2p(const ws_gemm_b2p_args* a, void* stream) {
   WS_REQUIRE(a && a->A && a->Wpack && a->C, "ws_gemm_b2p: null pointer");
   WS_REQUIRE(a->N == 128, "ws_gemm_b2p: N must be 128 (got %d)", a->N);
-  WS_REQUIRE(a->a_fmt >= 0 && a->a_fmt <= 3 && (a->a_fmt < 2 || a->amax), "ws_gemm_b2p: a_fmt %d (2 / 3 need amax)", a->a_fmt);
+  WS_REQUIRE(a->a_fmt >= 0 && a->a_fmt <= 4 && (a->a_fmt < 2 || a->a_fmt == 4 || a->amax), "ws_gemm_b2p: a_fmt %d (2 / 3 need amax)",
+             a->a_fmt);
   WS_REQUIRE(a->a_fmt == 0 || !a->a16_out, "ws_gemm_b2p: a16_out goes with a_fmt 0 (got a_fmt %d)", a->a_fmt);
   WS_REQUIRE(a->K > 0 && a->K % 64 == 0, "ws_gemm_b2p: K %% 64 (K=%d)", a->K);
   WS_REQUIRE(a->ldc >= a->N && a->ldc % 4 == 0, "ws_gemm_b2p: ldc >= N and ldc %% 4 == 0 (16-byte row pieces)");
@@ -606,7 +629,9 @@ extern "C" int ws_gemm_b2p(const ws_gemm_b2p_args* a, void* stream) {
   const int nblk = ((a->sm.nseq + 31) / 32) * a->sm.L;
   hipStream_t s = (hipStream_t)stream;
   ws_prof_begin(WS_PROF_GEMM_NT, s);
-  if (a->a_fmt == 3)
+  if (a->a_fmt == 4)
+    hipLaunchKernelGGL(gemm_b2p_kernel<4>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a);
+  else if (a->a_fmt == 3)
     hipLaunchKernelGGL(gemm_b2p_kernel<3>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a);
   else if (a->a_fmt == 2)
     hipLaunchKernelGGL(gemm_b2p_kernel<2>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a);

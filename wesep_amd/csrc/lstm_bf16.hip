@@ -196,8 +196,12 @@ int ws_launch_lstm_pack_dx_f8(const float* wcat, float* pack, hipStream_t s) {
 // workgroup's 32 sequences at one step), so every wave-level load/store is 1 KB contiguous.
 // GF (BLK only): WS_GATES_* storage of the saved gates; GF != 0: pre-activations from p.gates_in (fp32 BL), activated
 // gates to p.gates as unorm16 (BLH) -- lstm_bf16_common.h
-template <bool BLK, int DBG, int GF = 0>
+// H2P (BLK only; ws_lstm_args.rfmt = WS_LSTM_FWD_H2P): hcat leaves as two fp16 planes instead of BLS pairs.  An instantiation of
+// its own, not a run-time flag: the pair-format kernels sit at 240-242 registers, and a branch around the h store pushed them
+// into scratch inside the step loop.
+template <bool BLK, int DBG, int GF = 0, bool H2P = false>
 __global__ __launch_bounds__(512, 2) void lstm_fwd_bf16_kernel(const ws_lstm_args p) {
+  static_assert(!H2P || (BLK && DBG == 0), "the fp16 planes are a format of the blocked layout");
   __shared__ __attribute__((aligned(16))) __bf16 hl[2][2][SQ * HROW];  // [buf][part][seq][k] 66 KB
   __shared__ __attribute__((aligned(16))) float cl[SQ * (LH + 4)];     // cell state [seq][unit] 33 KB
   if (p.run_if && *p.run_if == 0u) return;  // predicated fall-back launch (wesep_hip.h): uniform
@@ -228,6 +232,13 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_bf16_kernel(const ws_lstm_arg
   auto grs = [&](int t) { return mkrsrc(gsrc + (long long)(blockIdx.x * L + t) * (SQ * 2 * LG), SQ * 2 * LG * 4); };
   auto hrs = [&](int t) { return mkrsrc(p.gates + (long long)(blockIdx.x * L + t) * (SQ * LG), SQ * 2 * LG * 2); };  // BLH
   auto crs = [&](float* b, int t) { return mkrsrc(b + (long long)(blockIdx.x * L + t) * (SQ * 2 * LH), SQ * 2 * LH * 4); };
+  // H2P: hcat as two fp16 planes of BLH(2H) blocks, the lo plane behind the hi plane's gridDim.x * L blocks
+  const char* hplane = reinterpret_cast<const char*>(p.hcat);
+  const long long hlo_off = ws_h2p_plane((long long)gridDim.x * L);
+  auto prs = [&](int t, int pl) {
+    return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + (long long)(blockIdx.x * L + t) * (SQ * 2 * LH * 2)),
+                  SQ * 2 * LH * 2);
+  };
   auto ld_gate = [&](int t, int g, int j) -> f32x4 {
     if constexpr (BLK) return bld(grs(t), glane, (g * 64 + 2 * j) * 512);
     else return *reinterpret_cast<const f32x4*>(p.gates + goff(t, g, j));
@@ -357,7 +368,12 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_bf16_kernel(const ws_lstm_arg
         st_gate(vg, t, 2, j);
         st_gate(vo, t, 3, j);
         st_ch(vc, p.cbuf, t, j);
-        if constexpr (BLK) st_ch(pack_hl4(h_hi, h_lo), p.hcat, t, j);  // BLS: h leaves as the split pair
+        if constexpr (H2P) {   // two fp16 planes: what the fused / cluster2 forward this launch stands in for writes
+          u32x2 ph, pl;
+          enc_h2p(vh, ph, pl);
+          bst8(ph, prs(t, 0), clane >> 1, j * 512);
+          bst8(pl, prs(t, 1), clane >> 1, j * 512);
+        } else if constexpr (BLK) st_ch(pack_hl4(h_hi, h_lo), p.hcat, t, j);  // BLS: h leaves as the split pair
         else st_ch(vh, p.hcat, t, j);
       }
       __builtin_amdgcn_sched_barrier(0);  // one run at a time: bounds the live temporaries
@@ -750,6 +766,13 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_bf16_kernel(const ws_lstm_arg
 
 int ws_launch_lstm_fwd_bf16(const ws_lstm_args* a, hipStream_t s) {
   dim3 grid((a->nseq + SQ - 1) / SQ, 2), block(512);
+  if (a->rfmt == WS_LSTM_FWD_H2P) {   // (lstm_check: ws_lstm_fwd, blocked-layout modes, no probe builds)
+    if (a->gfmt == WS_GATES_H2) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<true, 0, WS_GATES_H2, true>), grid, block, 0, s, *a);
+    else if (a->gfmt == WS_GATES_H2S) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<true, 0, WS_GATES_H2S, true>), grid, block, 0, s, *a);
+    else if (a->gfmt == WS_GATES_H2F) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<true, 0, WS_GATES_H2F, true>), grid, block, 0, s, *a);
+    else hipLaunchKernelGGL((lstm_fwd_bf16_kernel<true, 0, 0, true>), grid, block, 0, s, *a);
+    return 0;
+  }
   WS_DBG_DISPATCH(lstm_fwd_bf16_kernel)
   return 0;
 }

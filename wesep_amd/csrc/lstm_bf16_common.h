@@ -159,6 +159,27 @@ __device__ __forceinline__ u32x2 enc_f16x4(const f32x4& vs) {
   for (int j = 0; j < 4; ++j) h[j] = (_Float16)vs[j];
   return __builtin_bit_cast(u32x2, h);
 }
+// Two-plane fp16 storage of h ("H2P", include/wesep_hip.h): the 4-column cell of a lane as hi = fp16(h) and lo = fp16(h - hi), one
+// 8-byte BLH cell each (h - hi is exact in fp32 and at most 2^-12 |h|: the pair keeps >= 21 significant bits down to fp16's
+// subnormal floor).  The hi cell goes to the BLH(2H) plane at the buffer's base, the lo cell to the same place in the plane
+// `ws_h2p_plane(nblk)` bytes behind it.
+__device__ __forceinline__ void enc_h2p(const f32x4& vh, u32x2& hi, u32x2& lo) {
+  f16x4 h, l;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    // h as ONE fp32 value the compiler cannot look through: where vh[j] is still a product (o * tanh(c)) it otherwise contracts
+    // each use on its own (v_fma_mixlo_f16: fp16 of the unrounded product) and hi and lo come from two different roundings -- at
+    // a tie of the fp32 value they then point away from each other (found on the fused kernels: 5 of 147 456 elements)
+    float x = vh[j];
+    asm volatile("" : "+v"(x));
+    h[j] = (_Float16)x;
+    l[j] = (_Float16)(x - (float)h[j]);
+  }
+  hi = __builtin_bit_cast(u32x2, h);
+  lo = __builtin_bit_cast(u32x2, l);
+}
+__device__ __forceinline__ long long ws_h2p_plane(long long nblk) { return nblk * (SQ * 2 * LH * 2); }  // bytes of one plane
+
 // the 8-byte d(gates) cell of the two in-place-capable 2-byte formats (H2F: v is the SCALED value)
 template <int GF>
 __device__ __forceinline__ u32x2 enc_dgates(const f32x4& v, const bf16x4& hi) {

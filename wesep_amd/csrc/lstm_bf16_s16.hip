@@ -76,7 +76,7 @@ int ws_launch_lstm_pack_s16(const float* whh_f, const float* whh_r, float* pack_
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
-template <int GF>  // WS_GATES_* (lstm_bf16.hip)
+template <int GF, bool H2P = false>  // WS_GATES_*; H2P: hcat as two fp16 planes, an instantiation of its own (lstm_bf16.hip)
 __global__ __launch_bounds__(512, 2) void lstm_fwd_s16_kernel(const ws_lstm_args p) {
   __shared__ __attribute__((aligned(16))) __bf16 hl[2][2][S16 * HROW];  // [buf][part][seq][k] 33 KB
   __shared__ __attribute__((aligned(16))) float cl[S16 * (LH + 4)];     // cell state [seq][unit]
@@ -103,6 +103,13 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_s16_kernel(const ws_lstm_args
     else bst(v, grs(t), glane, (g * 64 + 4 * tu) * 512);
   };
   auto st_ch = [&](const f32x4& v, float* b, int t, int tu) { bst(v, crs(b, t), clane, 4 * tu * 512); };
+  // ws_lstm_args.rfmt = WS_LSTM_FWD_H2P: hcat as two fp16 planes of BLH(2H) blocks, the lo plane behind the hi plane's
+  // (gridDim.x / 2) * L blocks (lstm_bf16.hip)
+  const char* hplane = reinterpret_cast<const char*>(p.hcat);
+  const long long hlo_off = ws_h2p_plane((long long)(gridDim.x >> 1) * L);
+  auto prs = [&](int t, int pl) {
+    return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + (long long)(tile * L + t) * (SQ * 2 * LH * 2)), SQ * 2 * LH * 2);
+  };
 
   const int ubase = 32 * w + 4 * mq;  // unit of (tu, r): ubase + 16tu + r
   float* cme = &cl[n * (LH + 4) + ubase];
@@ -210,7 +217,14 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_s16_kernel(const ws_lstm_args
       st_gate(vg, t, 2, tu);
       st_gate(vo, t, 3, tu);
       st_ch(vc, p.cbuf, t, tu);
-      st_ch(pack_hl4(h_hi, h_lo), p.hcat, t, tu);  // BLS
+      if constexpr (H2P) {
+        u32x2 ph, pl;
+        enc_h2p(vh, ph, pl);
+        bst8(ph, prs(t, 0), clane >> 1, 2 * tu * 512);
+        bst8(pl, prs(t, 1), clane >> 1, 2 * tu * 512);
+      } else {
+        st_ch(pack_hl4(h_hi, h_lo), p.hcat, t, tu);  // BLS
+      }
       __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();
@@ -371,7 +385,10 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_s16_kernel(const ws_lstm_args
 
 int ws_launch_lstm_fwd_s16(const ws_lstm_args* a, hipStream_t s) {
   dim3 grid(2 * ((a->nseq + SQ - 1) / SQ), 2), block(512);
-  if (a->gfmt) hipLaunchKernelGGL(lstm_fwd_s16_kernel<WS_GATES_H2>, grid, block, 0, s, *a);
+  const bool h2p = a->rfmt == WS_LSTM_FWD_H2P;
+  if (a->gfmt && h2p) hipLaunchKernelGGL((lstm_fwd_s16_kernel<WS_GATES_H2, true>), grid, block, 0, s, *a);
+  else if (h2p) hipLaunchKernelGGL((lstm_fwd_s16_kernel<0, true>), grid, block, 0, s, *a);
+  else if (a->gfmt) hipLaunchKernelGGL(lstm_fwd_s16_kernel<WS_GATES_H2>, grid, block, 0, s, *a);
   else hipLaunchKernelGGL(lstm_fwd_s16_kernel<0>, grid, block, 0, s, *a);
   return 0;
 }

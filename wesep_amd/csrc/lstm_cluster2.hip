@@ -195,6 +195,14 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_cluster2_kernel(const ws_lstm
   const int gts = (int)(L * gblk * 4), cts = (int)(L * cblk * 4);            // bytes between the two tiles (fp32 element size)
   auto hrs = [&](int t) { return mkrsrc(p.gates + ((long long)2 * cc * L + t) * (gblk / 2), 0x7fffffffu); };  // BLH
   auto crs = [&](float* b, int t) { return mkrsrc(b + ((long long)2 * cc * L + t) * cblk, 0x7fffffffu); };
+  // rfmt bit 1 (H2P, wesep_hip.h): hcat leaves as two fp16 planes of BLH(2H) blocks (half the bytes of a BL block each); the lo
+  // plane starts behind the hi plane's ntile * L blocks.  Uniform over the launch.
+  const bool h2p = (p.rfmt & 2) != 0;
+  const char* hplane = reinterpret_cast<const char*>(p.hcat);
+  const long long hlo_off = ws_h2p_plane((long long)ntile * L);
+  auto prs = [&](int t, int pl) {
+    return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + ((long long)2 * cc * L + t) * (cblk * 2)), 0x7fffffffu);
+  };
   // xn: BL(128) blocks of 16 KB holding BLS pairs; EVERY thread feeds four 16-byte units of its own tile's block (tile
   // 2cc + st: the block is L blocks from the other tile's)
   const char* xbase = reinterpret_cast<const char*>(p.xn);
@@ -262,7 +270,13 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_cluster2_kernel(const ws_lstm
         bst8(u32x2{pr[2], pr[3]}, hrs(tprev), (gvo + e * gts) >> 1, (2 * g2 + 1) * 64 * 256);
       }
       bst(e == 0 ? c4 : outc[mt], crs(p.cbuf, tprev), cvo + e * cts, 0);
-      bst(outl[2][ct], crs(p.hcat, tprev), cvo + e * cts, 0);
+      if (h2p) {   // the staged cell is (hi cell | lo cell): one 8-byte BLH store into each plane
+        const u32x4 hc = __builtin_bit_cast(u32x4, outl[2][ct]);
+        bst8(u32x2{hc[0], hc[1]}, prs(tprev, 0), (cvo + e * cts) >> 1, 0);
+        bst8(u32x2{hc[2], hc[3]}, prs(tprev, 1), (cvo + e * cts) >> 1, 0);
+      } else {
+        bst(outl[2][ct], crs(p.hcat, tprev), cvo + e * cts, 0);
+      }
     }
   };
 
@@ -336,9 +350,15 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_cluster2_kernel(const ws_lstm
       outl[0][tid] = __builtin_bit_cast(f32x4, u32x4{ei[0], ei[1], ef[0], ef[1]});
       outl[1][tid] = __builtin_bit_cast(f32x4, u32x4{eg[0], eg[1], eo[0], eo[1]});
       if (!xrole) outc[mt] = c4;
-      bf16x4 hi, lo;
-      split4(vh, hi, lo);
-      outl[2][tid] = pack_hl4(hi, lo);  // hcat in HBM carries the split pair (BLS); NaN poison survives in hi
+      if (h2p) {   // hcat in HBM as fp16 hi | lo cells (enc_h2p); NaN poison survives in both
+        u32x2 ph, pl;
+        enc_h2p(vh, ph, pl);
+        outl[2][tid] = __builtin_bit_cast(f32x4, u32x4{ph[0], ph[1], pl[0], pl[1]});
+      } else {
+        bf16x4 hi, lo;
+        split4(vh, hi, lo);
+        outl[2][tid] = pack_hl4(hi, lo);  // hcat in HBM carries the split pair (BLS); NaN poison survives in hi
+      }
     }
     C2TS(3);
     // ---- the next step's x-projection, while h_t travels --------------------------------------------------------------
@@ -402,8 +422,9 @@ extern "C" int ws_lstm_fwd_cluster2(const ws_lstm_cluster2_args* a, void* stream
   e = hipMemsetAsync(a->tword, 0, sizeof(unsigned), s);
   WS_REQUIRE(e == hipSuccess, "ws_lstm_fwd_cluster2: hipMemsetAsync failed");
   ws_prof_begin(WS_PROF_LSTM_FWD, s);
-  WS_REQUIRE(a->rfmt == 0 || a->rfmt == 1, "ws_lstm_fwd_cluster2: rfmt %d (0: fp16 hi / lo of W_hh; 1: the lo term on the FP8 MFMA)", a->rfmt);
-  if (a->rfmt == 1) {
+  WS_REQUIRE((a->rfmt & ~3) == 0,
+             "ws_lstm_fwd_cluster2: rfmt %d (bit 0: the lo term of W_hh on the FP8 MFMA; bit 1: hcat out as two fp16 planes)", a->rfmt);
+  if (a->rfmt & 1) {
     if (a->dbg & 2048) hipLaunchKernelGGL((lstm_fwd_cluster2_kernel<false, true, true>), dim3(grid), dim3(512), 0, s, *a);
     else if (a->dbg & 8) hipLaunchKernelGGL((lstm_fwd_cluster2_kernel<true, false, true>), dim3(grid), dim3(512), 0, s, *a);
     else hipLaunchKernelGGL((lstm_fwd_cluster2_kernel<false, false, true>), dim3(grid), dim3(512), 0, s, *a);

@@ -157,9 +157,12 @@ extern "C" int ws_lstm_pack_fused_h8(const float* wih_f, const float* wih_r, con
 // H16: ws_lstm_fused_args.hfmt = 1 -- see lstm_fwd_fused64_body (fp16 h, one LDS plane per buffer, two recurrent terms)
 // F8 (hfmt 5, with H16): the lo term on the FP8 matrix instruction, as in lstm_fwd_fused64_body; the e4m3 image of h lives in the
 // part-1 plane of each buffer (unused by the fp16 format)
-template <int GF, bool H16 = false, bool F8 = false>  // WS_GATES_*: != 0 -> activated gates leave as unorm16 (BLH), lstm_bf16_common.h
+// H2P (hfmt bit 3, with H16): h leaves for HBM as two fp16 planes (enc_h2p: hi = the recurrent operand itself, lo = fp16(h - hi))
+// instead of the bf16 pair -- two 8-byte BLH stores per run instead of one 16-byte BLS store, the same bytes
+template <int GF, bool H16 = false, bool F8 = false, bool H2P = false>  // WS_GATES_*: != 0 -> activated gates leave as unorm16 (BLH), lstm_bf16_common.h
 __global__ __launch_bounds__(512, 1) void lstm_fwd_fused_kernel(const ws_lstm_fused_args p) {
   static_assert(!F8 || H16, "the FP8 lo term belongs to the fp16-h kernel");
+  static_assert(!H2P || H16, "the fp16 planes are written by the fp16-h kernels");
   __shared__ __attribute__((aligned(16))) __bf16 hl[2][2][SQ * HROW];  // [buf][part][seq][k]  66 KB
   __shared__ __attribute__((aligned(16))) __bf16 xl[2][2][SQ * XROW];  // [buf][part][seq][k]  34 KB
   __shared__ __attribute__((aligned(16))) float cl[SQ * (LH + 4)];     // cell state [seq][unit] 33 KB
@@ -184,6 +187,13 @@ __global__ __launch_bounds__(512, 1) void lstm_fwd_fused_kernel(const ws_lstm_fu
     else bst(v, grs(t), glane, (g * 64 + 2 * j) * 512);
   };
   auto st_ch = [&](const f32x4& v, float* b, int t, int j) { bst(v, crs(b, t), clane, 2 * j * 512); };
+  // H2P: block (tile, t) of plane pl -- 32 KB of BLH(2H); the lo plane starts behind the hi plane's gridDim.x * L blocks
+  const char* hplane = reinterpret_cast<const char*>(p.hcat);
+  const long long hlo_off = ws_h2p_plane((long long)gridDim.x * L);
+  auto prs = [&](int t, int pl) {
+    return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + (long long)(blockIdx.x * L + t) * (SQ * 2 * LH * 2)),
+                  SQ * 2 * LH * 2);
+  };
   // x tile of one step = one BL(128) block: 1024 cells of 16 B, cell u = quad * 32 + slot; thread: u = tid, tid + 512
   auto ld_x = [&](int t, int q) -> f32x4 { return bld(xrs(t), tid * 16, q * 8192); };
   auto st_x = [&](const f32x4& v, int buf, int q) {  // cell u -> row slot, columns 4*quad .. +3
@@ -357,7 +367,14 @@ __global__ __launch_bounds__(512, 1) void lstm_fwd_fused_kernel(const ws_lstm_fu
       st_gate(vg, t, 2, j);
       st_gate(vo, t, 3, j);
       st_ch(vc, p.cbuf, t, j);
-      st_ch(pack_hl4(h_hi, h_lo), p.hcat, t, j);  // BLS
+      if constexpr (H2P) {
+        u32x2 ph, pl;
+        enc_h2p(vh, ph, pl);
+        bst8(ph, prs(t, 0), clane >> 1, j * 512);
+        bst8(pl, prs(t, 1), clane >> 1, j * 512);
+      } else {
+        st_ch(pack_hl4(h_hi, h_lo), p.hcat, t, j);  // BLS
+      }
       __builtin_amdgcn_sched_barrier(0);  // one run at a time: bounds the live temporaries
     }
     __syncthreads();
@@ -402,9 +419,11 @@ struct fused64_lds {
 // e4m3 of the same h the fp16 plane holds) leave it good to 2^-16 of the whole, and ONE v_mfma_scale_f32_32x32x64_f8f6f4 (K = 64 at
 // twice the fp16 rate: 4 776 against 2 184 TFLOP/s measured, profiles/r06_c20_f8_probe.txt) replaces four fp16 MFMAs of K = 16:
 // per recurrent k-step four hi MFMAs + one FP8 MFMA (gate q & 3 of k block q >> 2) instead of eight, 6 KB of stream instead of 8.
-template <int GF, bool W1 = false, bool H16 = false, bool F8 = false>
+// H2P (hfmt bit 3, with H16): h leaves as two fp16 planes, as in lstm_fwd_fused_kernel.
+template <int GF, bool W1 = false, bool H16 = false, bool F8 = false, bool H2P = false>
 __device__ __forceinline__ void lstm_fwd_fused64_body(const ws_lstm_fused_args& p) {
   static_assert(!(W1 && H16), "W1 is a measurement build of the three-term kernel");
+  static_assert(!H2P || H16, "the fp16 planes are written by the fp16-h kernels");
   static_assert(!F8 || H16, "the FP8 lo term belongs to the fp16-h kernel");
   __shared__ __attribute__((aligned(16))) fused64_lds sm;
   auto& xw = sm.xw;
@@ -438,6 +457,12 @@ __device__ __forceinline__ void lstm_fwd_fused64_body(const ws_lstm_fused_args& 
   };
   auto crs = [&](float* b, int e, int t) { return mkrsrc(b + blk(e, t) * (SQ * 2 * LH), lim(e, SQ * 2 * LH * 4)); };
   auto xrs = [&](int e, int t) { return mkrsrc(p.xn + blk(e, t) * (SQ * 128), lim(e, SQ * 128 * 4)); };
+  // H2P: block (tile0 + e, t) of plane pl -- 32 KB of BLH(2H); the lo plane starts behind the hi plane's ntile * L blocks
+  const char* hplane = reinterpret_cast<const char*>(p.hcat);
+  const long long hlo_off = ws_h2p_plane((long long)ntile * L);
+  auto prs = [&](int e, int t, int pl) {
+    return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + blk(e, t) * (SQ * 2 * LH * 2)), lim(e, SQ * 2 * LH * 2));
+  };
   // x tile of one step = one BL(128) block of 16 KB: wave w copies cells 64w .. 64w+63 and 512 + 64w .. of each tile
   auto dma_x = [&](int e, int t) {
 #pragma unroll
@@ -629,7 +654,14 @@ __device__ __forceinline__ void lstm_fwd_fused64_body(const ws_lstm_fused_args& 
         st_gate(vg, e, t, 2, j);
         st_gate(vo, e, t, 3, j);
         bst(vc, crs(p.cbuf, e, t), clane, 2 * j * 512);
-        bst(pack_hl4(h_hi, h_lo), crs(p.hcat, e, t), clane, 2 * j * 512);  // BLS
+        if constexpr (H2P) {
+          u32x2 ph, pl;
+          enc_h2p(vh, ph, pl);
+          bst8(ph, prs(e, t, 0), clane >> 1, j * 512);
+          bst8(pl, prs(e, t, 1), clane >> 1, j * 512);
+        } else {
+          bst(pack_hl4(h_hi, h_lo), crs(p.hcat, e, t), clane, 2 * j * 512);  // BLS
+        }
         __builtin_amdgcn_sched_barrier(0);  // one run at a time: bounds the live temporaries
       }
     }
@@ -638,7 +670,10 @@ __device__ __forceinline__ void lstm_fwd_fused64_body(const ws_lstm_fused_args& 
     // vmcnt(48) is "the DMA has landed" -- rounds 3-5 waited for vmcnt(0): every step then also sat out the acknowledgement of
     // its 384 KB of stores (the HBM phase of the step, ~14 us chip-wide) before the next step's MFMAs could start, where now they
     // drain under them.  (ws_lstm_fused_args.hfmt bit 1, WESEP_FUSED_DRAIN=1: the old wait, for A/B.)
+    // H2P: h is two stores per run (hi and lo cell), 2 tiles x 4 runs x (4 gates + c + 2) = 56 behind the DMA loads; the counter
+    // holds 6 bits on this target (63).  A dead second tile's stores are still issued (zero-sized descriptors drop them).
     if (p.hfmt & 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else if constexpr (H2P) asm volatile("s_waitcnt vmcnt(56)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
     __syncthreads();
   }
@@ -659,14 +694,20 @@ __global__ __launch_bounds__(512, 1) void lstm_fwd_fused64h16_kernel(const ws_ls
 __global__ __launch_bounds__(512, 1) void lstm_fwd_fused64h8_kernel(const ws_lstm_fused_args p) {   // hfmt 5: + the lo term in FP8
   lstm_fwd_fused64_body<WS_GATES_H2, false, true, true>(p);
 }
+__global__ __launch_bounds__(512, 1) void lstm_fwd_fused64h16p_kernel(const ws_lstm_fused_args p) {   // hfmt 9: h out as fp16 planes
+  lstm_fwd_fused64_body<WS_GATES_H2, false, true, false, true>(p);
+}
+__global__ __launch_bounds__(512, 1) void lstm_fwd_fused64h8p_kernel(const ws_lstm_fused_args p) {   // hfmt 13
+  lstm_fwd_fused64_body<WS_GATES_H2, false, true, true, true>(p);
+}
 
 extern "C" int ws_lstm_fwd_fused(const ws_lstm_fused_args* a, void* stream) {
   WS_REQUIRE(a && a->gates && a->cbuf && a->hcat && a->xn && a->wpack && a->bias, "ws_lstm_fwd_fused: null pointer");
   WS_REQUIRE(a->nseq > 0 && a->L > 0, "ws_lstm_fwd_fused: bad nseq/L");
   WS_REQUIRE(a->gfmt >= WS_GATES_F32 && a->gfmt <= WS_GATES_H2F, "ws_lstm_fwd_fused: gfmt %d", a->gfmt);
-  WS_REQUIRE((a->hfmt & ~7) == 0 && (!(a->hfmt & 1) || a->gfmt != WS_GATES_F32) && (!(a->hfmt & 4) || (a->hfmt & 1)),
+  WS_REQUIRE((a->hfmt & ~15) == 0 && (!(a->hfmt & 1) || a->gfmt != WS_GATES_F32) && (!(a->hfmt & 12) || (a->hfmt & 1)),
              "ws_lstm_fwd_fused: hfmt %d (1 = fp16 h, pack from ws_lstm_pack_fused_h16; 5 = + FP8 lo term, pack from "
-             "ws_lstm_pack_fused_h8; 2-byte gate formats only)", a->hfmt);
+             "ws_lstm_pack_fused_h8; bit 3 = h out as two fp16 planes, with bit 0; 2-byte gate formats only)", a->hfmt);
   const int ntile = (a->nseq + SQ - 1) / SQ;
   dim3 grid(ntile, 2), block(512);
   hipStream_t s = (hipStream_t)stream;
@@ -681,7 +722,16 @@ extern "C" int ws_lstm_fwd_fused(const ws_lstm_fused_args* a, void* stream) {
   const bool wide = env ? atoi(env) == 64 : 9 * rounds64 < 5 * rounds32;
   ws_prof_begin(WS_PROF_LSTM_FWD, s);
   const char* w1 = getenv("WS_FUSED_W1");   // measurement only: one weight plane (bf16 weights), see lstm_fwd_fused64_body
-  if ((a->hfmt & 4) && wide)
+  const bool h2p = (a->hfmt & 8) != 0;
+  if (h2p && (a->hfmt & 4) && wide)
+    hipLaunchKernelGGL(lstm_fwd_fused64h8p_kernel, dim3((ntile + 1) / 2, 2), block, 0, s, *a);
+  else if (h2p && (a->hfmt & 4))
+    hipLaunchKernelGGL((lstm_fwd_fused_kernel<WS_GATES_H2, true, true, true>), grid, block, 0, s, *a);
+  else if (h2p && wide)
+    hipLaunchKernelGGL(lstm_fwd_fused64h16p_kernel, dim3((ntile + 1) / 2, 2), block, 0, s, *a);
+  else if (h2p)
+    hipLaunchKernelGGL((lstm_fwd_fused_kernel<WS_GATES_H2, true, false, true>), grid, block, 0, s, *a);
+  else if ((a->hfmt & 4) && wide)
     hipLaunchKernelGGL(lstm_fwd_fused64h8_kernel, dim3((ntile + 1) / 2, 2), block, 0, s, *a);
   else if (a->hfmt & 4)
     hipLaunchKernelGGL((lstm_fwd_fused_kernel<WS_GATES_H2, true, true>), grid, block, 0, s, *a);

@@ -432,10 +432,12 @@ def _lstm_args(gates, cbuf, hcat, wpack, sm: SeqMap, mode, dhcat=None, run_if=No
     return a
 
 
-def lstm_fwd(gates, cbuf, hcat, wpack, sm: SeqMap, mode=L.LSTM_BF16X3, run_if=None, gfmt=0, gates_in=None):
+def lstm_fwd(gates, cbuf, hcat, wpack, sm: SeqMap, mode=L.LSTM_BF16X3, run_if=None, gfmt=0, gates_in=None, h2p=False):
     """run_if: optional 1-element int32 device tensor; the launch is a no-op unless it is non-zero at kernel start.
-    gfmt != 0 (blocked-layout modes): pre-activations from `gates_in` (fp32 BL), `gates` receives unorm16 (BLH)."""
-    a = _lstm_args(gates, cbuf, hcat, wpack, sm, mode, run_if=run_if, gfmt=gfmt, gates_in=gates_in)
+    gfmt != 0 (blocked-layout modes): pre-activations from `gates_in` (fp32 BL), `gates` receives unorm16 (BLH).
+    h2p (blocked-layout modes): hcat leaves as two fp16 planes (H2P, wesep_hip.h) instead of BLS pairs."""
+    a = _lstm_args(gates, cbuf, hcat, wpack, sm, mode, run_if=run_if, gfmt=gfmt, gates_in=gates_in,
+                   rfmt=L.LSTM_FWD_H2P if h2p else 0)
     if run_if is None:     # fp32 pre-activations in, gates (fp32 in place / unorm16) + c + h out
         u = ALG_LSTM_UNITS or L.LSTM_H
         _alg("lstm_fwd", sm.nseq * sm.L * 2 * u * (16 + (2 if gfmt else 4) * 4 + 8), 2 * sm.nseq * sm.L * 2 * 4 * u * u)
@@ -469,13 +471,18 @@ def cu_count(device) -> int:
     return _CU_COUNT[key]
 
 
+def lstm_cluster_resident(sm: SeqMap, device) -> bool:
+    """Whether the cluster recurrences CAN run on this map and device: 64-sequence clusters whose workgroups are all
+    co-resident (8 per 64 sequences per direction <= CUs) -- what the launchers check."""
+    return sm.nseq % 64 == 0 and (sm.nseq // 32) * 8 <= cu_count(device)
+
+
 def lstm_cluster_ok(sm: SeqMap, device) -> bool:
     """The weight-stationary cluster recurrence needs 64-sequence clusters that are all co-resident
-    (8 workgroups per 64 sequences per direction <= CUs) and pays off for long sequences only.
-    WESEP_LSTM_CLUSTER=0 disables it."""
+    (lstm_cluster_resident) and pays off for long sequences only.  WESEP_LSTM_CLUSTER=0 disables it."""
     if os.environ.get("WESEP_LSTM_CLUSTER", "1") == "0":
         return False
-    return sm.nseq % 64 == 0 and (sm.nseq // 32) * 8 <= cu_count(device) and sm.L >= 64
+    return lstm_cluster_resident(sm, device) and sm.L >= 64
 
 
 class _ClusterScratch:
@@ -648,8 +655,9 @@ def cluster2_rfmt() -> int:
     return 1 if os.environ.get("WESEP_CLUSTER2_F8", "0") == "1" else 0
 
 
-def lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whh_f, whh_r, sm: SeqMap, status=None, dbg=0, dbg_buf=None, rfmt=None):
-    """ws_lstm_fwd_cluster2: gates (unorm16 BLH), cbuf, hcat (BLS) <- the BLSTM forward of the blocked-layout sequences from
+def lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whh_f, whh_r, sm: SeqMap, status=None, dbg=0, dbg_buf=None, rfmt=None,
+                      h2p=False):
+    """ws_lstm_fwd_cluster2: gates (unorm16 BLH), cbuf, hcat (BLS; h2p: two fp16 planes, rfmt bit 1) <- the BLSTM forward of the blocked-layout sequences from
     the normalised input xn (BL(128) of BLS pairs: gemm_p2b's A_bl), W_ih / biases as ws_lstm_cat_ih leaves them and the fp32
     W_hh.  Returns the launch's time-out word: pass it as `run_if` to gemm_p2b + lstm_fwd behind this call -- the predicated
     fall-back."""
@@ -666,7 +674,7 @@ def lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whh_f, whh_r, sm: SeqMa
     a.xchg, a.tword = C.c_void_p(xchg.data_ptr()), C.c_void_p(tw.data_ptr())
     a.status = C.c_void_p((status if status is not None else sc.status).data_ptr())
     a.nseq, a.L, a.dbg = sm.nseq, sm.L, dbg
-    a.rfmt = cluster2_rfmt() if rfmt is None else rfmt
+    a.rfmt = (cluster2_rfmt() if rfmt is None else rfmt) | (2 if h2p else 0)
     a.dbg_buf = C.c_void_p(dbg_buf.data_ptr()) if dbg_buf is not None else None
     u = ALG_LSTM_UNITS or L.LSTM_H     # (as lstm_fwd_fused: unorm16 gates + c + h out, the split-pair input in)
     _alg("lstm_fwd", sm.nseq * sm.L * (2 * u * 16 + 4 * 128), 2 * sm.nseq * sm.L * 2 * 4 * u * (u + 128))
@@ -1052,7 +1060,8 @@ def gemm_p2b(*, A, lda: int, sm: SeqMap, Wpack, N: int, C_out, K=128, bias=None,
 
 def gemm_b2p(*, A, K: int, sm: SeqMap, Wpack, C_out, ldc: int, N=128, bias=None, R=None, a_fmt=0, amax=None, a16_out=None):
     """a_fmt = 1: A holds bf16 elements in BLH(K) (d(gates) of WS_GATES_H2) instead of split pairs in BL(K); 2: fp16 elements
-    scaled by the power of two the word `amax` defines (WS_GATES_H2F).  a16_out (a_fmt 0, ABI v16): the A operand once more as
+    scaled by the power of two the word `amax` defines (WS_GATES_H2F); 4: h as two fp16 planes (H2P, wesep_hip.h), Wpack from
+    pack_w(f16=True).  a16_out (a_fmt 0, ABI v16): the A operand once more as
     fp16 in BLH(K) -- hcat for gemm_tnb (a_fmt = 1)."""
     for n, t in (("A", A), ("Wpack", Wpack), ("bias", bias), ("C", C_out), ("R", R), ("a16_out", a16_out)):
         _chk(t, n)
@@ -1066,7 +1075,8 @@ def gemm_b2p(*, A, K: int, sm: SeqMap, Wpack, C_out, ldc: int, N=128, bias=None,
     a.a16_out = _p(a16_out)
     if ALG is not None:
         rows = (getattr(sm, "nvalid", 0) or sm.nseq) * sm.L
-        _alg("gemm_nt", rows * ((2 if a_fmt else 4) * K + 4 * N * (1 + (R is not None)) + (2 * K if a16_out is not None else 0))
+        # (a_fmt 4: h as two fp16 planes -- 4 B per element like the pair, and no a16_out copy behind it)
+        _alg("gemm_nt", rows * ((4 if a_fmt in (0, 4) else 2) * K + 4 * N * (1 + (R is not None)) + (2 * K if a16_out is not None else 0))
              + 4 * N * K, 2 * rows * N * K)
     L.check(L.lib().ws_gemm_b2p(C.byref(a), L.stream_ptr()), "ws_gemm_b2p")
 
@@ -1105,6 +1115,50 @@ def gemm_tnb(*, G, g_width: int, g_off: int, g_cols: int, A0, a0_width: int, a0_
         _alg("gemm_tn", rows * ((2 if g_fmt else 4) * g_cols + (2 if a_fmt else 4) * acols) + 4 * nsplit * g_cols * acols,
              2 * rows * g_cols * acols)
     L.check(L.lib().ws_gemm_tnb(C.byref(a), L.stream_ptr()), "ws_gemm_tnb")
+
+
+def h2p_on(device) -> bool:
+    """h of the training forward as two fp16 planes (H2P, wesep_hip.h: hi = fp16(h), lo = fp16(h - hi)) instead of the bf16 pair
+    plus its fp16 twin: the projection reads the planes (gemm_b2p a_fmt 4) and writes no copy, both weight-gradient GEMMs read the
+    hi plane (gemm_tnb a_fmt 1, gemm_tnb_h16) -- 12 instead of 16 bytes per element of h and step.  Wherever the fp16 copies
+    exist (blstm_core.BlstmPlan.a16).  WESEP_H2P=0 keeps the pair format (A/B runs); unset: on for device buffers (host-side
+    stand-ins of the kernels that keep plain fp32 buffers have no such format); WESEP_H2P=1: on regardless."""
+    env = os.environ.get("WESEP_H2P")
+    return env != "0" if env is not None else device.type == "cuda"
+
+
+def h2p_hi(hcat, nblk: int, C_: int = 2 * L.LSTM_H):
+    """The hi plane of an H2P buffer: BLH(C_) of fp16(h), float32 storage (a view of the buffer's first half)."""
+    return hcat.reshape(-1)[: blh_floats(nblk, C_)]
+
+
+def h2p_unpack(hcat, nblk: int, C_: int = 2 * L.LSTM_H):
+    """(hi, lo) of an H2P buffer as BL-shaped fp32 [nblk][C_/4][32][4] each (tests / tools)."""
+    n = blh_floats(nblk, C_)
+    flat = hcat.reshape(-1)
+    return blh_f16_unpack(flat[:n], nblk, C_), blh_f16_unpack(flat[n:2 * n], nblk, C_)
+
+
+def gemm_tnb_h16(*, G, g_width: int, g_off: int, g_cols: int, A0, a0_width: int, a0_off: int, nblk: int, L_: int, slab,
+                 nsplit: int, blocks_per_split: int, amax, aslab=None):
+    """ws_gemm_tnb_h16: slab[split][g][a] = sum G[(b, i)][g_off + g] A0[(b, i)][a0_off + a] over 128 columns of A0 -- G the fp16
+    hi plane of h (BLH(g_width)), A0 the incoming gradient as BLS pairs, lifted into fp16 by the power of two `amax` defines
+    (max |A0| < 2^7 max |d(hcat)|: wesep_hip.h); aslab: the column sums of A0."""
+    for n, t in (("G", G), ("A0", A0), ("slab", slab), ("aslab", aslab)):
+        _chk(t, n)
+    if amax is None:
+        raise L.WesepHipError("gemm_tnb_h16: amax (the scale word of this backward) is required")
+    a = L.GemmTNBArgs()
+    a.G, a.A0, a.slab, a.aslab = _p(G), _p(A0), _p(slab), _p(aslab)
+    a.slab_stride, a.bslab_stride, a.aslab_stride = g_cols * 128, g_cols, 128
+    a.g_width, a.g_off, a.g_cols = g_width, g_off, g_cols
+    a.a0_width, a.a0_off, a.a0_cols = a0_width, a0_off, 128
+    a.nblk, a.L, a.nsplit, a.blocks_per_split = nblk, L_, nsplit, blocks_per_split
+    a.amax = C.c_void_p(amax.data_ptr())
+    if ALG is not None:     # fp16 G, split-pair A0, the slabs
+        rows = nblk * 32
+        _alg("gemm_tn", rows * (2 * g_cols + 4 * 128) + 4 * nsplit * g_cols * 128, 2 * rows * g_cols * 128)
+    L.check(L.lib().ws_gemm_tnb_h16(C.byref(a), L.stream_ptr()), "ws_gemm_tnb_h16")
 
 
 # ---- Conv-TasNet / SpEx+ pieces (tasnet.hip), channels-last [R*T'][C] -----------------------------
