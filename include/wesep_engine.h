@@ -383,6 +383,67 @@ int ws_engine_live_flush(ws_live* s, float* est, int est_cap, int* n_out);
 int ws_engine_live_reset(ws_live* s);
 void ws_engine_live_close(ws_live* s);
 
+/* ---- live pool (runtime/live_pool.cc; DESIGN sections 7 "Live pool" and 11b) -- new symbols, WS_ENGINE_ABI_VERSION 2 unchanged
+ * MANY independent live recordings on one engine: each slot is a ws_live's bookkeeping -- its own position, its own packet
+ * sizes, its own K enrollments -- and every window that one push completes, in whatever slot, goes through the separator in
+ * the same forwards.  N solo handles run N half-empty forwards one after another, each with its own upload, synchronisation
+ * and download; the pool runs one chain.  S = window, O = overlap, H = S - O, g_max = max(1, max_rows / K), cap = g_max + 3.
+ *   ws_engine_live_pool_open(e, slots, K, window, overlap, max_rows, &pool)  the window checks of ws_engine_separate_long (its
+ *     messages) and the plan's guards on a forward of max_rows rows; slots in [1, 65535], slots K g_max + slots <= 65535 (the
+ *     tables of a launch).  Makes ONE device allocation, ws_engine_info "live_pool_state_bytes", a function of (slots, K, S,
+ *     O, max_rows) only, that no attach, push, flush or detach grows.  Per slot: the ring [K][cap][S] of window estimates, the
+ *     ring [cap] of TF-GridNet's per-window factors, the K embeddings.  Per round: the staging block (the slots' spans of
+ *     (g - 1) H + S samples, the factors, the embedding rows, the three tables), the rows rectangle and the estimates
+ *     rectangle, slots K g_max rows of S samples each.  Pending samples (fewer than S + H a slot between pushes) stay on the host.
+ *   ws_engine_live_pool_attach(pool, enroll, enroll_kind, enroll_len, enroll_lengths, &slot)  takes the lowest free slot, checks
+ *     the K enrollments as ws_engine_separate_long does (every kind ws_engine_live_open takes, WS_ENROLL_SPEAKER included),
+ *     runs the speaker stage ONCE for them and puts the slot at sample 0.  A full pool is refused by name.
+ *   ws_engine_live_pool_push(pool, n_active, slots, chunks, n, est, est_cap, n_out)  one packet for each of n_active DISTINCT
+ *     attached slots: chunks[i] is n[i] >= 1 samples for slots[i]; est[i] is [K][est_cap[i]], n_out[i] samples a target -- per
+ *     slot the emission rule of ws_engine_live_push (WS_LIVE_PUSH_CAP(n[i], H) always suffices).  All packets are appended
+ *     first.  If no slot completed a window: every n_out[i] = 0, NO launch, NO synchronisation.  Otherwise the work runs in
+ *     ROUNDS: in ascending slot order every slot that still owes windows gives min(owed, g_max, cap - Wr % cap) consecutive
+ *     windows (the solo handle's cut).  A round's rows are ordered (slot, target, window); per round ONE upload of the staging
+ *     block, ONE ws_window_slots_fwd for all of its rows, the architecture's rectangular plan in forwards of at most max_rows
+ *     rows whichever slots they came from, ONE ws_rows_copy_fwd of the estimates (and TF-GridNet's factors, computed on the
+ *     host) into the rings, ONE ws_xfade_stream_rows_fwd for everything the round made final.  After the last round one copy
+ *     to the host and ONE synchronisation.  ws_engine_info "n_launches" after a push:
+ *         sum over its rounds of (the forwards' rectangular counts + WS_LIVE_POOL_ROUND_LAUNCHES) + 1
+ *     -- it depends on the number of participating slots only through the forwards' own counts.  "live_pool_rounds" and
+ *     "live_pool_forwards" report the last push or flush.
+ *   ws_engine_live_pool_flush(pool, slot, est, est_cap, &n_out)  the end of ONE slot's recording by the rule of
+ *     ws_engine_live_flush: the short window n < S (the architecture's lower bound on T is checked before anything runs; a
+ *     refusal leaves the slot as it was) or the end-aligned last window, as a round of this one slot whose cross-fade is the
+ *     final one; WS_LIVE_FLUSH_CAP(S, O) always suffices.  A flush that has no window to run is the cross-fade and the copy:
+ *     2 entry-point calls.  The slot then takes nothing until it is detached.
+ *   ws_engine_live_pool_detach(pool, slot)  frees the slot for the next attach.    ws_engine_live_pool_close(pool)  before
+ *     ws_engine_destroy.
+ * The engine's work arena is used under a scope and nothing of it is held between two calls: other calls on the engine between
+ * two pushes do not disturb the pool.  Dry-run engines take every call.  All pointers are HOST pointers; callers serialise.
+ * FAILURE: the slots named by a push or flush that failed half way are refused by name until they are detached; the other
+ * slots go on.
+ * PARITY, per slot: the concatenation of what its pushes and its flush return equals ws_engine_separate_long on that slot's
+ * concatenated audio -- whatever the packet sizes were, whenever the slot was attached, whatever the other slots were doing
+ *   - bit for bit with max_rows = 1: every forward then holds one row, so these are also the solo live handle's bits;
+ *   - otherwise to the rounding of forwards over other row counts (which rows share a forward depends on the other slots).
+ * No launch mixes rows: with the row composition of the forwards held fixed, a slot's bits do not depend on the other slots'
+ * sample values, NaN and inf included -- as far as the architecture's rectangular plan keeps its rows apart.
+ * NOT built: a sample rate per slot; a different K per slot; holding a complete window back to wait for company (the pool
+ * batches only windows that complete in the same push).
+ * WS_ERR_INVALID with a message and nothing launched: every refusal of ws_engine_live_* under this family's names; slots
+ * outside [1, 65535]; a full pool; a slot of a push or flush that is free, flushed, named twice or part of a failed call;
+ * n[i] < 1; est_cap below the emission, checked for every entry before any launch; a NULL pointer. */
+typedef struct ws_live_pool ws_live_pool;
+#define WS_LIVE_POOL_ROUND_LAUNCHES 3
+int ws_engine_live_pool_open(ws_engine* e, int slots, int K, int window, int overlap, int max_rows, ws_live_pool** out);
+int ws_engine_live_pool_attach(ws_live_pool* p, const void* enroll, int enroll_kind, int enroll_len, const int* enroll_lengths,
+                               int* slot);
+int ws_engine_live_pool_push(ws_live_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n,
+                             float* const* est, const int* est_cap, int* n_out);
+int ws_engine_live_pool_flush(ws_live_pool* p, int slot, float* est, int est_cap, int* n_out);
+int ws_engine_live_pool_detach(ws_live_pool* p, int slot);
+void ws_engine_live_pool_close(ws_live_pool* p);
+
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by
  * 2^-15 before the model, separate_engine.cc:81-84, and its wav writer scales back, frontend/wav.h:245-253).

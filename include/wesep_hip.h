@@ -1180,6 +1180,40 @@ int ws_xfade_ola(const float* y, int K, int W, int S, int O, int n, const float*
 int ws_xfade_stream_fwd(const float* ring, int K, int cap, int S, int O, const float* scale_ring, long long i0, long long count,
                         long long windows_run, int final, long long W, long long n, float* out, long long ld_out, void* stream);
 
+/* Live pool (longform.hip; runtime/live_pool.cc, DESIGN 7 "Live pool") -- new symbols, ABI 20 unchanged.  The rows forms of the
+ * gather and of the ring cross-fade: ONE launch for A table rows that share nothing but the launch, with the two-table
+ * convention of ws_rows_copy_fwd -- `rows` is a HOST pointer, validated, and sizes the grid; `d_rows` is a DEVICE pointer to the
+ * same bytes, uploaded by the caller on the same stream before the call.  Offsets count floats into arenas whose lengths are
+ * arguments.  Grid (blocks of the largest row, A); a workgroup beyond its own row's count leaves at once.  Plain C++, no packed
+ * FP32, no atomics, 64-bit offsets, no LDS.
+ *   ws_window_slots_fwd  row i: dst[dst_off + j] = fl(src[src_off + j] * scale), j < len -- ws_window_rows with the start, the
+ *                   destination and the factor taken from the table (scale = 1: a copy).  Sources are read with scalar loads
+ *                   (no start alignment is assumed), a destination quad is stored as 16 bytes where its address allows.  A row
+ *                   equals bit for bit what ws_window_rows writes for that window.
+ *   ws_xfade_stream_rows_fwd  row i is ws_xfade_stream_fwd with K = 1 for one target of one slot: its ring [cap][S] at
+ *                   ring + ring_off, its factor ring [cap] at scale_ring + scale_off (scale_off = -1: none), and `count`
+ *                   samples from position i0 written to out + out_off, with (windows_run, final, W, n) as in the solo call --
+ *                   the short final window n < S included.  Every sample comes from the one cross-fade body with exactly the
+ *                   arguments the solo call derives, so a row is bit for bit the solo call.  A row with count == 0 is skipped
+ *                   (a call whose rows are all empty launches nothing).  S, O and cap are shared by the rows.
+ * WS_ERR_INVALID before any launch, each with the row index: every check of the solo entry point, per row; a range that leaves
+ * its arena; a dst / out range that overlaps any other range of the call (by address); and A outside [1, 65535], a NULL
+ * pointer (scale_ring may be NULL when no row names a factor ring). */
+typedef struct ws_window_slot_row {
+  long long src_off, dst_off;
+  int len;
+  float scale;
+} ws_window_slot_row;
+typedef struct ws_xfade_stream_row {
+  long long ring_off, scale_off, out_off, i0, count, windows_run, W, n;
+  int final;
+} ws_xfade_stream_row;
+int ws_window_slots_fwd(const ws_window_slot_row* rows, const ws_window_slot_row* d_rows, int A, const float* src, long long n_src,
+                        float* dst, long long n_dst, void* stream);
+int ws_xfade_stream_rows_fwd(const ws_xfade_stream_row* rows, const ws_xfade_stream_row* d_rows, int A, int S, int O, int cap,
+                             const float* ring, long long n_ring, const float* scale_ring, long long n_scale, float* out,
+                             long long n_out, void* stream);
+
 /* ---- streaming Conv-TasNet (stream.hip; wesep_amd/streaming.py) -- new symbols, ABI 20 unchanged --------
  * The two kernels of a causal Conv-TasNet that look across time, in a chunked form with state carried on the device.
  *   ws_dwconv_stream_fwd  ws_dwconv_ex_fwd(causal = 1) on one chunk of Tc frames whose first frame has absolute index t0.

@@ -360,6 +360,10 @@ WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   if (k == "live_state_bytes") return e->live_state_bytes;
   if (k == "live_windows") return e->live_windows;
   if (k == "live_groups") return e->live_groups;
+  // the live pool opened last: its one device allocation; the pool that ran last: rounds and forwards of its last push or flush
+  if (k == "live_pool_state_bytes") return e->live_pool_state_bytes;
+  if (k == "live_pool_rounds") return e->live_pool_rounds;
+  if (k == "live_pool_forwards") return e->live_pool_forwards;
   auto it = e->meta.find(k);
   return it == e->meta.end() ? -1 : it->second;
 }

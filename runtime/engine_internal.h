@@ -10,6 +10,7 @@
 //   gridnet_plan.cc  TF-GridNet (arch 3)
 //   longform.cc      ws_engine_separate_long: one long mixture as overlapping windows through the rectangular plans
 //   live.cc          ws_engine_live_*: the windows of ws_engine_separate_long run as their samples arrive, any architecture
+//   live_pool.cc     ws_engine_live_pool_*: many live recordings, the windows one push completes in the same forwards
 //   stream.cc        what every streaming front end shares -- the launch chain of a group of frames (stream_chain), the state
 //                    block (StreamCore) and the speaker stage of a stream (stream_enroll) -- and ws_engine_stream_*: causal
 //                    cLN Conv-TasNet fed audio as it arrives, state carried on the device
@@ -310,6 +311,8 @@ struct ws_engine {
   long long long_windows = 0, long_forwards = 0;   // of the last ws_engine_separate_long
   long long live_state_bytes = 0;                  // device state of the live handle opened last (ws_engine_live_open)
   long long live_windows = 0, live_groups = 0;     // windows run since that handle's open / reset; groups of its last call
+  long long live_pool_state_bytes = 0;             // device state of the live pool opened last (ws_engine_live_pool_open)
+  long long live_pool_rounds = 0, live_pool_forwards = 0;   // rounds and forwards of the last live-pool push or flush
   long long stream_state_bytes = 0;                // device state of the stream opened last (ws_engine_stream_open)
   long long cluster_fallbacks = 0;   // forwards in which a cluster recurrence timed out and the streaming kernels took over
   unsigned* cl_status = nullptr;     // sticky device word set by ws_lstm_fwd_cluster on a timeout
@@ -542,6 +545,16 @@ inline int rate_push_cap(const Geom& a, const Geom& b, int L, int n) {
   const long long ma = ((long long)n / a.D + 1) * a.U;
   const long long mm = (ma / hop + 1) * hop;
   return static_cast<int>(std::min<long long>(0x7fffffff, (mm / b.D + 1) * b.U));
+}
+
+// ---- the emission rule of the live front ends (live.cc, live_pool.cc; include/wesep_engine.h "live windows") ----
+// windows run after N samples: window w starts at w H and runs once w H + S samples exist
+inline long long live_windows_run(long long N, int S, int H) { return N < S ? 0 : 1 + (N - S) / H; }
+// samples emitted once Wr windows have run: those before the start of the newest window
+inline long long live_emitted(long long Wr, int H) { return std::max<long long>(Wr - 1, 0) * H; }
+// the next group of a recording that has run Wr of Wr_new windows: at most g_max windows, cut where the ring of cap slots wraps
+inline int live_cut(long long Wr, long long Wr_new, int g_max, int cap) {
+  return static_cast<int>(std::min<long long>({Wr_new - Wr, (long long)g_max, cap - Wr % cap}));
 }
 
 // ---- copies and the synchronisation of a streaming call, on the engine's stream; who / what: the message of a failure.

@@ -60,8 +60,6 @@ void free_live(ws_live* s) {
   delete s;
 }
 
-long long windows_run(long long N, int S, int H) { return N < S ? 0 : 1 + (N - S) / H; }
-
 // g consecutive windows of L samples, the first with index w0, from the host span x [(g - 1) H + L] (g = 1 with L < S: the
 // one short window of a flush): upload, gather, the rectangular plan, estimates into ring slots w0 % cap .. (no wrap inside)
 int run_group(ws_live* s, const float* x, long long w0, int g, int L) {
@@ -240,7 +238,7 @@ WS_ENGINE_API int ws_engine_live_push(ws_live* s, const float* chunk, int n, flo
     return WS_ERR_INVALID;
   }
   const int S = s->S, H = s->H;
-  const long long N_new = s->N + n, Wr_new = windows_run(N_new, S, H), E_new = std::max<long long>(Wr_new - 1, 0) * H;
+  const long long N_new = s->N + n, Wr_new = live_windows_run(N_new, S, H), E_new = live_emitted(Wr_new, H);
   const long long emitted = E_new - s->E;
   if (emitted > est_cap || (emitted > 0 && !est)) {
     set_err("ws_engine_live_push: this push emits %lld samples a row, est_cap is %d%s (WS_LIVE_PUSH_CAP(n, H) = %lld always suffices)",
@@ -266,7 +264,7 @@ WS_ENGINE_API int ws_engine_live_push(ws_live* s, const float* chunk, int n, flo
   const long long E0 = s->E;
   while (s->Wr < Wr_new) {
     const long long w0 = s->Wr;
-    const int g = static_cast<int>(std::min<long long>({Wr_new - w0, (long long)s->g_max, s->cap - w0 % s->cap}));
+    const int g = live_cut(w0, Wr_new, s->g_max, s->cap);
     if ((rc = run_group(s, s->pend.data() + (w0 * H - s->base), w0, g, S)) != WS_OK) return rc;
     s->Wr += g;
     if ((rc = emit(s, (s->Wr - 1) * H, false, 0, d_out, emitted, s->E - E0)) != WS_OK) return rc;

@@ -4,7 +4,7 @@
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
 //                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
 //                 [--stream_ms 10 [--stream_pool 4 | --rate_pool 4] [--stream_block]] [--resample]
-//                 [--live_ms 100 --chunk_seconds 4]
+//                 [--live_ms 100 --chunk_seconds 4 [--live_pool 4]]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -33,6 +33,12 @@
 // Names, scaling and formats are those of the --chunk_seconds run, and with --chunk_rows 1 so are the samples, bit for bit.
 // Works with --jobs, --dry_run and --resample (the files are brought to the model's rate around the handle, as for
 // --chunk_seconds).  Refused without --chunk_seconds, and together with --batch N > 1, --stream_ms and the pools.
+// --live_ms M --live_pool N (with --chunk_seconds S; any model): N lines of the scp are in flight at once on one live pool
+// (ws_engine_live_pool_*, K = 2, one slot per line): every round feeds each line in flight its next M ms packet in ONE push, so
+// the windows that complete in the same round share their forwards (--chunk_rows rows each); a line that ends is flushed, its
+// slot detached and re-attached to the next line.  Names and formats are those of --live_ms; with N = 1 and --chunk_rows 1 so
+// are the samples, bit for bit.  Works with --jobs, --dry_run and --resample (files go through ws_engine_resample around the
+// pool, as for --live_ms).  Refused without --live_ms, and together with --batch N > 1, --stream_ms and the other pools.
 // --stream_ms M (causal cLN Conv-TasNet / SpEx+ models, ws_engine_info "streaming"): every line is fed to a stream
 // (ws_engine_stream_open / push / flush) in chunks of M milliseconds, as a live source would deliver it; the speaker encoder
 // runs once per line, at open.  Same files as the plain run: the streamed samples, then zeros where the plain run has its
@@ -165,6 +171,8 @@ int main(int argc, char** argv) {
   const bool live = args.has("live_ms");
   const double live_ms = atof(args.get("live_ms", "0").c_str());
   const int live_n = static_cast<int>(live_ms * sample_rate / 1000.0 + 0.5);
+  const bool live_pooled = args.has("live_pool");
+  const int live_pool_n = atoi(args.get("live_pool", "0").c_str());
   const bool rate_pooled = args.has("rate_pool");
   const int rate_pool_n = atoi(args.get("rate_pool", "0").c_str());
   // a dry run writes nothing -- except with --resample and an --output_dir: the (all-zero) files then show the rate and the
@@ -175,7 +183,7 @@ int main(int argc, char** argv) {
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
            "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]]\n"
            "                     [--stream_ms M [--stream_pool N | --rate_pool N] [--stream_block]] [--resample]\n"
-           "                     [--live_ms M --chunk_seconds S]\n"
+           "                     [--live_ms M --chunk_seconds S [--live_pool N]]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
@@ -187,6 +195,8 @@ int main(int argc, char** argv) {
            "  --live_ms M        with --chunk_seconds S, any model: feed every line to a live handle in packets of M ms; the\n"
            "                     windows run as their samples arrive (latency S .. 2 S - O seconds); same files as the\n"
            "                     --chunk_seconds run.  Not together with --batch N > 1, --stream_ms or a pool\n"
+           "  --live_pool N      with --live_ms M: N lines in flight at once on one live pool, one push per round of M ms\n"
+           "                     packets; windows that complete in the same round share their forwards; same files as --live_ms\n"
            "  --stream_ms M      causal cLN Conv-TasNet / SpEx+ models: feed every line to a stream in chunks of M ms; same\n"
            "                     files as the plain run.  Not together with --batch N > 1 or --chunk_seconds\n"
            "  --stream_pool N    with --stream_ms M: N consecutive lines at a time through one stream pool, one push per round\n"
@@ -199,6 +209,11 @@ int main(int argc, char** argv) {
            "                     file's sample rate (packets of M ms at that rate); outputs have the mixture's rate and length\n");
     return 0;
   }
+  if (live_pooled && !live) return die("--live_pool needs --live_ms M: the pool is fed packets of M milliseconds");
+  if (live_pooled && (batch > 1 || streamed || pooled || rate_pooled))
+    return die("--live_pool conflicts with --batch N > 1, --stream_ms, --stream_pool and --rate_pool: one pool per run, and a live pool "
+               "takes recordings as they arrive through the windows of --chunk_seconds");
+  if (live_pooled && live_pool_n < 1) return die("--live_pool needs a positive number of lines");
   if (live && !chunked) return die("--live_ms needs --chunk_seconds S: a live handle runs the windows of S seconds as their samples arrive");
   if (live && (batch > 1 || streamed || pooled || rate_pooled))
     return die("--live_ms conflicts with --batch N > 1, --stream_ms, --stream_pool and --rate_pool: a live handle takes one recording as "
@@ -317,6 +332,153 @@ int main(int argc, char** argv) {
       for (int r = 0; r < R; ++r) memcpy(out + size_t(r) * n, back.data() + size_t(r) * m, size_t(std::min(n, m)) * 4);
       return true;
     };
+    // --live_pool N: up to N lines in flight on one live pool of N slots (K = 2), each fed its next packet of live_n samples at the
+    // model's rate in one push per round; a lane takes the next line when its own ends.  With --resample a line's files are
+    // brought to the model's rate before and its estimates back after, as for --live_ms.
+    if (live_pooled) {
+      struct Lane {
+        bool live = false;
+        size_t line = 0;
+        std::vector<float> mix, out, got;      // at the model's rate: the mixture [n], the estimates [2][n]; a call's [2][cap]
+        int n = 0, pos = 0, done = 0, slot = -1, n_file = 0, rate = 0;
+        long long pushes = 0;
+        std::chrono::steady_clock::time_point t0;
+      };
+      ws_live_pool* lp = nullptr;
+      if (ws_engine_live_pool_open(engine, live_pool_n, 2, window, overlap, chunk_rows, &lp) != 0) {
+        fail(std::string("--live_pool: ") + ws_engine_last_error());
+        ws_engine_destroy(engine);
+        return;
+      }
+      const int cap = std::max(WS_LIVE_PUSH_CAP(live_n, window - overlap), WS_LIVE_FLUSH_CAP(window, overlap));
+      std::vector<Lane> lanes(live_pool_n);
+      bool ok = true;
+      long long rounds = 0, launches = 0, forwards = 0, pool_rounds = 0;
+      double audio_ms = 0.0;
+      const auto pool_t0 = std::chrono::steady_clock::now();
+      auto start = [&](Lane& ln) {                // the next line of the scp into this lane: read it, attach its two enrollments
+        const size_t i = next++;
+        if (i >= waves.size() || failed) return;
+        const auto& w = waves[i];
+        wesep_rt::Wav mix, s1, s2;
+        std::string err;
+        if (!wesep_rt::read_wav(w[1], &mix, &err) || !wesep_rt::read_wav(w[2], &s1, &err) || !wesep_rt::read_wav(w[3], &s2, &err)) {
+          fail(err);
+          ok = false;
+          return;
+        }
+        if (!resample && (mix.sample_rate != sample_rate || s1.sample_rate != sample_rate || s2.sample_rate != sample_rate)) {
+          fail(w[0] + ": sample rate is not " + std::to_string(sample_rate));
+          ok = false;
+          return;
+        }
+        std::vector<float> e[2];
+        if (!to_model(mix.samples, mix.sample_rate, &ln.mix) || !to_model(s1.samples, s1.sample_rate, &e[0]) ||
+            !to_model(s2.samples, s2.sample_rate, &e[1])) {
+          fail(w[0] + ": " + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        const int n_enroll = static_cast<int>(std::min(e[0].size(), e[1].size()));
+        std::vector<float> enr(size_t(2) * n_enroll);
+        memcpy(enr.data(), e[0].data(), size_t(n_enroll) * 4);
+        memcpy(enr.data() + n_enroll, e[1].data(), size_t(n_enroll) * 4);
+        ln.line = i, ln.n = static_cast<int>(ln.mix.size()), ln.pos = ln.done = 0, ln.pushes = 0;
+        ln.n_file = static_cast<int>(mix.samples.size()), ln.rate = resample ? mix.sample_rate : sample_rate;
+        ln.out.assign(size_t(2) * ln.n, 0.f);
+        ln.got.assign(size_t(2) * cap, 0.f);
+        ln.t0 = std::chrono::steady_clock::now();
+        if (ws_engine_live_pool_attach(lp, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, &ln.slot) != 0) {
+          fail(w[0] + ": " + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        ln.live = true;
+      };
+      auto take = [&](Lane& ln, int m) {          // got [2][cap], m samples each, behind what came before
+        for (int k = 0; k < 2; ++k) memcpy(ln.out.data() + size_t(k) * ln.n + ln.done, ln.got.data() + size_t(k) * cap, size_t(m) * 4);
+        ln.done += m;
+      };
+      auto finish = [&](Lane& ln) {               // flush the slot, free it, write the line's files at the mixture's rate
+        const auto& w = waves[ln.line];
+        std::string err;
+        int m = 0;
+        if (ws_engine_live_pool_flush(lp, ln.slot, ln.got.data(), cap, &m) != 0 || ws_engine_live_pool_detach(lp, ln.slot) != 0) {
+          fail(w[0] + ": " + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, "live_pool_forwards");
+        take(ln, m);
+        ln.live = false;
+        std::vector<float> out(size_t(2) * ln.n_file, 0.f);
+        if (!from_model(ln.out.data(), 2, ln.n, ln.rate, ln.n_file, out.data())) {
+          fail(w[0] + ": " + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ln.t0).count();
+        if (write_out && (!wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk1.wav", out.data(), ln.n_file, ln.rate, &err) ||
+                          !wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk2.wav", out.data() + ln.n_file, ln.n_file, ln.rate, &err))) {
+          fail(err);
+          ok = false;
+          return;
+        }
+        if (!dry && raw_out) {
+          for (int k = 0; k < 2; ++k) {
+            FILE* f = fopen((out_dir + "/" + w[0] + "-spk" + std::to_string(k + 1) + ".f32").c_str(), "wb");
+            if (!f || fwrite(out.data() + size_t(k) * ln.n_file, 4, ln.n_file, f) != size_t(ln.n_file)) fail("cannot write raw output");
+            if (f) fclose(f);
+          }
+        }
+        std::lock_guard<std::mutex> l(io_mu);
+        printf("process: %s RTF: %.4f (live pool of %d lines: %lld pushes of %d samples, %lld bytes of live pool state)%s\n", w[0].c_str(),
+               ms / (1000.0 * ln.n_file / ln.rate), live_pool_n, ln.pushes, live_n, ws_engine_info(engine, "live_pool_state_bytes"),
+               dry ? " [dry run]" : "");
+        audio_ms += 1000.0 * ln.n_file / ln.rate;
+      };
+      for (int a = 0; a < live_pool_n; ++a)
+        if (ok) start(lanes[a]);
+      while (ok && !failed) {
+        std::vector<int> slots, ns, caps, n_out, who;
+        std::vector<const float*> chunks;
+        std::vector<float*> ests;
+        for (int a = 0; a < live_pool_n; ++a) {
+          Lane& ln = lanes[a];
+          if (!ln.live) continue;
+          slots.push_back(ln.slot), ns.push_back(std::min(live_n, ln.n - ln.pos)), caps.push_back(cap), who.push_back(a);
+          chunks.push_back(ln.mix.data() + ln.pos), ests.push_back(ln.got.data());
+        }
+        if (slots.empty()) break;
+        n_out.assign(slots.size(), 0);
+        if (ws_engine_live_pool_push(lp, static_cast<int>(slots.size()), slots.data(), chunks.data(), ns.data(), ests.data(), caps.data(),
+                                     n_out.data()) != 0) {
+          fail(std::string("--live_pool: ") + ws_engine_last_error());
+          ok = false;
+          break;
+        }
+        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, "live_pool_forwards");
+        pool_rounds += ws_engine_info(engine, "live_pool_rounds"), ++rounds;
+        for (size_t r = 0; r < who.size() && ok; ++r) {
+          Lane& ln = lanes[who[r]];
+          take(ln, n_out[r]);
+          ln.pos += ns[r], ++ln.pushes;
+          if (ln.pos >= ln.n) {
+            finish(ln);
+            if (ok) start(ln);
+          }
+        }
+      }
+      ws_engine_live_pool_close(lp);
+      if (ok) {
+        std::lock_guard<std::mutex> l(io_mu);
+        printf("live pool: %lld pushes, %lld rounds, %lld forwards, %lld launches\n", rounds, pool_rounds, forwards, launches);
+        total_audio_ms += audio_ms;
+        total_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pool_t0).count();
+      }
+      ws_engine_destroy(engine);
+      return;
+    }
     // --stream_pool N: up to N lines in flight on one pool of 2 N slots; a lane takes the next line when its own ends.
     // --rate_pool N: the same through one rate pool (ws_engine_rate_pool_*), every line at its own file's rate; the accepted rates
     // are those of the scp's mixtures, read before the pool is opened; outputs have the mixture's rate and length.

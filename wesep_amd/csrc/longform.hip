@@ -7,11 +7,14 @@
 //            samples, and a third window with it).
 // ws_xfade_stream_fwd is ws_xfade_ola over a range of absolute positions, its windows read from a ring: the live form
 // (runtime/live.cc).  Both cross-fades inline ONE body, lf_blend, so their arithmetic cannot differ.
+// ws_window_slots_fwd and ws_xfade_stream_rows_fwd are the table-driven forms of the gather and of the ring cross-fade for the
+// live pool (runtime/live_pool.cc): row i names its own source, destination, ring and layout; same bodies, same bits.
 // The kernels compute the starts themselves; no table of them exists.  Two HBM-bound passes: ws_window_rows gathers the
 // rows (once per target speaker), ws_xfade_ola blends the estimates with linear ramps over the O overlapping samples,
 // normalised by the sum of the weights that cover a sample.  Offsets are 64-bit (n up to 2^31 - 1); sums run in ascending
 // window order, no atomics; plain C++, no packed FP32.
 #include <algorithm>
+#include <vector>
 
 #include "common.h"
 
@@ -139,7 +142,173 @@ __global__ __launch_bounds__(256) void xfade_stream_kernel(const float* __restri
   }
 }
 
+// ---- rows forms (the live pool, runtime/live_pool.cc): one launch for A table rows that share nothing but the launch.  Grid
+// (blocks of the largest row, A); a workgroup beyond its own row's count leaves at once.
+
+// Row i of the table is one window of one slot: window_rows_kernel with the start, the destination and the factor read from
+// the table.  A thread owns four consecutive samples; scalar loads (no start alignment is assumed), a 16-byte store where the
+// destination allows it.  scale == 1 is a copy, as window_rows_kernel without a factor table.
+__global__ __launch_bounds__(256) void window_slots_kernel(const ws_window_slot_row* __restrict__ rows, const float* __restrict__ src,
+                                                           float* __restrict__ dst) {
+  const ws_window_slot_row r = rows[blockIdx.y];
+  const long long q0 = (long long)blockIdx.x * 256;
+  const int L4 = (r.len + 3) >> 2;
+  if (q0 >= L4) return;
+  const int quad = (int)q0 + (int)threadIdx.x;
+  if (quad >= L4) return;
+  const int j0 = quad * 4, cnt = min(4, r.len - j0);
+  const float* s = src + r.src_off + j0;
+  float v[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) v[q] = q < cnt ? s[q] : 0.f;
+  if (r.scale != 1.f) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] *= r.scale;
+  }
+  float* d = dst + r.dst_off + j0;
+  if (cnt == 4 && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+    const f32x4 t = {v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(d) = t;
+  } else {
+    for (int q = 0; q < cnt; ++q) d[q] = v[q];
+  }
+}
+
+// Row i of the table is one target of one slot: xfade_stream_kernel with K = 1 on the row's own ring, factor ring, range and
+// layout.  The layout (L, Wk, last) is derived exactly as ws_xfade_stream_fwd derives it; one thread per output sample.
+__global__ __launch_bounds__(256) void xfade_stream_rows_kernel(const ws_xfade_stream_row* __restrict__ rows, int S, int O, int cap,
+                                                                const float* __restrict__ ring, const float* __restrict__ scale_ring,
+                                                                float* __restrict__ out) {
+  const ws_xfade_stream_row r = rows[blockIdx.y];
+  const long long c0 = (long long)blockIdx.x * 256;
+  if (c0 >= r.count) return;
+  const long long c = c0 + threadIdx.x;
+  if (c >= r.count) return;
+  int L = S;
+  long long Wk = r.windows_run + 1, last = 0x7fffffffffffffffLL;
+  if (r.final) {
+    if (r.n < S) L = (int)r.n;
+    Wk = r.W, last = r.n - L;
+  }
+  const float o1 = (float)(O + 1);
+  out[r.out_off + c] = lf_blend<true>(ring + r.ring_off, r.scale_off >= 0 ? scale_ring + r.scale_off : nullptr, r.i0 + c, Wk, L, S - O,
+                                      o1, last, S, cap);
+}
+
+// Address ranges of one rows call: a written range may meet no other range of the call, read or written (another workgroup
+// of the launch owns it).  Ranges that are only read may share.
+struct LfSpan {
+  uintptr_t lo, hi;
+  int row;
+  bool write;
+  const char* name;
+};
+
+inline LfSpan lf_span(const float* p, long long off, long long n, int row, bool write, const char* name) {
+  return LfSpan{reinterpret_cast<uintptr_t>(p + off), reinterpret_cast<uintptr_t>(p + off + n), row, write, name};
+}
+
+int lf_spans_disjoint(const char* who, std::vector<LfSpan>& v) {
+  std::sort(v.begin(), v.end(), [](const LfSpan& a, const LfSpan& b) { return a.lo < b.lo; });
+  const LfSpan *far_r = nullptr, *far_w = nullptr;      // the read / written range that ends last so far
+  for (const LfSpan& x : v) {
+    const LfSpan* hit = far_w && x.lo < far_w->hi ? far_w : (x.write && far_r && x.lo < far_r->hi ? far_r : nullptr);
+    WS_REQUIRE(!hit, "%s: row %d: its %s range overlaps the %s range of row %d", who, x.row, x.name, hit->name, hit->row);
+    const LfSpan*& far = x.write ? far_w : far_r;
+    if (!far || x.hi > far->hi) far = &x;
+  }
+  return WS_OK;
+}
+
 }  // namespace
+
+extern "C" int ws_window_slots_fwd(const ws_window_slot_row* rows, const ws_window_slot_row* d_rows, int A, const float* src,
+                                   long long n_src, float* dst, long long n_dst, void* stream) {
+  const char* who = "ws_window_slots_fwd";
+  WS_REQUIRE(rows && d_rows && src && dst, "%s: rows, d_rows, src or dst is NULL", who);
+  WS_REQUIRE(A > 0 && A <= 65535, "%s: A=%d is outside [1, 65535]", who, A);
+  WS_REQUIRE(n_src >= 0 && n_dst >= 0, "%s: an arena length is negative (src %lld, dst %lld)", who, n_src, n_dst);
+  std::vector<LfSpan> spans;
+  spans.reserve((size_t)A * 2);
+  long long nb_max = 0;
+  for (int i = 0; i < A; ++i) {
+    const ws_window_slot_row& r = rows[i];
+    WS_REQUIRE(r.len > 0 && (long long)r.len + 1024 < (1LL << 31), "%s: row %d: bad args (len=%d in [1, 2^31 - 1024))", who, i, r.len);
+    WS_REQUIRE(r.src_off >= 0 && r.src_off <= n_src - r.len, "%s: row %d: src [%lld, %lld + %d) leaves the arena of %lld floats", who, i,
+               r.src_off, r.src_off, r.len, n_src);
+    WS_REQUIRE(r.dst_off >= 0 && r.dst_off <= n_dst - r.len, "%s: row %d: dst [%lld, %lld + %d) leaves the arena of %lld floats", who, i,
+               r.dst_off, r.dst_off, r.len, n_dst);
+    spans.push_back(lf_span(src, r.src_off, r.len, i, false, "src"));
+    spans.push_back(lf_span(dst, r.dst_off, r.len, i, true, "dst"));
+    nb_max = std::max(nb_max, (((long long)r.len + 3) / 4 + 255) / 256);
+  }
+  const int rc = lf_spans_disjoint(who, spans);
+  if (rc != WS_OK) return rc;
+  hipLaunchKernelGGL(window_slots_kernel, dim3((unsigned)nb_max, (unsigned)A), dim3(256), 0, (hipStream_t)stream, d_rows, src, dst);
+  return ws_check_launch(who);
+}
+
+extern "C" int ws_xfade_stream_rows_fwd(const ws_xfade_stream_row* rows, const ws_xfade_stream_row* d_rows, int A, int S, int O, int cap,
+                                        const float* ring, long long n_ring, const float* scale_ring, long long n_scale, float* out,
+                                        long long n_out, void* stream) {
+  const char* who = "ws_xfade_stream_rows_fwd";
+  WS_REQUIRE(rows && d_rows && ring && out, "%s: rows, d_rows, ring or out is NULL", who);
+  WS_REQUIRE(A > 0 && A <= 65535, "%s: A=%d is outside [1, 65535]", who, A);
+  WS_REQUIRE(S > 0 && cap > 0, "%s: bad args (S=%d, cap=%d)", who, S, cap);
+  WS_REQUIRE(O >= 0 && O <= S / 2, "%s: overlap O=%d outside [0, S / 2] (S=%d)", who, O, S);
+  WS_REQUIRE(n_ring >= 0 && n_scale >= 0 && n_out >= 0, "%s: an arena length is negative (ring %lld, scale_ring %lld, out %lld)", who,
+             n_ring, n_scale, n_out);
+  const long long H = S - O;
+  std::vector<LfSpan> spans;
+  spans.reserve((size_t)A * 3);
+  long long nb_max = 0;
+  for (int i = 0; i < A; ++i) {
+    const ws_xfade_stream_row& r = rows[i];
+    WS_REQUIRE(r.i0 >= 0 && r.count >= 0 && r.windows_run >= 0 && r.count + 256 < (1LL << 31),
+               "%s: row %d: bad range (i0=%lld, count=%lld below 2^31 - 256, windows_run=%lld)", who, i, r.i0, r.count, r.windows_run);
+    const long long end = r.i0 + r.count;
+    long long Wk, last;                                      // what the kernel takes as the row's layout
+    int L = S;
+    if (r.final) {
+      WS_REQUIRE(r.n > 0 && r.W == lf_windows(r.n, S, H) && r.windows_run == r.W,
+                 "%s: row %d: a final range needs all W=%lld windows of (n=%lld, S=%d, O=%d) run: %lld windows, %lld run", who, i, r.W, r.n, S,
+                 O, r.n > 0 ? lf_windows(r.n, S, H) : 0LL, r.windows_run);
+      WS_REQUIRE(end <= r.n, "%s: row %d: the range [%lld, %lld) reaches past the recording's n=%lld samples", who, i, r.i0, end, r.n);
+      if (r.n < S) L = (int)r.n;
+      Wk = r.W, last = r.n - L;
+    } else {
+      const long long emitted = r.windows_run > 0 ? (r.windows_run - 1) * H : 0;
+      WS_REQUIRE(end <= emitted, "%s: row %d: the range [%lld, %lld) reaches past the %lld samples that the %lld windows run make final "
+                 "(pass the final layout at a flush)", who, i, r.i0, end, emitted, r.windows_run);
+      Wk = r.windows_run + 1, last = 0x7fffffffffffffffLL;
+    }
+    WS_REQUIRE(r.ring_off >= 0 && r.ring_off <= n_ring - (long long)cap * S, "%s: row %d: ring [%lld, %lld + %d * %d) leaves the arena of %lld floats",
+               who, i, r.ring_off, r.ring_off, cap, S, n_ring);
+    WS_REQUIRE(r.scale_off == -1 || (scale_ring && r.scale_off >= 0 && r.scale_off <= n_scale - cap),
+               "%s: row %d: scale_ring [%lld, %lld + %d) leaves the arena of %lld floats%s (-1: no factors)", who, i, r.scale_off, r.scale_off,
+               cap, n_scale, scale_ring ? "" : ", and scale_ring is NULL");
+    if (r.count == 0) continue;                              // skipped by the kernel
+    WS_REQUIRE(r.out_off >= 0 && r.out_off <= n_out - r.count, "%s: row %d: out [%lld, %lld + %lld) leaves the arena of %lld floats", who, i,
+               r.out_off, r.out_off, r.count, n_out);
+    // the windows the range reads, [w_min, w_max], must all be in the ring still: the newest `cap` windows are
+    const long long w_min = r.i0 < L ? 0 : (r.i0 - L) / H + 1;
+    long long w_max = std::min(Wk - 2, (end - 1) / H);
+    if (r.final && end - 1 >= last) w_max = Wk - 1;
+    WS_REQUIRE(w_min + cap >= r.windows_run && w_max - w_min < cap,
+               "%s: row %d: cap=%d slots do not hold windows %lld..%lld of the range [%lld, %lld) with %lld windows run", who, i, cap, w_min,
+               w_max, r.i0, end, r.windows_run);
+    spans.push_back(lf_span(ring, r.ring_off, (long long)cap * S, i, false, "ring"));
+    if (r.scale_off >= 0) spans.push_back(lf_span(scale_ring, r.scale_off, cap, i, false, "scale_ring"));
+    spans.push_back(lf_span(out, r.out_off, r.count, i, true, "out"));
+    nb_max = std::max(nb_max, (r.count + 255) / 256);
+  }
+  const int rc = lf_spans_disjoint(who, spans);
+  if (rc != WS_OK) return rc;
+  if (nb_max == 0) return WS_OK;                             // every row has count == 0
+  hipLaunchKernelGGL(xfade_stream_rows_kernel, dim3((unsigned)nb_max, (unsigned)A), dim3(256), 0, (hipStream_t)stream, d_rows, S, O, cap,
+                     ring, scale_ring, out);
+  return ws_check_launch(who);
+}
 
 extern "C" int ws_window_rows(const float* x, int n, int W, int S, int H, int reps, const float* scale, float* rows,
                               void* stream) {

@@ -2300,7 +2300,7 @@ def _rows_table(rows, dtype, who: str) -> np.ndarray:
         if unknown:
             raise L.WesepHipError(f"{who}: row {i} has unknown fields {sorted(unknown)}")
         for k, v in r.items():
-            tab[i][k] = int(v)
+            tab[i][k] = v if dtype[k].kind == "f" else int(v)
     return tab
 
 
@@ -2350,4 +2350,45 @@ def rows_copy_fwd(rows, src, dst):
         raise L.WesepHipError(f"{who}: src and dst must be given")
     d_tab = L.upload_struct_array(tab, src.device)
     _call(who, C.c_void_p(tab.ctypes.data), C.c_void_p(d_tab.data_ptr()), len(tab), _p(src), n_src, _p(dst), n_dst)
+    return d_tab
+
+
+def window_slots_table(rows) -> np.ndarray:
+    """ws_window_slot_row [A] from dicts with the fields src_off, dst_off, len, scale (left out: 1)."""
+    return _rows_table([dict({"scale": 1.0}, **r) for r in rows] if not isinstance(rows, np.ndarray) else rows, L.WINDOW_SLOT_ROW,
+                       "ws_window_slots_fwd")
+
+
+def xfade_stream_rows_table(rows) -> np.ndarray:
+    """ws_xfade_stream_row [A] from dicts with the fields ring_off, scale_off (left out: -1, no factors), out_off, i0, count,
+    windows_run, W, n, final."""
+    return _rows_table([dict({"scale_off": -1}, **r) for r in rows] if not isinstance(rows, np.ndarray) else rows, L.XFADE_STREAM_ROW,
+                       "ws_xfade_stream_rows_fwd")
+
+
+def window_slots_fwd(rows, src, dst):
+    """ws_window_slots_fwd: row i writes fl(src[src_off : src_off + len] * scale) to dst[dst_off :]; src and dst are arenas (1-D
+    float32 on one device).  Returns the device table (alive until the launch has run)."""
+    who = "ws_window_slots_fwd"
+    tab = window_slots_table(rows)
+    n_src, n_dst = _arena(src, who, "src"), _arena(dst, who, "dst")
+    if src is None or dst is None:
+        raise L.WesepHipError(f"{who}: src and dst must be given")
+    d_tab = L.upload_struct_array(tab, src.device)
+    _call(who, C.c_void_p(tab.ctypes.data), C.c_void_p(d_tab.data_ptr()), len(tab), _p(src), n_src, _p(dst), n_dst)
+    return d_tab
+
+
+def xfade_stream_rows_fwd(rows, S: int, O: int, cap: int, ring, out, scale_ring=None):
+    """ws_xfade_stream_rows_fwd: row i is xfade_stream_fwd with K = 1 on its own ring [cap][S] at ring_off, factor ring at
+    scale_off (-1: none), range [i0, i0 + count) and layout (windows_run, final, W, n), written to out[out_off :]; ring,
+    scale_ring and out are arenas.  Returns the device table."""
+    who = "ws_xfade_stream_rows_fwd"
+    tab = xfade_stream_rows_table(rows)
+    n_ring, n_scale, n_out = _arena(ring, who, "ring"), _arena(scale_ring, who, "scale_ring"), _arena(out, who, "out")
+    if ring is None or out is None:
+        raise L.WesepHipError(f"{who}: ring and out must be given")
+    d_tab = L.upload_struct_array(tab, ring.device)
+    _call(who, C.c_void_p(tab.ctypes.data), C.c_void_p(d_tab.data_ptr()), len(tab), int(S), int(O), int(cap), _p(ring), n_ring,
+          _p(scale_ring), n_scale, _p(out), n_out)
     return d_tab

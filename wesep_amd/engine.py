@@ -23,7 +23,9 @@ SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", 
            "ws_engine_rate_stream_reset", "ws_engine_rate_stream_close", "ws_engine_rate_stream_push_cap",
            "ws_engine_rate_pool_open", "ws_engine_rate_pool_attach", "ws_engine_rate_pool_push", "ws_engine_rate_pool_push_cap",
            "ws_engine_rate_pool_flush", "ws_engine_rate_pool_detach", "ws_engine_rate_pool_close",
-           "ws_engine_live_open", "ws_engine_live_push", "ws_engine_live_flush", "ws_engine_live_reset", "ws_engine_live_close")
+           "ws_engine_live_open", "ws_engine_live_push", "ws_engine_live_flush", "ws_engine_live_reset", "ws_engine_live_close",
+           "ws_engine_live_pool_open", "ws_engine_live_pool_attach", "ws_engine_live_pool_push", "ws_engine_live_pool_flush",
+           "ws_engine_live_pool_detach", "ws_engine_live_pool_close")
 STREAM_FLUSH_CAP = 160  # WS_STREAM_FLUSH_CAP
 STREAM_BLOCK_KERNEL = 1  # WS_STREAM_BLOCK_KERNEL: every block of a stream / pool group as one entry-point call
 _lib = None
@@ -130,6 +132,19 @@ def lib():
         l.ws_engine_live_reset.argtypes = [C.c_void_p]
         l.ws_engine_live_close.restype = None
         l.ws_engine_live_close.argtypes = [C.c_void_p]
+        l.ws_engine_live_pool_open.restype = C.c_int
+        l.ws_engine_live_pool_open.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        l.ws_engine_live_pool_attach.restype = C.c_int
+        l.ws_engine_live_pool_attach.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+        l.ws_engine_live_pool_push.restype = C.c_int
+        l.ws_engine_live_pool_push.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+        l.ws_engine_live_pool_flush.restype = C.c_int
+        l.ws_engine_live_pool_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_live_pool_detach.restype = C.c_int
+        l.ws_engine_live_pool_detach.argtypes = [C.c_void_p, C.c_int]
+        l.ws_engine_live_pool_close.restype = None
+        l.ws_engine_live_pool_close.argtypes = [C.c_void_p]
         if l.ws_engine_abi_version() != ENGINE_ABI_VERSION:
             raise WesepHipError("libwesep_engine.so ABI version mismatch; rebuild")
         _lib = l
@@ -298,6 +313,13 @@ class Engine:
         overlap, max_rows) -- bit for bit with max_rows = 1.  Latency: window .. window + hop samples.  Close the handle
         before the engine."""
         return EngineLive(self, enrolls, kind, window, overlap, max_rows)
+
+    def live_pool(self, slots, K, window, overlap, max_rows=8):
+        """A pool of `slots` independent live recordings on ANY container, K targets each: every window that one push
+        completes, in whatever slot, goes through the separator in the same forwards (at most max_rows rows each).  Per slot
+        the outputs are those of live() / separate_long() on that slot's audio -- bit for bit with max_rows = 1.  Close the
+        pool before the engine."""
+        return LivePool(self, slots, K, window, overlap, max_rows)
 
     def stream(self, rows, enroll, kind, max_chunk_frames=64, block_kernel=False):
         """A stream of `rows` rows on a causal cLN Conv-TasNet / SpEx+ container (info("streaming") == 1): enroll as in
@@ -483,6 +505,80 @@ class EngineLive:
     def close(self):
         if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
             _lib.ws_engine_live_close(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+LIVE_POOL_ROUND_LAUNCHES = 3        # WS_LIVE_POOL_ROUND_LAUNCHES: the gather, the scatter into the rings and the cross-fade of a round
+
+
+def live_pool_launches(round_plans):
+    """"n_launches" after a live-pool push: round_plans is one list per round of its forwards' rectangular counts."""
+    return sum(sum(f) + LIVE_POOL_ROUND_LAUNCHES for f in round_plans) + 1
+
+
+class LivePool:
+    """ws_engine_live_pool_* (include/wesep_engine.h): many live recordings, the windows that one push completes through the
+    same forwards.  Every slot is an EngineLive: the concatenation of what its pushes and its flush return is
+    Engine.separate_long on that slot's audio, whatever the other slots were fed in the meantime."""
+
+    def __init__(self, engine, slots, K, window, overlap, max_rows=8):
+        self._h, self._engine = C.c_void_p(), engine      # (the engine must outlive the pool)
+        self.slots, self.K, self.window, self.overlap, self.max_rows = int(slots), int(K), int(window), int(overlap), int(max_rows)
+        _quiesce_torch()
+        _check(lib().ws_engine_live_pool_open(engine._h, self.slots, self.K, self.window, self.overlap, self.max_rows,
+                                              C.byref(self._h)), "ws_engine_live_pool_open")
+
+    def attach(self, enrolls, kind):
+        """K enrollments as in Engine.separate_long() -> the slot they took.  The speaker stage runs here, once."""
+        enroll, pitch, lengths = _enroll_rows(enrolls, kind, None)
+        if enroll.shape[0] != self.K:
+            raise ValueError(f"LivePool.attach: {enroll.shape[0]} enrollments, the pool was opened for K = {self.K}")
+        slot = C.c_int(-1)
+        _quiesce_torch()
+        _check(lib().ws_engine_live_pool_attach(self._h, enroll.ctypes.data, kind, pitch,
+                                                None if lengths is None else lengths.ctypes.data, C.byref(slot)),
+               "ws_engine_live_pool_attach")
+        return slot.value
+
+    def push(self, chunks, est_cap=None):
+        """{slot: chunk [n_slot >= 1]} -> {slot: float32 [K, m_slot]}, the samples of each slot that became final (m = 0 while
+        no window of the slot became complete).  est_cap: {slot: samples a target the buffer holds} (default: what suffices)."""
+        ids = list(chunks)
+        data = [np.ascontiguousarray(chunks[i], dtype=np.float32).reshape(-1) for i in ids]
+        n = np.array([x.shape[0] for x in data], dtype=np.int32)
+        H = self.window - self.overlap
+        caps = np.array([live_push_cap(int(k), H) if est_cap is None else int(est_cap[i]) for i, k in zip(ids, n)], dtype=np.int32)
+        bufs = [np.zeros((self.K, max(int(c), 1)), dtype=np.float32) for c in caps]
+        A = len(ids)
+        slots, m = np.array(ids, dtype=np.int32), np.zeros(max(A, 1), dtype=np.int32)
+        cp = (C.c_void_p * max(A, 1))(*[x.ctypes.data for x in data])
+        ep = (C.c_void_p * max(A, 1))(*[b.ctypes.data for b in bufs])
+        _quiesce_torch()
+        _check(lib().ws_engine_live_pool_push(self._h, A, slots.ctypes.data, C.cast(cp, C.c_void_p), n.ctypes.data,
+                                              C.cast(ep, C.c_void_p), caps.ctypes.data, m.ctypes.data), "ws_engine_live_pool_push")
+        return {i: b[:, :int(k)].copy() for i, b, k in zip(ids, bufs, m)}
+
+    def flush(self, slot, est_cap=None):
+        """The end of one slot's recording: the end-aligned last window if one is due, then every sample not yet out."""
+        cap = live_flush_cap(self.window, self.overlap) if est_cap is None else int(est_cap)
+        buf, m = np.zeros((self.K, max(cap, 1)), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_live_pool_flush(self._h, int(slot), buf.ctypes.data, cap, C.byref(m)), "ws_engine_live_pool_flush")
+        return buf[:, :m.value].copy()
+
+    def detach(self, slot):
+        """Frees the slot for the next attach."""
+        _check(lib().ws_engine_live_pool_detach(self._h, int(slot)), "ws_engine_live_pool_detach")
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
+            _lib.ws_engine_live_pool_close(self._h)
         self._h = None
 
     def __del__(self):
