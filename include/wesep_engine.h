@@ -444,6 +444,78 @@ int ws_engine_live_pool_flush(ws_live_pool* p, int slot, float* est, int est_cap
 int ws_engine_live_pool_detach(ws_live_pool* p, int slot);
 void ws_engine_live_pool_close(ws_live_pool* p);
 
+/* ---- tail pool (runtime/tail_pool.cc; DESIGN sections 7 "Tail pool" and 11b) -- new symbols, WS_ENGINE_ABI_VERSION 2 unchanged
+ * LOW-LATENCY live separation on TRAILING windows, any container, many recordings.  The live families above emit a sample once
+ * every window of ws_engine_separate_long that covers it has run: S .. S + H samples late, and a live pool's slots complete
+ * windows together only when their recordings are aligned.  Here the clock is the caller's: a TICK runs, for every named slot
+ * with enough new audio, the window of its NEWEST S samples and emits the newest part of it.  Latency: the tick period plus the
+ * fade.  Every slot with new audio fires on the same tick, so the forwards fill up however the calls are staggered.  PRICE: one
+ * full window a slot a tick, the caller's to choose through the tick period.  The output is a rule of its own, NOT
+ * ws_engine_separate_long, and nothing is claimed about separation quality: the backward direction of a BLSTM sees no future at
+ * a window's end; callers trade that through S, the tick period and the fade.
+ * THE RULE, per slot.  Fixed at open: window S, fade C in [0, S / 2], warm in [max(C, 1, the architecture's lower bound on T), S],
+ * K targets.  N: samples pushed.  F: N at the last firing.  hold [K][C]: the last window's estimate of the newest C samples, kept
+ * back.  E: samples emitted, 0 before the first firing and F - C after it.
+ *   push   appends to the slot's pending samples on the host: NO launch, NO synchronisation.  A push that would make N - E > S is
+ *          refused ("tick first") before anything of the call is appended: what has not come out must fit one window.
+ *   tick   a named slot FIRES if N >= warm and it never fired or N - F >= max(C, 1); one that does not gets n_out = 0.  A firing
+ *          slot runs the window [a, N), a = max(0, N - S), L = N - a, one row per target, and emits [E, N - C): m = N - C - E
+ *          samples.  With h = C after a first firing, else 0, the first h of them are the held ones cross-faded into the new
+ *          window's estimate of the same positions, the rest come from the new window alone; the window's last C samples become
+ *          the new hold; then F = N.
+ *   flush  ends one recording.  N > F, or never fired: one last window [max(0, N - S), N) emits [E, N), no new hold; its L only
+ *          has to meet the architecture's own lower bound on T -- a refusal launches nothing and leaves the slot as it was.
+ *          N == F: the hold comes out as it is, a copy with no forward.  The slot then takes nothing until it is detached.
+ *   blend  with y the window's estimate: v = fl(y scale), scale the window's standard deviation for TF-GridNet (computed on the
+ *          host over the window's own L samples, 1 / std folded into the gather) and exactly 1 otherwise; for j < h
+ *          out = fma(ramp[j], fl(v - hold[j]), hold[j]), ramp[j] = float(j + 1) / float(C + 1); for j >= h out = v; the new hold
+ *          stores v.  hold is double-buffered per slot and target and flipped at every firing.
+ *   ws_engine_tail_pool_open(e, slots, K, window, fade, warm, max_rows, &pool)  the window checks of ws_engine_separate_long (its
+ *     messages), the plan's guards on a forward of max_rows rows of S samples, the bounds on fade and warm above; slots in
+ *     [1, 65535], slots K <= 65535 (the tables of a launch).  Makes ONE device allocation, ws_engine_info
+ *     "tail_pool_state_bytes", a function of (slots, K, S, C, max_rows) only, that no later call grows: per slot the two hold
+ *     buffers [2][K][C] and the K embeddings; per tick the staging block (the slots' spans of at most S samples, the embedding
+ *     rows, the two tables), the rows, estimates and output rectangles, slots K rows of pitch S each; the ramp.  Pending samples
+ *     (at most S a slot) stay on the host.
+ *   ws_engine_tail_pool_attach(pool, enroll, enroll_kind, enroll_len, enroll_lengths, &slot)  takes the lowest free slot, runs the
+ *     speaker stage ONCE for its K enrollments (every kind ws_engine_live_pool_attach takes, WS_ENROLL_SPEAKER included) and
+ *     puts the slot at sample 0.  A full pool is refused by name.
+ *   ws_engine_tail_pool_push(pool, n_active, slots, chunks, n)  chunks[i] is n[i] >= 1 samples for slots[i], DISTINCT slots.
+ *   ws_engine_tail_pool_tick(pool, n_active, slots, est, est_cap, n_out)  est[i] is [K][est_cap[i]], n_out[i] samples a target
+ *     (WS_TAIL_CAP(S) always suffices).  If no named slot fires: NO launch, NO synchronisation.  Otherwise, in order: one upload
+ *     of the staging block, ONE ws_window_slots_fwd for all rows, the forwards, ONE ws_tail_emit_rows_fwd, one copy to the
+ *     host, ONE synchronisation.  Forwards: the rows of full windows (L = S), ordered (slot, target), in forwards of at most
+ *     max_rows rows whichever slots they came from; the rows of a slot still in warm-up (L < S) in forwards of that slot's own
+ *     rows (the rectangular plans take one length a forward).  ws_engine_info "n_launches" after a tick:
+ *         the forwards' rectangular counts + WS_TAIL_TICK_LAUNCHES + 1
+ *     "tail_pool_forwards" and "tail_pool_rows" report the last tick or flush.
+ *   ws_engine_tail_pool_flush(pool, slot, est, est_cap, &n_out)  a tick of this one slot with the final rule; with N == F it is
+ *     ws_rows_copy_fwd of the hold and the copy to the host: 2 entry-point calls (nothing at all when the fade is 0).
+ *   ws_engine_tail_pool_detach(pool, slot)  frees the slot.    ws_engine_tail_pool_close(pool)  before ws_engine_destroy.
+ * The engine's work arena is used under a scope and nothing of it is held between two calls.  Dry-run engines take every call.
+ * All pointers are HOST pointers; callers serialise.
+ * FAILURE: the slots named by a tick or flush that failed half way are refused by name until they are detached; the other
+ * slots go on.
+ * No launch mixes rows: with the row composition of the forwards held fixed, a slot's bits do not depend on the other slots'
+ * sample values -- as far as the architecture's rectangular plan keeps its rows apart.  With one row per forward
+ * (max_rows = 1) every window is bit for bit ws_engine_separate on that window alone.
+ * NOT built: a sample rate per slot; a different K per slot; backlog handling beyond one window (a caller that falls behind
+ * has to tick, or drop audio itself).
+ * WS_ERR_INVALID with a message and nothing launched: a slot of a push, tick or flush that is free, flushed, named twice or
+ * part of a failed call; n[i] < 1; est_cap below the emission, checked for every entry before any launch; a NULL pointer; the
+ * push overflow above; a full pool; the bounds of open. */
+typedef struct ws_tail_pool ws_tail_pool;
+#define WS_TAIL_TICK_LAUNCHES 2          /* ws_window_slots_fwd + ws_tail_emit_rows_fwd */
+#define WS_TAIL_CAP(S) (S)               /* est_cap that always suffices, per target */
+int ws_engine_tail_pool_open(ws_engine* e, int slots, int K, int window, int fade, int warm, int max_rows, ws_tail_pool** out);
+int ws_engine_tail_pool_attach(ws_tail_pool* p, const void* enroll, int enroll_kind, int enroll_len, const int* enroll_lengths,
+                               int* slot);
+int ws_engine_tail_pool_push(ws_tail_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n);
+int ws_engine_tail_pool_tick(ws_tail_pool* p, int n_active, const int* slots, float* const* est, const int* est_cap, int* n_out);
+int ws_engine_tail_pool_flush(ws_tail_pool* p, int slot, float* est, int est_cap, int* n_out);
+int ws_engine_tail_pool_detach(ws_tail_pool* p, int slot);
+void ws_engine_tail_pool_close(ws_tail_pool* p);
+
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by
  * 2^-15 before the model, separate_engine.cc:81-84, and its wav writer scales back, frontend/wav.h:245-253).

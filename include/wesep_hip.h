@@ -1214,6 +1214,30 @@ int ws_xfade_stream_rows_fwd(const ws_xfade_stream_row* rows, const ws_xfade_str
                              const float* ring, long long n_ring, const float* scale_ring, long long n_scale, float* out,
                              long long n_out, void* stream);
 
+/* Tail pool (longform.hip; runtime/tail_pool.cc, DESIGN 7 "Tail pool") -- a new symbol, ABI 20 unchanged.  The emission of one
+ * tick as ONE launch, in the rows form and with the two-table convention above.  Row i is one target of one slot: of its
+ * window's estimate y [L] at y + y_off it emits the m samples from local index p on, and holds the last c_new samples back for
+ * the next window to cross-fade into.  With v = fl(y * scale) (scale exactly 1: y itself), the roundings spelled out as the
+ * cross-fade body of ws_xfade_ola spells its own and contraction off:
+ *     out[out_off + j]       = j < h ? fma(ramp[j], fl(v - hold[hold_in_off + j]), hold[hold_in_off + j]) : v,     j < m
+ *     hold[hold_out_off + q] = fl(y[y_off + p + m + q] * scale),                                                 q < c_new
+ * ramp [C] is the caller's, ramp[j] = float(j + 1) / float(C + 1) in the tail pool; h and c_new are 0 or C.  A row's new hold
+ * is another buffer than the one it reads (the caller double-buffers), so no thread reads what another thread of the launch
+ * writes.  Grid (blocks of the largest m + c_new, A); a workgroup beyond its own row's count leaves at once; a thread owns four
+ * consecutive floats of one destination counted from the 16-byte boundary below its first float, so whole quads are stored as
+ * 16 bytes wherever a destination starts; sources are read with scalar loads.  64-bit offsets, no LDS, no atomics, plain C++.
+ * WS_ERR_INVALID before any launch, each with the row index: A outside [1, 65535]; a NULL pointer (ramp may be NULL when
+ * C == 0); C < 0; h or c_new that is neither 0 nor C; h > m; p < 0; p + m + c_new != L; m + c_new < 1; a range that leaves its
+ * arena; an out or hold_out range that overlaps any other range of the call (by address), so also a hold_in range that meets a
+ * hold_out range. */
+typedef struct ws_tail_emit_row {
+  long long y_off, hold_in_off, hold_out_off, out_off;
+  int L, p, h, m, c_new;
+  float scale;
+} ws_tail_emit_row;
+int ws_tail_emit_rows_fwd(const ws_tail_emit_row* rows, const ws_tail_emit_row* d_rows, int A, int C, const float* ramp,
+                          const float* y, long long n_y, float* hold, long long n_hold, float* out, long long n_out, void* stream);
+
 /* ---- streaming Conv-TasNet (stream.hip; wesep_amd/streaming.py) -- new symbols, ABI 20 unchanged --------
  * The two kernels of a causal Conv-TasNet that look across time, in a chunked form with state carried on the device.
  *   ws_dwconv_stream_fwd  ws_dwconv_ex_fwd(causal = 1) on one chunk of Tc frames whose first frame has absolute index t0.

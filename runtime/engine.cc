@@ -364,6 +364,10 @@ WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   if (k == "live_pool_state_bytes") return e->live_pool_state_bytes;
   if (k == "live_pool_rounds") return e->live_pool_rounds;
   if (k == "live_pool_forwards") return e->live_pool_forwards;
+  // the tail pool opened last: its one device allocation; the pool that ran last: forwards and rows of its last tick or flush
+  if (k == "tail_pool_state_bytes") return e->tail_pool_state_bytes;
+  if (k == "tail_pool_forwards") return e->tail_pool_forwards;
+  if (k == "tail_pool_rows") return e->tail_pool_rows;
   auto it = e->meta.find(k);
   return it == e->meta.end() ? -1 : it->second;
 }

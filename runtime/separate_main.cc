@@ -5,6 +5,7 @@
 //                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
 //                 [--stream_ms 10 [--stream_pool 4 | --rate_pool 4] [--stream_block]] [--resample]
 //                 [--live_ms 100 --chunk_seconds 4 [--live_pool 4]]
+//                 [--tail_ms 100 --chunk_seconds 4 [--tail_fade_ms 10] [--tail_warm_seconds 4] [--tail_pool 4]]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -39,6 +40,12 @@
 // slot detached and re-attached to the next line.  Names and formats are those of --live_ms; with N = 1 and --chunk_rows 1 so
 // are the samples, bit for bit.  Works with --jobs, --dry_run and --resample (files go through ws_engine_resample around the
 // pool, as for --live_ms).  Refused without --live_ms, and together with --batch N > 1, --stream_ms and the other pools.
+// --tail_ms M [--tail_fade_ms F, default 10] [--tail_warm_seconds W, default S] [--tail_pool N, default 1] (with --chunk_seconds S;
+// any model): low-latency separation on trailing windows -- N lines in flight on one tail pool (ws_engine_tail_pool_*, K = 2):
+// every round pushes each line its next M ms packet and ticks, so every line runs the window of its newest S seconds and what
+// is new comes out M ms plus the fade after it went in; a line that ends is flushed and its slot re-attached.  The samples
+// follow the tail rule (include/wesep_engine.h), NOT the --chunk_seconds run.  A packet is cut where more than one window of
+// samples would be waiting.  Works with --jobs, --dry_run and --resample; refused together with every other mode.
 // --stream_ms M (causal cLN Conv-TasNet / SpEx+ models, ws_engine_info "streaming"): every line is fed to a stream
 // (ws_engine_stream_open / push / flush) in chunks of M milliseconds, as a live source would deliver it; the speaker encoder
 // runs once per line, at open.  Same files as the plain run: the streamed samples, then zeros where the plain run has its
@@ -173,6 +180,12 @@ int main(int argc, char** argv) {
   const int live_n = static_cast<int>(live_ms * sample_rate / 1000.0 + 0.5);
   const bool live_pooled = args.has("live_pool");
   const int live_pool_n = atoi(args.get("live_pool", "0").c_str());
+  const bool tail = args.has("tail_ms");
+  const double tail_ms = atof(args.get("tail_ms", "0").c_str());
+  const int tail_n = static_cast<int>(tail_ms * sample_rate / 1000.0 + 0.5);
+  const int tail_fade = static_cast<int>(atof(args.get("tail_fade_ms", "10").c_str()) * sample_rate / 1000.0 + 0.5);
+  const int tail_warm = args.has("tail_warm_seconds") ? static_cast<int>(atof(args.get("tail_warm_seconds", "0").c_str()) * sample_rate + 0.5) : window;
+  const int tail_pool_n = atoi(args.get("tail_pool", "1").c_str());
   const bool rate_pooled = args.has("rate_pool");
   const int rate_pool_n = atoi(args.get("rate_pool", "0").c_str());
   // a dry run writes nothing -- except with --resample and an --output_dir: the (all-zero) files then show the rate and the
@@ -184,6 +197,7 @@ int main(int argc, char** argv) {
            "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]]\n"
            "                     [--stream_ms M [--stream_pool N | --rate_pool N] [--stream_block]] [--resample]\n"
            "                     [--live_ms M --chunk_seconds S [--live_pool N]]\n"
+           "                     [--tail_ms M --chunk_seconds S [--tail_fade_ms F] [--tail_warm_seconds W] [--tail_pool N]]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
@@ -197,6 +211,14 @@ int main(int argc, char** argv) {
            "                     --chunk_seconds run.  Not together with --batch N > 1, --stream_ms or a pool\n"
            "  --live_pool N      with --live_ms M: N lines in flight at once on one live pool, one push per round of M ms\n"
            "                     packets; windows that complete in the same round share their forwards; same files as --live_ms\n"
+           "  --tail_ms M        with --chunk_seconds S, any model: low-latency separation on trailing windows (a tail pool): every\n"
+           "                     line is fed in packets of M ms with a tick after every packet round and a flush at the end; a\n"
+           "                     sample comes out M ms plus the fade after it went in, each tick costs one window of S seconds a\n"
+           "                     line.  A rule of its own: NOT the files of the --chunk_seconds run\n"
+           "  --tail_fade_ms F   the cross-fade between consecutive trailing windows (default 10, not a tuned value), at most S / 2\n"
+           "  --tail_warm_seconds W  the audio a line needs before its first window (default S)\n"
+           "  --tail_pool N      N lines in flight at once on one tail pool (default 1); every line with new audio fires on the\n"
+           "                     same tick and shares the forwards; a lane takes the next line when its own ends\n"
            "  --stream_ms M      causal cLN Conv-TasNet / SpEx+ models: feed every line to a stream in chunks of M ms; same\n"
            "                     files as the plain run.  Not together with --batch N > 1 or --chunk_seconds\n"
            "  --stream_pool N    with --stream_ms M: N consecutive lines at a time through one stream pool, one push per round\n"
@@ -209,6 +231,14 @@ int main(int argc, char** argv) {
            "                     file's sample rate (packets of M ms at that rate); outputs have the mixture's rate and length\n");
     return 0;
   }
+  if ((args.has("tail_fade_ms") || args.has("tail_warm_seconds") || args.has("tail_pool")) && !tail)
+    return die("--tail_fade_ms, --tail_warm_seconds and --tail_pool need --tail_ms M: the tail pool is fed packets of M milliseconds");
+  if (tail && !chunked) return die("--tail_ms needs --chunk_seconds S: a tail pool runs the trailing window of S seconds at every tick");
+  if (tail && (batch > 1 || streamed || live || live_pooled || pooled || rate_pooled))
+    return die("--tail_ms conflicts with --batch N > 1, --stream_ms, --live_ms, --live_pool, --stream_pool and --rate_pool: one mode per "
+               "run, and a tail pool takes recordings as they arrive through the trailing windows of --chunk_seconds");
+  if (tail && tail_n < 1) return die("--tail_ms needs a positive packet length");
+  if (tail && tail_pool_n < 1) return die("--tail_pool needs a positive number of lines");
   if (live_pooled && !live) return die("--live_pool needs --live_ms M: the pool is fed packets of M milliseconds");
   if (live_pooled && (batch > 1 || streamed || pooled || rate_pooled))
     return die("--live_pool conflicts with --batch N > 1, --stream_ms, --stream_pool and --rate_pool: one pool per run, and a live pool "
@@ -335,7 +365,10 @@ int main(int argc, char** argv) {
     // --live_pool N: up to N lines in flight on one live pool of N slots (K = 2), each fed its next packet of live_n samples at the
     // model's rate in one push per round; a lane takes the next line when its own ends.  With --resample a line's files are
     // brought to the model's rate before and its estimates back after, as for --live_ms.
-    if (live_pooled) {
+    // --tail_ms M [--tail_pool N]: the same lanes on one tail pool (ws_engine_tail_pool_*): a round pushes every lane its next packet
+    // -- cut so that what has not come out still fits one window -- and ticks all of them; outputs follow the tail rule.
+    if (live_pooled || tail) {
+      const int lanes_n = tail ? tail_pool_n : live_pool_n;
       struct Lane {
         bool live = false;
         size_t line = 0;
@@ -345,13 +378,18 @@ int main(int argc, char** argv) {
         std::chrono::steady_clock::time_point t0;
       };
       ws_live_pool* lp = nullptr;
-      if (ws_engine_live_pool_open(engine, live_pool_n, 2, window, overlap, chunk_rows, &lp) != 0) {
-        fail(std::string("--live_pool: ") + ws_engine_last_error());
+      ws_tail_pool* tp = nullptr;
+      const char* flag = tail ? "--tail_ms: " : "--live_pool: ";
+      if ((tail ? ws_engine_tail_pool_open(engine, lanes_n, 2, window, tail_fade, tail_warm, chunk_rows, &tp)
+                : ws_engine_live_pool_open(engine, lanes_n, 2, window, overlap, chunk_rows, &lp)) != 0) {
+        fail(std::string(flag) + ws_engine_last_error());
         ws_engine_destroy(engine);
         return;
       }
-      const int cap = std::max(WS_LIVE_PUSH_CAP(live_n, window - overlap), WS_LIVE_FLUSH_CAP(window, overlap));
-      std::vector<Lane> lanes(live_pool_n);
+      const int packet = tail ? tail_n : live_n;
+      const int cap = tail ? WS_TAIL_CAP(window) : std::max(WS_LIVE_PUSH_CAP(live_n, window - overlap), WS_LIVE_FLUSH_CAP(window, overlap));
+      const char* forwards_key = tail ? "tail_pool_forwards" : "live_pool_forwards";
+      std::vector<Lane> lanes(lanes_n);
       bool ok = true;
       long long rounds = 0, launches = 0, forwards = 0, pool_rounds = 0;
       double audio_ms = 0.0;
@@ -388,7 +426,8 @@ int main(int argc, char** argv) {
         ln.out.assign(size_t(2) * ln.n, 0.f);
         ln.got.assign(size_t(2) * cap, 0.f);
         ln.t0 = std::chrono::steady_clock::now();
-        if (ws_engine_live_pool_attach(lp, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, &ln.slot) != 0) {
+        if ((tail ? ws_engine_tail_pool_attach(tp, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, &ln.slot)
+                  : ws_engine_live_pool_attach(lp, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, &ln.slot)) != 0) {
           fail(w[0] + ": " + ws_engine_last_error());
           ok = false;
           return;
@@ -403,12 +442,13 @@ int main(int argc, char** argv) {
         const auto& w = waves[ln.line];
         std::string err;
         int m = 0;
-        if (ws_engine_live_pool_flush(lp, ln.slot, ln.got.data(), cap, &m) != 0 || ws_engine_live_pool_detach(lp, ln.slot) != 0) {
+        if (tail ? ws_engine_tail_pool_flush(tp, ln.slot, ln.got.data(), cap, &m) != 0 || ws_engine_tail_pool_detach(tp, ln.slot) != 0
+                 : ws_engine_live_pool_flush(lp, ln.slot, ln.got.data(), cap, &m) != 0 || ws_engine_live_pool_detach(lp, ln.slot) != 0) {
           fail(w[0] + ": " + ws_engine_last_error());
           ok = false;
           return;
         }
-        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, "live_pool_forwards");
+        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, forwards_key);
         take(ln, m);
         ln.live = false;
         std::vector<float> out(size_t(2) * ln.n_file, 0.f);
@@ -432,33 +472,42 @@ int main(int argc, char** argv) {
           }
         }
         std::lock_guard<std::mutex> l(io_mu);
-        printf("process: %s RTF: %.4f (live pool of %d lines: %lld pushes of %d samples, %lld bytes of live pool state)%s\n", w[0].c_str(),
-               ms / (1000.0 * ln.n_file / ln.rate), live_pool_n, ln.pushes, live_n, ws_engine_info(engine, "live_pool_state_bytes"),
-               dry ? " [dry run]" : "");
+        if (tail)
+          printf("process: %s RTF: %.4f (tail pool of %d lines: %lld ticks, packets of %d samples, fade %d, %lld bytes of tail pool state)%s\n",
+                 w[0].c_str(), ms / (1000.0 * ln.n_file / ln.rate), lanes_n, ln.pushes, packet, tail_fade,
+                 ws_engine_info(engine, "tail_pool_state_bytes"), dry ? " [dry run]" : "");
+        else
+          printf("process: %s RTF: %.4f (live pool of %d lines: %lld pushes of %d samples, %lld bytes of live pool state)%s\n", w[0].c_str(),
+                 ms / (1000.0 * ln.n_file / ln.rate), live_pool_n, ln.pushes, live_n, ws_engine_info(engine, "live_pool_state_bytes"),
+                 dry ? " [dry run]" : "");
         audio_ms += 1000.0 * ln.n_file / ln.rate;
       };
-      for (int a = 0; a < live_pool_n; ++a)
+      for (int a = 0; a < lanes_n; ++a)
         if (ok) start(lanes[a]);
       while (ok && !failed) {
         std::vector<int> slots, ns, caps, n_out, who;
         std::vector<const float*> chunks;
         std::vector<float*> ests;
-        for (int a = 0; a < live_pool_n; ++a) {
+        for (int a = 0; a < lanes_n; ++a) {
           Lane& ln = lanes[a];
           if (!ln.live) continue;
-          slots.push_back(ln.slot), ns.push_back(std::min(live_n, ln.n - ln.pos)), caps.push_back(cap), who.push_back(a);
+          // (a tail pool holds at most one window of samples that have not come out: ln.pos - ln.done of them are waiting)
+          const int room = tail ? window - (ln.pos - ln.done) : packet;
+          slots.push_back(ln.slot), ns.push_back(std::min({packet, ln.n - ln.pos, room})), caps.push_back(cap), who.push_back(a);
           chunks.push_back(ln.mix.data() + ln.pos), ests.push_back(ln.got.data());
         }
         if (slots.empty()) break;
         n_out.assign(slots.size(), 0);
-        if (ws_engine_live_pool_push(lp, static_cast<int>(slots.size()), slots.data(), chunks.data(), ns.data(), ests.data(), caps.data(),
-                                     n_out.data()) != 0) {
-          fail(std::string("--live_pool: ") + ws_engine_last_error());
+        const int A = static_cast<int>(slots.size());
+        if (tail ? ws_engine_tail_pool_push(tp, A, slots.data(), chunks.data(), ns.data()) != 0 ||
+                       ws_engine_tail_pool_tick(tp, A, slots.data(), ests.data(), caps.data(), n_out.data()) != 0
+                 : ws_engine_live_pool_push(lp, A, slots.data(), chunks.data(), ns.data(), ests.data(), caps.data(), n_out.data()) != 0) {
+          fail(std::string(flag) + ws_engine_last_error());
           ok = false;
           break;
         }
-        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, "live_pool_forwards");
-        pool_rounds += ws_engine_info(engine, "live_pool_rounds"), ++rounds;
+        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, forwards_key);
+        pool_rounds += tail ? ws_engine_info(engine, "tail_pool_rows") : ws_engine_info(engine, "live_pool_rounds"), ++rounds;
         for (size_t r = 0; r < who.size() && ok; ++r) {
           Lane& ln = lanes[who[r]];
           take(ln, n_out[r]);
@@ -470,9 +519,13 @@ int main(int argc, char** argv) {
         }
       }
       ws_engine_live_pool_close(lp);
+      ws_engine_tail_pool_close(tp);
       if (ok) {
         std::lock_guard<std::mutex> l(io_mu);
-        printf("live pool: %lld pushes, %lld rounds, %lld forwards, %lld launches\n", rounds, pool_rounds, forwards, launches);
+        if (tail)
+          printf("tail pool: %lld ticks, %lld rows, %lld forwards, %lld launches\n", rounds, pool_rounds, forwards, launches);
+        else
+          printf("live pool: %lld pushes, %lld rounds, %lld forwards, %lld launches\n", rounds, pool_rounds, forwards, launches);
         total_audio_ms += audio_ms;
         total_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pool_t0).count();
       }

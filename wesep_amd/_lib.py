@@ -332,6 +332,8 @@ _SIGS = {
     # live pool (longform.hip): the rows forms of the window gather and of the ring cross-fade
     "ws_window_slots_fwd": (_i, [_p, _p, _i, _p, _ll, _p, _ll, _p]),
     "ws_xfade_stream_rows_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p]),
+    # tail pool (longform.hip): the emission of one tick -- (host table, device table, A), C, ramp, then the arenas y, hold, out
+    "ws_tail_emit_rows_fwd": (_i, [_p, _p, _i, _i, _p, _p, _ll, _p, _ll, _p, _ll, _p]),
 }
 
 # the descriptors of the rows forms (include/wesep_hip.h: ws_resample_row, ws_rows_copy_row), field for field
@@ -343,6 +345,9 @@ ROWS_COPY_ROW = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("len", "<i4")
 WINDOW_SLOT_ROW = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("scale", "<f4")])
 XFADE_STREAM_ROW = np.dtype([("ring_off", "<i8"), ("scale_off", "<i8"), ("out_off", "<i8"), ("i0", "<i8"), ("count", "<i8"),
                              ("windows_run", "<i8"), ("W", "<i8"), ("n", "<i8"), ("final", "<i4"), ("_pad", "<i4")])
+# ws_tail_emit_row
+TAIL_EMIT_ROW = np.dtype([("y_off", "<i8"), ("hold_in_off", "<i8"), ("hold_out_off", "<i8"), ("out_off", "<i8"), ("L", "<i4"), ("p", "<i4"),
+                          ("h", "<i4"), ("m", "<i4"), ("c_new", "<i4"), ("scale", "<f4")])
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None

@@ -9,6 +9,8 @@
 // (runtime/live.cc).  Both cross-fades inline ONE body, lf_blend, so their arithmetic cannot differ.
 // ws_window_slots_fwd and ws_xfade_stream_rows_fwd are the table-driven forms of the gather and of the ring cross-fade for the
 // live pool (runtime/live_pool.cc): row i names its own source, destination, ring and layout; same bodies, same bits.
+// ws_tail_emit_rows_fwd is the emission of the tail pool (runtime/tail_pool.cc), a rule of its own: the newest part of a trailing
+// window, its first samples cross-faded with what the window before held back.
 // The kernels compute the starts themselves; no table of them exists.  Two HBM-bound passes: ws_window_rows gathers the
 // rows (once per target speaker), ws_xfade_ola blends the estimates with linear ramps over the O overlapping samples,
 // normalised by the sum of the weights that cover a sample.  Offsets are 64-bit (n up to 2^31 - 1); sums run in ascending
@@ -195,6 +197,64 @@ __global__ __launch_bounds__(256) void xfade_stream_rows_kernel(const ws_xfade_s
                                       o1, last, S, cap);
 }
 
+// ---- tail pool (runtime/tail_pool.cc): row i is one target of one slot at a tick.  Of the window's estimate y [L] it emits the m
+// samples from local index p on -- the first h of them cross-faded with what the last window held back for the same positions --
+// and holds the last c_new back in turn.  With v = fl(y * scale) (scale == 1: y itself):
+//   out[j]  = j < h ? fma(ramp[j], fl(v - hold_in[j]), hold_in[j]) : v,   j < m
+//   hold_out[q] = fl(y[p + m + q] * scale),                               q < c_new
+// the roundings spelled out as in lf_blend, contraction off.  A thread owns four consecutive floats of ONE destination, counted
+// from the 16-byte boundary at or below the destination's first float (sh = the floats between the two), so every whole quad is
+// stored as 16 bytes wherever the destination starts; y and hold_in are read with scalar loads (no alignment is assumed).  The
+// out quads come first, then the hold quads; tail_quads is the count the host sizes the grid with.
+__host__ __device__ inline int tail_shift(const float* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3); }
+__host__ __device__ inline int tail_quads(int n, int sh) { return n > 0 ? (n + sh + 3) >> 2 : 0; }
+
+__global__ __launch_bounds__(256) void tail_emit_rows_kernel(const ws_tail_emit_row* __restrict__ rows, const float* __restrict__ ramp,
+                                                             const float* __restrict__ y, const float* __restrict__ hold_in,
+                                                             float* __restrict__ hold_out, float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const ws_tail_emit_row r = rows[blockIdx.y];
+  float* const d_out = out + r.out_off;
+  float* const d_hold = hold_out + r.hold_out_off;
+  const int sh_o = tail_shift(d_out), sh_h = tail_shift(d_hold);
+  const int nq_o = tail_quads(r.m, sh_o), nq_h = tail_quads(r.c_new, sh_h);
+  const long long q0 = (long long)blockIdx.x * 256;
+  if (q0 >= nq_o + nq_h) return;
+  int quad = (int)q0 + (int)threadIdx.x;
+  if (quad >= nq_o + nq_h) return;
+  const bool held = quad >= nq_o;            // this quad belongs to the new hold
+  if (held) quad -= nq_o;
+  const int n = held ? r.c_new : r.m, j0 = quad * 4 - (held ? sh_h : sh_o);
+  const float* src = y + r.y_off + r.p + (held ? r.m : 0);
+  const float* hin = hold_in + r.hold_in_off;
+  float* dst = held ? d_hold : d_out;
+  const int h = held ? 0 : r.h;
+  float v[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int j = j0 + q;
+    float t = 0.f;
+    if (j >= 0 && j < n) {
+      t = src[j];
+      if (r.scale != 1.f) t = t * r.scale;
+      if (j < h) {
+        const float hd = hin[j];
+        const float d = t - hd;
+        t = __builtin_fmaf(ramp[j], d, hd);
+      }
+    }
+    v[q] = t;
+  }
+  if (j0 >= 0 && j0 + 4 <= n) {              // a whole quad: 16-byte aligned by the choice of j0
+    const f32x4 t = {v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(dst + j0) = t;
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (j0 + q >= 0 && j0 + q < n) dst[j0 + q] = v[q];
+  }
+}
+
 // Address ranges of one rows call: a written range may meet no other range of the call, read or written (another workgroup
 // of the launch owns it).  Ranges that are only read may share.
 struct LfSpan {
@@ -307,6 +367,54 @@ extern "C" int ws_xfade_stream_rows_fwd(const ws_xfade_stream_row* rows, const w
   if (nb_max == 0) return WS_OK;                             // every row has count == 0
   hipLaunchKernelGGL(xfade_stream_rows_kernel, dim3((unsigned)nb_max, (unsigned)A), dim3(256), 0, (hipStream_t)stream, d_rows, S, O, cap,
                      ring, scale_ring, out);
+  return ws_check_launch(who);
+}
+
+extern "C" int ws_tail_emit_rows_fwd(const ws_tail_emit_row* rows, const ws_tail_emit_row* d_rows, int A, int C, const float* ramp,
+                                     const float* y, long long n_y, float* hold, long long n_hold, float* out, long long n_out,
+                                     void* stream) {
+  const char* who = "ws_tail_emit_rows_fwd";
+  WS_REQUIRE(rows && d_rows && y && hold && out, "%s: rows, d_rows, y, hold or out is NULL", who);
+  WS_REQUIRE(A > 0 && A <= 65535, "%s: A=%d is outside [1, 65535]", who, A);
+  WS_REQUIRE(C >= 0, "%s: fade C=%d is negative", who, C);
+  WS_REQUIRE(ramp || C == 0, "%s: ramp is NULL with fade C=%d (it may be NULL when C == 0 only)", who, C);
+  WS_REQUIRE(n_y >= 0 && n_hold >= 0 && n_out >= 0, "%s: an arena length is negative (y %lld, hold %lld, out %lld)", who, n_y, n_hold,
+             n_out);
+  std::vector<LfSpan> spans;
+  spans.reserve((size_t)A * 4);
+  long long nb_max = 0;
+  for (int i = 0; i < A; ++i) {
+    const ws_tail_emit_row& r = rows[i];
+    WS_REQUIRE(r.h == 0 || r.h == C, "%s: row %d: h=%d held samples, the fade takes 0 or C=%d", who, i, r.h, C);
+    WS_REQUIRE(r.c_new == 0 || r.c_new == C, "%s: row %d: c_new=%d samples for the new hold, 0 or C=%d", who, i, r.c_new, C);
+    WS_REQUIRE(r.m >= 0 && r.h <= r.m, "%s: row %d: h=%d held samples do not fit the m=%d emitted ones", who, i, r.h, r.m);
+    WS_REQUIRE(r.p >= 0, "%s: row %d: p=%d is negative", who, i, r.p);
+    WS_REQUIRE((long long)r.m + r.c_new >= 1, "%s: row %d: nothing to do (m=%d, c_new=%d)", who, i, r.m, r.c_new);
+    WS_REQUIRE((long long)r.p + r.m + r.c_new == r.L, "%s: row %d: p + m + c_new = %d + %d + %d is not the window's L=%d", who, i, r.p,
+               r.m, r.c_new, r.L);
+    WS_REQUIRE((long long)r.L + 4096 < (1LL << 31), "%s: row %d: L=%d is not below 2^31 - 4096", who, i, r.L);
+    WS_REQUIRE(r.y_off >= 0 && r.y_off <= n_y - r.L, "%s: row %d: y [%lld, %lld + %d) leaves the arena of %lld floats", who, i, r.y_off,
+               r.y_off, r.L, n_y);
+    WS_REQUIRE(r.h == 0 || (r.hold_in_off >= 0 && r.hold_in_off <= n_hold - r.h),
+               "%s: row %d: hold_in [%lld, %lld + %d) leaves the arena of %lld floats", who, i, r.hold_in_off, r.hold_in_off, r.h, n_hold);
+    WS_REQUIRE(r.c_new == 0 || (r.hold_out_off >= 0 && r.hold_out_off <= n_hold - r.c_new),
+               "%s: row %d: hold_out [%lld, %lld + %d) leaves the arena of %lld floats", who, i, r.hold_out_off, r.hold_out_off, r.c_new,
+               n_hold);
+    WS_REQUIRE(r.m == 0 || (r.out_off >= 0 && r.out_off <= n_out - r.m), "%s: row %d: out [%lld, %lld + %d) leaves the arena of %lld floats",
+               who, i, r.out_off, r.out_off, r.m, n_out);
+    spans.push_back(lf_span(y, r.y_off, r.L, i, false, "y"));
+    if (r.h > 0) spans.push_back(lf_span(hold, r.hold_in_off, r.h, i, false, "hold_in"));
+    if (r.c_new > 0) spans.push_back(lf_span(hold, r.hold_out_off, r.c_new, i, true, "hold_out"));
+    if (r.m > 0) spans.push_back(lf_span(out, r.out_off, r.m, i, true, "out"));
+    // the quads of the row, counted as the kernel counts them (an empty destination is never addressed)
+    const long long nq = (long long)tail_quads(r.m, r.m > 0 ? tail_shift(out + r.out_off) : 0) +
+                         tail_quads(r.c_new, r.c_new > 0 ? tail_shift(hold + r.hold_out_off) : 0);
+    nb_max = std::max(nb_max, (nq + 255) / 256);
+  }
+  const int rc = lf_spans_disjoint(who, spans);
+  if (rc != WS_OK) return rc;
+  hipLaunchKernelGGL(tail_emit_rows_kernel, dim3((unsigned)nb_max, (unsigned)A), dim3(256), 0, (hipStream_t)stream, d_rows, ramp, y, hold,
+                     hold, out);
   return ws_check_launch(who);
 }
 

@@ -2392,3 +2392,29 @@ def xfade_stream_rows_fwd(rows, S: int, O: int, cap: int, ring, out, scale_ring=
     _call(who, C.c_void_p(tab.ctypes.data), C.c_void_p(d_tab.data_ptr()), len(tab), int(S), int(O), int(cap), _p(ring), n_ring,
           _p(scale_ring), n_scale, _p(out), n_out)
     return d_tab
+
+
+def tail_emit_rows_table(rows) -> np.ndarray:
+    """ws_tail_emit_row [A] from dicts with the fields y_off, hold_in_off, hold_out_off, out_off, L, p, h, m, c_new, scale (left
+    out: 1)."""
+    return _rows_table([dict({"scale": 1.0}, **r) for r in rows] if not isinstance(rows, np.ndarray) else rows, L.TAIL_EMIT_ROW,
+                       "ws_tail_emit_rows_fwd")
+
+
+def tail_emit_rows(rows, C_: int, ramp, y, hold, out):
+    """ws_tail_emit_rows_fwd: row i emits m samples of its window's estimate y[y_off : y_off + L] from local index p on to
+    out[out_off :] -- the first h cross-faded with hold[hold_in_off :] by ramp [C_] -- and writes the last c_new samples to
+    hold[hold_out_off :], all times `scale`; y, hold and out are arenas (1-D float32 on one device), ramp may be None when C_ == 0.
+    Returns the device table (alive until the launch has run)."""
+    who = "ws_tail_emit_rows_fwd"
+    tab = tail_emit_rows_table(rows)
+    n_y, n_hold, n_out = _arena(y, who, "y"), _arena(hold, who, "hold"), _arena(out, who, "out")
+    if y is None or hold is None or out is None:
+        raise L.WesepHipError(f"{who}: y, hold and out must be given")
+    if ramp is not None:
+        _chk(ramp, f"{who}: ramp")
+        _chk_room(ramp, int(C_), who, "ramp")
+    d_tab = L.upload_struct_array(tab, y.device)
+    _call(who, C.c_void_p(tab.ctypes.data), C.c_void_p(d_tab.data_ptr()), len(tab), int(C_), _p(ramp), _p(y), n_y, _p(hold), n_hold,
+          _p(out), n_out)
+    return d_tab
