@@ -244,6 +244,36 @@ int ws_gn_bwd_apply_pg(const float* x, const float* dxn, const float* stats, con
                        const float* gamma, const float* res, const ws_groups_geom* geo, float* dx,
                        float* pslab, float* pout, unsigned* counter, void* stream);
 
+/* ---- speaker-fusion affine FOLDED into its consumers ------------------------------------------------------------------
+ * The operand z' = z * (a0 + a[r]) + b[r] of ws_affine_fwd, formed in registers by the kernel that reads it instead of being
+ * written by one launch and read back by five: r = position / rows_per_r selects the row of a / b ([R][128], device); position =
+ * the row of the plain Z layout (element offset / 128).  a NULL means 0, b NULL means 0; both NULL switches the fold off (the
+ * *_film entry points then ARE the plain ones).  One fused multiply-add per element (ws_film, csrc/common.h), the same one
+ * ws_affine_fwd executes: a folded consumer sees the bits a materialised z' would hold.
+ * New symbols only (WS_ABI_VERSION unchanged): no existing struct or signature moves.                                       */
+typedef struct ws_film_desc {
+  const float* a;
+  const float* b;
+  float a0;
+  int rows_per_r;
+} ws_film_desc;
+/* ws_group_stats / ws_gn_bwd_reduce with x = film(z).  Vectorised geometries with single-band groups of 128-float rows whose
+ * bases and strides are multiples of 128 floats (a row of a group = one position).                                          */
+int ws_group_stats_film(const float* z, const ws_film_desc* film, const ws_groups_geom* geo, float eps, float* stats, void* stream);
+int ws_gn_bwd_reduce_film(const float* z, const ws_film_desc* film, const float* dxn, const float* stats, const float* gamma,
+                          const ws_groups_geom* geo, float* ab, void* stream);
+/* ws_gn_bwd_apply_pg with xhat from film(z) and the affine's own backward on the way out: with r = the value
+ * ws_gn_bwd_apply_pg writes (= d z'),  dx = r * (a0 + a[row]),  da[row][c] = sum r * z,  db[row][c] = sum r  over the positions
+ * of the row.  Groups of contiguous rows that tile the positions (gdiv = 1, gs1 = L * 128, rs = 128, rows_per_r % L == 0: the
+ * time view); every group leaves its partial [2][128] in fslab [ngroups][2][128] and the last workgroup of each ROW adds that
+ * row's rows_per_r / L partials up in group order into da[row] / db[row] (deterministic).  fcounter: ngroups * L / rows_per_r
+ * device words, zero at launch, left at zero.  da / db: NULL where a / b is NULL (multiply / additive fusion).  dgamma / dbeta
+ * (pslab, pout, counter) exactly as ws_gn_bwd_apply_pg.                                                                     */
+int ws_gn_bwd_apply_pg_film(const float* z, const ws_film_desc* film, const float* dxn, const float* stats, const float* ab,
+                            const float* gamma, const float* res, const ws_groups_geom* geo, float* dx, float* pslab,
+                            float* pout, unsigned* counter, float* fslab, float* da, float* db, unsigned* fcounter,
+                            void* stream);
+
 /* ---- bidirectional LSTM recurrence (nn.LSTM inside ResRNN, bsrnn.py:27-33,40) -----------
  * Sequence s, step t lives at row  p = (s / sq_div) * sq_s1 + (s % sq_div) * sq_s2 + t * step_rows.
  * gates [P][2][4H] holds x-projection + biases on entry (gate order i,f,g,o) and the
@@ -577,6 +607,12 @@ typedef struct ws_gemm_b2p_args {
                         here, so the copy costs no extra read (hcat -> ws_gemm_tnb a_fmt = 1) */
 } ws_gemm_b2p_args;
 int ws_gemm_b2p(const ws_gemm_b2p_args* a, void* stream);
+/* The two GEMMs with a folded speaker-fusion affine (ws_film_desc, above; rows of a / b by the POSITION of a slot, which may differ
+ * between the 32 slots of a block): ws_gemm_p2b_film passes A through film before the normalisation (A_bl / A_bl16 are those of
+ * z'; lda = 128); ws_gemm_b2p_film adds film(R) instead of R (a_fmt 0 and 4, the projections; R required, ldc = 128).  A film
+ * with both pointers NULL is the plain call.                                                                                */
+int ws_gemm_p2b_film(const ws_gemm_p2b_args* a, const ws_film_desc* film, void* stream);
+int ws_gemm_b2p_film(const ws_gemm_b2p_args* a, const ws_film_desc* film, void* stream);
 
 /* BL x BL -> weight gradients, one pass over G:
  *   slab[split][g][a] = sum_{b in split} sum_i G[(b,i)][g_off + g] * Acat[(b + shift,i)][a]

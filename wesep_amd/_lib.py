@@ -117,6 +117,11 @@ class GemmB2PArgs(C.Structure):
                                                                          ("a_fmt", _i), ("pad_", _i), ("amax", _p), ("a16_out", _p)]
 
 
+class FilmDesc(C.Structure):
+    """ws_film_desc: the speaker-fusion affine z * (a0 + a[r]) + b[r] folded into a consumer's operand load; r = position // rows_per_r"""
+    _fields_ = [("a", _p), ("b", _p), ("a0", _f), ("rows_per_r", _i)]
+
+
 class GemmTNBArgs(C.Structure):
     _fields_ = [(n, _p) for n in ("G", "A0", "A1", "slab", "bslab", "aslab")] + \
                [(n, _ll) for n in ("slab_stride", "bslab_stride", "aslab_stride")] + \
@@ -184,6 +189,10 @@ _SIGS = {
     "ws_gn_bwd_fused": (_i, [_p, _p, _p, _p, _p, C.POINTER(GroupsGeom), _i, _p, _p, _p, _p, _p]),
     "ws_gn_bwd_fused2": (_i, [_p, _p, _p, _p, _p, _p, C.POINTER(GroupsGeom), _i, _p, _p, _p, _p, _p]),
     "ws_gn_bwd_apply_pg": (_i, [_p, _p, _p, _p, _p, _p, C.POINTER(GroupsGeom), _p, _p, _p, _p, _p]),
+    "ws_group_stats_film": (_i, [_p, C.POINTER(FilmDesc), C.POINTER(GroupsGeom), _f, _p, _p]),
+    "ws_gn_bwd_reduce_film": (_i, [_p, C.POINTER(FilmDesc), _p, _p, _p, C.POINTER(GroupsGeom), _p, _p]),
+    "ws_gn_bwd_apply_pg_film": (_i, [_p, C.POINTER(FilmDesc), _p, _p, _p, _p, _p, C.POINTER(GroupsGeom), _p, _p, _p, _p,
+                                     _p, _p, _p, _p, _p]),
     "ws_lstm_pack": (_i, [_p, _p, _p, _p, _i, _p]),
     "ws_lstm_fwd": (_i, [C.POINTER(LstmArgs), _p]),
     "ws_lstm_bwd": (_i, [C.POINTER(LstmArgs), _p]),
@@ -202,6 +211,8 @@ _SIGS = {
     "ws_gemm_p2b": (_i, [C.POINTER(GemmP2BArgs), _p]),
     "ws_gemm_p2b_len": (_i, [C.POINTER(GemmP2BArgs), _p, _i, _p]),
     "ws_gemm_b2p": (_i, [C.POINTER(GemmB2PArgs), _p]),
+    "ws_gemm_p2b_film": (_i, [C.POINTER(GemmP2BArgs), C.POINTER(FilmDesc), _p]),
+    "ws_gemm_b2p_film": (_i, [C.POINTER(GemmB2PArgs), C.POINTER(FilmDesc), _p]),
     "ws_gemm_tnb": (_i, [C.POINTER(GemmTNBArgs), _p]),
     "ws_gemm_tnb_h16": (_i, [C.POINTER(GemmTNBArgs), _p]),
     "ws_stft_bandsplit": (_i, [_p, _i, _i, C.POINTER(Bands), _p, _p]),

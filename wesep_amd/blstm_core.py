@@ -541,7 +541,7 @@ def consume_once(ctx, who):
 # ---------------------------------------------------------------------------------------------
 # the steps, in launch order
 # ---------------------------------------------------------------------------------------------
-def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
+def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None, film=None):
     """out = res + Linear(BLSTM(x')) over the rows of the sequence map `seq`; x [rows, 128] plain, x' = x, or GroupNorm(x) with
     norm = dict(stats=, gamma=, beta=, stat_map=) (applied by ws_gemm_p2b on the way into BL).  W: the pack provider
     (WeightPacks).  Returns (out, saved): saved = (gates, cbuf, hcat, xn, hcat16) for ctx.save_for_backward -- xn is its
@@ -549,9 +549,16 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
     (hcat then holds h as two fp16 planes and the copy is its first half: one tensor for h).
     steps (ragged batches, inference): (int32 device table, div) -- sequence s has table[s // div] valid steps; the
     pre-activations behind them are exact zeros, so the reverse direction reaches a sequence's last valid step with zero
-    state (plan from make_plan(ragged=True); a branch that was not taught lengths refuses them)."""
+    state (plan from make_plan(ragged=True); a branch that was not taught lengths refuses them).
+    film (dev.Film; res is x): x and the residual are read through a folded speaker-fusion affine -- the relay / x-projection
+    normalises film(x), the projection adds film(res); nothing else reads x."""
     d = x.device
-    norm = norm or {}
+    norm = dict(norm or {})
+    if film is not None:
+        if res is not x or steps is not None:
+            raise L.WesepHipError("blstm_forward: film= folds ONE affine into operand and residual (res is x), no step counts")
+        norm["film"] = film
+    rk = dict(film=film) if film is not None else {}
     if steps is not None and (plan.fwd in ("fused", "cluster2") or plan.grad):
         raise L.WesepHipError(f"blstm_forward: per-sequence step counts with forward branch '{plan.fwd}', grad={plan.grad}: "
                               "only the branches over precomputed gates know them, and only the forward")
@@ -626,9 +633,9 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None):
         del pre
     out = torch.empty_like(res)
     if h2p:     # both planes against the fp16 hi / lo pack of 256 w: three fp16 MFMAs per product, no copy written
-        dev.gemm_b2p(A=hcat, K=2 * H, sm=seq, Wpack=W("proj16"), C_out=out, ldc=N, bias=bias, R=res, a_fmt=4)
+        dev.gemm_b2p(A=hcat, K=2 * H, sm=seq, Wpack=W("proj16"), C_out=out, ldc=N, bias=bias, R=res, a_fmt=4, **rk)
     else:
-        dev.gemm_b2p(A=hcat, K=2 * H, sm=seq, Wpack=W("proj"), C_out=out, ldc=N, bias=bias, R=res, a16_out=hcat16)
+        dev.gemm_b2p(A=hcat, K=2 * H, sm=seq, Wpack=W("proj"), C_out=out, ldc=N, bias=bias, R=res, a16_out=hcat16, **rk)
     if _h2_probe() and not h2:
         if _h2_probe() & 1:
             _probe_round(gates, "f16")

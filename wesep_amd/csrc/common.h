@@ -142,6 +142,18 @@ __device__ __forceinline__ void ws_tree_sum256(float* pslab, unsigned nblocks, f
 
 __device__ __forceinline__ float ws_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
+// Speaker-fusion affine z' = z * (a0 + a) + b as ONE fused multiply-add (ws_film, wesep_hip.h): ws_affine_fwd and every kernel
+// that folds the affine into its operand load go through here, so a folded consumer sees the bits of a materialised z'.
+__device__ __forceinline__ float ws_film(float z, float a, float b, float a0) { return __builtin_fmaf(z, a0 + a, b); }
+__device__ __forceinline__ f32x4 ws_film(const f32x4 z, const f32x4 a, const f32x4 b, float a0) {
+  return f32x4{ws_film(z[0], a[0], b[0], a0), ws_film(z[1], a[1], b[1], a0), ws_film(z[2], a[2], b[2], a0),
+               ws_film(z[3], a[3], b[3], a0)};
+}
+// the 16-byte pieces of row r of a / b at column c (a null pointer reads as zeros)
+__device__ __forceinline__ f32x4 ws_film_row(const float* p, long long r, int c) {
+  return p ? *reinterpret_cast<const f32x4*>(p + r * 128 + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 // row index -> element offset under the two-level row addressing used across the C ABI:
 //   off(m) = (m / div) * s1 + (m % div) * s2
 __device__ __forceinline__ long long ws_row_off(int m, int div, long long s1, long long s2) {

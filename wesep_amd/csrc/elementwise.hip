@@ -22,10 +22,10 @@ __global__ void affine_fwd_kernel(const float* z, const float* __restrict__ a,
     const int c = (int)(i - row * n4) * 4;
     const int r = (int)(row / rows_per_r);
     f32x4 v = *reinterpret_cast<const f32x4*>(z + i * 4);
-    f32x4 av = {a0, a0, a0, a0}, bv = {0.f, 0.f, 0.f, 0.f};
-    if (a) av += *reinterpret_cast<const f32x4*>(a + (long long)r * N + c);
+    f32x4 av = {0.f, 0.f, 0.f, 0.f}, bv = {0.f, 0.f, 0.f, 0.f};
+    if (a) av = *reinterpret_cast<const f32x4*>(a + (long long)r * N + c);
     if (b) bv = *reinterpret_cast<const f32x4*>(b + (long long)r * N + c);
-    *reinterpret_cast<f32x4*>(out + i * 4) = v * av + bv;
+    *reinterpret_cast<f32x4*>(out + i * 4) = ws_film(v, av, bv, a0);   // (the folded consumers: the same fma, common.h)
   }
 }
 

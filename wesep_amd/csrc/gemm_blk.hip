@@ -232,9 +232,11 @@ extern "C" int ws_pack_w(const float* W, int N, int K, long long ldw, int trans,
 // padded slots -- operand and output exactly zero, no bias -- so a recurrence that enters them with zero state leaves
 // them with zero state (the reverse direction of a ragged time view starts at its sequence's last valid step)
 #define P2B_K 128
-template <bool LEN>
+// FILM (ws_gemm_p2b_film): the A operand passes through the speaker-fusion affine (ws_film) before the normalisation -- row of
+// a / b by the lane's own position, so the relayed A_bl / A_bl16 are those of z' = film(z) and z' itself is never stored.
+template <bool LEN, bool FILM = false>
 __global__ __launch_bounds__(512, 4) void gemm_p2b_kernel(const ws_gemm_p2b_args p, const int* __restrict__ steps,
-                                                          int steps_div) {
+                                                          int steps_div, const ws_film_desc fm) {
   __shared__ __attribute__((aligned(16))) u32x4 wl[2][2048];  // 2 stages x 32 KB
   if (p.run_if && *p.run_if == 0u) return;  // predicated fall-back launch (wesep_hip.h): uniform
   const int tid = threadIdx.x, lane = tid & 63, i = lane & 31, half = lane >> 5;
@@ -261,6 +263,7 @@ __global__ __launch_bounds__(512, 4) void gemm_p2b_kernel(const ws_gemm_p2b_args
       mean = p.stats[2 * s];
       rstd = p.stats[2 * s + 1];
     }
+    const long long frow = FILM ? pos / fm.rows_per_r : 0;
     float* eb = p.A_bl ? p.A_bl + (long long)bb * (32 * P2B_K) + i * 4 : nullptr;
     unsigned short* eb16 = p.A_bl16 ? reinterpret_cast<unsigned short*>(p.A_bl16) + (long long)bb * (32 * P2B_K) + i * 4 : nullptr;
 #pragma unroll
@@ -268,6 +271,10 @@ __global__ __launch_bounds__(512, 4) void gemm_p2b_kernel(const ws_gemm_p2b_args
       const int k0 = 16 * ks + 8 * half;
       f32x4 v0 = *reinterpret_cast<const f32x4*>(arow + k0);
       f32x4 v1 = *reinterpret_cast<const f32x4*>(arow + k0 + 4);
+      if constexpr (FILM) {
+        v0 = ws_film(v0, ws_film_row(fm.a, frow, k0), ws_film_row(fm.b, frow, k0), fm.a0);
+        v1 = ws_film(v1, ws_film_row(fm.a, frow, k0 + 4), ws_film_row(fm.b, frow, k0 + 4), fm.a0);
+      }
       if (p.stats) {
         const f32x4 g0 = *reinterpret_cast<const f32x4*>(p.gamma + k0), g1 = *reinterpret_cast<const f32x4*>(p.gamma + k0 + 4);
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.beta + k0), b1 = *reinterpret_cast<const f32x4*>(p.beta + k0 + 4);
@@ -356,7 +363,8 @@ __global__ __launch_bounds__(512, 4) void gemm_p2b_kernel(const ws_gemm_p2b_args
   }
 }
 
-static int gemm_p2b_launch(const char* who, const ws_gemm_p2b_args* a, const int* steps, int steps_div, void* stream) {
+static int gemm_p2b_launch(const char* who, const ws_gemm_p2b_args* a, const int* steps, int steps_div, void* stream,
+                           const ws_film_desc* film = nullptr) {
   WS_REQUIRE(a && a->A && ((a->Wpack && a->C) || (a->N == 0 && (a->A_bl || a->A_bl16))), "%s: null pointer", who);
   WS_REQUIRE(a->K == P2B_K, "%s: K must be %d (got %d)", who, P2B_K, a->K);
   WS_REQUIRE(a->N >= 0 && a->N % 64 == 0, "%s: N %% 64 (N=%d)", who, a->N);
@@ -367,16 +375,25 @@ static int gemm_p2b_launch(const char* who, const ws_gemm_p2b_args* a, const int
   hipStream_t s = (hipStream_t)stream;
   const bool timed = a->run_if == nullptr;  // a predicated fall-back launch is normally empty: not a sample of this kind
   if (timed) ws_prof_begin(WS_PROF_GEMM_NT, s);
-  if (steps)
-    hipLaunchKernelGGL((gemm_p2b_kernel<true>), dim3((nblk + 7) / 8), dim3(512), 0, s, *a, steps, steps_div);
+  const ws_film_desc off = {nullptr, nullptr, 0.f, 1};
+  if (film)
+    hipLaunchKernelGGL((gemm_p2b_kernel<false, true>), dim3((nblk + 7) / 8), dim3(512), 0, s, *a, steps, steps_div, *film);
+  else if (steps)
+    hipLaunchKernelGGL((gemm_p2b_kernel<true>), dim3((nblk + 7) / 8), dim3(512), 0, s, *a, steps, steps_div, off);
   else
-    hipLaunchKernelGGL((gemm_p2b_kernel<false>), dim3((nblk + 7) / 8), dim3(512), 0, s, *a, steps, steps_div);
+    hipLaunchKernelGGL((gemm_p2b_kernel<false>), dim3((nblk + 7) / 8), dim3(512), 0, s, *a, steps, steps_div, off);
   if (timed) ws_prof_end(WS_PROF_GEMM_NT, s);
   return ws_check_launch(who);
 }
 
 extern "C" int ws_gemm_p2b(const ws_gemm_p2b_args* a, void* stream) {
   return gemm_p2b_launch("ws_gemm_p2b", a, nullptr, 1, stream);
+}
+
+extern "C" int ws_gemm_p2b_film(const ws_gemm_p2b_args* a, const ws_film_desc* film, void* stream) {
+  if (!film || (!film->a && !film->b)) return ws_gemm_p2b(a, stream);
+  WS_REQUIRE(film->rows_per_r > 0 && a && a->lda == P2B_K, "ws_gemm_p2b_film: rows_per_r > 0, lda = %d (a row = a position)", P2B_K);
+  return gemm_p2b_launch("ws_gemm_p2b_film", a, nullptr, 1, stream, film);
 }
 
 extern "C" int ws_gemm_p2b_len(const ws_gemm_p2b_args* a, const int* steps, int steps_div, void* stream) {
@@ -409,10 +426,13 @@ extern "C" int ws_gemm_p2b_len(const ws_gemm_p2b_args* a, const int* steps, int 
 //  128 registers; a_fmt 2 fits as it was (0.69 -> 0.58 ms per launch alone, 4.5 ms per training step: profiles/r06_c28_*), the
 //  other formats once the weight stages go to LDS without a register stop and a_fmt 0's activations are requested half a stage
 //  ahead -- no spills in any of the four; nor in a_fmt 4: 118 registers.)
-template <int A16>
-__global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args p) {
+// FILM (ws_gemm_b2p_film; a_fmt 0 and 4): the residual is film(R) (ws_film) -- the row of a / b of every slot's position is
+// looked up once, next to the position (the 32 slots of a block may lie in different rows: nseq no multiple of 32, padding).
+template <int A16, bool FILM = false>
+__global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args p, const ws_film_desc fm) {
   __shared__ __attribute__((aligned(16))) u32x4 wl[2][2048];
   __shared__ long long posl[8][32];
+  __shared__ int frowl[FILM ? 8 : 1][32];
   const int tid = threadIdx.x, lane = tid & 63, i = lane & 31, half = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nblk = ((p.sm.nseq + 31) / 32) * p.sm.L;
@@ -423,6 +443,9 @@ __global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args
     bool valid;
     const long long pos = seq_pos(p.sm, bb, i, valid);
     if (half == 0) posl[w][i] = valid ? pos : -1;
+    if constexpr (FILM) {
+      if (half == 0) frowl[w][i] = (int)(pos / fm.rows_per_r);
+    }
   }
   const int K = p.K, nstage = K / 64;
   // A-operand source: cell (quad, slot) of block bb; lane reads quads 4ks + 2half, +1 (cell = 16 B, A16: 8 B; `ab` in
@@ -605,7 +628,14 @@ __global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args
       off[k] = (active && pos >= 0) ? pos * p.ldc + pass * 64 + 4 * c4 : -1;
       v[k] = *reinterpret_cast<const f32x4*>(stg + m * 64 + 4 * c4);
     }
-    if (p.R) {
+    if constexpr (FILM) {   // (R is required)
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (off[k] >= 0) {
+          const int fr = frowl[w][r0 + 4 * k], c = pass * 64 + 4 * c4;
+          v[k] += ws_film(*reinterpret_cast<const f32x4*>(p.R + off[k]), ws_film_row(fm.a, fr, c), ws_film_row(fm.b, fr, c), fm.a0);
+        }
+    } else if (p.R) {
 #pragma unroll
       for (int k = 0; k < 8; ++k)
         if (off[k] >= 0) v[k] += *reinterpret_cast<const f32x4*>(p.R + off[k]);
@@ -617,30 +647,46 @@ __global__ __launch_bounds__(512, 4) void gemm_b2p_kernel(const ws_gemm_b2p_args
   }
 }
 
-extern "C" int ws_gemm_b2p(const ws_gemm_b2p_args* a, void* stream) {
-  WS_REQUIRE(a && a->A && a->Wpack && a->C, "ws_gemm_b2p: null pointer");
-  WS_REQUIRE(a->N == 128, "ws_gemm_b2p: N must be 128 (got %d)", a->N);
-  WS_REQUIRE(a->a_fmt >= 0 && a->a_fmt <= 4 && (a->a_fmt < 2 || a->a_fmt == 4 || a->amax), "ws_gemm_b2p: a_fmt %d (2 / 3 need amax)",
+static int gemm_b2p_launch(const char* who, const ws_gemm_b2p_args* a, const ws_film_desc* film, void* stream);
+
+extern "C" int ws_gemm_b2p(const ws_gemm_b2p_args* a, void* stream) { return gemm_b2p_launch("ws_gemm_b2p", a, nullptr, stream); }
+
+extern "C" int ws_gemm_b2p_film(const ws_gemm_b2p_args* a, const ws_film_desc* film, void* stream) {
+  if (!film || (!film->a && !film->b)) return ws_gemm_b2p(a, stream);
+  WS_REQUIRE(a && (a->a_fmt == 0 || a->a_fmt == 4) && a->R && a->ldc == 128 && film->rows_per_r > 0,
+             "ws_gemm_b2p_film: the projections (a_fmt 0 / 4) with a residual, ldc = 128 (a row = a position), rows_per_r > 0");
+  return gemm_b2p_launch("ws_gemm_b2p_film", a, film, stream);
+}
+
+static int gemm_b2p_launch(const char* who, const ws_gemm_b2p_args* a, const ws_film_desc* film, void* stream) {
+  WS_REQUIRE(a && a->A && a->Wpack && a->C, "%s: null pointer", who);
+  WS_REQUIRE(a->N == 128, "%s: N must be 128 (got %d)", who, a->N);
+  WS_REQUIRE(a->a_fmt >= 0 && a->a_fmt <= 4 && (a->a_fmt < 2 || a->a_fmt == 4 || a->amax), "%s: a_fmt %d (2 / 3 need amax)", who,
              a->a_fmt);
-  WS_REQUIRE(a->a_fmt == 0 || !a->a16_out, "ws_gemm_b2p: a16_out goes with a_fmt 0 (got a_fmt %d)", a->a_fmt);
-  WS_REQUIRE(a->K > 0 && a->K % 64 == 0, "ws_gemm_b2p: K %% 64 (K=%d)", a->K);
-  WS_REQUIRE(a->ldc >= a->N && a->ldc % 4 == 0, "ws_gemm_b2p: ldc >= N and ldc %% 4 == 0 (16-byte row pieces)");
-  WS_REQUIRE(a->sm.nseq > 0 && a->sm.L > 0 && a->sm.sq_div > 0, "ws_gemm_b2p: bad sequence map");
+  WS_REQUIRE(a->a_fmt == 0 || !a->a16_out, "%s: a16_out goes with a_fmt 0 (got a_fmt %d)", who, a->a_fmt);
+  WS_REQUIRE(a->K > 0 && a->K % 64 == 0, "%s: K %% 64 (K=%d)", who, a->K);
+  WS_REQUIRE(a->ldc >= a->N && a->ldc % 4 == 0, "%s: ldc >= N and ldc %% 4 == 0 (16-byte row pieces)", who);
+  WS_REQUIRE(a->sm.nseq > 0 && a->sm.L > 0 && a->sm.sq_div > 0, "%s: bad sequence map", who);
   const int nblk = ((a->sm.nseq + 31) / 32) * a->sm.L;
   hipStream_t s = (hipStream_t)stream;
+  const ws_film_desc off = {nullptr, nullptr, 0.f, 1};
   ws_prof_begin(WS_PROF_GEMM_NT, s);
-  if (a->a_fmt == 4)
-    hipLaunchKernelGGL(gemm_b2p_kernel<4>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a);
+  if (film && a->a_fmt == 4)
+    hipLaunchKernelGGL((gemm_b2p_kernel<4, true>), dim3((nblk + 7) / 8), dim3(512), 0, s, *a, *film);
+  else if (film)
+    hipLaunchKernelGGL((gemm_b2p_kernel<0, true>), dim3((nblk + 7) / 8), dim3(512), 0, s, *a, *film);
+  else if (a->a_fmt == 4)
+    hipLaunchKernelGGL(gemm_b2p_kernel<4>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a, off);
   else if (a->a_fmt == 3)
-    hipLaunchKernelGGL(gemm_b2p_kernel<3>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a);
+    hipLaunchKernelGGL(gemm_b2p_kernel<3>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a, off);
   else if (a->a_fmt == 2)
-    hipLaunchKernelGGL(gemm_b2p_kernel<2>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a);
+    hipLaunchKernelGGL(gemm_b2p_kernel<2>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a, off);
   else if (a->a_fmt == 1)
-    hipLaunchKernelGGL(gemm_b2p_kernel<1>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a);
+    hipLaunchKernelGGL(gemm_b2p_kernel<1>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a, off);
   else
-    hipLaunchKernelGGL(gemm_b2p_kernel<0>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a);
+    hipLaunchKernelGGL(gemm_b2p_kernel<0>, dim3((nblk + 7) / 8), dim3(512), 0, s, *a, off);
   ws_prof_end(WS_PROF_GEMM_NT, s);
-  return ws_check_launch("ws_gemm_b2p");
+  return ws_check_launch(who);
 }
 
 // ---------------------------------------------------------------------------------------------

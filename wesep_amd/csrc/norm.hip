@@ -27,11 +27,39 @@ static bool geom_vec4(const ws_groups_geom* g) {
   return !g->band_w && !g->band_off && g->W % 4 == 0 && g->rs % 4 == 0 && g->gs1 % 4 == 0 && g->gs2 % 4 == 0;
 }
 
-template <bool V4>
+// Folded speaker-fusion affine (ws_film_desc, wesep_hip.h) of the *_film kernels below: x = film(z) along the rows of one group.
+// Groups of 128-float rows at bases and strides that are multiples of 128, so a thread keeps ONE column quad c4 and a row is a
+// position; the row of a / b is that of the group's first position -- looked up per row only where a group straddles two rows of
+// the embedding (no caller's geometry does: a uniform branch).
+struct FilmQuad {
+  f32x4 a, b;
+  long long p0;   // first position of the group
+  bool uni;
+  __device__ __forceinline__ FilmQuad(const ws_film_desc& fm, const ws_groups_geom& geo, long long base, int c4) {
+    p0 = base >> 7;
+    const long long r = p0 / fm.rows_per_r;
+    uni = r == (p0 + (long long)(geo.L - 1) * (geo.rs >> 7)) / fm.rows_per_r;
+    a = ws_film_row(fm.a, r, 4 * c4);
+    b = ws_film_row(fm.b, r, 4 * c4);
+  }
+  __device__ __forceinline__ f32x4 operator()(const ws_film_desc& fm, const ws_groups_geom& geo, const f32x4 z, int row, int c4) {
+    if (!uni) {
+      const long long r = (p0 + (long long)row * (geo.rs >> 7)) / fm.rows_per_r;
+      a = ws_film_row(fm.a, r, 4 * c4);
+      b = ws_film_row(fm.b, r, 4 * c4);
+    }
+    return ws_film(z, a, b, fm.a0);
+  }
+};
+
+static int film_check(const ws_film_desc* fm, const ws_groups_geom* g, const char* who);
+
+// FILM (ws_group_stats_film): both passes read film(z); V4 geometries of 128-float rows only (film_check).
+template <bool V4, bool FILM = false>
 __global__ __launch_bounds__(256) void group_stats_kernel(const float* __restrict__ x,
                                                           const ws_groups_geom geo, float eps,
                                                           float* __restrict__ stats,
-                                                          const int* __restrict__ glen, int glen_div) {
+                                                          const int* __restrict__ glen, int glen_div, const ws_film_desc fm) {
   __shared__ float red[16];
   const int g = blockIdx.x;
   const GroupView v = group_view(geo, g);
@@ -39,6 +67,27 @@ __global__ __launch_bounds__(256) void group_stats_kernel(const float* __restric
   const int n = (glen ? min(max(glen[g / glen_div], 1), geo.L) : geo.L) * v.W;
   const float* xb = x + v.base;
   float s = 0.f;
+  if constexpr (FILM) {
+    FilmQuad fq(fm, geo, v.base, threadIdx.x & 31);
+    for (int i = threadIdx.x; i < (n >> 2); i += 256) {
+      const int row = i >> 5, c4 = i & 31;
+      const f32x4 t = fq(fm, geo, *reinterpret_cast<const f32x4*>(xb + (long long)row * geo.rs + 4 * c4), row, c4);
+      s += (t[0] + t[1]) + (t[2] + t[3]);
+    }
+    const float mean = ws_block_sum(s, red) / (float)n;
+    float q = 0.f;
+    for (int i = threadIdx.x; i < (n >> 2); i += 256) {
+      const int row = i >> 5, c4 = i & 31;
+      const f32x4 t = fq(fm, geo, *reinterpret_cast<const f32x4*>(xb + (long long)row * geo.rs + 4 * c4), row, c4) - mean;
+      q += (t[0] * t[0] + t[1] * t[1]) + (t[2] * t[2] + t[3] * t[3]);
+    }
+    const float var = ws_block_sum(q, red) / (float)n;
+    if (threadIdx.x == 0) {
+      stats[2 * (long long)g] = mean;
+      stats[2 * (long long)g + 1] = 1.f / sqrtf(var + eps);
+    }
+    return;
+  }
   if (V4) {
     const int w4 = v.W >> 2;
     for (int i = threadIdx.x; i < (n >> 2); i += 256) {
@@ -80,18 +129,41 @@ static int geom_check(const ws_groups_geom* geo, const char* who) {
   return WS_OK;
 }
 
+// the folded affine's geometry (FilmQuad): vectorised single-band groups of 128-float rows on 128-float boundaries
+static int film_check(const ws_film_desc* fm, const ws_groups_geom* g, const char* who) {
+  WS_REQUIRE(fm && fm->rows_per_r > 0, "%s: film descriptor / rows_per_r", who);
+  WS_REQUIRE(geom_vec4(g) && g->nbands == 1 && g->W == 128 && g->rs > 0 && g->rs % 128 == 0 && g->gs1 % 128 == 0 &&
+                 g->gs2 % 128 == 0,
+             "%s: the folded affine takes single-band groups of 128-float rows, strides %% 128 == 0", who);
+  return WS_OK;
+}
+static bool film_on(const ws_film_desc* fm) { return fm && (fm->a || fm->b); }
+
 static int group_stats_launch(const char* who, const float* x, const ws_groups_geom* geo, const int* glen, int glen_div,
                               float eps, float* stats, void* stream) {
   int rc = geom_check(geo, who);
   if (rc != WS_OK) return rc;
   WS_REQUIRE(x && stats, "%s: null pointer", who);
+  const ws_film_desc off = {nullptr, nullptr, 0.f, 1};
   if (geom_vec4(geo))
     hipLaunchKernelGGL((group_stats_kernel<true>), dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream, x,
-                       *geo, eps, stats, glen, glen_div);
+                       *geo, eps, stats, glen, glen_div, off);
   else
     hipLaunchKernelGGL((group_stats_kernel<false>), dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream, x,
-                       *geo, eps, stats, glen, glen_div);
+                       *geo, eps, stats, glen, glen_div, off);
   return ws_check_launch(who);
+}
+
+extern "C" int ws_group_stats_film(const float* z, const ws_film_desc* film, const ws_groups_geom* geo, float eps, float* stats,
+                                   void* stream) {
+  if (!film_on(film)) return ws_group_stats(z, geo, eps, stats, stream);
+  int rc = geom_check(geo, "ws_group_stats_film");
+  if (rc != WS_OK) return rc;
+  if ((rc = film_check(film, geo, "ws_group_stats_film")) != WS_OK) return rc;
+  WS_REQUIRE(z && stats, "ws_group_stats_film: null pointer");
+  hipLaunchKernelGGL((group_stats_kernel<true, true>), dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream, z, *geo, eps,
+                     stats, nullptr, 1, *film);
+  return ws_check_launch("ws_group_stats_film");
 }
 
 extern "C" int ws_group_stats(const float* x, const ws_groups_geom* geo, float eps, float* stats,
@@ -105,11 +177,12 @@ extern "C" int ws_group_stats_len(const float* x, const ws_groups_geom* geo, con
   return group_stats_launch("ws_group_stats_len", x, geo, glen, glen_div, eps, stats, stream);
 }
 
-template <bool V4>
+// FILM (ws_gn_bwd_reduce_film): x = film(z), as in group_stats_kernel
+template <bool V4, bool FILM = false>
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(
     const float* __restrict__ x, const float* __restrict__ dxn, const float* __restrict__ stats,
     const float* __restrict__ gamma, const float* const* __restrict__ gamma_tab,
-    const ws_groups_geom geo, float* __restrict__ ab) {
+    const ws_groups_geom geo, float* __restrict__ ab, const ws_film_desc fm) {
   __shared__ float red[16];
   const int g = blockIdx.x;
   const GroupView v = group_view(geo, g);
@@ -117,7 +190,17 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(
   const int n = geo.L * v.W;
   const float mean = stats[2 * (long long)g], rstd = stats[2 * (long long)g + 1];
   float s1 = 0.f, s2 = 0.f;
-  if (V4) {
+  if constexpr (FILM) {
+    FilmQuad fq(fm, geo, v.base, threadIdx.x & 31);
+    for (int i = threadIdx.x; i < (n >> 2); i += 256) {
+      const int row = i >> 5, c4 = i & 31;
+      const long long o = v.base + (long long)row * geo.rs + 4 * c4;
+      const f32x4 dg = *reinterpret_cast<const f32x4*>(dxn + o) * *reinterpret_cast<const f32x4*>(gm + 4 * c4);
+      const f32x4 xh = (fq(fm, geo, *reinterpret_cast<const f32x4*>(x + o), row, c4) - mean) * rstd;
+      s1 += (dg[0] + dg[1]) + (dg[2] + dg[3]);
+      s2 += (dg[0] * xh[0] + dg[1] * xh[1]) + (dg[2] * xh[2] + dg[3] * xh[3]);
+    }
+  } else if (V4) {
     const int w4 = v.W >> 2;
     // (a 4-way unrolled version with eight loads in flight per thread measured SLOWER in the step: 920 vs 500 us)
     for (int i = threadIdx.x; i < (n >> 2); i += 256) {
@@ -150,13 +233,26 @@ extern "C" int ws_gn_bwd_reduce(const float* x, const float* dxn, const float* s
   int rc = geom_check(geo, "ws_gn_bwd_reduce");
   if (rc != WS_OK) return rc;
   WS_REQUIRE(x && dxn && stats && ab && (gamma || gamma_tab), "ws_gn_bwd_reduce: null pointer");
+  const ws_film_desc off = {nullptr, nullptr, 0.f, 1};
   if (geom_vec4(geo))
     hipLaunchKernelGGL((gn_bwd_reduce_kernel<true>), dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream,
-                       x, dxn, stats, gamma, gamma_tab, *geo, ab);
+                       x, dxn, stats, gamma, gamma_tab, *geo, ab, off);
   else
     hipLaunchKernelGGL((gn_bwd_reduce_kernel<false>), dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream,
-                       x, dxn, stats, gamma, gamma_tab, *geo, ab);
+                       x, dxn, stats, gamma, gamma_tab, *geo, ab, off);
   return ws_check_launch("ws_gn_bwd_reduce");
+}
+
+extern "C" int ws_gn_bwd_reduce_film(const float* z, const ws_film_desc* film, const float* dxn, const float* stats,
+                                     const float* gamma, const ws_groups_geom* geo, float* ab, void* stream) {
+  if (!film_on(film)) return ws_gn_bwd_reduce(z, dxn, stats, gamma, nullptr, geo, ab, stream);
+  int rc = geom_check(geo, "ws_gn_bwd_reduce_film");
+  if (rc != WS_OK) return rc;
+  if ((rc = film_check(film, geo, "ws_gn_bwd_reduce_film")) != WS_OK) return rc;
+  WS_REQUIRE(z && dxn && stats && ab && gamma, "ws_gn_bwd_reduce_film: null pointer");
+  hipLaunchKernelGGL((gn_bwd_reduce_kernel<true, true>), dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream, z, dxn, stats,
+                     gamma, nullptr, *geo, ab, *film);
+  return ws_check_launch("ws_gn_bwd_reduce_film");
 }
 
 // Apply + PARAMETER SUMS in one pass (round 4; single-band groups of 128-float rows -- the time view of ResRNN.norm): the
@@ -164,10 +260,17 @@ extern "C" int ws_gn_bwd_reduce(const float* x, const float* dxn, const float* s
 // keeps one column quad: 256 threads = 8 row lanes x 32 quads), one partial [2][128] per group goes to `pslab`, and the last
 // workgroup of the launch adds the partials up in group order into `pout` [2][128] (ws_last_block): ws_gn_param_grad's pass
 // over x and dxn and the ws_reduce_slabs launch behind it are gone.
+// FILM (ws_gn_bwd_apply_pg_film): x is z, the input of the speaker-fusion affine in front of the norm -- xhat comes from film(z)
+// (ws_film), and the affine's own backward rides on the way out: r below IS d(z'), so dx = r * (a0 + a[row]) and the row's
+// da = sum r * z, db = sum r are two more column partials of the shape of (dgamma, dbeta): one [2][128] per group to `fslab`,
+// added up in group order by the last workgroup of each ROW (groups gpr * row .. gpr * row + gpr - 1; counter word `row`),
+// as affine_bwd4_kernel adds its splits.  z' never crosses HBM and affine_bwd4_kernel's pass over d(z') and z is gone.
+template <bool FILM>
 __global__ __launch_bounds__(256) void gn_bwd_apply_pg_kernel(
     const float* __restrict__ x, const float* dxn, const float* __restrict__ stats, const float* __restrict__ ab,
     const float* __restrict__ gamma, const float* __restrict__ res, const ws_groups_geom geo, float* dx,
-    float* __restrict__ pslab, float* __restrict__ pout, unsigned* counter) {
+    float* __restrict__ pslab, float* __restrict__ pout, unsigned* counter, const ws_film_desc fm, int gpr,
+    float* __restrict__ fslab, float* __restrict__ da, float* __restrict__ db, unsigned* fcounter) {
   __shared__ f32x4 sh[2][8][32];
   const int g = blockIdx.x;
   const GroupView v = group_view(geo, g);
@@ -177,13 +280,28 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_pg_kernel(
   const int c4 = threadIdx.x & 31, rl = threadIdx.x >> 5;
   const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * c4);
   f32x4 sg = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
+  f32x4 fa, fb, fsa = {0.f, 0.f, 0.f, 0.f}, fsb = {0.f, 0.f, 0.f, 0.f};
+  const int frow = FILM ? g / gpr : 0;   // (the launcher checks that a group lies inside one row of a / b)
+  if constexpr (FILM) {
+    fa = ws_film_row(fm.a, frow, 4 * c4);
+    fb = ws_film_row(fm.b, frow, 4 * c4);
+  }
   for (int row = rl; row < geo.L; row += 8) {
     const long long o = v.base + (long long)row * geo.rs + 4 * c4;
     const f32x4 d = *reinterpret_cast<const f32x4*>(dxn + o);
-    const f32x4 xh = (*reinterpret_cast<const f32x4*>(x + o) - mean) * rstd;
+    f32x4 xv = *reinterpret_cast<const f32x4*>(x + o);
+    const f32x4 zv = xv;
+    if constexpr (FILM) xv = ws_film(xv, fa, fb, fm.a0);
+    const f32x4 xh = (xv - mean) * rstd;
     f32x4 r = (d * gm - a0 - xh * a1) * rstd;
     if (res) r += *reinterpret_cast<const f32x4*>(res + o);
-    *reinterpret_cast<f32x4*>(dx + o) = r;
+    if constexpr (FILM) {
+      *reinterpret_cast<f32x4*>(dx + o) = r * (fa + fm.a0);
+      fsa += r * zv;
+      fsb += r;
+    } else {
+      *reinterpret_cast<f32x4*>(dx + o) = r;
+    }
     sg += d * xh;
     sb += d;
   }
@@ -199,6 +317,31 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_pg_kernel(
 #pragma unroll
     for (int q = 0; q < 4; ++q) ws_st_agent(o + q, t[q]);
   }
+  if constexpr (FILM) {  // the same for (da, db) of this group's row: rl 0 -> sum r * z, rl 1 -> sum r
+    __syncthreads();
+    sh[0][rl][c4] = fsa;
+    sh[1][rl][c4] = fsb;
+    __syncthreads();
+    if (rl < 2) {
+      f32x4 t = sh[rl][0][c4];
+#pragma unroll
+      for (int r = 1; r < 8; ++r) t += sh[rl][r][c4];
+      float* o = fslab + ((long long)g * 2 + rl) * 128 + 4 * c4;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ws_st_agent(o + q, t[q]);
+    }
+    if (ws_last_block(fcounter + frow, (unsigned)gpr)) {   // threads 0..127 -> da[row], 128..255 -> db[row]; groups in order
+      const int which = threadIdx.x >> 7, col = threadIdx.x & 127;
+      float* dst = which == 0 ? da : db;
+      if (dst) {
+        // (a form with eight of these loads in flight measured the same on one box: 0.472 against 0.471 ms per launch, 87.36
+        //  against 87.39 ms per step, profiles/film_fold.md)
+        float t = 0.f;
+        for (int k = 0; k < gpr; ++k) t += ws_ld_agent(fslab + (((long long)frow * gpr + k) * 2 + which) * 128 + col);
+        dst[(long long)frow * 128 + col] = t;
+      }
+    }
+  }
   ws_tree_sum256(pslab, gridDim.x, pout, counter);  // 256 threads = the 256 outputs (dgamma | dbeta)
 }
 
@@ -209,9 +352,32 @@ extern "C" int ws_gn_bwd_apply_pg(const float* x, const float* dxn, const float*
   if (rc != WS_OK) return rc;
   WS_REQUIRE(x && dxn && stats && ab && dx && gamma && pslab && pout && counter, "ws_gn_bwd_apply_pg: null pointer");
   WS_REQUIRE(geom_vec4(geo) && geo->nbands == 1 && geo->W == 128, "ws_gn_bwd_apply_pg: single-band groups of 128-float rows");
-  hipLaunchKernelGGL(gn_bwd_apply_pg_kernel, dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream, x, dxn, stats, ab,
-                     gamma, res, *geo, dx, pslab, pout, counter);
+  const ws_film_desc off = {nullptr, nullptr, 0.f, 1};
+  hipLaunchKernelGGL(gn_bwd_apply_pg_kernel<false>, dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream, x, dxn, stats, ab,
+                     gamma, res, *geo, dx, pslab, pout, counter, off, 1, nullptr, nullptr, nullptr, nullptr);
   return ws_check_launch("ws_gn_bwd_apply_pg");
+}
+
+extern "C" int ws_gn_bwd_apply_pg_film(const float* z, const ws_film_desc* film, const float* dxn, const float* stats,
+                                       const float* ab, const float* gamma, const float* res, const ws_groups_geom* geo,
+                                       float* dx, float* pslab, float* pout, unsigned* counter, float* fslab, float* da,
+                                       float* db, unsigned* fcounter, void* stream) {
+  if (!film_on(film)) return ws_gn_bwd_apply_pg(z, dxn, stats, ab, gamma, res, geo, dx, pslab, pout, counter, stream);
+  int rc = geom_check(geo, "ws_gn_bwd_apply_pg_film");
+  if (rc != WS_OK) return rc;
+  if ((rc = film_check(film, geo, "ws_gn_bwd_apply_pg_film")) != WS_OK) return rc;
+  WS_REQUIRE(z && dxn && stats && ab && dx && gamma && pslab && pout && counter && fslab && fcounter,
+             "ws_gn_bwd_apply_pg_film: null pointer");
+  WS_REQUIRE((!film->a || da) && (!film->b || db), "ws_gn_bwd_apply_pg_film: da / db go with a / b");
+  // groups of contiguous rows that tile the positions: group g covers positions [g L, g L + L), row = g / (rows_per_r / L)
+  WS_REQUIRE(geo->gdiv == 1 && geo->rs == 128 && geo->gs1 == (long long)geo->L * 128 && film->rows_per_r % geo->L == 0 &&
+                 geo->ngroups % (film->rows_per_r / geo->L) == 0,
+             "ws_gn_bwd_apply_pg_film: groups of contiguous rows that tile the rows of a / b (L=%d, rows_per_r=%d, ngroups=%d)",
+             geo->L, film->rows_per_r, geo->ngroups);
+  hipLaunchKernelGGL(gn_bwd_apply_pg_kernel<true>, dim3(geo->ngroups), dim3(256), 0, (hipStream_t)stream, z, dxn, stats, ab,
+                     gamma, res, *geo, dx, pslab, pout, counter, *film, film->rows_per_r / geo->L, fslab, film->a ? da : nullptr,
+                     film->b ? db : nullptr, fcounter);
+  return ws_check_launch("ws_gn_bwd_apply_pg_film");
 }
 
 template <bool V4>

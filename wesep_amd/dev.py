@@ -223,11 +223,35 @@ class Geom(NamedTuple):
         return g
 
 
-def group_stats(x, geo: Geom, stats, eps=GN_EPS, glen=None, glen_div=1):
-    """glen (ragged batches): int32 device table; group g's statistics cover its first glen[g // glen_div] rows only."""
+class Film(NamedTuple):
+    """ws_film_desc: the speaker-fusion affine z' = z * (a0 + a[r]) + b[r] FOLDED into the operand load of the kernel that
+    consumes z' (a, b: [R, 128] or None = 0; r = position // rows_per_r).  The five consumers of a time-view ResRNN's input take
+    it as `film=`: z' then never exists in memory.  Same fused multiply-add as affine_fwd (csrc/common.h ws_film)."""
+    a: Optional[torch.Tensor]
+    b: Optional[torch.Tensor]
+    a0: float
+    rows_per_r: int
+
+    def c(self):
+        _chk(self.a, "film.a")
+        _chk(self.b, "film.b")
+        f = L.FilmDesc()
+        f.a, f.b, f.a0, f.rows_per_r = _p(self.a), _p(self.b), self.a0, self.rows_per_r
+        return f
+
+
+def group_stats(x, geo: Geom, stats, eps=GN_EPS, glen=None, glen_div=1, film: Optional[Film] = None):
+    """glen (ragged batches): int32 device table; group g's statistics cover its first glen[g // glen_div] rows only.
+    film: the statistics are those of film(x) (ws_group_stats_film)."""
     _chk(x, "x")
     _chk(stats, "stats")
     g = geo.c()
+    if film is not None:
+        if glen is not None:
+            raise L.WesepHipError("group_stats: the folded affine has no per-group lengths")
+        fd = film.c()
+        L.check(L.lib().ws_group_stats_film(_p(x), C.byref(fd), C.byref(g), eps, _p(stats), L.stream_ptr()), "ws_group_stats_film")
+        return
     if glen is not None:
         _chk_lens(glen, -(-geo.ngroups // glen_div), "ws_group_stats_len")
         L.check(L.lib().ws_group_stats_len(_p(x), C.byref(g), _tab(glen), glen_div, eps, _p(stats), L.stream_ptr()),
@@ -265,10 +289,18 @@ def _word(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def gn_bwd_reduce(x, dxn, stats, geo: Geom, ab, gamma=None, gamma_tab=None):
+def gn_bwd_reduce(x, dxn, stats, geo: Geom, ab, gamma=None, gamma_tab=None, film: Optional[Film] = None):
+    """film: x is the input of the folded affine, the means are those over xhat of film(x) (ws_gn_bwd_reduce_film)."""
     for n, t in (("x", x), ("dxn", dxn), ("stats", stats), ("ab", ab), ("gamma", gamma)):
         _chk(t, n)
     g = geo.c()
+    if film is not None:
+        if gamma_tab is not None:
+            raise L.WesepHipError("gn_bwd_reduce: the folded affine takes one gamma")
+        fd = film.c()
+        L.check(L.lib().ws_gn_bwd_reduce_film(_p(x), C.byref(fd), _p(dxn), _p(stats), _p(gamma), C.byref(g), _p(ab),
+                                              L.stream_ptr()), "ws_gn_bwd_reduce_film")
+        return
     L.check(L.lib().ws_gn_bwd_reduce(_p(x), _p(dxn), _p(stats), _p(gamma), _tab(gamma_tab),
                                      C.byref(g), _p(ab), L.stream_ptr()), "ws_gn_bwd_reduce")
 
@@ -314,13 +346,28 @@ def gn_bwd_apply_pg_ok(geo: Geom) -> bool:
             and geo.band_off is None and geo.rs % 4 == 0 and geo.gs1 % 4 == 0 and geo.gs2 % 4 == 0)
 
 
-def gn_bwd_apply_pg(x, dxn, stats, ab, geo: Geom, dx, gamma, pslab, pout, counter, res=None):
+def gn_bwd_apply_pg(x, dxn, stats, ab, geo: Geom, dx, gamma, pslab, pout, counter, res=None, film: Optional[Film] = None,
+                    fslab=None, da=None, db=None, fcounter=None):
     """GroupNorm backward pass 2 with the parameter sums (norm.hip gn_bwd_apply_pg_kernel): dx, and (dgamma, dbeta) in
-    pout [2, 128] via pslab [ngroups, 2, 128] and the launch's last workgroup; counter: a zeroed int32 device word."""
+    pout [2, 128] via pslab [ngroups, 2, 128] and the launch's last workgroup; counter: a zeroed int32 device word.
+    film (ws_gn_bwd_apply_pg_film): x is the input z of the folded affine; dx = d(z), and the affine's own gradients come out
+    with it: da / db [R, 128] (those film.a / film.b has) via fslab [ngroups, 2, 128] and the last workgroup of each row;
+    fcounter: R zeroed int32 device words."""
     for n, t in (("x", x), ("dxn", dxn), ("stats", stats), ("ab", ab), ("gamma", gamma), ("res", res), ("dx", dx),
-                 ("pslab", pslab), ("pout", pout)):
+                 ("pslab", pslab), ("pout", pout), ("fslab", fslab), ("da", da), ("db", db)):
         _chk(t, n)
     g = geo.c()
+    if film is not None:
+        R = geo.ngroups * geo.L // film.rows_per_r
+        if (fslab is None or fslab.numel() < geo.ngroups * 256 or fcounter is None or fcounter.numel() < R
+                or any(t is not None and t.numel() < R * 128 for t in (da, db, film.a, film.b))):
+            raise L.WesepHipError("gn_bwd_apply_pg: the folded affine needs fslab [ngroups, 2, 128], R counter words and "
+                                  "[R, 128] a / b / da / db")
+        fd = film.c()
+        L.check(L.lib().ws_gn_bwd_apply_pg_film(_p(x), C.byref(fd), _p(dxn), _p(stats), _p(ab), _p(gamma), _p(res), C.byref(g),
+                                                _p(dx), _p(pslab), _p(pout), _word(counter), _p(fslab), _p(da), _p(db),
+                                                _word(fcounter), L.stream_ptr()), "ws_gn_bwd_apply_pg_film")
+        return
     L.check(L.lib().ws_gn_bwd_apply_pg(_p(x), _p(dxn), _p(stats), _p(ab), _p(gamma), _p(res), C.byref(g), _p(dx),
                                        _p(pslab), _p(pout), _word(counter), L.stream_ptr()), "ws_gn_bwd_apply_pg")
 
@@ -1029,10 +1076,11 @@ def pack_w(W, N: int, K: int, ldw: int, out, trans=False, order=0, w_off=0, f16=
 
 def gemm_p2b(*, A, lda: int, sm: SeqMap, Wpack, N: int, C_out, K=128, bias=None, A_bl=None, stats=None,
              gamma=None, beta=None, stat_map: Optional[StatMap] = None, run_if=None, amax=None, A_bl16=None, steps=None,
-             steps_div=1):
+             steps_div=1, film: Optional[Film] = None):
     """A_bl16 (ABI v16): the (normalised) operand once more as fp16 in BLH(K) (float32 storage of half the element count:
     blh_floats) -- the 2-byte A operand of gemm_tnb (a_fmt = 1).  steps (ragged batches): int32 device table; sequence s has
-    steps[s // steps_div] valid steps, the slots of later steps come out as exact zeros (ws_gemm_p2b_len)."""
+    steps[s // steps_div] valid steps, the slots of later steps come out as exact zeros (ws_gemm_p2b_len).
+    film: A passes through the folded affine before the normalisation (ws_gemm_p2b_film); the same operand bytes are read."""
     for n, t in (("A", A), ("Wpack", Wpack), ("bias", bias), ("C", C_out), ("A_bl", A_bl), ("stats", stats),
                  ("gamma", gamma), ("beta", beta), ("A_bl16", A_bl16)):
         _chk(t, n)
@@ -1051,6 +1099,12 @@ def gemm_p2b(*, A, lda: int, sm: SeqMap, Wpack, N: int, C_out, K=128, bias=None,
         rows = (getattr(sm, "nvalid", 0) or sm.nseq) * sm.L
         _alg("gemm_nt", rows * (4 * K + 4 * N + (4 * K if A_bl is not None else 0) + (2 * K if A_bl16 is not None else 0)) + 4 * N * K,
              2 * rows * N * K)
+    if film is not None:
+        if steps is not None:
+            raise L.WesepHipError("gemm_p2b: the folded affine has no per-sequence step counts")
+        fd = film.c()
+        L.check(L.lib().ws_gemm_p2b_film(C.byref(a), C.byref(fd), L.stream_ptr()), "ws_gemm_p2b_film")
+        return
     if steps is not None:
         _chk_lens(steps, -(-(getattr(sm, "nvalid", 0) or sm.nseq) // steps_div), "ws_gemm_p2b_len")
         L.check(L.lib().ws_gemm_p2b_len(C.byref(a), _tab(steps), steps_div, L.stream_ptr()), "ws_gemm_p2b_len")
@@ -1058,11 +1112,12 @@ def gemm_p2b(*, A, lda: int, sm: SeqMap, Wpack, N: int, C_out, K=128, bias=None,
     L.check(L.lib().ws_gemm_p2b(C.byref(a), L.stream_ptr()), "ws_gemm_p2b")
 
 
-def gemm_b2p(*, A, K: int, sm: SeqMap, Wpack, C_out, ldc: int, N=128, bias=None, R=None, a_fmt=0, amax=None, a16_out=None):
+def gemm_b2p(*, A, K: int, sm: SeqMap, Wpack, C_out, ldc: int, N=128, bias=None, R=None, a_fmt=0, amax=None, a16_out=None,
+             film: Optional[Film] = None):
     """a_fmt = 1: A holds bf16 elements in BLH(K) (d(gates) of WS_GATES_H2) instead of split pairs in BL(K); 2: fp16 elements
     scaled by the power of two the word `amax` defines (WS_GATES_H2F); 4: h as two fp16 planes (H2P, wesep_hip.h), Wpack from
     pack_w(f16=True).  a16_out (a_fmt 0, ABI v16): the A operand once more as
-    fp16 in BLH(K) -- hcat for gemm_tnb (a_fmt = 1)."""
+    fp16 in BLH(K) -- hcat for gemm_tnb (a_fmt = 1).  film: the residual is film(R) (ws_gemm_b2p_film; a_fmt 0 / 4)."""
     for n, t in (("A", A), ("Wpack", Wpack), ("bias", bias), ("C", C_out), ("R", R), ("a16_out", a16_out)):
         _chk(t, n)
     if a16_out is not None and a_fmt != 0:
@@ -1078,6 +1133,10 @@ def gemm_b2p(*, A, K: int, sm: SeqMap, Wpack, C_out, ldc: int, N=128, bias=None,
         # (a_fmt 4: h as two fp16 planes -- 4 B per element like the pair, and no a16_out copy behind it)
         _alg("gemm_nt", rows * ((4 if a_fmt in (0, 4) else 2) * K + 4 * N * (1 + (R is not None)) + (2 * K if a16_out is not None else 0))
              + 4 * N * K, 2 * rows * N * K)
+    if film is not None:
+        fd = film.c()
+        L.check(L.lib().ws_gemm_b2p_film(C.byref(a), C.byref(fd), L.stream_ptr()), "ws_gemm_b2p_film")
+        return
     L.check(L.lib().ws_gemm_b2p(C.byref(a), L.stream_ptr()), "ws_gemm_b2p")
 
 

@@ -173,11 +173,28 @@ def tail_flush() -> bool:
     return os.environ.get("WESEP_TAIL_FLUSH", "1") != "0"
 
 
-def _resrnn_blk_fwd(z, view, norm_w, norm_b, wparams, cache, grad, frames=None):
+def film_fold(z) -> bool:
+    """The speaker-fusion affine in front of a time-view ResRNN is FOLDED into that ResRNN (default on; WESEP_FILM_FOLD=0
+    restores the affine_fwd / affine_bwd launches): its five consumers -- statistics, relay, the projection's residual, the two
+    GroupNorm backward passes -- form z' = z * (a0 + a[r]) + b[r] in registers from z (dev.Film), the backward apply pass
+    multiplies d(z') by a0 + a on the way out and sums (da, db) beside (dgamma, dbeta): two passes over Z per fuse layer and
+    one saved copy of Z are gone.  z: the [R, K, Tf, N] input of the fuse layer.  Blocked path on a real device only (the host
+    emulation and the ABI dry run keep the unfolded launches), and only where the time view's GroupNorm backward is the
+    reduce + apply pair that carries the fold (dev.gn_bwd_apply_pg_ok, not the one-wave kernel of short groups)."""
+    if os.environ.get("WESEP_FILM_FOLD", "1") == "0" or not (z.is_cuda and torch.cuda.is_available()):
+        return False
+    if resrnn_mode() != "blocked" or z.dim() != 4 or z.shape[3] != 128:
+        return False
+    geo = _view_maps("time", *z.shape)[0]
+    return dev.gn_bwd_apply_pg_ok(geo) and not dev.gn_bwd_fused_ok(geo)
+
+
+def _resrnn_blk_fwd(z, view, norm_w, norm_b, wparams, cache, grad, frames=None, film=None):
     """The launches of ResRNNBlkFn.forward: statistics, plan, packs, the blocked BLSTM.  z contiguous [R, K, Tf, N].
     frames (ragged batches, inference): int32 device table [R] of the rows' valid frames -- the time view's statistics
     cover them only and its pre-activations behind them are zeros (blstm_forward's `steps`); the band view is per frame
-    and ignores it.  Returns (out, stats, plan, W, saved)."""
+    and ignores it.  film (dev.Film, time view): z is the input of a folded speaker-fusion affine -- every consumer below reads
+    film(z), `out` is film(z) + Linear(BLSTM(GroupNorm(film(z)))).  Returns (out, stats, plan, W, saved)."""
     _need_cuda(z, "ResRNN")
     wih_f, whh_f, proj_b = wparams[0], wparams[1], wparams[9]
     R, K, Tf, N = z.shape
@@ -187,18 +204,21 @@ def _resrnn_blk_fwd(z, view, norm_w, norm_b, wparams, cache, grad, frames=None):
     d = z.device
     geo, smap, seq, _ = _view_maps(view, R, K, Tf, N)
     ragged = frames is not None and view == "time"
+    if film is not None and (view != "time" or frames is not None):
+        raise L.WesepHipError("ResRNN: the folded speaker-fusion affine belongs to the time view of rectangular batches")
+    fk = dict(film=film) if film is not None else {}
     stats = _empty(d, geo.ngroups, 2)
     if ragged:
         dev.group_stats(z, geo, stats, glen=frames, glen_div=K)
     else:
-        dev.group_stats(z, geo, stats)
+        dev.group_stats(z, geo, stats, **fk)
     cache = cache if cache is not None else _NO_CACHE
     sig = cache.begin(wparams)
     plan = make_plan(seq, d, grad, gn_geo=geo, ragged=ragged) if ragged else make_plan(seq, d, grad, gn_geo=geo)
     W = WeightPacks(cache, sig, plan.lmode, plan.pair_rfmt, *wparams[:9])
     steps = dict(steps=(frames, K)) if ragged else {}
     out, saved = blstm_forward(plan, W, z, seq, res=z, bias=proj_b,
-                               norm=dict(stats=stats, gamma=norm_w, beta=norm_b, stat_map=smap), **steps)
+                               norm=dict(stats=stats, gamma=norm_w, beta=norm_b, stat_map=smap), **steps, **fk)
     return out, stats, plan, W, saved
 
 
@@ -210,16 +230,23 @@ class ResRNNBlkFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, dummy, box, cache, view, norm_w, norm_b, wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r,
-                bhh_r, proj_w, proj_b):
+                bhh_r, proj_w, proj_b, film_a=None, film_b=None, film_a0=1.0):
         """dummy/box: None, or the output and the box of this ResRNN's WGradCarrierFn -- then the ten
         LSTM / proj tensors are passed detached and their gradients travel through the box.  cache: the owning
-        module's PackCache or None."""
+        module's PackCache or None.  film_a / film_b [R, N] (either may be None), film_a0: a folded speaker-fusion affine in front
+        (film_fold): z is ITS input, saved as it is -- no z' exists --, and the backward returns d(z), d(film_a), d(film_b)."""
         z = z.contiguous()
         d = z.device
+        film = None
+        if film_a is not None or film_b is not None:
+            film_a = film_a.contiguous() if film_a is not None else None
+            film_b = film_b.contiguous() if film_b is not None else None
+            film = dev.Film(film_a, film_b, float(film_a0), z.shape[1] * z.shape[2])
         out, stats, plan, W, saved = _resrnn_blk_fwd(
             z, view, norm_w, norm_b, (wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r, proj_w, proj_b), cache,
-            any(ctx.needs_input_grad))
-        ctx.save_for_backward(z, stats, norm_w, *saved)
+            any(ctx.needs_input_grad), film=film)
+        ctx.save_for_backward(z, stats, norm_w, *saved, film_a, film_b)
+        ctx.film_a0 = float(film_a0)
         if view == "time" and box is not None and plan.grad:
             key = (d.type, d.index)
             _TIME_LEFT[key] = _TIME_LEFT.get(key, 0) + 1
@@ -230,7 +257,7 @@ class ResRNNBlkFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         consume_once(ctx, "ResRNN")
-        z, stats, norm_w, gates, cbuf, hcat, xn, hcat16 = ctx.saved_tensors   # (xn: fp16 copy if hcat16)
+        z, stats, norm_w, gates, cbuf, hcat, xn, hcat16, film_a, film_b = ctx.saved_tensors   # (xn: fp16 copy if hcat16)
         plan, W, box = ctx.plan, ctx.packs, ctx.box
         dout = dout.contiguous()
         R, K, Tf, N = z.shape
@@ -254,7 +281,20 @@ class ResRNNBlkFn(torch.autograd.Function):
         # a separate ws_reduce_slabs launch on this stream can sit out a whole weight-gradient GEMM of the side stream
         # before its four workgroups get a CU (round 3: 7 ms per step in 62 such launches)
         dgb = _empty(d, 2, N)
-        if dev.gn_bwd_fused_ok(geo):
+        da = db = None
+        if film_a is not None or film_b is not None:
+            # folded speaker-fusion affine (film_fold: time view, the reduce + apply pair): xhat from film(z) in both passes; the
+            # apply pass writes d(z) = d(z') * (a0 + a) and sums (da, db) per row beside (dgamma, dbeta) -- affine_bwd's pass over
+            # d(z') and z does not exist
+            film = dev.Film(film_a, film_b, ctx.film_a0, K * Tf)
+            ab = _empty(d, geo.ngroups, 2)
+            dev.gn_bwd_reduce(z, dxn, stats, geo, ab, gamma=norm_w, film=film)
+            pslab = _empty(d, geo.ngroups + dev.tree_groups(geo.ngroups), 2, N)
+            da = _empty(d, R, N) if film_a is not None else None
+            db = _empty(d, R, N) if film_b is not None else None
+            dev.gn_bwd_apply_pg(z, dxn, stats, ab, geo, dz, norm_w, pslab, dgb, zero_words(d, 1 + dev.tree_groups(geo.ngroups)),
+                                res=dout, film=film, fslab=_empty(d, geo.ngroups, 2, N), da=da, db=db, fcounter=zero_words(d, R))
+        elif dev.gn_bwd_fused_ok(geo):
             # band view: 16 032 groups of 16 KB -- one wave per group, x / dxn / dout cross HBM once (norm.hip)
             ns2 = min(1024, -(-geo.ngroups // 4))
             pslab = _empty(d, ns2 + dev.tree_groups(ns2), 2, N)
@@ -276,7 +316,7 @@ class ResRNNBlkFn(torch.autograd.Function):
             dev.gn_bwd_apply(z, dxn, stats, ab, geo, dz, gamma=norm_w, res=dout)
             dgb = _reduce_new(pslab, ns2, 2 * N, (2, N))
         gd = torch.zeros((), device=d) if box is not None else None
-        return (dz, gd, None, None, None, dgb[0], dgb[1]) + tuple(wg)
+        return (dz, gd, None, None, None, dgb[0], dgb[1]) + tuple(wg) + (da, db, None)
 
 
 def pack_prefetch() -> bool:
@@ -335,9 +375,13 @@ def make_wgrad_carrier(params, blocked=None):
     return WGradCarrierFn.apply(box, *params), box
 
 
-def resrnn(z, view, norm_w, norm_b, *params, carrier=None, cache=None, frames=None):
+def resrnn(z, view, norm_w, norm_b, *params, carrier=None, cache=None, frames=None, film=None):
     """ResRNN forward (autograd-aware) on the path selected by WESEP_RESRNN.  cache: the owning module's PackCache.
-    frames (ragged batches): int32 device table [R] of the rows' valid frames; inference on the blocked path only."""
+    frames (ragged batches): int32 device table [R] of the rows' valid frames; inference on the blocked path only.
+    film: (a, b, a0) of a speaker-fusion affine folded into this (time-view, blocked) ResRNN -- the caller asked film_fold()."""
+    if film is not None and (frames is not None or resrnn_mode() != "blocked" or view != "time"):
+        raise L.WesepHipError("resrnn: film= goes with the time view of the blocked path (functional.film_fold)")
+    fa, fb, fa0 = film if film is not None else (None, None, 1.0)
     if frames is not None:
         if torch.is_grad_enabled() or resrnn_mode() != "blocked":
             raise L.WesepHipError("ResRNN: per-row lengths are an inference feature of the blocked path "
@@ -347,9 +391,9 @@ def resrnn(z, view, norm_w, norm_b, *params, carrier=None, cache=None, frames=No
     if resrnn_mode() != "blocked":
         return ResRNNFn.apply(z, view, norm_w, norm_b, *params)
     if carrier is None:
-        return ResRNNBlkFn.apply(z, None, None, cache, view, norm_w, norm_b, *params)
+        return ResRNNBlkFn.apply(z, None, None, cache, view, norm_w, norm_b, *params, fa, fb, fa0)
     dummy, box = carrier
-    return ResRNNBlkFn.apply(z, dummy, box, cache, view, norm_w, norm_b, *(p.detach() for p in params))
+    return ResRNNBlkFn.apply(z, dummy, box, cache, view, norm_w, norm_b, *(p.detach() for p in params), fa, fb, fa0)
 
 
 # ---------------------------------------------------------------------------------------------

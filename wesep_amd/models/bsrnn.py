@@ -63,12 +63,14 @@ class ResRNN(nn.Module):
         """Weight-gradient carrier of this layer (functional.WGradCarrierFn) or None."""
         return F_.make_wgrad_carrier(self._wparams())
 
-    def forward(self, z, view="time", carrier=None, frames=None):
-        """frames: ragged batches (BSRNN.forward(lengths=)): int32 device table [R] of the rows' valid frames."""
+    def forward(self, z, view="time", carrier=None, frames=None, film=None):
+        """frames: ragged batches (BSRNN.forward(lengths=)): int32 device table [R] of the rows' valid frames.
+        film: (a, b, a0) of the speaker-fusion affine in front, folded into this layer's kernels (functional.film_fold)."""
         if frames is not None:
             return F_.resrnn(z, view, self.norm.weight, self.norm.bias, *self._wparams(), cache=self._packs, frames=frames)
+        fk = dict(film=film) if film is not None else {}
         return F_.resrnn(z, view, self.norm.weight, self.norm.bias, *self._wparams(), carrier=carrier,
-                         cache=self._packs)
+                         cache=self._packs, **fk)
 
 
 class BSNet(nn.Module):
@@ -81,11 +83,11 @@ class BSNet(nn.Module):
         self.band_rnn = ResRNN(self.feature_dim, self.feature_dim * 2, bidirectional)
         self.band_comm = ResRNN(self.feature_dim, self.feature_dim * 2, bidirectional)
 
-    def forward(self, z, dummy: Optional[torch.Tensor] = None, carriers=None, frames=None):
+    def forward(self, z, dummy: Optional[torch.Tensor] = None, carriers=None, frames=None, film=None):
         c_t, c_b = carriers if carriers is not None else (None, None)
         if frames is not None:      # ragged batch (inference): only the time view has to know where a row ends
             return self.band_comm(self.band_rnn(z, "time", frames=frames), "band")
-        return self.band_comm(self.band_rnn(z, "time", c_t), "band", c_b)
+        return self.band_comm(self.band_rnn(z, "time", c_t, film=film), "band", c_b)
 
 
 class FuseSeparation(nn.Module):
@@ -123,13 +125,18 @@ class FuseSeparation(nn.Module):
     def forward(self, z, spk_embedding, nch=None, carriers=None, frames=None):
         if carriers is None:
             carriers = self.make_carriers(z.device)
+        film = None      # operands of a fuse layer that the BSNet behind it folds into its time-view ResRNN (functional.film_fold)
         for i, layer in enumerate(self.separation):
             if isinstance(layer, BSNet) and frames is not None:
                 z = layer(z, frames=frames)
             elif isinstance(layer, BSNet):
-                z = layer(z, spk_embedding, carriers[i])
+                z, film = layer(z, spk_embedding, carriers[i], film=film), None
             else:
-                z = layer(z, spk_embedding)
+                nxt = self.separation[i + 1] if i + 1 < len(self.separation) else None
+                if isinstance(nxt, BSNet) and frames is None and F_.film_fold(z):
+                    film = layer.affine_operands(spk_embedding)      # None: concat, which is no broadcast affine
+                if film is None:
+                    z = layer(z, spk_embedding)
         return z
 
 

@@ -58,10 +58,14 @@ class FiLM(nn.Module):
             nn.init.zeros_(fc.weight)
             nn.init.zeros_(fc.bias)
 
-    def forward(self, embed, x):
+    def operands(self, embed):
+        """(gamma(e), beta(e), 1.0): the affine x * (1 + gamma) + beta as its per-row operands."""
         g = F_.LinearFn.apply(embed, self.gamma_fcs[0].weight, self.gamma_fcs[0].bias)
         b = F_.LinearFn.apply(embed, self.beta_fcs[0].weight, self.beta_fcs[0].bias)
-        return F_.AffineFn.apply(x, g, b, 1.0)
+        return g, b, 1.0
+
+    def forward(self, embed, x):
+        return F_.AffineFn.apply(x, *self.operands(embed))
 
 
 class SpeakerFuseLayer(nn.Module):
@@ -78,15 +82,25 @@ class SpeakerFuseLayer(nn.Module):
         else:
             raise ValueError("Fuse type not defined.")
 
-    def forward(self, x, embed):
-        """x: Z layout [R, K, Tf, N]; embed: [R, E] (or the reference's [R, 1, E, 1])."""
+    def affine_operands(self, embed):
+        """(a, b, a0) of the fuse types that are a broadcast affine x * (a0 + a[r]) + b[r] -- additive, multiply, FiLM --, or None
+        (concat).  A caller whose next layer folds the affine into its own operand loads (functional.film_fold) takes these
+        instead of the materialised result of forward()."""
+        if self.fuse_type == "concat":
+            return None
         if embed.dim() == 4:
             embed = embed[:, 0, :, 0]
         embed = embed.contiguous()
-        if self.fuse_type == "concat":
-            return F_.ConcatFuseFn.apply(x, embed, self.fc.linear.weight, self.fc.linear.bias)
         if self.fuse_type == "additive":
-            return F_.AffineFn.apply(x, None, self.fc(embed), 1.0)
+            return None, self.fc(embed), 1.0
         if self.fuse_type == "multiply":
-            return F_.AffineFn.apply(x, self.fc(embed), None, 0.0)
-        return self.fc(embed, x)
+            return self.fc(embed), None, 0.0
+        return self.fc.operands(embed)
+
+    def forward(self, x, embed):
+        """x: Z layout [R, K, Tf, N]; embed: [R, E] (or the reference's [R, 1, E, 1])."""
+        if self.fuse_type == "concat":
+            if embed.dim() == 4:
+                embed = embed[:, 0, :, 0]
+            return F_.ConcatFuseFn.apply(x, embed.contiguous(), self.fc.linear.weight, self.fc.linear.bias)
+        return F_.AffineFn.apply(x, *self.affine_operands(embed))
