@@ -308,7 +308,10 @@ typedef struct ws_lstm_args {
                             columns instead of eight fp16 MFMAs; not with `dxn`.
                             ws_lstm_fwd (which reads nothing else of this field), blocked-layout modes: WS_LSTM_FWD_H2P (16) =
                             hcat leaves as two fp16 planes (H2P, below) instead of BLS pairs -- what a launch that stands behind
-                            ws_lstm_fwd_cluster2 with rfmt bit 1 has to leave                                              */
+                            ws_lstm_fwd_cluster2 with rfmt bit 1 has to leave.
+                            Bit 5, WS_LSTM_C16 (32), or-ed to either (no new ABI version: 0 = every earlier behaviour): `cbuf` holds
+                            the saved cell state as fp16 in BLH(2H) (C16, below).  WS_GATES_H2F and the blocked-layout modes only;
+                            ws_lstm_fwd: together with WS_LSTM_FWD_H2P; ws_lstm_bwd: with rfmt 0 / 2 / 3, not with `dxn`        */
   const unsigned* amax;  /* WS_GATES_H2F, backward: max |dhcat| of this launch as float bits (see WS_GATES_H2F) */
   /* ABI v19 (three trailing fields, zero = every earlier behaviour), ws_lstm_bwd with rfmt = 2 only: d(normalised input) of
    * the ResRNN computed INSIDE the BPTT from the d(gates) image its recurrent product reads anyway (autograd's d(input) of
@@ -360,6 +363,7 @@ typedef struct ws_lstm_args {
                                   sequences to fill the chip with 32-sequence workgroups         */
 #define WS_LSTM_H 256
 #define WS_LSTM_FWD_H2P 16 /* ws_lstm_args.rfmt of a forward launch: hcat as two fp16 planes */
+#define WS_LSTM_C16 32     /* ws_lstm_args.rfmt / ws_lstm_pair_args.rfmt, or-ed in: cbuf as fp16 in BLH(2H) (C16, below) */
 #define WS_LSTM_PACK_FLOATS (2 * 4 * WS_LSTM_H * WS_LSTM_H) /* per pass, both directions */
 /* Packs weight_hh_l0 / _reverse [4H][H] into MFMA fragment order for the fwd and bwd pass
  * (fp32 for WS_LSTM_F32_*, bf16 hi/lo pairs for WS_LSTM_BF16X3; same byte size).           */
@@ -433,7 +437,8 @@ typedef struct ws_lstm_cluster2_args {
   int dbg, rfmt;        /* rfmt (ABI v20, the former pad_: 0 = every earlier behaviour): 1 = the lo term of the recurrent product on
                            v_mfma_scale_f32_32x32x64_f8f6f4 (e4m3 codes of 256 w - hi, one exponent per wave, against e4m3 of h): four
                            fp16 MFMAs + one FP8 MFMA per 64 columns instead of eight fp16 MFMAs.  Bit 1 (value 2): hcat leaves as
-                           two fp16 planes (H2P, below) instead of BLS pairs                                             */
+                           two fp16 planes (H2P, below) instead of BLS pairs.  Bit 2 (value 4): cbuf leaves as fp16 in BLH(2H)
+                           (C16, below) instead of fp32 BL                                                               */
   float* dbg_buf;      /* dbg 2048: L * 2 * 8 64-bit cycle stamps of cluster 0 / member 0 (tools/r05_recur_probe.py) */
 } ws_lstm_cluster2_args;
 int ws_lstm_fwd_cluster2(const ws_lstm_cluster2_args* a, void* stream);
@@ -483,7 +488,8 @@ typedef struct ws_lstm_pair_args {
                            3 (ABI v20; WS_GATES_H2F only): rfmt 2 with the lo term on v_mfma_scale_f32_32x32x64_f8f6f4 --
                            the same codes as A operands of K = 64 (wpack from ws_lstm_pack_pair_f8mx) against e4m3 of
                            d(gates) / 256 built in registers from the fp16 fragments: per 64 gate columns four fp16 MFMAs
-                           + one FP8 MFMA at twice the rate instead of eight fp16 MFMAs                               */
+                           + one FP8 MFMA at twice the rate instead of eight fp16 MFMAs.
+                           Bit 5, WS_LSTM_C16 (32), or-ed to 2 or 3: `cbuf` holds fp16 cells in BLH(2H) (C16, below)   */
 } ws_lstm_pair_args;
 int ws_lstm_pack_pair(const float* whh_f, const float* whh_r, float* pack, void* stream);
 /* ABI v17: the pack of rfmt = 1 (same size and unit order, fp16 hi / lo of 256 w; |w| < 255) */
@@ -521,6 +527,13 @@ int ws_lstm_cat_ih(const float* wih_f, const float* wih_r, const float* bih_f, c
  * hold two BLH(2H) planes of nblk blocks each -- first hi = fp16(h), then lo = fp16(h - hi), both round to nearest even; value =
  * hi + lo, >= 21 significant bits down to fp16's subnormal floor (|h| < 1).  The hi plane alone is the fp16 A operand of
  * ws_gemm_tnb (a_fmt = 1) and the G operand of ws_gemm_tnb_h16; ws_gemm_b2p reads both planes (a_fmt = 4).
+ * fp16 storage C16 of cbuf (training with WS_GATES_H2F; selected per launch: ws_lstm_fused_args.hfmt bit 4,
+ * ws_lstm_cluster2_args.rfmt bit 2, ws_lstm_args.rfmt / ws_lstm_pair_args.rfmt bit 5 = WS_LSTM_C16): cbuf is ONE BLH(2H) plane of nblk
+ * blocks -- nblk * 32 * 2H * 2 bytes, the layout of H2P's hi plane -- holding fp16(c), round to nearest even, of the fp32 cell
+ * the recurrence itself continues from; padded slots hold what the fp32 format holds there.  The BPTT kernels are the only
+ * readers: tanh(c_t) in d(o) and d(c), and the factor c_{t-1} of d(f).  |c_t| <= t, so sequences of up to 32768 steps cannot
+ * overflow fp16 (the callers' limit).  A fall-back launch behind ws_lstm_fwd_cluster2 / ws_lstm_bwd_pair must name the format
+ * of the launch it stands behind.
  * ws_seqmap maps a slot to its position (row) in the plain Z-layout tensors:
  *   pos = (seq / sq_div) * sq_s1 + (seq % sq_div) * sq_s2 + step * step_rows.              */
 typedef struct ws_seqmap {
@@ -854,7 +867,9 @@ typedef struct ws_lstm_fused_args {
                            fragment against an e4m3 image of h: four fp16 MFMAs + one FP8 MFMA (K = 64, twice the rate) per
                            recurrent k-step instead of eight; wpack from ws_lstm_pack_fused_h8 (64- and 32-sequence kernels).
                            Bit 3 (value 8, with bit 0): hcat leaves as two fp16 planes (H2P, above) instead of BLS pairs; gates
-                           and cbuf are bit-identical to the launch without it                                              */
+                           and cbuf are bit-identical to the launch without it.
+                           Bit 4 (value 16, with bit 3; no new ABI version): cbuf leaves as fp16 in BLH(2H) (C16, above) instead
+                           of fp32 BL; gates and both planes of h are bit-identical to the launch without it              */
 } ws_lstm_fused_args;
 #define WS_LSTM_FUSED_PACK_FLOATS (2 * 8 * 24 * 4 * 2 * 64 * 4)
 int ws_lstm_pack_fused(const float* wih_f, const float* wih_r, const float* whh_f, const float* whh_r,

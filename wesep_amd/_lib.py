@@ -30,6 +30,7 @@ def dgates_scale(amax_bits: int) -> float:
 
 LSTM_F32_MT1, LSTM_F32_MT2, LSTM_BF16X3, LSTM_BF16X3_BLK, LSTM_BF16X3_BLK16 = 1, 2, 3, 4, 5
 LSTM_FWD_H2P = 16          # WS_LSTM_FWD_H2P: ws_lstm_args.rfmt of a forward launch that leaves hcat as two fp16 planes
+LSTM_C16 = 32              # WS_LSTM_C16: ws_lstm_args.rfmt / ws_lstm_pair_args.rfmt bit -- cbuf holds fp16 cells in BLH(2H)
 LSTM_PACK_FLOATS = 2 * 4 * LSTM_H * LSTM_H
 
 _p = C.c_void_p

@@ -490,6 +490,7 @@ class BlstmPlan(NamedTuple):
     band_dx: bool       # the streaming BPTT writes d(xn) itself (band_dx)
     a_fmt: int          # a_fmt of the d(xn) GEMM over d(gates) (dxn_fmt)
     h2p: bool = False   # h leaves the recurrence as two fp16 planes: one buffer serves projection and weight gradients (dev.h2p_on)
+    c16: bool = False   # the saved cell state is fp16 in BLH(2H): half the bytes written by the forward and read by the BPTT (dev.c16_on)
 
 
 _WIHT_KIND = {0: "wihT", 1: "wihT", 2: "wihT16", 3: "wihT8"}     # BlstmPlan.a_fmt -> pack of W_ih^T for the d(xn) GEMM
@@ -523,10 +524,18 @@ def make_plan(seq, device, grad, gn_geo=None, ragged=False) -> BlstmPlan:
     # pair); the fused forward writes them from its fp16-h kernels only
     h2p = (a16 and dev.h2p_on(device) and not ragged and fwd in ("fused", "cluster2", "stream")
            and (fwd != "fused" or bool(dev.lstm_fused_hfmt(gfmt) & 1)))
+    prf = pair_rfmt(gfmt) if grad and bptt == "pair" else 0
+    bdx = bool(brf) and gn_geo is not None and band_dx(brf, seq, gn_geo)
+    # the cell state in fp16 (C16, wesep_hip.h): every writer of the plan's forward branch -- the fall-back behind cluster2
+    # included -- and every reader of its BPTT -- the fall-back behind the pair kernel included -- know the format; the writers
+    # have it next to the fp16 planes of h (h2p: a backward follows, WS_GATES_H2F, device buffers, no ragged batch, forward
+    # 'fused' on the fp16-h kernels / 'cluster2' / 'stream'), the readers are the pair kernel with all of W_hh resident (rfmt 2 /
+    # 3) and the streaming kernels without their own d(xn).  |c_t| <= t: fp16 cannot overflow below 65 504 steps
+    c16 = (h2p and grad and gfmt == L.GATES_H2F and dev.c16_on(device) and not ragged and seq.L <= dev.C16_MAX_STEPS
+           and ((bptt == "pair" and prf in (2, 3) and not _pair_stamp_on()) or (bptt == "stream" and not bdx)))
     return BlstmPlan(
         nb=dev.bl_num_blocks(seq), lmode=lmode, cluster=cluster, fwd=fwd, bptt=bptt, grad=grad, gfmt=gfmt, g_fmt=g_fmt,
-        a16=a16, pair_rfmt=pair_rfmt(gfmt) if grad and bptt == "pair" else 0,
-        band_rfmt=brf, band_dx=bool(brf) and gn_geo is not None and band_dx(brf, seq, gn_geo), a_fmt=dxn_fmt(g_fmt), h2p=h2p)
+        a16=a16, pair_rfmt=prf, band_rfmt=brf, band_dx=bdx, a_fmt=dxn_fmt(g_fmt), h2p=h2p, c16=c16)
 
 
 def consume_once(ctx, who):
@@ -568,7 +577,9 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None, film=None):
     wcat, bcat = W("cat")
     whf, whr = W("whh")
     xn = _empty(d, nb, 32 * N)
-    cbuf, hcat = _empty(d, nb, 32 * 2 * H), _empty(d, nb, 32 * 2 * H)
+    hcat = _empty(d, nb, 32 * 2 * H)
+    cells = dict(c16=True) if plan.c16 else {}      # (the recurrences' keyword for the fp16 cell state)
+    cbuf = _empty(d, dev.blh_floats(nb, 2 * H)) if plan.c16 else _empty(d, nb, 32 * 2 * H)
     gates = _empty(d, dev.blh_floats(nb, 2 * G4)) if h2 else _empty(d, nb, 32 * 2 * G4)
     # fp16 copies of the weight-gradient GEMM's A operand [xn | h] (ABI v16; written by the two GEMMs that touch these
     # operands anyway): ws_gemm_tnb then loads 32 instead of 56 KB per block and runs ONE MFMA per product.  TF-GridNet's
@@ -589,7 +600,7 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None, film=None):
         dev.gemm_p2b(A=x, lda=N, sm=seq, Wpack=None, N=0, C_out=None, A_bl=xn, A_bl16=xn16, **norm)
         hf = dev.lstm_fused_hfmt(gfmt)
         dev.lstm_fwd_fused(gates, cbuf, hcat, xn, W("fused8" if hf & 4 else "fused16" if hf else "fused"), bcat, seq, gfmt=gfmt,
-                           hfmt=hf | (8 if h2p else 0))
+                           hfmt=hf | (8 if h2p else 0), **cells)
     elif plan.fwd == "cluster2":
         # few long sequences (time view, inter-frame path), 2-byte formats (round 5): the cluster kernel computes x W_ih^T
         # itself from the normalised input (lstm_cluster2.hip) -- ws_gemm_p2b only normalises / relays (reads E, writes E
@@ -603,10 +614,10 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None, film=None):
         # (profiles/r05_tfg_cfg5_precision_split.txt); the input keeps its split pair since.  WESEP_LSTM_CLUSTER2=0 selects
         # the round-4 cluster kernel on fp32 pre-activations
         dev.gemm_p2b(A=x, lda=N, sm=seq, Wpack=None, N=0, C_out=None, A_bl=xn, A_bl16=xn16, **norm)
-        tw = dev.lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whf, whr, seq, dbg=_cluster_dbg(), **planes)
+        tw = dev.lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whf, whr, seq, dbg=_cluster_dbg(), **planes, **cells)
         pre = dev.fallback_scratch(d, nb * 32 * 2 * G4)       # (untouched after a clean launch; one buffer per stream)
         dev.gemm_p2b(A=x, lda=N, sm=seq, Wpack=W("wih"), N=2 * G4, C_out=pre, bias=bcat, run_if=tw, **norm)
-        dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, run_if=tw, gfmt=gfmt, gates_in=pre, **planes)
+        dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, run_if=tw, gfmt=gfmt, gates_in=pre, **planes, **cells)
         del pre
     else:
         # pre-activations: in `gates` itself with the fp32 format (one buffer, three lives); with the 2-byte formats a
@@ -629,7 +640,7 @@ def blstm_forward(plan, W, x, seq, res, bias, norm=None, steps=None, film=None):
                 dev.gemm_p2b(run_if=tw, **xproj)
             dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, run_if=tw, **rec)
         else:
-            dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, **planes, **rec)
+            dev.lstm_fwd(gates, cbuf, hcat, W("hh")[0], seq, lmode, **planes, **cells, **rec)
         del pre
     out = torch.empty_like(res)
     if h2p:     # both planes against the fp16 hi / lo pack of 256 w: three fp16 MFMAs per product, no copy written
@@ -674,6 +685,7 @@ def blstm_bptt(plan, W, gates, cbuf, hcat, dout, seq, release):
     # WS_GATES_H2F: the d(hcat) GEMM raises max |d(hcat)| of this launch in a device word; the BPTT scales its fp16 d(gates)
     # by the power of two it defines, the two consumers of d(gates) undo it (wesep_hip.h)
     amax = amax_word(d) if gfmt == L.GATES_H2F else None
+    cells = dict(c16=True) if plan.c16 else {}      # (cbuf holds fp16 cells: blstm_forward)
     dev.gemm_p2b(A=dout, lda=N, sm=seq, Wpack=W("projT"), N=2 * H, C_out=dh, A_bl=dout_bl, amax=amax)
     if _h2_probe() & 16:
         _probe_round(dh, "bf16")
@@ -703,8 +715,8 @@ def blstm_bptt(plan, W, gates, cbuf, hcat, dout, seq, release):
         dg = _empty(d, nb, 32 * 2 * G4) if gfmt == L.GATES_H2S else _empty(d, dev.blh_floats(nb, 2 * G4))
         rf = plan.pair_rfmt
         tw = dev.lstm_bwd_pair(gates, cbuf, dh, W("hhp16" if rf else "hhp"), seq, gfmt=gfmt, dgates=dg, repairable=True,
-                               dbg=_pair_dbg(), amax=amax, rfmt=rf, dbg_buf=_pair_stamp_buf(d, seq.L))
-        dev.lstm_bwd(gates, cbuf, hcat, dh, W("hh")[1], seq, plan.lmode, gfmt=gfmt, dgates=dg, run_if=tw, amax=amax)
+                               dbg=_pair_dbg(), amax=amax, rfmt=rf, dbg_buf=_pair_stamp_buf(d, seq.L), **cells)
+        dev.lstm_bwd(gates, cbuf, hcat, dh, W("hh")[1], seq, plan.lmode, gfmt=gfmt, dgates=dg, run_if=tw, amax=amax, **cells)
     else:
         # streaming BPTT (many short sequences): bf16 d(gates) in place over the unorm16 gates (H2) / split pairs to their own
         # buffer (H2S)
@@ -714,7 +726,7 @@ def blstm_bptt(plan, W, gates, cbuf, hcat, dout, seq, release):
             dxn2 = _empty(d, 2, dout.numel() // N, N)        # d(xn) of each direction, written by the BPTT itself
         dev.lstm_bwd(gates, cbuf, hcat, dh, W("hh8") if brf else W("hh")[1], seq, plan.lmode, gfmt=gfmt,
                      dgates=dg if gfmt == L.GATES_H2S else None, amax=amax, rfmt=brf, dxn=dxn2,
-                     wxpack=W("wx8") if dxn2 is not None else None)
+                     wxpack=W("wx8") if dxn2 is not None else None, **cells)
     if _h2_probe() & 2 and gfmt == L.GATES_F32:
         _probe_round(gates, "bf16", packed=True)
     if _h2_probe() & 32 and gfmt == L.GATES_F32 and not torch.cuda.is_available():

@@ -407,12 +407,17 @@ static int lstm_check(const ws_lstm_args* a, bool bwd, const char* who) {
              a->gfmt);
   WS_REQUIRE(a->gfmt != WS_GATES_H2S || !bwd || a->dgates, "%s: WS_GATES_H2S needs dgates", who);
   WS_REQUIRE(a->gfmt == WS_GATES_F32 || ((a->mode >> 8) & 7) == 0, "%s: probe builds are WS_GATES_F32 only", who);
-  WS_REQUIRE(a->rfmt == 0 || ((a->rfmt == 2 || a->rfmt == 3) && bwd && a->mode == WS_LSTM_BF16X3_BLK && a->gfmt == WS_GATES_H2F) ||
-                 (a->rfmt == WS_LSTM_FWD_H2P && !bwd && (a->mode == WS_LSTM_BF16X3_BLK || a->mode == WS_LSTM_BF16X3_BLK16)),
+  const int rfmt = a->rfmt & ~WS_LSTM_C16;
+  WS_REQUIRE(rfmt == 0 || ((rfmt == 2 || rfmt == 3) && bwd && a->mode == WS_LSTM_BF16X3_BLK && a->gfmt == WS_GATES_H2F) ||
+                 (rfmt == WS_LSTM_FWD_H2P && !bwd && (a->mode == WS_LSTM_BF16X3_BLK || a->mode == WS_LSTM_BF16X3_BLK16)),
              "%s: rfmt %d (2 / 3 = fp16 recurrence on fp16 + FP8 weights, 3: the lo term on the FP8 MFMA: ws_lstm_bwd, "
              "WS_LSTM_BF16X3_BLK, WS_GATES_H2F only; 16 = hcat out as two fp16 planes: ws_lstm_fwd, blocked-layout modes only)",
              who, a->rfmt);
-  WS_REQUIRE(!a->dxn || (bwd && a->rfmt == 2 && a->wxpack && a->dxn_dir_stride > 0 && a->dxn_dir_stride < (1ll << 29) && !a->run_if),
+  WS_REQUIRE(!(a->rfmt & WS_LSTM_C16) || (a->gfmt == WS_GATES_H2F && (a->mode == WS_LSTM_BF16X3_BLK || a->mode == WS_LSTM_BF16X3_BLK16) &&
+                                          (bwd ? !a->dxn : rfmt == WS_LSTM_FWD_H2P)),
+             "%s: rfmt %d: cbuf as fp16 (bit WS_LSTM_C16) needs WS_GATES_H2F and a blocked-layout mode; ws_lstm_fwd: with "
+             "WS_LSTM_FWD_H2P; ws_lstm_bwd: no dxn", who, a->rfmt);
+  WS_REQUIRE(!a->dxn || (bwd && rfmt == 2 && a->wxpack && a->dxn_dir_stride > 0 && a->dxn_dir_stride < (1ll << 29) && !a->run_if),
              "%s: dxn (d(xn) inside the BPTT, ABI v19) needs rfmt 2, wxpack (ws_lstm_pack_dx_f8), 0 < dxn_dir_stride < 2^29 floats "
              "(32-bit store offsets) and no run_if", who);
   return WS_OK;

@@ -199,9 +199,13 @@ int ws_launch_lstm_pack_dx_f8(const float* wcat, float* pack, hipStream_t s) {
 // H2P (BLK only; ws_lstm_args.rfmt = WS_LSTM_FWD_H2P): hcat leaves as two fp16 planes instead of BLS pairs.  An instantiation of
 // its own, not a run-time flag: the pair-format kernels sit at 240-242 registers, and a branch around the h store pushed them
 // into scratch inside the step loop.
-template <bool BLK, int DBG, int GF = 0, bool H2P = false>
+// C16 (with H2P; ws_lstm_args.rfmt bit WS_LSTM_C16): the saved cell state leaves as fp16 in BLH(2H) (lstm_bf16_common.h enc_c16) --
+// one 8-byte store per run where the fp32 format has a 16-byte one, at the address of the hi plane's store.  Its own instantiation
+// for the reason H2P is one.
+template <bool BLK, int DBG, int GF = 0, bool H2P = false, bool C16 = false>
 __global__ __launch_bounds__(512, 2) void lstm_fwd_bf16_kernel(const ws_lstm_args p) {
   static_assert(!H2P || (BLK && DBG == 0), "the fp16 planes are a format of the blocked layout");
+  static_assert(!C16 || H2P, "the fp16 cell state is written next to the fp16 planes");
   __shared__ __attribute__((aligned(16))) __bf16 hl[2][2][SQ * HROW];  // [buf][part][seq][k] 66 KB
   __shared__ __attribute__((aligned(16))) float cl[SQ * (LH + 4)];     // cell state [seq][unit] 33 KB
   if (p.run_if && *p.run_if == 0u) return;  // predicated fall-back launch (wesep_hip.h): uniform
@@ -239,6 +243,7 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_bf16_kernel(const ws_lstm_arg
     return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + (long long)(blockIdx.x * L + t) * (SQ * 2 * LH * 2)),
                   SQ * 2 * LH * 2);
   };
+  auto c16rs = [&](int t) { return mkrsrc(p.cbuf + (long long)(blockIdx.x * L + t) * (SQ * LH), SQ * 2 * LH * 2); };   // BLH(2H)
   auto ld_gate = [&](int t, int g, int j) -> f32x4 {
     if constexpr (BLK) return bld(grs(t), glane, (g * 64 + 2 * j) * 512);
     else return *reinterpret_cast<const f32x4*>(p.gates + goff(t, g, j));
@@ -367,7 +372,8 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_bf16_kernel(const ws_lstm_arg
         st_gate(vf, t, 1, j);
         st_gate(vg, t, 2, j);
         st_gate(vo, t, 3, j);
-        st_ch(vc, p.cbuf, t, j);
+        if constexpr (C16) bst8(enc_c16(vc), c16rs(t), clane >> 1, j * 512);
+        else st_ch(vc, p.cbuf, t, j);
         if constexpr (H2P) {   // two fp16 planes: what the fused / cluster2 forward this launch stands in for writes
           u32x2 ph, pl;
           enc_h2p(vh, ph, pl);
@@ -405,8 +411,11 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_bf16_kernel(const ws_lstm_arg
 // parities' partial tiles meet in 16 KB of LDS behind the step's closing barrier, and waves 0..3 store plain rows of p.dxn + d *
 // p.dxn_dir_stride at the sequence map's positions.  ws_gemm_b2p(a_fmt 2) over d(gates) -- 2.1 GB read per band-view layer at
 // R = 32 -- is not launched; the GroupNorm backward adds the two directions (ws_gn_bwd_fused2).
-template <bool BLK, int DBG, int GF = 0, int RF = 0, bool DX = false>
+// C16 (ws_lstm_args.rfmt bit WS_LSTM_C16; BLK and WS_GATES_H2F only): p.cbuf holds fp16 cells in BLH(2H) (enc_c16): an 8-byte load
+// per run instead of 16; the raw cell waits in two registers and is decoded at its use, behind the prefetch fence (gate_cell).
+template <bool BLK, int DBG, int GF = 0, int RF = 0, bool DX = false, bool C16 = false>
 __global__ __launch_bounds__(512, 2) void lstm_bwd_bf16_kernel(const ws_lstm_args p) {
+  static_assert(!C16 || (BLK && GF == WS_GATES_H2F && !DX), "the fp16 cell state comes with the blocked layout and WS_GATES_H2F");
   static_assert(RF == 0 || (BLK && GF == WS_GATES_H2F), "the fp16 recurrence takes the scaled-fp16 d(gates) of WS_GATES_H2F");
   static_assert(!DX || RF == 2, "d(xn) in the BPTT rides on the fp16 d(gates) image of rfmt 2");
   __shared__ __attribute__((aligned(16))) __bf16 dgl[RF ? 1 : 2][SQ * DROW];  // [part][seq][gate col] 129 / 65 KB
@@ -452,6 +461,11 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_bf16_kernel(const ws_lstm_arg
   auto ld_ch = [&](const float* b, int t, int j) -> f32x4 {
     if constexpr (BLK) return bld(crs(b, t), clane, 2 * j * 512);
     else return *reinterpret_cast<const f32x4*>(b + coff(t, j));
+  };
+  typedef typename c_cell<C16>::type ccell;
+  auto ld_c = [&](int t, int j) -> ccell {
+    if constexpr (C16) return bld8(mkrsrc(p.cbuf + (long long)(bx * L + t) * (SQ * LH), SQ * 2 * LH * 2), clane >> 1, j * 512);   // BLH(2H)
+    else return ld_ch(p.cbuf, t, j);
   };
 
   // this wave's d(xn) k-steps of a chunk are kpar and kpar + 2, kpar = w >> 2 (the pack's order).  Waves 4..7 walk every PAIR of
@@ -527,7 +541,8 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_bf16_kernel(const ws_lstm_arg
   const __amdgpu_buffer_rsrc_t xors = __builtin_amdgcn_make_buffer_rsrc(
       DX ? p.dxn + (long long)d * p.dxn_dir_stride : nullptr, 0, DX ? (unsigned)(p.dxn_dir_stride * 4) : 0u, 0x00020000);
   gcell n_i[4], n_f[4], n_g[4], n_o[4];
-  f32x4 n_dh[4], n_cp[4], c_cur[4], dc[4];  // [run]
+  f32x4 n_dh[4], dc[4];  // [run]
+  ccell n_cp[4], c_cur[4];
   f32x16 dhr;
   const f32x4 zero4v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -544,14 +559,14 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_bf16_kernel(const ws_lstm_arg
     n_dh[j] = ld_ch(p.dhcat, t, j);
     // c_{t-1}; at the sequence start the step is clamped and the value is masked at its use
     const int tp = d == 0 ? max(t - 1, 0) : min(t + 1, L - 1);
-    n_cp[j] = ld_ch(p.cbuf, tp, j);
+    n_cp[j] = ld_c(tp, j);
   };
   {
     const int t0 = d == 0 ? L - 1 : 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       load_step(t0, j);
-      c_cur[j] = ld_ch(p.cbuf, t0, j);
+      c_cur[j] = ld_c(t0, j);
     }
   }
   // the ring's first two chunks BEHIND the first step's inputs, in the order of the steady state (there the inputs of step t + 1
@@ -583,12 +598,12 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_bf16_kernel(const ws_lstm_arg
       for (int r = 0; r < 4; ++r) {
         const float ig = vi[r], fg = vf[r], gg = vg[r], og = vo[r];
         const float dhv = dh_in<GF>(n_dh[j][r], dhr[4 * j + r], dS);
-        const float tc = ftanh(c_cur[j][r]);
+        const float tc = ftanh(c_at(c_cur[j], r));
         const float dov = dhv * tc;
         const float dcv = dc[j][r] + dhv * og * (1.f - tc * tc);
         dc[j][r] = dcv * fg;
         pi[r] = dcv * gg * ig * (1.f - ig);
-        pf[r] = dcv * (has_prev ? n_cp[j][r] : 0.f) * fg * (1.f - fg);
+        pf[r] = dcv * (has_prev ? c_at(n_cp[j], r) : 0.f) * fg * (1.f - fg);
         pg[r] = dcv * ig * (1.f - gg * gg);
         po[r] = dov * og * (1.f - og);
       }
@@ -766,6 +781,10 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_bf16_kernel(const ws_lstm_arg
 
 int ws_launch_lstm_fwd_bf16(const ws_lstm_args* a, hipStream_t s) {
   dim3 grid((a->nseq + SQ - 1) / SQ, 2), block(512);
+  if (a->rfmt == (WS_LSTM_FWD_H2P | WS_LSTM_C16)) {   // (lstm_check: with the planes and WS_GATES_H2F only)
+    hipLaunchKernelGGL((lstm_fwd_bf16_kernel<true, 0, WS_GATES_H2F, true, true>), grid, block, 0, s, *a);
+    return 0;
+  }
   if (a->rfmt == WS_LSTM_FWD_H2P) {   // (lstm_check: ws_lstm_fwd, blocked-layout modes, no probe builds)
     if (a->gfmt == WS_GATES_H2) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<true, 0, WS_GATES_H2, true>), grid, block, 0, s, *a);
     else if (a->gfmt == WS_GATES_H2S) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<true, 0, WS_GATES_H2S, true>), grid, block, 0, s, *a);
@@ -779,6 +798,13 @@ int ws_launch_lstm_fwd_bf16(const ws_lstm_args* a, hipStream_t s) {
 
 int ws_launch_lstm_bwd_bf16(const ws_lstm_args* a, hipStream_t s) {
   dim3 grid((a->nseq + SQ - 1) / SQ, 2), block(512);
+  if (a->rfmt & WS_LSTM_C16) {   // (lstm_check: WS_LSTM_BF16X3_BLK + WS_GATES_H2F, no dxn; rfmt 0 = the fall-back behind the pair BPTT)
+    const int rf = a->rfmt & ~WS_LSTM_C16;
+    if (rf == 2) hipLaunchKernelGGL((lstm_bwd_bf16_kernel<true, 0, WS_GATES_H2F, 2, false, true>), grid, block, 0, s, *a);
+    else if (rf == 3) hipLaunchKernelGGL((lstm_bwd_bf16_kernel<true, 0, WS_GATES_H2F, 3, false, true>), grid, block, 0, s, *a);
+    else hipLaunchKernelGGL((lstm_bwd_bf16_kernel<true, 0, WS_GATES_H2F, 0, false, true>), grid, block, 0, s, *a);
+    return 0;
+  }
   if (a->rfmt == 2 && a->dxn) {   // (lstm_check: rfmt 2, wxpack and a sequence map given)
     hipLaunchKernelGGL((lstm_bwd_bf16_kernel<true, 0, WS_GATES_H2F, 2, true>), grid, block, 0, s, *a);
     return 0;

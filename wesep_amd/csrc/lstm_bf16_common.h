@@ -180,6 +180,28 @@ __device__ __forceinline__ void enc_h2p(const f32x4& vh, u32x2& hi, u32x2& lo) {
 }
 __device__ __forceinline__ long long ws_h2p_plane(long long nblk) { return nblk * (SQ * 2 * LH * 2); }  // bytes of one plane
 
+// fp16 storage of the saved cell state ("C16", include/wesep_hip.h): cbuf holds fp16(c), round to nearest even, in BLH(2H) -- the
+// hi plane's layout, a lane's 4-column cell 8 bytes at half the fp32 cell's offset.  The recurrence itself keeps c in fp32; the
+// BPTT reads c only as tanh(c_t) and as the factor c_{t-1} of d(f).  The value is pinned before the conversion like h in enc_h2p:
+// where vc[j] is still fg * c + ig * gg the compiler otherwise converts the UNROUNDED sum (v_fma_mixlo_f16) and the stored
+// cell is no longer fp16 of the fp32 cell the next step continues from.
+__device__ __forceinline__ u32x2 enc_c16(const f32x4& vc) {
+  f16x4 h;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float x = vc[j];
+    asm volatile("" : "+v"(x));
+    h[j] = (_Float16)x;
+  }
+  return __builtin_bit_cast(u32x2, h);
+}
+// A saved cell as the BPTT kernels keep it between its (prefetching) load and its use: raw, decoded at the use (gate_cell below)
+template <bool C16> struct c_cell { typedef f32x4 type; };
+template <> struct c_cell<true> { typedef u32x2 type; };
+// element r of a cell (the fp32 form is the plain subscript: those instantiations compile to what they were)
+__device__ __forceinline__ float c_at(const f32x4& c, int r) { return c[r]; }
+__device__ __forceinline__ float c_at(const u32x2& c, int r) { return (float)__builtin_bit_cast(f16x4, c)[r]; }
+
 // the 8-byte d(gates) cell of the two in-place-capable 2-byte formats (H2F: v is the SCALED value)
 template <int GF>
 __device__ __forceinline__ u32x2 enc_dgates(const f32x4& v, const bf16x4& hi) {

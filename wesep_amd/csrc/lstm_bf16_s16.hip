@@ -76,8 +76,10 @@ int ws_launch_lstm_pack_s16(const float* whh_f, const float* whh_r, float* pack_
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
-template <int GF, bool H2P = false>  // WS_GATES_*; H2P: hcat as two fp16 planes, an instantiation of its own (lstm_bf16.hip)
+// C16 (with H2P): the saved cell state as fp16 in BLH(2H) (lstm_bf16_common.h enc_c16)
+template <int GF, bool H2P = false, bool C16 = false>  // WS_GATES_*; H2P: hcat as two fp16 planes, an instantiation of its own (lstm_bf16.hip)
 __global__ __launch_bounds__(512, 2) void lstm_fwd_s16_kernel(const ws_lstm_args p) {
+  static_assert(!C16 || H2P, "the fp16 cell state is written next to the fp16 planes");
   __shared__ __attribute__((aligned(16))) __bf16 hl[2][2][S16 * HROW];  // [buf][part][seq][k] 33 KB
   __shared__ __attribute__((aligned(16))) float cl[S16 * (LH + 4)];     // cell state [seq][unit]
   if (p.run_if && *p.run_if == 0u) return;  // predicated fall-back launch (wesep_hip.h): uniform
@@ -110,6 +112,8 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_s16_kernel(const ws_lstm_args
   auto prs = [&](int t, int pl) {
     return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + (long long)(tile * L + t) * (SQ * 2 * LH * 2)), SQ * 2 * LH * 2);
   };
+
+  auto c16rs = [&](int t) { return mkrsrc(p.cbuf + (long long)(tile * L + t) * (SQ * LH), SQ * 2 * LH * 2); };   // BLH(2H)
 
   const int ubase = 32 * w + 4 * mq;  // unit of (tu, r): ubase + 16tu + r
   float* cme = &cl[n * (LH + 4) + ubase];
@@ -216,7 +220,8 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_s16_kernel(const ws_lstm_args
       st_gate(vf, t, 1, tu);
       st_gate(vg, t, 2, tu);
       st_gate(vo, t, 3, tu);
-      st_ch(vc, p.cbuf, t, tu);
+      if constexpr (C16) bst8(enc_c16(vc), c16rs(t), clane >> 1, 2 * tu * 512);
+      else st_ch(vc, p.cbuf, t, tu);
       if constexpr (H2P) {
         u32x2 ph, pl;
         enc_h2p(vh, ph, pl);
@@ -238,8 +243,10 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_s16_kernel(const ws_lstm_args
 #ifndef S16_DBG
 #define S16_DBG 0  // probe builds: 1 no next-step loads, 2 no gate-gradient stores, 4 no weight reloads
 #endif
-template <int GF>
+// C16 (WS_GATES_H2F only): p.cbuf holds fp16 cells in BLH(2H), kept raw until their use (lstm_bf16.hip)
+template <int GF, bool C16 = false>
 __global__ __launch_bounds__(512, 2) void lstm_bwd_s16_kernel(const ws_lstm_args p) {
+  static_assert(!C16 || GF == WS_GATES_H2F, "the fp16 cell state comes with WS_GATES_H2F");
   __shared__ __attribute__((aligned(16))) __bf16 dgl[2][S16 * DROW];  // [part][seq][gate col] 66 KB
   if (p.run_if && *p.run_if == 0u) return;  // predicated fall-back launch (wesep_hip.h): uniform
   const int d = blockIdx.y;
@@ -264,6 +271,11 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_s16_kernel(const ws_lstm_args
   };
   auto st_gate = [&](const f32x4& v, int t, int g, int tu) { bst(v, grs(t), glane, (g * 64 + 4 * tu) * 512); };
   auto ld_ch = [&](const float* b, int t, int tu) -> f32x4 { return bld(crs(b, t), clane, 4 * tu * 512); };
+  typedef typename c_cell<C16>::type ccell;
+  auto ld_c = [&](int t, int tu) -> ccell {
+    if constexpr (C16) return bld8(mkrsrc(p.cbuf + (long long)(tile * L + t) * (SQ * LH), SQ * 2 * LH * 2), clane >> 1, 2 * tu * 512);
+    else return ld_ch(p.cbuf, t, tu);
+  };
   const int ubase = 32 * w + 4 * mq;
 
   // weight stream: per k-step (32 gate columns) 4 fragments (2 tiles x {hi, lo}); ring slots hold 4 k-steps
@@ -277,7 +289,8 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_s16_kernel(const ws_lstm_args
     for (int f = 0; f < 16; ++f) wr[s][f] = wload(wrs, wlane + (f & 3) * 1024, s * 16384 + (f >> 2) * 4096);
 
   gcell n_i[2], n_f[2], n_g[2], n_o[2];
-  f32x4 n_dh[2], n_cp[2], c_cur[2], dc[2], dhr[2];
+  f32x4 n_dh[2], dc[2], dhr[2];
+  ccell n_cp[2], c_cur[2];
   const f32x4 zero4v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int tu = 0; tu < 2; ++tu) dc[tu] = dhr[tu] = zero4v;
@@ -288,14 +301,14 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_s16_kernel(const ws_lstm_args
     n_o[tu] = ld_gate(t, 3, tu);
     n_dh[tu] = ld_ch(p.dhcat, t, tu);
     const int tp = d == 0 ? max(t - 1, 0) : min(t + 1, L - 1);  // clamped; masked at its use
-    n_cp[tu] = ld_ch(p.cbuf, tp, tu);
+    n_cp[tu] = ld_c(tp, tu);
   };
   {
     const int t0 = d == 0 ? L - 1 : 0;
 #pragma unroll
     for (int tu = 0; tu < 2; ++tu) {
       load_step(t0, tu);
-      c_cur[tu] = ld_ch(p.cbuf, t0, tu);
+      c_cur[tu] = ld_c(t0, tu);
     }
   }
 
@@ -317,12 +330,12 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_s16_kernel(const ws_lstm_args
       for (int r = 0; r < 4; ++r) {
         const float ig = vi[r], fg = vf[r], gg = vg[r], og = vo[r];
         const float dhv = dh_in<GF>(n_dh[tu][r], dhr[tu][r], dS);
-        const float tc = ftanh(c_cur[tu][r]);
+        const float tc = ftanh(c_at(c_cur[tu], r));
         const float dov = dhv * tc;
         const float dcv = dc[tu][r] + dhv * og * (1.f - tc * tc);
         dc[tu][r] = dcv * fg;
         pi[r] = dcv * gg * ig * (1.f - ig);
-        pf[r] = dcv * (has_prev ? n_cp[tu][r] : 0.f) * fg * (1.f - fg);
+        pf[r] = dcv * (has_prev ? c_at(n_cp[tu], r) : 0.f) * fg * (1.f - fg);
         pg[r] = dcv * ig * (1.f - gg * gg);
         po[r] = dov * og * (1.f - og);
       }
@@ -386,7 +399,8 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_s16_kernel(const ws_lstm_args
 int ws_launch_lstm_fwd_s16(const ws_lstm_args* a, hipStream_t s) {
   dim3 grid(2 * ((a->nseq + SQ - 1) / SQ), 2), block(512);
   const bool h2p = a->rfmt == WS_LSTM_FWD_H2P;
-  if (a->gfmt && h2p) hipLaunchKernelGGL((lstm_fwd_s16_kernel<WS_GATES_H2, true>), grid, block, 0, s, *a);
+  if (a->rfmt == (WS_LSTM_FWD_H2P | WS_LSTM_C16)) hipLaunchKernelGGL((lstm_fwd_s16_kernel<WS_GATES_H2, true, true>), grid, block, 0, s, *a);
+  else if (a->gfmt && h2p) hipLaunchKernelGGL((lstm_fwd_s16_kernel<WS_GATES_H2, true>), grid, block, 0, s, *a);
   else if (h2p) hipLaunchKernelGGL((lstm_fwd_s16_kernel<0, true>), grid, block, 0, s, *a);
   else if (a->gfmt) hipLaunchKernelGGL(lstm_fwd_s16_kernel<WS_GATES_H2>, grid, block, 0, s, *a);
   else hipLaunchKernelGGL(lstm_fwd_s16_kernel<0>, grid, block, 0, s, *a);
@@ -395,7 +409,8 @@ int ws_launch_lstm_fwd_s16(const ws_lstm_args* a, hipStream_t s) {
 
 int ws_launch_lstm_bwd_s16(const ws_lstm_args* a, hipStream_t s) {
   dim3 grid(2 * ((a->nseq + SQ - 1) / SQ), 2), block(512);
-  if (a->gfmt == WS_GATES_H2) hipLaunchKernelGGL(lstm_bwd_s16_kernel<WS_GATES_H2>, grid, block, 0, s, *a);
+  if (a->rfmt & WS_LSTM_C16) hipLaunchKernelGGL((lstm_bwd_s16_kernel<WS_GATES_H2F, true>), grid, block, 0, s, *a);
+  else if (a->gfmt == WS_GATES_H2) hipLaunchKernelGGL(lstm_bwd_s16_kernel<WS_GATES_H2>, grid, block, 0, s, *a);
   else if (a->gfmt == WS_GATES_H2S) hipLaunchKernelGGL(lstm_bwd_s16_kernel<WS_GATES_H2S>, grid, block, 0, s, *a);
   else if (a->gfmt == WS_GATES_H2F) hipLaunchKernelGGL(lstm_bwd_s16_kernel<WS_GATES_H2F>, grid, block, 0, s, *a);
   else hipLaunchKernelGGL(lstm_bwd_s16_kernel<0>, grid, block, 0, s, *a);

@@ -203,6 +203,10 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_cluster2_kernel(const ws_lstm
   auto prs = [&](int t, int pl) {
     return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + ((long long)2 * cc * L + t) * (cblk * 2)), 0x7fffffffu);
   };
+  // rfmt bit 2 (C16, wesep_hip.h): the saved cell state leaves as fp16 in BLH(2H) blocks -- the hi plane's layout, ONE 8-byte store
+  // where the fp32 format has a 16-byte one (the stores per step do not change).  Uniform over the launch.
+  const bool c16 = (p.rfmt & 4) != 0;
+  auto c16rs = [&](int t) { return mkrsrc(p.cbuf + ((long long)2 * cc * L + t) * (cblk / 2), 0x7fffffffu); };
   // xn: BL(128) blocks of 16 KB holding BLS pairs; EVERY thread feeds four 16-byte units of its own tile's block (tile
   // 2cc + st: the block is L blocks from the other tile's)
   const char* xbase = reinterpret_cast<const char*>(p.xn);
@@ -269,7 +273,8 @@ __global__ __launch_bounds__(512, 2) void lstm_fwd_cluster2_kernel(const ws_lstm
         bst8(u32x2{pr[0], pr[1]}, hrs(tprev), (gvo + e * gts) >> 1, (2 * g2) * 64 * 256);
         bst8(u32x2{pr[2], pr[3]}, hrs(tprev), (gvo + e * gts) >> 1, (2 * g2 + 1) * 64 * 256);
       }
-      bst(e == 0 ? c4 : outc[mt], crs(p.cbuf, tprev), cvo + e * cts, 0);
+      if (c16) bst8(enc_c16(e == 0 ? c4 : outc[mt]), c16rs(tprev), (cvo + e * cts) >> 1, 0);
+      else bst(e == 0 ? c4 : outc[mt], crs(p.cbuf, tprev), cvo + e * cts, 0);
       if (h2p) {   // the staged cell is (hi cell | lo cell): one 8-byte BLH store into each plane
         const u32x4 hc = __builtin_bit_cast(u32x4, outl[2][ct]);
         bst8(u32x2{hc[0], hc[1]}, prs(tprev, 0), (cvo + e * cts) >> 1, 0);
@@ -422,8 +427,9 @@ extern "C" int ws_lstm_fwd_cluster2(const ws_lstm_cluster2_args* a, void* stream
   e = hipMemsetAsync(a->tword, 0, sizeof(unsigned), s);
   WS_REQUIRE(e == hipSuccess, "ws_lstm_fwd_cluster2: hipMemsetAsync failed");
   ws_prof_begin(WS_PROF_LSTM_FWD, s);
-  WS_REQUIRE((a->rfmt & ~3) == 0,
-             "ws_lstm_fwd_cluster2: rfmt %d (bit 0: the lo term of W_hh on the FP8 MFMA; bit 1: hcat out as two fp16 planes)", a->rfmt);
+  WS_REQUIRE((a->rfmt & ~7) == 0,
+             "ws_lstm_fwd_cluster2: rfmt %d (bit 0: the lo term of W_hh on the FP8 MFMA; bit 1: hcat out as two fp16 planes; bit 2: "
+             "cbuf out as fp16)", a->rfmt);
   if (a->rfmt & 1) {
     if (a->dbg & 2048) hipLaunchKernelGGL((lstm_fwd_cluster2_kernel<false, true, true>), dim3(grid), dim3(512), 0, s, *a);
     else if (a->dbg & 8) hipLaunchKernelGGL((lstm_fwd_cluster2_kernel<true, false, true>), dim3(grid), dim3(512), 0, s, *a);

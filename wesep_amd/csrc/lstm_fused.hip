@@ -159,9 +159,12 @@ extern "C" int ws_lstm_pack_fused_h8(const float* wih_f, const float* wih_r, con
 // part-1 plane of each buffer (unused by the fp16 format)
 // H2P (hfmt bit 3, with H16): h leaves for HBM as two fp16 planes (enc_h2p: hi = the recurrent operand itself, lo = fp16(h - hi))
 // instead of the bf16 pair -- two 8-byte BLH stores per run instead of one 16-byte BLS store, the same bytes
-template <int GF, bool H16 = false, bool F8 = false, bool H2P = false>  // WS_GATES_*: != 0 -> activated gates leave as unorm16 (BLH), lstm_bf16_common.h
+// C16 (hfmt bit 4, with H2P): the saved cell state leaves as fp16 in BLH(2H) (enc_c16) -- one 8-byte store per run at the hi plane's
+// address where the fp32 format has a 16-byte one; the recurrence keeps c in fp32 (LDS)
+template <int GF, bool H16 = false, bool F8 = false, bool H2P = false, bool C16 = false>  // WS_GATES_*: != 0 -> activated gates leave as unorm16 (BLH), lstm_bf16_common.h
 __global__ __launch_bounds__(512, 1) void lstm_fwd_fused_kernel(const ws_lstm_fused_args p) {
   static_assert(!F8 || H16, "the FP8 lo term belongs to the fp16-h kernel");
+  static_assert(!C16 || H2P, "the fp16 cell state is written next to the fp16 planes");
   static_assert(!H2P || H16, "the fp16 planes are written by the fp16-h kernels");
   __shared__ __attribute__((aligned(16))) __bf16 hl[2][2][SQ * HROW];  // [buf][part][seq][k]  66 KB
   __shared__ __attribute__((aligned(16))) __bf16 xl[2][2][SQ * XROW];  // [buf][part][seq][k]  34 KB
@@ -194,6 +197,7 @@ __global__ __launch_bounds__(512, 1) void lstm_fwd_fused_kernel(const ws_lstm_fu
     return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + (long long)(blockIdx.x * L + t) * (SQ * 2 * LH * 2)),
                   SQ * 2 * LH * 2);
   };
+  auto c16rs = [&](int t) { return mkrsrc(p.cbuf + (long long)(blockIdx.x * L + t) * (SQ * LH), SQ * 2 * LH * 2); };   // BLH(2H)
   // x tile of one step = one BL(128) block: 1024 cells of 16 B, cell u = quad * 32 + slot; thread: u = tid, tid + 512
   auto ld_x = [&](int t, int q) -> f32x4 { return bld(xrs(t), tid * 16, q * 8192); };
   auto st_x = [&](const f32x4& v, int buf, int q) {  // cell u -> row slot, columns 4*quad .. +3
@@ -366,7 +370,8 @@ __global__ __launch_bounds__(512, 1) void lstm_fwd_fused_kernel(const ws_lstm_fu
       st_gate(vf, t, 1, j);
       st_gate(vg, t, 2, j);
       st_gate(vo, t, 3, j);
-      st_ch(vc, p.cbuf, t, j);
+      if constexpr (C16) bst8(enc_c16(vc), c16rs(t), clane >> 1, j * 512);
+      else st_ch(vc, p.cbuf, t, j);
       if constexpr (H2P) {
         u32x2 ph, pl;
         enc_h2p(vh, ph, pl);
@@ -420,11 +425,13 @@ struct fused64_lds {
 // twice the fp16 rate: 4 776 against 2 184 TFLOP/s measured, profiles/r06_c20_f8_probe.txt) replaces four fp16 MFMAs of K = 16:
 // per recurrent k-step four hi MFMAs + one FP8 MFMA (gate q & 3 of k block q >> 2) instead of eight, 6 KB of stream instead of 8.
 // H2P (hfmt bit 3, with H16): h leaves as two fp16 planes, as in lstm_fwd_fused_kernel.
-template <int GF, bool W1 = false, bool H16 = false, bool F8 = false, bool H2P = false>
+// C16 (hfmt bit 4, with H2P): the saved cell state leaves as fp16 in BLH(2H), as in lstm_fwd_fused_kernel.
+template <int GF, bool W1 = false, bool H16 = false, bool F8 = false, bool H2P = false, bool C16 = false>
 __device__ __forceinline__ void lstm_fwd_fused64_body(const ws_lstm_fused_args& p) {
   static_assert(!(W1 && H16), "W1 is a measurement build of the three-term kernel");
   static_assert(!H2P || H16, "the fp16 planes are written by the fp16-h kernels");
   static_assert(!F8 || H16, "the FP8 lo term belongs to the fp16-h kernel");
+  static_assert(!C16 || H2P, "the fp16 cell state is written next to the fp16 planes");
   __shared__ __attribute__((aligned(16))) fused64_lds sm;
   auto& xw = sm.xw;
   auto& hl = sm.hl;
@@ -463,6 +470,7 @@ __device__ __forceinline__ void lstm_fwd_fused64_body(const ws_lstm_fused_args& 
   auto prs = [&](int e, int t, int pl) {
     return mkrsrc(reinterpret_cast<const float*>(hplane + pl * hlo_off + blk(e, t) * (SQ * 2 * LH * 2)), lim(e, SQ * 2 * LH * 2));
   };
+  auto c16rs = [&](int e, int t) { return mkrsrc(p.cbuf + blk(e, t) * (SQ * LH), lim(e, SQ * 2 * LH * 2)); };   // BLH(2H)
   // x tile of one step = one BL(128) block of 16 KB: wave w copies cells 64w .. 64w+63 and 512 + 64w .. of each tile
   auto dma_x = [&](int e, int t) {
 #pragma unroll
@@ -653,7 +661,8 @@ __device__ __forceinline__ void lstm_fwd_fused64_body(const ws_lstm_fused_args& 
         st_gate(vf, e, t, 1, j);
         st_gate(vg, e, t, 2, j);
         st_gate(vo, e, t, 3, j);
-        bst(vc, crs(p.cbuf, e, t), clane, 2 * j * 512);
+        if constexpr (C16) bst8(enc_c16(vc), c16rs(e, t), clane >> 1, j * 512);   // (ONE store, like the fp32 cell: the count below stands)
+        else bst(vc, crs(p.cbuf, e, t), clane, 2 * j * 512);
         if constexpr (H2P) {
           u32x2 ph, pl;
           enc_h2p(vh, ph, pl);
@@ -672,6 +681,7 @@ __device__ __forceinline__ void lstm_fwd_fused64_body(const ws_lstm_fused_args& 
     // drain under them.  (ws_lstm_fused_args.hfmt bit 1, WESEP_FUSED_DRAIN=1: the old wait, for A/B.)
     // H2P: h is two stores per run (hi and lo cell), 2 tiles x 4 runs x (4 gates + c + 2) = 56 behind the DMA loads; the counter
     // holds 6 bits on this target (63).  A dead second tile's stores are still issued (zero-sized descriptors drop them).
+    // C16 changes the WIDTH of the c store (8 bytes instead of 16), not the number of stores: 48 / 56 stay exactly as they are.
     if (p.hfmt & 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else if constexpr (H2P) asm volatile("s_waitcnt vmcnt(56)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
@@ -701,13 +711,22 @@ __global__ __launch_bounds__(512, 1) void lstm_fwd_fused64h8p_kernel(const ws_ls
   lstm_fwd_fused64_body<WS_GATES_H2, false, true, true, true>(p);
 }
 
+__global__ __launch_bounds__(512, 1) void lstm_fwd_fused64h16pc_kernel(const ws_lstm_fused_args p) {   // hfmt 25: + c out as fp16
+  lstm_fwd_fused64_body<WS_GATES_H2, false, true, false, true, true>(p);
+}
+__global__ __launch_bounds__(512, 1) void lstm_fwd_fused64h8pc_kernel(const ws_lstm_fused_args p) {   // hfmt 29
+  lstm_fwd_fused64_body<WS_GATES_H2, false, true, true, true, true>(p);
+}
+
 extern "C" int ws_lstm_fwd_fused(const ws_lstm_fused_args* a, void* stream) {
   WS_REQUIRE(a && a->gates && a->cbuf && a->hcat && a->xn && a->wpack && a->bias, "ws_lstm_fwd_fused: null pointer");
   WS_REQUIRE(a->nseq > 0 && a->L > 0, "ws_lstm_fwd_fused: bad nseq/L");
   WS_REQUIRE(a->gfmt >= WS_GATES_F32 && a->gfmt <= WS_GATES_H2F, "ws_lstm_fwd_fused: gfmt %d", a->gfmt);
-  WS_REQUIRE((a->hfmt & ~15) == 0 && (!(a->hfmt & 1) || a->gfmt != WS_GATES_F32) && (!(a->hfmt & 12) || (a->hfmt & 1)),
+  WS_REQUIRE((a->hfmt & ~31) == 0 && (!(a->hfmt & 1) || a->gfmt != WS_GATES_F32) && (!(a->hfmt & 12) || (a->hfmt & 1)) &&
+                 (!(a->hfmt & 16) || (a->hfmt & 8)),
              "ws_lstm_fwd_fused: hfmt %d (1 = fp16 h, pack from ws_lstm_pack_fused_h16; 5 = + FP8 lo term, pack from "
-             "ws_lstm_pack_fused_h8; bit 3 = h out as two fp16 planes, with bit 0; 2-byte gate formats only)", a->hfmt);
+             "ws_lstm_pack_fused_h8; bit 3 = h out as two fp16 planes, with bit 0; bit 4 = cbuf out as fp16, with bit 3; 2-byte gate "
+             "formats only)", a->hfmt);
   const int ntile = (a->nseq + SQ - 1) / SQ;
   dim3 grid(ntile, 2), block(512);
   hipStream_t s = (hipStream_t)stream;
@@ -723,7 +742,15 @@ extern "C" int ws_lstm_fwd_fused(const ws_lstm_fused_args* a, void* stream) {
   ws_prof_begin(WS_PROF_LSTM_FWD, s);
   const char* w1 = getenv("WS_FUSED_W1");   // measurement only: one weight plane (bf16 weights), see lstm_fwd_fused64_body
   const bool h2p = (a->hfmt & 8) != 0;
-  if (h2p && (a->hfmt & 4) && wide)
+  if ((a->hfmt & 16) && (a->hfmt & 4) && wide)
+    hipLaunchKernelGGL(lstm_fwd_fused64h8pc_kernel, dim3((ntile + 1) / 2, 2), block, 0, s, *a);
+  else if ((a->hfmt & 16) && (a->hfmt & 4))
+    hipLaunchKernelGGL((lstm_fwd_fused_kernel<WS_GATES_H2, true, true, true, true>), grid, block, 0, s, *a);
+  else if ((a->hfmt & 16) && wide)
+    hipLaunchKernelGGL(lstm_fwd_fused64h16pc_kernel, dim3((ntile + 1) / 2, 2), block, 0, s, *a);
+  else if (a->hfmt & 16)
+    hipLaunchKernelGGL((lstm_fwd_fused_kernel<WS_GATES_H2, true, false, true, true>), grid, block, 0, s, *a);
+  else if (h2p && (a->hfmt & 4) && wide)
     hipLaunchKernelGGL(lstm_fwd_fused64h8p_kernel, dim3((ntile + 1) / 2, 2), block, 0, s, *a);
   else if (h2p && (a->hfmt & 4))
     hipLaunchKernelGGL((lstm_fwd_fused_kernel<WS_GATES_H2, true, true, true>), grid, block, 0, s, *a);

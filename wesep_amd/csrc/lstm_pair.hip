@@ -276,9 +276,13 @@ __device__ __forceinline__ f32x16 pair_mfma(const bf16x8& a, const bf16x8& b, co
 // into the MFMA (v_cvt_scalef32_pk_f16_fp8 at scale 1: codes are exact in fp16; the block scale multiplies the lo
 // accumulator once per step).  No load of W_hh inside the step loop: what the side stream's GEMMs do to L2 no longer
 // reaches the MFMA phase.  Emulation first (probe 32768: no gradient moves, fixture size and 501 frames).
-template <int V, int GF = 0, int RF = 0>
+// C16 (ws_lstm_pair_args.rfmt bit WS_LSTM_C16, with RF = 2 / 3): p.cbuf holds the saved cells as fp16 in BLH(2H) (lstm_bf16_common.h
+// enc_c16): 8-byte loads, the raw cell waits in two registers and is decoded at its use (as the gates: gate_cell); the touches
+// go to the same lines.
+template <int V, int GF = 0, int RF = 0, bool C16 = false>
 __global__ __launch_bounds__(512, 2) void lstm_bwd_pair_kernel(const ws_lstm_pair_args p) {
   static_assert(RF == 0 || GF == WS_GATES_H2F, "the fp16 recurrence takes the scaled-fp16 d(gates) of WS_GATES_H2F");
+  static_assert(!C16 || RF >= 2, "the fp16 cell state comes with the resident-weight kernels");
   constexpr int PAIR_LDSK = pair_ldsk<RF>::value;
   __shared__ __attribute__((aligned(16))) __bf16 bimg[RF ? 1 : 2][SQ * PR_ROW];  // [part][seq][local gate col] 65 / 33 KB
   constexpr int LDSK8 = 27;   // RF = 2: k-steps of the 8-byte lo fragments in LDS (108 KB: what 160 KB leave); 5 in registers
@@ -321,6 +325,12 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_pair_kernel(const ws_lstm_pai
   auto ld_gate = [&](int t, int g, int e) -> gcell {
     if constexpr (GF != 0) return bld8(hrs(t), gvo >> 1, (g * 64 + 2 * e) * 256);
     else return bld(grs(t), gvo, (g * 64 + 2 * e) * 512);
+  };
+  typedef typename c_cell<C16>::type ccell;
+  auto c16rs = [&](int t) { return mkrsrc(p.cbuf + (long long)(tile * L + t) * (SQ * LH), SQ * 2 * LH * 2); };   // BLH(2H)
+  auto ld_c = [&](int t, int e) -> ccell {
+    if constexpr (C16) return bld8(c16rs(t), cvo >> 1, e * 512);
+    else return bld(crs(p.cbuf, t), cvo, 2 * e * 512);
   };
   // ---- exchange: X[pair][parity][destination member][cell] x 16 B; flags[pair][source member][wave]
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
@@ -377,7 +387,8 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_pair_kernel(const ws_lstm_pai
   f32x4* mineo = &rec[role ^ 1][(wx * 2) * 64 + lane];  // ... and write the half the other role's cells need
 
   gcell n_i[2], n_f[2], n_g[2], n_o[2];
-  f32x4 n_dh[2], n_cp[2], c_cur[2], dc[2], mine[2];
+  f32x4 n_dh[2], dc[2], mine[2];
+  ccell n_cp[2], c_cur[2];
   const f32x4 zero4v = {0.f, 0.f, 0.f, 0.f};
   auto load_step = [&](int t, int e) {
     n_i[e] = ld_gate(t, 0, e);
@@ -386,7 +397,7 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_pair_kernel(const ws_lstm_pai
     n_o[e] = ld_gate(t, 3, e);
     n_dh[e] = bld(crs(p.dhcat, t), cvo, 2 * e * 512);
     const int tp = d == 0 ? max(t - 1, 0) : min(t + 1, L - 1);  // clamped; masked at its use
-    n_cp[e] = bld(crs(p.cbuf, tp), cvo, 2 * e * 512);
+    n_cp[e] = ld_c(tp, e);
   };
   // the same twelve addresses as load_step(t, 0 / 1), one dword per lane, normal cache policy (the loads proper are nt),
   // destination: one register nobody reads.  Inline asm: the compiler keeps no count of these loads (its own vmcnt waits
@@ -403,7 +414,8 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_pair_kernel(const ws_lstm_pai
 #pragma unroll
       for (int g = 0; g < 4; ++g) touch(hrs(t), gvo >> 1, (g * 64 + 2 * e) * 256);
       touch(crs(p.dhcat, t), cvo, 2 * e * 512);
-      touch(crs(p.cbuf, tp), cvo, 2 * e * 512);
+      if constexpr (C16) touch(c16rs(tp), cvo >> 1, e * 512);
+      else touch(crs(p.cbuf, tp), cvo, 2 * e * 512);
     }
   };
   {
@@ -411,7 +423,7 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_pair_kernel(const ws_lstm_pai
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       load_step(t0, e);
-      c_cur[e] = bld(crs(p.cbuf, t0), cvo, 2 * e * 512);
+      c_cur[e] = ld_c(t0, e);
       dc[e] = mine[e] = zero4v;
     }
   }
@@ -453,12 +465,12 @@ __global__ __launch_bounds__(512, 2) void lstm_bwd_pair_kernel(const ws_lstm_pai
       for (int r = 0; r < 4; ++r) {
         const float ig = vi[r], fg = vf[r], gg = vg[r], og = vo[r];
         const float dhv = dh_in<GF>(n_dh[e][r], dhr[r], dS);
-        const float tc = ftanh(c_cur[e][r]);
+        const float tc = ftanh(c_at(c_cur[e], r));
         const float dov = dhv * tc;
         const float dcv = dc[e][r] + dhv * og * (1.f - tc * tc);
         dc[e][r] = dcv * fg;
         pi[r] = dcv * gg * ig * (1.f - ig);
-        pf[r] = dcv * (has_prev ? n_cp[e][r] : 0.f) * fg * (1.f - fg);
+        pf[r] = dcv * (has_prev ? c_at(n_cp[e], r) : 0.f) * fg * (1.f - fg);
         pg[r] = dcv * ig * (1.f - gg * gg);
         po[r] = dov * og * (1.f - og);
       }
@@ -727,9 +739,13 @@ extern "C" int ws_lstm_bwd_pair(const ws_lstm_pair_args* a, void* stream) {
   WS_REQUIRE(a->gfmt >= WS_GATES_F32 && a->gfmt <= WS_GATES_H2F && (a->gfmt != WS_GATES_H2S || a->dgates) &&
                  (a->gfmt != WS_GATES_H2F || a->amax),
              "ws_lstm_bwd_pair: gfmt %d (WS_GATES_H2S needs dgates, WS_GATES_H2F needs amax)", a->gfmt);
-  WS_REQUIRE(a->rfmt == 0 || (a->rfmt >= 1 && a->rfmt <= 3 && a->gfmt == WS_GATES_H2F),
+  const int rfmt = a->rfmt & ~WS_LSTM_C16;
+  const bool c16 = (a->rfmt & WS_LSTM_C16) != 0;
+  WS_REQUIRE(rfmt == 0 || (rfmt >= 1 && rfmt <= 3 && a->gfmt == WS_GATES_H2F),
              "ws_lstm_bwd_pair: rfmt %d (1 / 2 / 3 = fp16 recurrence, fp16 + fp16 / fp16 + fp8 weights / + the lo term on the FP8 "
              "MFMA: WS_GATES_H2F only)", a->rfmt);
+  WS_REQUIRE(!c16 || ((rfmt == 2 || rfmt == 3) && !(a->dbg & 2048)),
+             "ws_lstm_bwd_pair: rfmt %d: the fp16 cell state (bit WS_LSTM_C16) goes with rfmt 2 / 3, no cycle stamps", a->rfmt);
   const int npair = 2 * ((a->nseq + SQ - 1) / SQ);
   static int cus = 0;      // same part on every device of a node; queried once
   if (!cus && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0) != hipSuccess) cus = 0;
@@ -739,11 +755,19 @@ extern "C" int ws_lstm_bwd_pair(const ws_lstm_pair_args* a, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(a->flags, 0, ((size_t)npair * 8 + 8) * sizeof(unsigned), s);
   WS_REQUIRE(e == hipSuccess, "ws_lstm_bwd_pair: hipMemsetAsync failed");
-  if (a->rfmt != 0) {   // data-tagged hand-off: every dword of the exchange slots starts with tag 1 (LSB set)
+  if (rfmt != 0) {   // data-tagged hand-off: every dword of the exchange slots starts with tag 1 (LSB set)
     e = hipMemsetAsync(a->xchg, 0x01, (size_t)npair * 4 * PR_XSLOT, s);
     WS_REQUIRE(e == hipSuccess, "ws_lstm_bwd_pair: hipMemsetAsync failed");
   }
   ws_prof_begin(WS_PROF_LSTM_BWD, s);
+  if (c16) {
+    if (rfmt == 3 && (a->dbg & 8)) hipLaunchKernelGGL((lstm_bwd_pair_kernel<8, WS_GATES_H2F, 3, true>), dim3(grid), dim3(512), 0, s, *a);
+    else if (rfmt == 3) hipLaunchKernelGGL((lstm_bwd_pair_kernel<0, WS_GATES_H2F, 3, true>), dim3(grid), dim3(512), 0, s, *a);
+    else if (a->dbg & 8) hipLaunchKernelGGL((lstm_bwd_pair_kernel<8, WS_GATES_H2F, 2, true>), dim3(grid), dim3(512), 0, s, *a);
+    else hipLaunchKernelGGL((lstm_bwd_pair_kernel<0, WS_GATES_H2F, 2, true>), dim3(grid), dim3(512), 0, s, *a);
+    ws_prof_end(WS_PROF_LSTM_BWD, s);
+    return ws_check_launch("ws_lstm_bwd_pair");
+  }
   if (a->rfmt == 3) {
     // (no stamped build of this variant: with the stamps in, the register allocator spills 128 registers -- not the kernel any more)
     WS_REQUIRE(!(a->dbg & 2048), "ws_lstm_bwd_pair: cycle stamps (dbg 2048) exist for rfmt 0 .. 2");

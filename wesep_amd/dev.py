@@ -438,10 +438,25 @@ def lstm_cat_ih(wih_f, wih_r, bih_f, bhh_f, bih_r, bhh_r, n_in, wcat, bcat):
                                    n_in, _p(wcat), _p(bcat), L.stream_ptr()), "ws_lstm_cat_ih")
 
 
-def _bptt_bytes(gfmt: int) -> int:
+def c16_on(device) -> bool:
+    """The saved cell state of the blocked BLSTM as fp16 in BLH(2H) (C16, wesep_hip.h) instead of fp32 BL: the forward
+    recurrences write 2 bytes per cell instead of 4, the BPTT kernels -- its only readers -- read 2.  Device buffers only, like
+    h2p_on: the host emulation and the ABI dry run keep fp32 cells.  WESEP_C16=0 restores fp32 (A/B runs; it reproduces the
+    launches of the format's absence bit for bit)."""
+    return device.type == "cuda" and torch.cuda.is_available() and os.environ.get("WESEP_C16", "1") != "0"
+
+
+C16_MAX_STEPS = 32768      # |c_t| <= t: below 65 504 steps fp16 cannot overflow; the plan keeps fp32 cells for longer sequences
+
+
+def _bptt_bytes(gfmt: int, c16=None) -> int:
     """Algorithmic bytes of one BPTT cell (position, direction, unit): 4 saved gates in, c and d(h) in (fp32), 4 d(gates)
-    out -- 40 B with fp32 gates / split-pair d(gates), 24 B with unorm16 gates and bf16 d(gates), 32 B for H2S."""
-    return {L.GATES_F32: 40, L.GATES_H2: 24, L.GATES_H2S: 32, L.GATES_H2F: 24}[gfmt]
+    out -- 40 B with fp32 gates / split-pair d(gates), 24 B with unorm16 gates and bf16 d(gates), 32 B for H2S; 2 B less with
+    the cell state as fp16 (C16).  c16 None (the bench tools): what the default plan of a device run stores -- fp16 cells with
+    GATES_H2F unless WESEP_C16=0; a launch passes its own format."""
+    if c16 is None:
+        c16 = gfmt == L.GATES_H2F and torch.cuda.is_available() and os.environ.get("WESEP_C16", "1") != "0"
+    return {L.GATES_F32: 40, L.GATES_H2: 24, L.GATES_H2S: 32, L.GATES_H2F: 24}[gfmt] - (2 if c16 else 0)
 
 
 def gates_fmt() -> int:
@@ -479,31 +494,33 @@ def _lstm_args(gates, cbuf, hcat, wpack, sm: SeqMap, mode, dhcat=None, run_if=No
     return a
 
 
-def lstm_fwd(gates, cbuf, hcat, wpack, sm: SeqMap, mode=L.LSTM_BF16X3, run_if=None, gfmt=0, gates_in=None, h2p=False):
+def lstm_fwd(gates, cbuf, hcat, wpack, sm: SeqMap, mode=L.LSTM_BF16X3, run_if=None, gfmt=0, gates_in=None, h2p=False, c16=False):
     """run_if: optional 1-element int32 device tensor; the launch is a no-op unless it is non-zero at kernel start.
     gfmt != 0 (blocked-layout modes): pre-activations from `gates_in` (fp32 BL), `gates` receives unorm16 (BLH).
-    h2p (blocked-layout modes): hcat leaves as two fp16 planes (H2P, wesep_hip.h) instead of BLS pairs."""
+    h2p (blocked-layout modes): hcat leaves as two fp16 planes (H2P, wesep_hip.h) instead of BLS pairs.
+    c16 (with h2p and GATES_H2F): cbuf leaves as fp16 in BLH(2H) (C16, wesep_hip.h) instead of fp32 BL."""
     a = _lstm_args(gates, cbuf, hcat, wpack, sm, mode, run_if=run_if, gfmt=gfmt, gates_in=gates_in,
-                   rfmt=L.LSTM_FWD_H2P if h2p else 0)
+                   rfmt=(L.LSTM_FWD_H2P if h2p else 0) | (L.LSTM_C16 if c16 else 0))
     if run_if is None:     # fp32 pre-activations in, gates (fp32 in place / unorm16) + c + h out
         u = ALG_LSTM_UNITS or L.LSTM_H
-        _alg("lstm_fwd", sm.nseq * sm.L * 2 * u * (16 + (2 if gfmt else 4) * 4 + 8), 2 * sm.nseq * sm.L * 2 * 4 * u * u)
+        _alg("lstm_fwd", sm.nseq * sm.L * 2 * u * (16 + (2 if gfmt else 4) * 4 + (6 if c16 else 8)), 2 * sm.nseq * sm.L * 2 * 4 * u * u)
     L.check(L.lib().ws_lstm_fwd(C.byref(a), L.stream_ptr()), "ws_lstm_fwd")
 
 
 def lstm_bwd(gates, cbuf, hcat, dhcat, wpack, sm: SeqMap, mode=L.LSTM_BF16X3, gfmt=0, dgates=None, run_if=None, amax=None,
-             rfmt=0, dxn=None, wxpack=None):
+             rfmt=0, dxn=None, wxpack=None, c16=False):
     """run_if (blocked-layout modes): 1-element int32 device tensor; the launch is a no-op unless it is non-zero at
     kernel start -- the predicated fall-back behind lstm_bwd_pair.  dgates: out-of-place d(gates) (required for
     GATES_H2S; optional BLH buffer for GATES_H2, which then leaves the saved gates intact).  rfmt = 2 (LSTM_BF16X3_BLK with
     GATES_H2F only): fp16 recurrence on fp16 + FP8 weights, wpack from lstm_pack_bwd_f8.  dxn [2, P, 128] + wxpack
     (lstm_pack_dx_f8; rfmt 2 only, ABI v19): the kernel also writes d(normalised input) per direction -- plain rows at the
-    sequence map's positions -- so that gemm_b2p over d(gates) is not needed (gn_bwd_fused(..., dxn2=) adds the two)."""
-    a = _lstm_args(gates, cbuf, hcat, wpack, sm, mode, dhcat, gfmt=gfmt, dgates=dgates, run_if=run_if, amax=amax, rfmt=rfmt,
-                   dxn=dxn, wxpack=wxpack)
+    sequence map's positions -- so that gemm_b2p over d(gates) is not needed (gn_bwd_fused(..., dxn2=) adds the two).
+    c16 (blocked-layout modes, GATES_H2F, no dxn): cbuf holds fp16 cells in BLH(2H) (C16, wesep_hip.h)."""
+    a = _lstm_args(gates, cbuf, hcat, wpack, sm, mode, dhcat, gfmt=gfmt, dgates=dgates, run_if=run_if, amax=amax,
+                   rfmt=rfmt | (L.LSTM_C16 if c16 else 0), dxn=dxn, wxpack=wxpack)
     # per (position, direction, unit): read 4 gates + c + dh, write 4 d(gates); 2 * 4H * H MACs per position
     if run_if is None:
-        _alg("lstm_bwd", _bptt_bytes(gfmt) * sm.nseq * sm.L * 2 * (ALG_LSTM_UNITS or L.LSTM_H),
+        _alg("lstm_bwd", _bptt_bytes(gfmt, c16) * sm.nseq * sm.L * 2 * (ALG_LSTM_UNITS or L.LSTM_H),
              2 * sm.nseq * sm.L * 2 * 4 * (ALG_LSTM_UNITS or L.LSTM_H) ** 2)
     L.check(L.lib().ws_lstm_bwd(C.byref(a), L.stream_ptr()), "ws_lstm_bwd")
 
@@ -703,8 +720,8 @@ def cluster2_rfmt() -> int:
 
 
 def lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whh_f, whh_r, sm: SeqMap, status=None, dbg=0, dbg_buf=None, rfmt=None,
-                      h2p=False):
-    """ws_lstm_fwd_cluster2: gates (unorm16 BLH), cbuf, hcat (BLS; h2p: two fp16 planes, rfmt bit 1) <- the BLSTM forward of the blocked-layout sequences from
+                      h2p=False, c16=False):
+    """ws_lstm_fwd_cluster2: gates (unorm16 BLH), cbuf (fp32 BL; c16: fp16 in BLH(2H), rfmt bit 2), hcat (BLS; h2p: two fp16 planes, rfmt bit 1) <- the BLSTM forward of the blocked-layout sequences from
     the normalised input xn (BL(128) of BLS pairs: gemm_p2b's A_bl), W_ih / biases as ws_lstm_cat_ih leaves them and the fp32
     W_hh.  Returns the launch's time-out word: pass it as `run_if` to gemm_p2b + lstm_fwd behind this call -- the predicated
     fall-back."""
@@ -721,10 +738,10 @@ def lstm_fwd_cluster2(gates, cbuf, hcat, xn, wcat, bcat, whh_f, whh_r, sm: SeqMa
     a.xchg, a.tword = C.c_void_p(xchg.data_ptr()), C.c_void_p(tw.data_ptr())
     a.status = C.c_void_p((status if status is not None else sc.status).data_ptr())
     a.nseq, a.L, a.dbg = sm.nseq, sm.L, dbg
-    a.rfmt = (cluster2_rfmt() if rfmt is None else rfmt) | (2 if h2p else 0)
+    a.rfmt = (cluster2_rfmt() if rfmt is None else rfmt) | (2 if h2p else 0) | (4 if c16 else 0)
     a.dbg_buf = C.c_void_p(dbg_buf.data_ptr()) if dbg_buf is not None else None
     u = ALG_LSTM_UNITS or L.LSTM_H     # (as lstm_fwd_fused: unorm16 gates + c + h out, the split-pair input in)
-    _alg("lstm_fwd", sm.nseq * sm.L * (2 * u * 16 + 4 * 128), 2 * sm.nseq * sm.L * 2 * 4 * u * (u + 128))
+    _alg("lstm_fwd", sm.nseq * sm.L * (2 * u * (14 if c16 else 16) + 4 * 128), 2 * sm.nseq * sm.L * 2 * 4 * u * (u + 128))
     L.check(L.lib().ws_lstm_fwd_cluster2(C.byref(a), L.stream_ptr()), "ws_lstm_fwd_cluster2")
     return tw
 
@@ -768,10 +785,11 @@ def lstm_pack_pair(whh_f, whh_r, pack, f16=False):
 
 
 def lstm_bwd_pair(gates, cbuf, dhcat, wpack, sm: SeqMap, status=None, dbg=0, dbg_buf=None, gfmt=0, dgates=None,
-                  repairable=False, amax=None, rfmt=0):
+                  repairable=False, amax=None, rfmt=0, c16=False):
     """BPTT on the blocked layout over pairs of workgroups (lstm_pair.hip); gates: activated gates in,
     d(pre-activation gates) (BLS) out.  Returns the launch's timeout word; in place, so there is no device-side
-    fall-back: poll_cluster_status raises (one step late, without a host sync) when a bounded wait timed out."""
+    fall-back: poll_cluster_status raises (one step late, without a host sync) when a bounded wait timed out.
+    c16 (rfmt 2 / 3): cbuf holds fp16 cells in BLH(2H) (C16, wesep_hip.h)."""
     for n, t in (("gates", gates), ("cbuf", cbuf), ("dhcat", dhcat), ("wpack", wpack), ("dgates", dgates)):
         _chk(t, n)
     npair = 2 * (-(-sm.nseq // 32))
@@ -787,8 +805,8 @@ def lstm_bwd_pair(gates, cbuf, dhcat, wpack, sm: SeqMap, status=None, dbg=0, dbg
     a.dbg_buf = C.c_void_p(dbg_buf.data_ptr()) if dbg_buf is not None else None
     a.gfmt, a.dgates = gfmt, _p(dgates)
     a.amax = C.c_void_p(amax.data_ptr()) if amax is not None else None
-    a.rfmt = rfmt           # 1 / 2: fp16 recurrence (wpack from lstm_pack_pair(..., f16=rfmt); WS_GATES_H2F only)
-    _alg("lstm_bwd", _bptt_bytes(gfmt) * sm.nseq * sm.L * 2 * (ALG_LSTM_UNITS or L.LSTM_H),
+    a.rfmt = rfmt | (L.LSTM_C16 if c16 else 0)   # 1 / 2 / 3: fp16 recurrence (wpack from lstm_pack_pair(..., f16=rfmt); WS_GATES_H2F only)
+    _alg("lstm_bwd", _bptt_bytes(gfmt, c16) * sm.nseq * sm.L * 2 * (ALG_LSTM_UNITS or L.LSTM_H),
              2 * sm.nseq * sm.L * 2 * 4 * (ALG_LSTM_UNITS or L.LSTM_H) ** 2)
     L.check(L.lib().ws_lstm_bwd_pair(C.byref(a), L.stream_ptr()), "ws_lstm_bwd_pair")
     return flags[npair * 8:npair * 8 + 1]
@@ -1460,16 +1478,19 @@ def lstm_pack_fused(wih_f, wih_r, whh_f, whh_r, pack, hfmt=0):
           _p(wih_f), _p(wih_r), _p(whh_f), _p(whh_r), _p(pack))
 
 
-def lstm_fwd_fused(gates, cbuf, hcat, xn, wpack, bias, sm: SeqMap, gfmt=0, hfmt=0):
+def lstm_fwd_fused(gates, cbuf, hcat, xn, wpack, bias, sm: SeqMap, gfmt=0, hfmt=0, c16=False):
+    """hfmt: ws_lstm_fused_args.hfmt (lstm_fused_hfmt; bit 3: hcat as two fp16 planes).  c16 (with hfmt bit 3): cbuf leaves as fp16
+    in BLH(2H) (C16, wesep_hip.h; hfmt bit 4)."""
     for n, t in (("gates", gates), ("cbuf", cbuf), ("hcat", hcat), ("xn", xn), ("wpack", wpack), ("bias", bias)):
         _chk(t, n)
     a = L.LstmFusedArgs()
     a.gates, a.cbuf, a.hcat, a.xn, a.wpack, a.bias = _p(gates), _p(cbuf), _p(hcat), _p(xn), _p(wpack), _p(bias)
     a.nseq, a.L, a.gfmt = sm.nseq, sm.L, gfmt
-    a.hfmt = hfmt | (2 if os.environ.get("WESEP_FUSED_DRAIN", "0") == "1" else 0)      # (bit 1: A/B of the end-of-step wait)
+    a.hfmt = hfmt | (16 if c16 else 0) | (2 if os.environ.get("WESEP_FUSED_DRAIN", "0") == "1" else 0)   # (bit 1: A/B of the end-of-step wait)
     # per (position, direction): 4H gates (2 B / 4 B) + c + h out, the 128-wide split-pair input in (shared by both directions)
     u = ALG_LSTM_UNITS or L.LSTM_H
-    _alg("lstm_fwd", sm.nseq * sm.L * (2 * u * ((2 if gfmt else 4) * 4 + 8) + 4 * 128), 2 * sm.nseq * sm.L * 2 * 4 * u * (u + 128))
+    _alg("lstm_fwd", sm.nseq * sm.L * (2 * u * ((2 if gfmt else 4) * 4 + (6 if a.hfmt & 16 else 8)) + 4 * 128),
+         2 * sm.nseq * sm.L * 2 * 4 * u * (u + 128))
     L.check(L.lib().ws_lstm_fwd_fused(C.byref(a), L.stream_ptr()), "ws_lstm_fwd_fused")
 
 
