@@ -418,9 +418,33 @@ void ws_engine_live_close(ws_live* s);
  *     2 entry-point calls.  The slot then takes nothing until it is detached.
  *   ws_engine_live_pool_detach(pool, slot)  frees the slot for the next attach.    ws_engine_live_pool_close(pool)  before
  *     ws_engine_destroy.
+ * STORE, RUN, DUE -- the windows run on the CALLER's clock.  A push runs what it completes at once, so recordings that did not
+ * start together never share a forward.  Every slot completes exactly one window per H samples: a caller that holds complete
+ * windows back for up to H samples lets every slot in flight ride in the same forwards however the calls are staggered.
+ * LATENCY: a sample then comes out S .. S + H samples after it went in, plus whatever the caller holds.
+ *   ws_engine_live_pool_store(pool, n_active, slots, chunks, n)  push's packets (its argument checks, under this name) appended
+ *     to the slots' pending samples on the host: NO launch, NO synchronisation, "n_launches" 0 after it.  The backlog is
+ *     bounded: a store that would leave a slot with WS_LIVE_POOL_STORE_LIMIT(S, H) = 2 S + H or more pending samples is refused
+ *     ("run first") before anything of the call is appended.
+ *   ws_engine_live_pool_run(pool, n_active, slots, final, est, est_cap, n_out)  for every named slot ALL windows that are complete
+ *     and not yet run, through the rounds of a push: ascending slot order, the solo cut per slot and round, one upload, one
+ *     ws_window_slots_fwd, forwards of at most max_rows rows whichever slots they came from, one ws_rows_copy_fwd and one
+ *     ws_xfade_stream_rows_fwd per round, one download and one synchronisation per call; the emission rule of a push.  final
+ *     may be NULL; final[i] != 0 ends slot i's recording by the rule of ws_engine_live_pool_flush once its regular windows have
+ *     run: with n >= S the end-aligned last window is a row of S samples like any other and shares the round's forwards with
+ *     the other slots' windows (in the round after the slot's last regular one, if the call ran any); a short recording
+ *     (n < S) gets forwards of its own rows in that round, behind the rows of S samples (the rectangular plans take one length
+ *     a forward), its lower bound on T checked before anything runs.  The slot then takes nothing until it is detached.  No
+ *     named slot has work: every n_out[i] = 0, NO launch, NO synchronisation.  WS_LIVE_POOL_RUN_CAP(S, H) = 2 S + H always
+ *     suffices as est_cap; est_cap is checked for every entry before any launch.  "n_launches", "live_pool_rounds" and
+ *     "live_pool_forwards" report the last run by the formula of a push.
+ *   ws_engine_live_pool_due(pool, &rows_ready, &oldest_age)  a query for a scheduler, no launch, no change of state: rows_ready
+ *     = K x the complete windows not yet run over all slots a run would take; oldest_age = the largest number of samples a slot
+ *     has received since its oldest such window w became complete, N - (w H + S), 0 if none is ready.  Either pointer may be NULL.
+ *   push and flush on a slot with stored audio are store + run and run(final) of their slots: one code path serves all.
  * The engine's work arena is used under a scope and nothing of it is held between two calls: other calls on the engine between
  * two pushes do not disturb the pool.  Dry-run engines take every call.  All pointers are HOST pointers; callers serialise.
- * FAILURE: the slots named by a push or flush that failed half way are refused by name until they are detached; the other
+ * FAILURE: the slots named by a push, run or flush that failed half way are refused by name until they are detached; the other
  * slots go on.
  * PARITY, per slot: the concatenation of what its pushes and its flush return equals ws_engine_separate_long on that slot's
  * concatenated audio -- whatever the packet sizes were, whenever the slot was attached, whatever the other slots were doing
@@ -428,19 +452,25 @@ void ws_engine_live_close(ws_live* s);
  *   - otherwise to the rounding of forwards over other row counts (which rows share a forward depends on the other slots).
  * No launch mixes rows: with the row composition of the forwards held fixed, a slot's bits do not depend on the other slots'
  * sample values, NaN and inf included -- as far as the architecture's rectangular plan keeps its rows apart.
- * NOT built: a sample rate per slot; a different K per slot; holding a complete window back to wait for company (the pool
- * batches only windows that complete in the same push).
+ * NOT built: a sample rate per slot; a different K per slot; a clock inside the pool (the caller's due + run is the policy).
  * WS_ERR_INVALID with a message and nothing launched: every refusal of ws_engine_live_* under this family's names; slots
- * outside [1, 65535]; a full pool; a slot of a push or flush that is free, flushed, named twice or part of a failed call;
- * n[i] < 1; est_cap below the emission, checked for every entry before any launch; a NULL pointer. */
+ * outside [1, 65535]; a full pool; a slot of a push, store, run or flush that is free, flushed, named twice or part of a failed
+ * call; n[i] < 1; est_cap below the emission, checked for every entry before any launch; a store past its limit; a final entry
+ * of a run whose slot was never fed; a NULL pointer. */
 typedef struct ws_live_pool ws_live_pool;
 #define WS_LIVE_POOL_ROUND_LAUNCHES 3
+#define WS_LIVE_POOL_STORE_LIMIT(S, H) (2 * (S) + (H))   /* pending samples a slot: a store must stay below */
+#define WS_LIVE_POOL_RUN_CAP(S, H) (2 * (S) + (H))       /* est_cap that always suffices for a run, per target */
 int ws_engine_live_pool_open(ws_engine* e, int slots, int K, int window, int overlap, int max_rows, ws_live_pool** out);
 int ws_engine_live_pool_attach(ws_live_pool* p, const void* enroll, int enroll_kind, int enroll_len, const int* enroll_lengths,
                                int* slot);
 int ws_engine_live_pool_push(ws_live_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n,
                              float* const* est, const int* est_cap, int* n_out);
 int ws_engine_live_pool_flush(ws_live_pool* p, int slot, float* est, int est_cap, int* n_out);
+int ws_engine_live_pool_store(ws_live_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n);
+int ws_engine_live_pool_run(ws_live_pool* p, int n_active, const int* slots, const int* final, float* const* est, const int* est_cap,
+                            int* n_out);
+int ws_engine_live_pool_due(ws_live_pool* p, long long* rows_ready, long long* oldest_age);
 int ws_engine_live_pool_detach(ws_live_pool* p, int slot);
 void ws_engine_live_pool_close(ws_live_pool* p);
 

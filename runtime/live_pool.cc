@@ -13,6 +13,10 @@
 //     factors) into the rings and ONE ws_xfade_stream_rows_fwd for what the round made final.  After the last round one copy
 //     to the host and ONE synchronisation;
 //   * transient activations come from the engine's work arena under an ArenaScope; nothing of it is held between two calls.
+//   * store / run / due: store appends packets and launches nothing, run works off every complete window of the slots it names
+//     (and ends the recordings marked final) in the same rounds, due tells a scheduler what waits.  push is store + run of its
+//     slots, flush is run with its slot final: one path, run_jobs, serves all of them.  A final recording's end-aligned last
+//     window is a row of S samples like any other; a short one (n < S) gets forwards of its own rows behind the round's S rows.
 // No launch mixes rows: a slot's samples do not depend on what the other slots carry.
 // =================================================================================================================
 #include <deque>
@@ -38,7 +42,16 @@ struct LpPart {
   long long w0 = 0;
   const float* x = nullptr;
   long long i0 = 0, count = 0, windows_run = 0, W = 0, n = 0, out_off = 0, ld = 0;
-  int final = 0;
+  int final = 0, job = 0;
+};
+
+// what a call does for one slot it names: the regular windows up to wr_new, then (final) the end of the recording; `emitted`
+// samples a target come out, into est [K][cap], at out_base of the call's block
+struct LpJob {
+  int slot = 0, final = 0, cap = 0;
+  bool ended = false;
+  long long wr_new = 0, e0 = 0, emitted = 0, out_base = 0;
+  float* est = nullptr;
 };
 
 }  // namespace
@@ -98,18 +111,25 @@ void free_pool(ws_live_pool* p) {
 }
 
 // One round.  The staging block -- spans | factors | embedding rows | gather table | scatter table | cross-fade table, each
-// part 256-byte aligned -- is built on the host and uploaded once.
+// part 256-byte aligned -- is built on the host and uploaded once.  The rows of S samples come first, ordered (slot, target,
+// window), and go through the separator in forwards of at most max_rows rows whichever slots they came from; the rows of a
+// short final recording (L < S) follow, each recording's in forwards of their own (one length a forward).
 int run_round(ws_live_pool* p, const std::vector<LpPart>& parts, float* d_out, long long n_out) {
   ws_engine* e = p->e;
   const int K = p->K, S = p->S, H = p->H, cap = p->cap, E = e->E;
   const bool grid = e->arch == 3;
   float* const state = reinterpret_cast<float*>(p->state);
   const long long state_floats = static_cast<long long>(p->state_bytes / 4);
-  int R = 0, L = S, n_fac = 0, n_scatter = 0, n_fade = 0;
+  int R = 0, n_fac = 0, n_scatter = 0, n_fade = 0;
   size_t span_floats = 0;
+  std::vector<const LpPart*> ord;         // full-length parts (and those without a window), then the short ones
+  for (const LpPart& q : parts)
+    if (q.g == 0 || q.L == S) ord.push_back(&q);
+  for (const LpPart& q : parts)
+    if (q.g > 0 && q.L != S) ord.push_back(&q);
   for (const LpPart& q : parts) {
     if (q.g > 0) {
-      R += K * q.g, L = q.L, n_fac += q.g, n_scatter += K + (grid ? 1 : 0);
+      R += K * q.g, n_fac += q.g, n_scatter += K + (grid ? 1 : 0);
       span_floats += size_t(q.g - 1) * H + q.L;
     }
     n_fade += K;
@@ -132,22 +152,30 @@ int run_round(ws_live_pool* p, const std::vector<LpPart>& parts, float* d_out, l
   ws_rows_copy_row* const scatter = reinterpret_cast<ws_rows_copy_row*>(blk + o_scatter);
   ws_xfade_stream_row* const fade = reinterpret_cast<ws_xfade_stream_row*>(blk + o_fade);
   const long long stage = p->stage_off;       // floats
+  struct Seg { int r0, rows, L; long long at; };      // a run of rows of one length: first row, count, float offset in the rectangles
+  std::vector<Seg> segs;
   size_t sp = 0;
+  long long at = 0;                            // floats of the rows and estimates rectangles used so far
   int r = 0, fc = 0, sc = 0, fd = 0;
-  for (const LpPart& q : parts) {
+  for (const LpPart* qp : ord) {
+    const LpPart& q = *qp;
     const LpSlot& sl = p->sl[q.slot];
     const long long ring0 = p->ring_off + (long long)q.slot * K * cap * S, fac_ring = p->scale_off + (long long)q.slot * cap;
     if (q.g > 0) {
       const int slot0 = static_cast<int>(q.w0 % cap);
       const size_t n_span = size_t(q.g - 1) * H + q.L;
+      if (q.L == S && !segs.empty())
+        segs.back().rows += K * q.g;
+      else
+        segs.push_back(Seg{r, K * q.g, q.L, at});
       memcpy(h_span + sp, q.x, n_span * 4);
       for (int w = 0; w < q.g; ++w) {      // TF-GridNet: every window scaled by its own standard deviation, its estimate back
         if (grid) row_std_scale(q.x + size_t(w) * H, q.L, &h_fac[fc + w], nullptr);
       }
       for (int k = 0; k < K; ++k) {
-        scatter[sc++] = ws_rows_copy_row{p->y_off + (long long)r * q.L, ring0 + ((long long)k * cap + slot0) * S, q.g * q.L, 0};
-        for (int w = 0; w < q.g; ++w, ++r) {
-          gather[r] = ws_window_slot_row{stage + (long long)(o_span / 4 + sp) + (long long)w * H, p->rows_off + (long long)r * q.L, q.L,
+        scatter[sc++] = ws_rows_copy_row{p->y_off + at, ring0 + ((long long)k * cap + slot0) * S, q.g * q.L, 0};
+        for (int w = 0; w < q.g; ++w, ++r, at += q.L) {
+          gather[r] = ws_window_slot_row{stage + (long long)(o_span / 4 + sp) + (long long)w * H, p->rows_off + at, q.L,
                                          grid ? 1.0f / h_fac[fc + w] : 1.0f};
           memcpy(h_emb + size_t(r) * E, sl.emb.data() + size_t(k) * E, size_t(E) * 4);
         }
@@ -166,22 +194,25 @@ int run_round(ws_live_pool* p, const std::vector<LpPart>& parts, float* d_out, l
     WS_RUN(e, ws_window_slots_fwd(gather, reinterpret_cast<const ws_window_slot_row*>(d_blk + o_gather), R, state, state_floats, state,
                                   state_floats, e->stream));
     Arena& a = e->work;
-    const float* d_rows = state + p->rows_off;
     const float* d_emb = reinterpret_cast<const float*>(d_blk + o_emb);
-    float* d_y = state + p->y_off;
-    const int G = R < p->max_rows ? R : p->max_rows;
     const Arena::Mark mk = a.mark();
-    for (int r0 = 0; r0 < R; r0 += G) {
-      const int Gn = R - r0 < G ? R - r0 : G;
-      a.release(mk);
-      const float* in = d_rows + size_t(r0) * L;
-      float* out = d_y + size_t(r0) * L;
-      rc = e->arch == 1   ? tasnet_device(e, in, Gn, L, d_emb + size_t(r0) * E, nullptr, 0, out)
-           : e->arch == 2 ? dpccn_device(e, in, Gn, L, d_emb + size_t(r0) * E, out)
-           : e->arch == 3 ? gridnet_device(e, in, Gn, L, d_emb + size_t(r0) * E, out)
-                          : separate_device(e, in, Gn, L, d_emb + size_t(r0) * E, out);
-      if (rc != WS_OK) return rc;
-      ++p->forwards;
+    for (const Seg& sg : segs) {
+      const float* d_rows = state + p->rows_off + sg.at;
+      float* d_y = state + p->y_off + sg.at;
+      const int L = sg.L, G = sg.rows < p->max_rows ? sg.rows : p->max_rows;
+      for (int r0 = 0; r0 < sg.rows; r0 += G) {
+        const int Gn = sg.rows - r0 < G ? sg.rows - r0 : G;
+        a.release(mk);
+        const float* in = d_rows + size_t(r0) * L;
+        float* out = d_y + size_t(r0) * L;
+        const float* emb = d_emb + size_t(sg.r0 + r0) * E;
+        rc = e->arch == 1   ? tasnet_device(e, in, Gn, L, emb, nullptr, 0, out)
+             : e->arch == 2 ? dpccn_device(e, in, Gn, L, emb, out)
+             : e->arch == 3 ? gridnet_device(e, in, Gn, L, emb, out)
+                            : separate_device(e, in, Gn, L, emb, out);
+        if (rc != WS_OK) return rc;
+        ++p->forwards;
+      }
     }
     a.release(mk);
     WS_RUN(e, ws_rows_copy_fwd(scatter, reinterpret_cast<const ws_rows_copy_row*>(d_blk + o_scatter), n_scatter, state, state_floats, state,
@@ -319,102 +350,264 @@ WS_ENGINE_API int ws_engine_live_pool_attach(ws_live_pool* p, const void* enroll
   return WS_OK;
 }
 
-WS_ENGINE_API int ws_engine_live_pool_push(ws_live_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n,
-                                           float* const* est, const int* est_cap, int* n_out) {
-  const char* who = "ws_engine_live_pool_push";
-  int rc = check_pool(p, who);
-  if (rc != WS_OK) return rc;
-  ws_engine* e = p->e;
-  if (n_active < 1 || !slots || !chunks || !n || !est || !est_cap || !n_out) {
-    set_err("%s: bad arguments (n_active=%d >= 1%s)", who, n_active, slots && chunks && n && est && est_cap && n_out ? "" : ", a NULL array");
+namespace {
+
+// one entry of a push or a store: an attached slot named once, a packet of n >= 1 samples
+int check_packet(const ws_live_pool* p, const char* who, int i, int id, std::vector<char>& seen, const float* chunk, int n) {
+  int rc;
+  if ((rc = check_slot(p, who, id, i)) != WS_OK) return rc;
+  if (seen[id]) {
+    set_err("%s: slot %d is named twice (entry %d): one packet a slot in a push", who, id, i);
     return WS_ERR_INVALID;
   }
-  const int S = p->S, H = p->H, K = p->K;
-  std::vector<char> seen(p->slots, 0);
-  std::vector<long long> wr_new(n_active), emitted(n_active), e0(n_active), out_base(n_active);
-  long long total = 0;
-  bool any = false;
-  for (int i = 0; i < n_active; ++i) {
-    const int id = slots[i];
-    if ((rc = check_slot(p, who, id, i)) != WS_OK) return rc;
-    if (seen[id]) {
-      set_err("%s: slot %d is named twice (entry %d): one packet a slot in a push", who, id, i);
-      return WS_ERR_INVALID;
-    }
-    if (n[i] < 1 || !chunks[i]) {
-      set_err("%s: entry %d (slot %d): n=%d >= 1, chunk %s", who, i, id, n[i], chunks[i] ? "given" : "NULL");
-      return WS_ERR_INVALID;
-    }
-    seen[id] = 1;
-    const LpSlot& sl = p->sl[id];
-    wr_new[i] = live_windows_run(sl.N + n[i], S, H);
-    e0[i] = sl.E;
-    emitted[i] = live_emitted(wr_new[i], H) - sl.E;
-    if (emitted[i] > est_cap[i] || (emitted[i] > 0 && !est[i])) {
-      set_err("%s: entry %d (slot %d) emits %lld samples a row, est_cap is %d%s (WS_LIVE_PUSH_CAP(n, H) = %lld always suffices)", who, i, id,
-              emitted[i], est_cap[i], est[i] ? "" : ", est is NULL", (long long)WS_LIVE_PUSH_CAP((long long)n[i], H));
-      return WS_ERR_INVALID;
-    }
-    out_base[i] = total;
-    total += (long long)K * emitted[i];
-    any = any || wr_new[i] > sl.Wr;
+  if (n < 1 || !chunk) {
+    set_err("%s: entry %d (slot %d): n=%d >= 1, chunk %s", who, i, id, n, chunk ? "given" : "NULL");
+    return WS_ERR_INVALID;
   }
-  // all packets first
+  seen[id] = 1;
+  return WS_OK;
+}
+
+void append(ws_live_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n) {
   for (int i = 0; i < n_active; ++i) {
     LpSlot& sl = p->sl[slots[i]];
     sl.pend.insert(sl.pend.end(), chunks[i], chunks[i] + n[i]);
     sl.N += n[i];
   }
+}
+
+// The one path of push, flush and run.  Every job is checked by its caller.  Rounds: in ascending slot order a job that still
+// owes regular windows gives the solo cut of them; a final job that owes none gives the end of its recording -- the short
+// window, the end-aligned last window or no window at all -- with the final cross-fade, once.  Nothing to do in any job: no
+// launch, no synchronisation.
+int run_jobs(ws_live_pool* p, std::vector<LpJob>& jobs, int* n_out) {
+  ws_engine* e = p->e;
+  const int S = p->S, H = p->H, K = p->K, A = static_cast<int>(jobs.size());
+  int rc;
+  long long total = 0;
+  bool any = false;
+  for (LpJob& j : jobs) {
+    j.out_base = total;
+    total += (long long)K * j.emitted;
+    any = any || j.final || j.wr_new > p->sl[j.slot].Wr;
+  }
   p->rounds = p->forwards = 0;
   if (!any) {                           // no window became complete in any slot: no launch, no synchronisation
     e->n_launches = 0;
     e->live_pool_rounds = e->live_pool_forwards = 0;
-    for (int i = 0; i < n_active; ++i) n_out[i] = 0;
+    for (int i = 0; i < A; ++i) n_out[i] = 0;
     return WS_OK;
   }
-  std::vector<int> order(n_active);
-  for (int i = 0; i < n_active; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return slots[a] < slots[b]; });
-  for (int i = 0; i < n_active; ++i) p->sl[slots[i]].failed = true;      // until the push is complete
+  std::vector<int> order(A);
+  for (int i = 0; i < A; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return jobs[a].slot < jobs[b].slot; });
   ForwardTurn turn(e);
   if (turn.rc != WS_OK) return turn.rc;
+  for (const LpJob& j : jobs) p->sl[j.slot].failed = true;      // until the call is complete
   e->n_launches = 0;
   ArenaScope scope(e->work);
-  float* d_out = e->work.alloc(size_t(std::max<long long>(total, 1)));
+  const long long n_dev = std::max<long long>(total, 1);
+  float* d_out = e->work.alloc(size_t(n_dev));
   WS_PTR(d_out);
   while (true) {
     std::vector<LpPart> parts;
     for (int i : order) {
-      LpSlot& sl = p->sl[slots[i]];
-      if (sl.Wr >= wr_new[i]) continue;
+      LpJob& j = jobs[i];
+      LpSlot& sl = p->sl[j.slot];
       LpPart q;
-      q.slot = slots[i], q.w0 = sl.Wr, q.L = S;
-      q.g = live_cut(sl.Wr, wr_new[i], p->g_max, p->cap);
-      q.x = sl.pend.data() + (sl.Wr * H - sl.base);
-      q.windows_run = sl.Wr + q.g;
-      q.i0 = sl.E, q.count = (q.windows_run - 1) * H - sl.E;
-      q.ld = emitted[i], q.out_off = out_base[i] + (sl.E - e0[i]);
+      q.slot = j.slot, q.job = i, q.L = S;
+      q.i0 = sl.E, q.ld = j.emitted, q.out_off = j.out_base + (sl.E - j.e0);
+      if (sl.Wr < j.wr_new) {
+        q.w0 = sl.Wr;
+        q.g = live_cut(sl.Wr, j.wr_new, p->g_max, p->cap);
+        q.x = sl.pend.data() + (sl.Wr * H - sl.base);
+        q.windows_run = sl.Wr + q.g;
+        q.count = (q.windows_run - 1) * H - sl.E;
+      } else if (j.final && !j.ended) {
+        const long long n = sl.N;
+        q.W = sl.Wr;
+        if (n < S) {
+          q.g = 1, q.w0 = 0, q.L = static_cast<int>(n), q.x = sl.pend.data(), q.W = 1;
+        } else if ((n - S) % H != 0) {    // the end-aligned last window, index W - 1
+          q.g = 1, q.w0 = sl.Wr, q.x = sl.pend.data() + (n - S - sl.base), q.W = sl.Wr + 1;
+        }
+        q.windows_run = q.W, q.n = n, q.final = 1;
+        q.count = n - sl.E;
+      } else {
+        continue;
+      }
       parts.push_back(q);
     }
     if (parts.empty()) break;
-    if ((rc = run_round(p, parts, d_out, std::max<long long>(total, 1))) != WS_OK) return rc;
+    if ((rc = run_round(p, parts, d_out, n_dev)) != WS_OK) return rc;
     for (const LpPart& q : parts) {
       LpSlot& sl = p->sl[q.slot];
-      sl.Wr = q.windows_run, sl.E = (sl.Wr - 1) * H;
+      sl.Wr = q.windows_run;
+      sl.E = q.final ? q.n : (sl.Wr - 1) * H;
+      if (q.final) jobs[q.job].ended = true;
     }
   }
   if ((rc = finish(p, d_out, total)) != WS_OK) return rc;
-  for (int i = 0; i < n_active; ++i) {
-    LpSlot& sl = p->sl[slots[i]];
+  for (int i = 0; i < A; ++i) {
+    const LpJob& j = jobs[i];
+    LpSlot& sl = p->sl[j.slot];
     if (!e->dry)
-      for (int k = 0; k < K && emitted[i] > 0; ++k)
-        memcpy(est[i] + size_t(k) * est_cap[i], p->out_host.data() + out_base[i] + k * emitted[i], size_t(emitted[i]) * 4);
-    // what a later window can still read starts at the newest window's start
-    sl.pend.erase(sl.pend.begin(), sl.pend.begin() + static_cast<ptrdiff_t>(sl.E - sl.base));
-    sl.base = sl.E;
+      for (int k = 0; k < K && j.emitted > 0; ++k)
+        memcpy(j.est + size_t(k) * j.cap, p->out_host.data() + j.out_base + k * j.emitted, size_t(j.emitted) * 4);
+    if (j.final) {
+      sl.pend.clear();
+      sl.state = LpSlot::kDone;
+    } else {                            // what a later window can still read starts at the newest window's start
+      sl.pend.erase(sl.pend.begin(), sl.pend.begin() + static_cast<ptrdiff_t>(sl.E - sl.base));
+      sl.base = sl.E;
+    }
     sl.failed = false;
-    n_out[i] = static_cast<int>(emitted[i]);
+    n_out[i] = static_cast<int>(j.emitted);
   }
+  return WS_OK;
+}
+
+// the end of slot id's recording as a job: flush's checks, under who's name
+int final_job(const ws_live_pool* p, const char* who, int id, int entry, float* est, int est_cap, bool outs, LpJob* j) {
+  const LpSlot& sl = p->sl[id];
+  const int S = p->S, H = p->H, K = p->K;
+  const long long n = sl.N, emitted = n - sl.E;
+  int rc;
+  if (n < 1) {
+    set_err("%s: slot %d: nothing was pushed", who, id);
+    return WS_ERR_INVALID;
+  }
+  if (entry >= 0 && (!est || emitted > est_cap)) {      // a run: its backlog may exceed what a flush after pushes emits
+    set_err("%s: entry %d (slot %d) emits %lld samples a row, est_cap is %d%s (WS_LIVE_POOL_RUN_CAP(S, H) = %lld always suffices)", who, entry,
+            id, emitted, est_cap, est ? "" : ", est is NULL", (long long)WS_LIVE_POOL_RUN_CAP((long long)S, H));
+    return WS_ERR_INVALID;
+  }
+  if (!est || !outs || emitted > est_cap) {
+    set_err("%s: slot %d: the flush emits %lld samples a row, est_cap is %d%s (WS_LIVE_FLUSH_CAP(S, O) = %d always suffices)", who, id,
+            emitted, est_cap, est && outs ? "" : ", est or n_out is NULL", WS_LIVE_FLUSH_CAP(S, p->O));
+    return WS_ERR_INVALID;
+  }
+  // n < S: the whole recording is one short row with the architecture's own lower bound on T; refused before anything runs,
+  // so a later push goes on from here
+  if (n < S && (rc = check_rows(p->e, true, K < p->max_rows ? K : p->max_rows, static_cast<int>(n))) != WS_OK) return rc;
+  j->slot = id, j->final = 1, j->cap = est_cap, j->est = est;
+  j->wr_new = live_windows_run(n, S, H), j->e0 = sl.E, j->emitted = emitted;
+  return WS_OK;
+}
+
+}  // namespace
+
+WS_ENGINE_API int ws_engine_live_pool_push(ws_live_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n,
+                                           float* const* est, const int* est_cap, int* n_out) {
+  const char* who = "ws_engine_live_pool_push";
+  int rc = check_pool(p, who);
+  if (rc != WS_OK) return rc;
+  if (n_active < 1 || !slots || !chunks || !n || !est || !est_cap || !n_out) {
+    set_err("%s: bad arguments (n_active=%d >= 1%s)", who, n_active, slots && chunks && n && est && est_cap && n_out ? "" : ", a NULL array");
+    return WS_ERR_INVALID;
+  }
+  const int S = p->S, H = p->H;
+  std::vector<char> seen(p->slots, 0);
+  std::vector<LpJob> jobs(n_active);
+  for (int i = 0; i < n_active; ++i) {
+    const int id = slots[i];
+    if ((rc = check_packet(p, who, i, id, seen, chunks[i], n[i])) != WS_OK) return rc;
+    const LpSlot& sl = p->sl[id];
+    LpJob& j = jobs[i];
+    j.slot = id, j.cap = est_cap[i], j.est = est[i];
+    j.wr_new = live_windows_run(sl.N + n[i], S, H);
+    j.e0 = sl.E;
+    j.emitted = live_emitted(j.wr_new, H) - sl.E;
+    if (j.emitted > est_cap[i] || (j.emitted > 0 && !est[i])) {
+      set_err("%s: entry %d (slot %d) emits %lld samples a row, est_cap is %d%s (WS_LIVE_PUSH_CAP(n, H) = %lld always suffices)", who, i, id,
+              j.emitted, est_cap[i], est[i] ? "" : ", est is NULL", (long long)WS_LIVE_PUSH_CAP((long long)n[i], H));
+      return WS_ERR_INVALID;
+    }
+  }
+  append(p, n_active, slots, chunks, n);       // all packets first
+  return run_jobs(p, jobs, n_out);
+}
+
+WS_ENGINE_API int ws_engine_live_pool_store(ws_live_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n) {
+  const char* who = "ws_engine_live_pool_store";
+  int rc = check_pool(p, who);
+  if (rc != WS_OK) return rc;
+  if (n_active < 1 || !slots || !chunks || !n) {
+    set_err("%s: bad arguments (n_active=%d >= 1%s)", who, n_active, slots && chunks && n ? "" : ", a NULL array");
+    return WS_ERR_INVALID;
+  }
+  const long long limit = WS_LIVE_POOL_STORE_LIMIT((long long)p->S, p->H);
+  std::vector<char> seen(p->slots, 0);
+  for (int i = 0; i < n_active; ++i) {
+    const int id = slots[i];
+    if ((rc = check_packet(p, who, i, id, seen, chunks[i], n[i])) != WS_OK) return rc;
+    const long long pending = (long long)p->sl[id].pend.size() + n[i];
+    if (pending >= limit) {              // the backlog is bounded: what a run gives back fits WS_LIVE_POOL_RUN_CAP
+      set_err("%s: entry %d (slot %d): %d more samples make %lld pending, WS_LIVE_POOL_STORE_LIMIT(S, H) = %lld: run first", who, i, id, n[i],
+              pending, limit);
+      return WS_ERR_INVALID;
+    }
+  }
+  append(p, n_active, slots, chunks, n);       // no launch, no synchronisation: the samples wait on the host for a run
+  p->rounds = p->forwards = 0;
+  p->e->n_launches = 0;
+  p->e->live_pool_rounds = p->e->live_pool_forwards = 0;
+  return WS_OK;
+}
+
+WS_ENGINE_API int ws_engine_live_pool_run(ws_live_pool* p, int n_active, const int* slots, const int* final, float* const* est,
+                                          const int* est_cap, int* n_out) {
+  const char* who = "ws_engine_live_pool_run";
+  int rc = check_pool(p, who);
+  if (rc != WS_OK) return rc;
+  if (n_active < 1 || !slots || !est || !est_cap || !n_out) {
+    set_err("%s: bad arguments (n_active=%d >= 1%s)", who, n_active, slots && est && est_cap && n_out ? "" : ", a NULL array");
+    return WS_ERR_INVALID;
+  }
+  const int S = p->S, H = p->H;
+  std::vector<char> seen(p->slots, 0);
+  std::vector<LpJob> jobs(n_active);
+  for (int i = 0; i < n_active; ++i) {
+    const int id = slots[i];
+    if ((rc = check_slot(p, who, id, i)) != WS_OK) return rc;
+    if (seen[id]) {
+      set_err("%s: slot %d is named twice (entry %d): one entry a slot in a run", who, id, i);
+      return WS_ERR_INVALID;
+    }
+    seen[id] = 1;
+    const LpSlot& sl = p->sl[id];
+    LpJob& j = jobs[i];
+    if (final && final[i]) {
+      if ((rc = final_job(p, who, id, i, est[i], est_cap[i], true, &j)) != WS_OK) return rc;
+      continue;
+    }
+    j.slot = id, j.cap = est_cap[i], j.est = est[i];
+    j.wr_new = live_windows_run(sl.N, S, H);
+    j.e0 = sl.E;
+    j.emitted = live_emitted(j.wr_new, H) - sl.E;
+    if (j.emitted > est_cap[i] || (j.emitted > 0 && !est[i])) {
+      set_err("%s: entry %d (slot %d) emits %lld samples a row, est_cap is %d%s (WS_LIVE_POOL_RUN_CAP(S, H) = %lld always suffices)", who, i, id,
+              j.emitted, est_cap[i], est[i] ? "" : ", est is NULL", (long long)WS_LIVE_POOL_RUN_CAP((long long)S, H));
+      return WS_ERR_INVALID;
+    }
+  }
+  return run_jobs(p, jobs, n_out);
+}
+
+WS_ENGINE_API int ws_engine_live_pool_due(ws_live_pool* p, long long* rows_ready, long long* oldest_age) {
+  const char* who = "ws_engine_live_pool_due";
+  const int rc = check_pool(p, who);
+  if (rc != WS_OK) return rc;
+  long long windows = 0, age = 0;
+  for (const LpSlot& sl : p->sl) {       // the slots a run takes: attached, not ended, not part of a failed call
+    if (sl.state != LpSlot::kAttached || sl.failed) continue;
+    const long long ready = live_windows_run(sl.N, p->S, p->H) - sl.Wr;
+    if (ready < 1) continue;
+    windows += ready;
+    age = std::max(age, sl.N - (sl.Wr * p->H + p->S));
+  }
+  if (rows_ready) *rows_ready = p->K * windows;
+  if (oldest_age) *oldest_age = age;
   return WS_OK;
 }
 
@@ -422,50 +615,10 @@ WS_ENGINE_API int ws_engine_live_pool_flush(ws_live_pool* p, int slot, float* es
   const char* who = "ws_engine_live_pool_flush";
   int rc = check_pool(p, who);
   if (rc != WS_OK) return rc;
-  ws_engine* e = p->e;
   if ((rc = check_slot(p, who, slot, -1)) != WS_OK) return rc;
-  LpSlot& sl = p->sl[slot];
-  const int S = p->S, H = p->H, K = p->K;
-  const long long n = sl.N, emitted = n - sl.E;
-  if (n < 1) {
-    set_err("%s: slot %d: nothing was pushed", who, slot);
-    return WS_ERR_INVALID;
-  }
-  if (!est || !n_out || emitted > est_cap) {
-    set_err("%s: slot %d: the flush emits %lld samples a row, est_cap is %d%s (WS_LIVE_FLUSH_CAP(S, O) = %d always suffices)", who, slot,
-            emitted, est_cap, est && n_out ? "" : ", est or n_out is NULL", WS_LIVE_FLUSH_CAP(S, p->O));
-    return WS_ERR_INVALID;
-  }
-  // n < S: the whole recording is one short row with the architecture's own lower bound on T; refused before anything runs,
-  // so a later push goes on from here
-  if (n < S && (rc = check_rows(e, true, K < p->max_rows ? K : p->max_rows, static_cast<int>(n))) != WS_OK) return rc;
-  ForwardTurn turn(e);
-  if (turn.rc != WS_OK) return turn.rc;
-  e->n_launches = 0;
-  p->rounds = p->forwards = 0;
-  sl.failed = true;
-  ArenaScope scope(e->work);
-  float* d_out = e->work.alloc(size_t(K) * emitted);
-  WS_PTR(d_out);
-  LpPart q;
-  q.slot = slot, q.L = S, q.W = sl.Wr;
-  if (n < S) {
-    q.g = 1, q.w0 = 0, q.L = static_cast<int>(n), q.x = sl.pend.data(), q.W = 1;
-  } else if ((n - S) % H != 0) {        // the end-aligned last window, index W - 1
-    q.g = 1, q.w0 = sl.Wr, q.x = sl.pend.data() + (n - S - sl.base), q.W = sl.Wr + 1;
-  }
-  q.windows_run = q.W, q.n = n, q.final = 1;
-  q.i0 = sl.E, q.count = emitted, q.ld = emitted, q.out_off = 0;
-  if ((rc = run_round(p, std::vector<LpPart>(1, q), d_out, (long long)K * emitted)) != WS_OK) return rc;
-  sl.Wr = q.W, sl.E = n;
-  if ((rc = finish(p, d_out, (long long)K * emitted)) != WS_OK) return rc;
-  if (!e->dry)
-    for (int k = 0; k < K; ++k) memcpy(est + size_t(k) * est_cap, p->out_host.data() + k * emitted, size_t(emitted) * 4);
-  sl.pend.clear();
-  sl.failed = false;
-  sl.state = LpSlot::kDone;
-  *n_out = static_cast<int>(emitted);
-  return WS_OK;
+  std::vector<LpJob> jobs(1);
+  if ((rc = final_job(p, who, slot, -1, est, est_cap, n_out != nullptr, &jobs[0])) != WS_OK) return rc;
+  return run_jobs(p, jobs, n_out);
 }
 
 WS_ENGINE_API int ws_engine_live_pool_detach(ws_live_pool* p, int slot) {

@@ -4,7 +4,7 @@
 //   separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1] [--jobs 4]
 //                 [--batch 8] [--sort_by_length] [--chunk_seconds 4 [--overlap_seconds 1] [--chunk_rows 8]] [--dry_run]
 //                 [--stream_ms 10 [--stream_pool 4 | --rate_pool 4] [--stream_block]] [--resample]
-//                 [--live_ms 100 --chunk_seconds 4 [--live_pool 4]]
+//                 [--live_ms 100 --chunk_seconds 4 [--live_pool 4 [--live_hold_ms 3000]]]
 //                 [--tail_ms 100 --chunk_seconds 4 [--tail_fade_ms 10] [--tail_warm_seconds 4] [--tail_pool 4]]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
@@ -40,6 +40,13 @@
 // slot detached and re-attached to the next line.  Names and formats are those of --live_ms; with N = 1 and --chunk_rows 1 so
 // are the samples, bit for bit.  Works with --jobs, --dry_run and --resample (files go through ws_engine_resample around the
 // pool, as for --live_ms).  Refused without --live_ms, and together with --batch N > 1, --stream_ms and the other pools.
+// --live_hold_ms W (with --live_pool N): the windows run on the tool's clock, not the packets'.  Every round of packets is a
+// ws_engine_live_pool_store (no launch); then ws_engine_live_pool_due is read and ONE ws_engine_live_pool_run takes every line
+// with a complete window once --chunk_rows rows wait or the oldest complete window has waited W ms of audio (and before a
+// store that would pass the pool's backlog limit).  Lines that did not start together then share their forwards: a hold of
+// the hop S - O lets every line in flight ride in the same ones.  A line that ends is passed as final in the next run, its
+// last window beside the others', not flushed alone.  The files are those of --live_pool (bit for bit with --chunk_rows 1);
+// a sample comes out up to W ms later.  Refused without --live_pool.
 // --tail_ms M [--tail_fade_ms F, default 10] [--tail_warm_seconds W, default S] [--tail_pool N, default 1] (with --chunk_seconds S;
 // any model): low-latency separation on trailing windows -- N lines in flight on one tail pool (ws_engine_tail_pool_*, K = 2):
 // every round pushes each line its next M ms packet and ticks, so every line runs the window of its newest S seconds and what
@@ -180,6 +187,9 @@ int main(int argc, char** argv) {
   const int live_n = static_cast<int>(live_ms * sample_rate / 1000.0 + 0.5);
   const bool live_pooled = args.has("live_pool");
   const int live_pool_n = atoi(args.get("live_pool", "0").c_str());
+  const bool live_hold = args.has("live_hold_ms");
+  const double live_hold_ms = atof(args.get("live_hold_ms", "0").c_str());
+  const long long live_hold_n = static_cast<long long>(live_hold_ms * sample_rate / 1000.0 + 0.5);
   const bool tail = args.has("tail_ms");
   const double tail_ms = atof(args.get("tail_ms", "0").c_str());
   const int tail_n = static_cast<int>(tail_ms * sample_rate / 1000.0 + 0.5);
@@ -196,7 +206,7 @@ int main(int argc, char** argv) {
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
            "                     [--chunk_seconds S [--overlap_seconds O] [--chunk_rows N]]\n"
            "                     [--stream_ms M [--stream_pool N | --rate_pool N] [--stream_block]] [--resample]\n"
-           "                     [--live_ms M --chunk_seconds S [--live_pool N]]\n"
+           "                     [--live_ms M --chunk_seconds S [--live_pool N [--live_hold_ms W]]]\n"
            "                     [--tail_ms M --chunk_seconds S [--tail_fade_ms F] [--tail_warm_seconds W] [--tail_pool N]]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
@@ -211,6 +221,9 @@ int main(int argc, char** argv) {
            "                     --chunk_seconds run.  Not together with --batch N > 1, --stream_ms or a pool\n"
            "  --live_pool N      with --live_ms M: N lines in flight at once on one live pool, one push per round of M ms\n"
            "                     packets; windows that complete in the same round share their forwards; same files as --live_ms\n"
+           "  --live_hold_ms W   with --live_pool N: store every packet round and run all lines with a complete window at once, when\n"
+           "                     --chunk_rows rows wait or the oldest window has waited W ms of audio; lines that end ride in the\n"
+           "                     next run.  Lines that started apart share forwards; output up to W ms later; same files\n"
            "  --tail_ms M        with --chunk_seconds S, any model: low-latency separation on trailing windows (a tail pool): every\n"
            "                     line is fed in packets of M ms with a tick after every packet round and a flush at the end; a\n"
            "                     sample comes out M ms plus the fade after it went in, each tick costs one window of S seconds a\n"
@@ -239,6 +252,9 @@ int main(int argc, char** argv) {
                "run, and a tail pool takes recordings as they arrive through the trailing windows of --chunk_seconds");
   if (tail && tail_n < 1) return die("--tail_ms needs a positive packet length");
   if (tail && tail_pool_n < 1) return die("--tail_pool needs a positive number of lines");
+  if (live_hold && !live_pooled)
+    return die("--live_hold_ms needs --live_pool N: only a live pool can hold complete windows back until the lines in flight share a run");
+  if (live_hold && live_hold_ms < 0) return die("--live_hold_ms needs a hold of 0 ms or more");
   if (live_pooled && !live) return die("--live_pool needs --live_ms M: the pool is fed packets of M milliseconds");
   if (live_pooled && (batch > 1 || streamed || pooled || rate_pooled))
     return die("--live_pool conflicts with --batch N > 1, --stream_ms, --stream_pool and --rate_pool: one pool per run, and a live pool "
@@ -374,6 +390,7 @@ int main(int argc, char** argv) {
         size_t line = 0;
         std::vector<float> mix, out, got;      // at the model's rate: the mixture [n], the estimates [2][n]; a call's [2][cap]
         int n = 0, pos = 0, done = 0, slot = -1, n_file = 0, rate = 0;
+        bool ending = false;                   // --live_hold_ms: every packet is stored, the next run is the line's last
         long long pushes = 0;
         std::chrono::steady_clock::time_point t0;
       };
@@ -387,7 +404,9 @@ int main(int argc, char** argv) {
         return;
       }
       const int packet = tail ? tail_n : live_n;
-      const int cap = tail ? WS_TAIL_CAP(window) : std::max(WS_LIVE_PUSH_CAP(live_n, window - overlap), WS_LIVE_FLUSH_CAP(window, overlap));
+      const int cap = tail        ? WS_TAIL_CAP(window)
+                      : live_hold ? WS_LIVE_POOL_RUN_CAP(window, window - overlap)
+                                  : std::max(WS_LIVE_PUSH_CAP(live_n, window - overlap), WS_LIVE_FLUSH_CAP(window, overlap));
       const char* forwards_key = tail ? "tail_pool_forwards" : "live_pool_forwards";
       std::vector<Lane> lanes(lanes_n);
       bool ok = true;
@@ -421,7 +440,7 @@ int main(int argc, char** argv) {
         std::vector<float> enr(size_t(2) * n_enroll);
         memcpy(enr.data(), e[0].data(), size_t(n_enroll) * 4);
         memcpy(enr.data() + n_enroll, e[1].data(), size_t(n_enroll) * 4);
-        ln.line = i, ln.n = static_cast<int>(ln.mix.size()), ln.pos = ln.done = 0, ln.pushes = 0;
+        ln.line = i, ln.n = static_cast<int>(ln.mix.size()), ln.pos = ln.done = 0, ln.pushes = 0, ln.ending = false;
         ln.n_file = static_cast<int>(mix.samples.size()), ln.rate = resample ? mix.sample_rate : sample_rate;
         ln.out.assign(size_t(2) * ln.n, 0.f);
         ln.got.assign(size_t(2) * cap, 0.f);
@@ -438,18 +457,9 @@ int main(int argc, char** argv) {
         for (int k = 0; k < 2; ++k) memcpy(ln.out.data() + size_t(k) * ln.n + ln.done, ln.got.data() + size_t(k) * cap, size_t(m) * 4);
         ln.done += m;
       };
-      auto finish = [&](Lane& ln) {               // flush the slot, free it, write the line's files at the mixture's rate
+      auto write_line = [&](Lane& ln) {           // the line is complete: write its files at the mixture's rate
         const auto& w = waves[ln.line];
         std::string err;
-        int m = 0;
-        if (tail ? ws_engine_tail_pool_flush(tp, ln.slot, ln.got.data(), cap, &m) != 0 || ws_engine_tail_pool_detach(tp, ln.slot) != 0
-                 : ws_engine_live_pool_flush(lp, ln.slot, ln.got.data(), cap, &m) != 0 || ws_engine_live_pool_detach(lp, ln.slot) != 0) {
-          fail(w[0] + ": " + ws_engine_last_error());
-          ok = false;
-          return;
-        }
-        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, forwards_key);
-        take(ln, m);
         ln.live = false;
         std::vector<float> out(size_t(2) * ln.n_file, 0.f);
         if (!from_model(ln.out.data(), 2, ln.n, ln.rate, ln.n_file, out.data())) {
@@ -482,23 +492,102 @@ int main(int argc, char** argv) {
                  dry ? " [dry run]" : "");
         audio_ms += 1000.0 * ln.n_file / ln.rate;
       };
+      auto finish = [&](Lane& ln) {               // flush the slot, free it, write the line's files
+        int m = 0;
+        if (tail ? ws_engine_tail_pool_flush(tp, ln.slot, ln.got.data(), cap, &m) != 0 || ws_engine_tail_pool_detach(tp, ln.slot) != 0
+                 : ws_engine_live_pool_flush(lp, ln.slot, ln.got.data(), cap, &m) != 0 || ws_engine_live_pool_detach(lp, ln.slot) != 0) {
+          fail(waves[ln.line][0] + ": " + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, forwards_key);
+        take(ln, m);
+        write_line(ln);
+      };
+      // --live_hold_ms: ONE run of every line in flight -- the complete windows of all of them in the same forwards, the lines
+      // that have ended as final -- then the ended lines' files and the next lines of the scp into their lanes
+      auto run_held = [&]() {
+        std::vector<int> slots, finals, caps, n_out, who;
+        std::vector<float*> ests;
+        for (int a = 0; a < lanes_n; ++a) {
+          Lane& ln = lanes[a];
+          if (!ln.live) continue;
+          slots.push_back(ln.slot), finals.push_back(ln.ending ? 1 : 0), caps.push_back(cap), who.push_back(a), ests.push_back(ln.got.data());
+        }
+        if (slots.empty()) return;
+        n_out.assign(slots.size(), 0);
+        if (ws_engine_live_pool_run(lp, static_cast<int>(slots.size()), slots.data(), finals.data(), ests.data(), caps.data(), n_out.data()) != 0) {
+          fail(std::string(flag) + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, forwards_key);
+        pool_rounds += ws_engine_info(engine, "live_pool_rounds");
+        for (size_t r = 0; r < who.size() && ok; ++r) {
+          Lane& ln = lanes[who[r]];
+          take(ln, n_out[r]);
+          if (!ln.ending) continue;
+          if (ws_engine_live_pool_detach(lp, ln.slot) != 0) {
+            fail(waves[ln.line][0] + ": " + ws_engine_last_error());
+            ok = false;
+            return;
+          }
+          write_line(ln);
+          if (ok) start(ln);
+        }
+      };
       for (int a = 0; a < lanes_n; ++a)
         if (ok) start(lanes[a]);
       while (ok && !failed) {
         std::vector<int> slots, ns, caps, n_out, who;
         std::vector<const float*> chunks;
         std::vector<float*> ests;
+        if (live_hold) {                          // a store must leave every line below the pool's backlog limit: run first
+          bool full = false;
+          for (const Lane& ln : lanes)
+            full = full || (ln.live && !ln.ending &&
+                            (long long)(ln.pos - ln.done) + std::min(packet, ln.n - ln.pos) >= WS_LIVE_POOL_STORE_LIMIT((long long)window, window - overlap));
+          if (full) run_held();
+          if (!ok) break;
+        }
         for (int a = 0; a < lanes_n; ++a) {
           Lane& ln = lanes[a];
-          if (!ln.live) continue;
+          if (!ln.live || ln.ending) continue;
           // (a tail pool holds at most one window of samples that have not come out: ln.pos - ln.done of them are waiting)
           const int room = tail ? window - (ln.pos - ln.done) : packet;
           slots.push_back(ln.slot), ns.push_back(std::min({packet, ln.n - ln.pos, room})), caps.push_back(cap), who.push_back(a);
           chunks.push_back(ln.mix.data() + ln.pos), ests.push_back(ln.got.data());
         }
-        if (slots.empty()) break;
+        if (slots.empty() && !live_hold) break;
         n_out.assign(slots.size(), 0);
         const int A = static_cast<int>(slots.size());
+        if (live_hold) {
+          bool waiting = false;                   // lines that have ended and wait for their last run
+          for (const Lane& ln : lanes) waiting = waiting || (ln.live && ln.ending);
+          if (slots.empty() && !waiting) break;
+          if (!slots.empty()) {
+            if (ws_engine_live_pool_store(lp, A, slots.data(), chunks.data(), ns.data()) != 0) {
+              fail(std::string(flag) + ws_engine_last_error());
+              ok = false;
+              break;
+            }
+            ++rounds;
+            for (size_t r = 0; r < who.size(); ++r) {
+              Lane& ln = lanes[who[r]];
+              ln.pos += ns[r], ++ln.pushes;
+              ln.ending = ln.pos >= ln.n;
+            }
+          }
+          long long rows_ready = 0, oldest_age = 0;
+          if (ws_engine_live_pool_due(lp, &rows_ready, &oldest_age) != 0) {
+            fail(std::string(flag) + ws_engine_last_error());
+            ok = false;
+            break;
+          }
+          // run: enough rows for a forward, a window that has waited its hold, or nothing left to store (only ended lines wait)
+          if (rows_ready >= chunk_rows || (rows_ready > 0 && oldest_age >= live_hold_n) || slots.empty()) run_held();
+          continue;
+        }
         if (tail ? ws_engine_tail_pool_push(tp, A, slots.data(), chunks.data(), ns.data()) != 0 ||
                        ws_engine_tail_pool_tick(tp, A, slots.data(), ests.data(), caps.data(), n_out.data()) != 0
                  : ws_engine_live_pool_push(lp, A, slots.data(), chunks.data(), ns.data(), ests.data(), caps.data(), n_out.data()) != 0) {

@@ -26,6 +26,7 @@ SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", 
            "ws_engine_live_open", "ws_engine_live_push", "ws_engine_live_flush", "ws_engine_live_reset", "ws_engine_live_close",
            "ws_engine_live_pool_open", "ws_engine_live_pool_attach", "ws_engine_live_pool_push", "ws_engine_live_pool_flush",
            "ws_engine_live_pool_detach", "ws_engine_live_pool_close",
+           "ws_engine_live_pool_store", "ws_engine_live_pool_run", "ws_engine_live_pool_due",
            "ws_engine_tail_pool_open", "ws_engine_tail_pool_attach", "ws_engine_tail_pool_push", "ws_engine_tail_pool_tick",
            "ws_engine_tail_pool_flush", "ws_engine_tail_pool_detach", "ws_engine_tail_pool_close")
 STREAM_FLUSH_CAP = 160  # WS_STREAM_FLUSH_CAP
@@ -143,6 +144,12 @@ def lib():
                                                C.c_void_p]
         l.ws_engine_live_pool_flush.restype = C.c_int
         l.ws_engine_live_pool_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_live_pool_store.restype = C.c_int
+        l.ws_engine_live_pool_store.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.ws_engine_live_pool_run.restype = C.c_int
+        l.ws_engine_live_pool_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.ws_engine_live_pool_due.restype = C.c_int
+        l.ws_engine_live_pool_due.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
         l.ws_engine_live_pool_detach.restype = C.c_int
         l.ws_engine_live_pool_detach.argtypes = [C.c_void_p, C.c_int]
         l.ws_engine_live_pool_close.restype = None
@@ -552,14 +559,27 @@ def live_pool_launches(round_plans):
     return sum(sum(f) + LIVE_POOL_ROUND_LAUNCHES for f in round_plans) + 1
 
 
+def live_pool_store_limit(S, H):
+    """WS_LIVE_POOL_STORE_LIMIT: a store must leave a slot with fewer pending samples than this."""
+    return 2 * S + H
+
+
+def live_pool_run_cap(S, H):
+    """WS_LIVE_POOL_RUN_CAP: samples a target that a live-pool run can emit at most for one slot."""
+    return 2 * S + H
+
+
 class LivePool:
     """ws_engine_live_pool_* (include/wesep_engine.h): many live recordings, the windows that one push completes through the
     same forwards.  Every slot is an EngineLive: the concatenation of what its pushes and its flush return is
-    Engine.separate_long on that slot's audio, whatever the other slots were fed in the meantime."""
+    Engine.separate_long on that slot's audio, whatever the other slots were fed in the meantime.  store() / due() / run()
+    put the windows on the caller's clock: packets are stored without a launch, and one run works off every complete window
+    of every slot in the same forwards, and ends the recordings named final."""
 
     def __init__(self, engine, slots, K, window, overlap, max_rows=8):
         self._h, self._engine = C.c_void_p(), engine      # (the engine must outlive the pool)
         self.slots, self.K, self.window, self.overlap, self.max_rows = int(slots), int(K), int(window), int(overlap), int(max_rows)
+        self._fed = {}                                    # attached, not ended: slot -> [samples fed, windows run]
         _quiesce_torch()
         _check(lib().ws_engine_live_pool_open(engine._h, self.slots, self.K, self.window, self.overlap, self.max_rows,
                                               C.byref(self._h)), "ws_engine_live_pool_open")
@@ -574,7 +594,17 @@ class LivePool:
         _check(lib().ws_engine_live_pool_attach(self._h, enroll.ctypes.data, kind, pitch,
                                                 None if lengths is None else lengths.ctypes.data, C.byref(slot)),
                "ws_engine_live_pool_attach")
+        self._fed[slot.value] = [0, 0]
         return slot.value
+
+    def _windows(self, N):
+        """Wr(N) of the emission rule: the windows that are complete after N samples"""
+        S, H = self.window, self.window - self.overlap
+        return 0 if N < S else 1 + (N - S) // H
+
+    def _emitted(self, Wr):
+        """E of the emission rule: the samples before the start of the newest window run"""
+        return max(Wr - 1, 0) * (self.window - self.overlap)
 
     def push(self, chunks, est_cap=None):
         """{slot: chunk [n_slot >= 1]} -> {slot: float32 [K, m_slot]}, the samples of each slot that became final (m = 0 while
@@ -592,19 +622,77 @@ class LivePool:
         _quiesce_torch()
         _check(lib().ws_engine_live_pool_push(self._h, A, slots.ctypes.data, C.cast(cp, C.c_void_p), n.ctypes.data,
                                               C.cast(ep, C.c_void_p), caps.ctypes.data, m.ctypes.data), "ws_engine_live_pool_push")
+        for i, k in zip(ids, n):
+            f = self._fed[int(i)]
+            f[0] += int(k)
+            f[1] = self._windows(f[0])
+        return {i: b[:, :int(k)].copy() for i, b, k in zip(ids, bufs, m)}
+
+    def store(self, chunks):
+        """{slot: chunk [n_slot >= 1]}: the samples wait on the host for the next run.  No launch."""
+        ids = list(chunks)
+        data = [np.ascontiguousarray(chunks[i], dtype=np.float32).reshape(-1) for i in ids]
+        n = np.array([x.shape[0] for x in data], dtype=np.int32)
+        A = len(ids)
+        slots = np.array(ids, dtype=np.int32)
+        cp = (C.c_void_p * max(A, 1))(*[x.ctypes.data for x in data])
+        _check(lib().ws_engine_live_pool_store(self._h, A, slots.ctypes.data, C.cast(cp, C.c_void_p), n.ctypes.data), "ws_engine_live_pool_store")
+        for i, k in zip(ids, n):
+            self._fed[int(i)][0] += int(k)
+
+    def due(self):
+        """-> (rows_ready, oldest_age): separator rows of the complete windows that no run has taken yet, and the samples the
+        slot that waits longest has received since its oldest such window became complete.  No launch, no change of state."""
+        rows, age = C.c_longlong(0), C.c_longlong(0)
+        _check(lib().ws_engine_live_pool_due(self._h, C.byref(rows), C.byref(age)), "ws_engine_live_pool_due")
+        return rows.value, age.value
+
+    def run(self, slots=None, final=(), est_cap=None):
+        """Runs every complete window of the named slots in shared forwards and ends the recordings of the slots in `final`
+        -> {slot: float32 [K, m_slot]}.  slots=None: every attached slot with a complete window that has not run, and the slots
+        in final.  est_cap: {slot: samples a target the buffer holds} (default: exactly what comes out)."""
+        final = [int(s) for s in final]
+        if slots is None:
+            ids = sorted(s for s, (N, Wr) in self._fed.items() if s in final or self._windows(N) > Wr)
+        else:
+            ids = [int(s) for s in slots]
+        ids += [s for s in final if s not in ids]
+        if not ids:
+            return {}
+        A = len(ids)
+        fin = np.array([1 if s in final else 0 for s in ids], dtype=np.int32)
+        want = []                                         # per slot what comes out: up to the newest window's start, or to the end
+        for s in ids:
+            N, Wr = self._fed.get(s, (0, 0))
+            want.append((N if s in final else self._emitted(self._windows(N))) - self._emitted(Wr))
+        caps = np.array([w if est_cap is None else int(est_cap[s]) for s, w in zip(ids, want)], dtype=np.int32)
+        bufs = [np.zeros((self.K, max(int(c), 1)), dtype=np.float32) for c in caps]
+        arr, m = np.array(ids, dtype=np.int32), np.zeros(A, dtype=np.int32)
+        ep = (C.c_void_p * A)(*[b.ctypes.data for b in bufs])
+        _quiesce_torch()
+        _check(lib().ws_engine_live_pool_run(self._h, A, arr.ctypes.data, fin.ctypes.data, C.cast(ep, C.c_void_p), caps.ctypes.data,
+                                             m.ctypes.data), "ws_engine_live_pool_run")
+        for s in ids:
+            if s in final:
+                self._fed.pop(s, None)
+            else:
+                self._fed[s][1] = self._windows(self._fed[s][0])
         return {i: b[:, :int(k)].copy() for i, b, k in zip(ids, bufs, m)}
 
     def flush(self, slot, est_cap=None):
         """The end of one slot's recording: the end-aligned last window if one is due, then every sample not yet out."""
-        cap = live_flush_cap(self.window, self.overlap) if est_cap is None else int(est_cap)
+        N, Wr = self._fed.get(int(slot), (0, 0))             # (stored audio: more may come out than after pushes alone)
+        cap = max(live_flush_cap(self.window, self.overlap), N - self._emitted(Wr)) if est_cap is None else int(est_cap)
         buf, m = np.zeros((self.K, max(cap, 1)), dtype=np.float32), C.c_int(0)
         _quiesce_torch()
         _check(lib().ws_engine_live_pool_flush(self._h, int(slot), buf.ctypes.data, cap, C.byref(m)), "ws_engine_live_pool_flush")
+        self._fed.pop(int(slot), None)
         return buf[:, :m.value].copy()
 
     def detach(self, slot):
         """Frees the slot for the next attach."""
         _check(lib().ws_engine_live_pool_detach(self._h, int(slot)), "ws_engine_live_pool_detach")
+        self._fed.pop(int(slot), None)
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
