@@ -773,7 +773,8 @@ int ws_flat_stats(const float* x, int ngroups, long long n_per_group, float eps,
  * y = x > 0 ? x : a[0] * x                                                                         */
 int ws_prelu_fwd(float* x, const float* rb, const float* a, long long rows, int C, int rows_per_r,
                  float* y, void* stream);
-/* dx = dy * (pre > 0 ? 1 : a[0]) (dx may alias dy); slab[i < nslab] partial sums of dy * min(pre, 0)  */
+/* dx = dy * (pre > 0 ? 1 : a[0]) (dx may alias dy); slab[i < nslab] partial sums of dy * min(pre, 0): every entry is
+ * written, a block that owns no quad (nslab above n / 1024) leaves an exact 0                        */
 int ws_prelu_bwd(const float* pre, const float* dy, const float* a, long long n, float* dx, float* slab,
                  int nslab, void* stream);
 /* y = b + depthwise_conv(norm(x)), norm applied on load with stats index m / st_div, zero "same" padding,
@@ -781,7 +782,11 @@ int ws_prelu_bwd(const float* pre, const float* dy, const float* a, long long n,
 int ws_dwconv_fwd(const float* x, const float* stats, const float* gamma, const float* beta,
                   const float* w, const float* b, int R, int Tp, int C, int P, int dil, int st_div,
                   float* y, void* stream);
-/* dxn = d(norm(x)); slab[split][P + 1][C]: rows 0..P-1 = dw[.][p] partials, row P = db partials       */
+/* dxn = d(norm(x)); slab[split][P + 1][C]: rows 0..P-1 = dw[.][p] partials, row P = db partials.  Split s owns the rows
+ * [s * rows_per_split, (s + 1) * rows_per_split) below R * Tp (nsplit * rows_per_split >= R * Tp; a split may straddle
+ * two sequences); every slab element is written, a split that owns no row as exact zeros.  Every odd P <= 7 with any
+ * C % 4 == 0 launches: above 64 KB of dynamic LDS (C >= 516 with P = 7, C >= 772 with P = 5) the entry raises the
+ * kernel's limit once per device and returns WS_ERR_LAUNCH, before any launch, if the device refuses.  */
 int ws_dwconv_bwd(const float* dy, const float* x, const float* stats, const float* gamma,
                   const float* beta, const float* w, int R, int Tp, int C, int P, int dil, int st_div,
                   float* dxn, int nsplit, int rows_per_split, float* slab, void* stream);
@@ -795,7 +800,8 @@ int ws_dwconv_ex_bwd(const float* dy, const float* x, const float* stats, const 
                      float* dxn, int nsplit, int rows_per_split, float* slab, void* stream);
 /* slab[split * ngroups + grp][2][C]: per-channel sums of g and of g * xhat over the rows of group grp
  * (rows_per_group consecutive rows) that fall into the split; xhat = (x - mean_s) * rstd_s, s = m / st_div
- * (stats NULL: xhat = x; x NULL: second row zero)                                                    */
+ * (stats NULL: xhat = x; x NULL: second row exactly zero).  Split s owns the rows [s * per, (s + 1) * per) of every group,
+ * per = ceil(rows_per_group / nsplit); every slab element is written, a split that owns no row as exact zeros.  */
 int ws_chan_sums(const float* g, const float* x, const float* stats, int st_div, int rows_per_group,
                  int ngroups, int nsplit, int C, float* slab, void* stream);
 /* ab[grp] = (sum_c gamma[c] * S0[grp][c], sum_c gamma[c] * S1[grp][c]) / n_per_group, sums [ngroups][2][C] */
@@ -818,7 +824,7 @@ int ws_relu_mask(float* d, const float* y, long long n, void* stream);
 int ws_ola_fwd(const float* frames, const float* bias, int R, int Tp, int L, int hop, int Tout,
                float* est, void* stream);
 int ws_ola_bwd(const float* dest, int R, int Tp, int L, int hop, int Tout, float* dframes, void* stream);
-/* slab[i < nslab] = partial sums of x[0..n)                                                          */
+/* slab[i < nslab] = partial sums of x[0..n): every entry written, exactly 0 for a block that owns nothing */
 int ws_sum_partial(const float* x, long long n, float* slab, int nslab, void* stream);
 
 /* ---- SpEx+ speaker encoder (wesep/modules/tasnet/speaker.py:7-64), channels-last [M][C] ------------------
@@ -831,7 +837,8 @@ int ws_bn_stats(const float* x, long long M, int C, float eps, float momentum, f
 int ws_bn_prelu_fwd(const float* x, const float* stats, const float* gamma, const float* beta,
                     const float* res, const float* a, long long M, int C, float* u, float* y, void* stream);
 /* BatchNorm backward from du: sums [2][C] = (sum du, sum du * xhat) = (dbeta, dgamma);
- * dx = gamma * rstd * (du - sums0/M - xhat * sums1/M) (dx may alias du); slab: nsplit * 2 * C floats     */
+ * dx = gamma * rstd * (du - sums0/M - xhat * sums1/M) (dx may alias du); slab: nsplit * 2 * C floats, split s = the rows
+ * [s * ceil(M / nsplit), +ceil(M / nsplit)) below M, exact zeros where it owns none                      */
 int ws_bn_bwd(const float* x, const float* du, const float* stats, const float* gamma, long long M, int C,
               int nsplit, float* slab, float* sums, float* dx, void* stream);
 /* nn.MaxPool1d(3) over time on [R][T][C] -> [R][T/3][C]; backward to the first maximal position        */

@@ -273,6 +273,30 @@ static int dw_check(const char* who, int R, int Tp, int C, int P, int dil, int s
   return WS_OK;
 }
 
+// dwconv_bwd_w_kernel takes (DW_RY - 1) * (P + 1) * blockDim.x * 16 bytes of dynamic LDS: 73 728 with 192 lanes at
+// P = 7 and with 256 lanes at P = 5, 98 304 with 256 lanes at P = 7.  A launch above 64 KB needs the function's limit
+// raised first (to the largest geometry dw_check admits), once per device; a refusal is an error of the entry point,
+// not a silent launch.
+#define DW_MAX_DEVICES 64
+static int dw_bwd_w_raise_lds(size_t lds) {
+  if (lds <= 65536) return WS_OK;
+  static bool raised[DW_MAX_DEVICES] = {};
+  int dev = -1;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess && dev >= 0 && dev < DW_MAX_DEVICES && raised[dev]) return WS_OK;
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_bwd_w_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (DW_RY - 1) * (TN_MAXP + 1) * 256 * (int)sizeof(f32x4));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    ws_set_error("ws_dwconv_bwd: %zu bytes of dynamic LDS refused (%s)", lds, hipGetErrorString(e));
+    return WS_ERR_LAUNCH;
+  }
+  if (dev >= 0 && dev < DW_MAX_DEVICES) raised[dev] = true;
+  return WS_OK;
+}
+
 extern "C" int ws_dwconv_ex_fwd(const float* x, const float* stats, const float* gamma, const float* beta,
                                 const float* w, const float* b, int R, int Tp, int C, int P, int dil, int st_div,
                                 int causal, float* y, void* stream) {
@@ -300,10 +324,12 @@ extern "C" int ws_dwconv_ex_bwd(const float* dy, const float* x, const float* st
              "ws_dwconv_bwd: bad args");
   const DwGeom g{R, Tp, C, P, dil, st_div, causal ? P - 1 : (P - 1) / 2};
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(dwconv_bwd_dx_kernel, dim3(ew_blocks((long long)R * Tp * (C / 4), 256)), dim3(256), 0, s, dy, w,
-                     g, dxn);
   const int threads = C / 4 >= 256 ? 256 : ((C / 4 + 63) / 64) * 64;
   const size_t lds = (size_t)(DW_RY - 1) * (P + 1) * threads * sizeof(f32x4);
+  rc = dw_bwd_w_raise_lds(lds);  // before the first launch: an entry point that fails has written nothing
+  if (rc != WS_OK) return rc;
+  hipLaunchKernelGGL(dwconv_bwd_dx_kernel, dim3(ew_blocks((long long)R * Tp * (C / 4), 256)), dim3(256), 0, s, dy, w,
+                     g, dxn);
   hipLaunchKernelGGL(dwconv_bwd_w_kernel, dim3(nsplit, (C / 4 + threads - 1) / threads), dim3(threads, DW_RY), lds, s,
                      dy, x, stats, gamma, beta, g, rows_per_split, slab);
   return ws_check_launch("ws_dwconv_bwd");

@@ -1262,17 +1262,18 @@ def prelu_fwd(x, rb, a, rows: int, Cc: int, rows_per_r: int, y):
     _call("ws_prelu_fwd", _p(x), _p(rb), _p(a), rows, Cc, rows_per_r, _p(y))
 
 
-def prelu_bwd(pre, dy, a, dx):
-    """returns d(slope) as a [1] tensor"""
+def prelu_bwd(pre, dy, a, dx, nslab=None, with_slab=False):
+    """returns d(slope) as a [1] tensor; nslab = None: one slab entry per 4096 floats, at most 1024; with_slab: (da, slab)"""
     for n, t in (("pre", pre), ("dy", dy), ("a", a), ("dx", dx)):
         _chk(t, n)
     n = pre.numel()
-    nslab = max(1, min(1024, n // 4096))
+    if nslab is None:
+        nslab = max(1, min(1024, n // 4096))
     slab = torch.empty(nslab, device=pre.device, dtype=torch.float32)
     _call("ws_prelu_bwd", _p(pre), _p(dy), _p(a), n, _p(dx), _p(slab), nslab)
     da = torch.empty(1, device=pre.device, dtype=torch.float32)
     reduce_slabs(slab, nslab, 1, 1, da)
-    return da
+    return (da, slab) if with_slab else da
 
 
 def dwconv_fwd(x, stats, gamma, beta, w, b, R: int, Tp: int, Cc: int, P: int, dil: int, st_div: int, y, causal=False):
@@ -1288,29 +1289,34 @@ def row_splits(M: int, target=1024):
     return -(-M // rows), rows
 
 
-def dwconv_bwd(dy, x, stats, gamma, beta, w, R: int, Tp: int, Cc: int, P: int, dil: int, st_div: int, dxn, causal=False):
-    """returns (dw [C, P], db [C])"""
+def dwconv_bwd(dy, x, stats, gamma, beta, w, R: int, Tp: int, Cc: int, P: int, dil: int, st_div: int, dxn, causal=False,
+               splits=None, with_slab=False):
+    """returns (dw [C, P], db [C]); splits = None: row_splits(R * Tp), else the pair (nsplit, rows_per_split);
+    with_slab: (dw, db, slab [nsplit, P + 1, C])"""
     for n, t in (("dy", dy), ("x", x), ("stats", stats), ("gamma", gamma), ("beta", beta), ("w", w), ("dxn", dxn)):
         _chk(t, n)
-    nsplit, rows = row_splits(R * Tp)
+    nsplit, rows = row_splits(R * Tp) if splits is None else splits
     slab = torch.empty(nsplit, P + 1, Cc, device=dy.device, dtype=torch.float32)
     _call("ws_dwconv_ex_bwd", _p(dy), _p(x), _p(stats), _p(gamma), _p(beta), _p(w), R, Tp, Cc, P, dil, st_div,
           int(causal), _p(dxn), nsplit, rows, _p(slab))
     out = torch.empty(P + 1, Cc, device=dy.device, dtype=torch.float32)
     reduce_slabs(slab, nsplit, (P + 1) * Cc, (P + 1) * Cc, out)
-    return out[:P].t().contiguous(), out[P].contiguous()
+    dw, db = out[:P].t().contiguous(), out[P].contiguous()
+    return (dw, db, slab) if with_slab else (dw, db)
 
 
-def chan_sums(g, x, stats, st_div: int, rows_per_group: int, ngroups: int, Cc: int):
-    """[ngroups, 2, C]: per-channel sums of g and g * xhat over each group of rows_per_group rows."""
+def chan_sums(g, x, stats, st_div: int, rows_per_group: int, ngroups: int, Cc: int, nsplit=None, with_slab=False):
+    """[ngroups, 2, C]: per-channel sums of g and g * xhat over each group of rows_per_group rows.  nsplit = None: one split
+    per 32 rows of a group, at most 1024 workgroups; with_slab: (sums, slab [nsplit, ngroups, 2, C])"""
     for n, t in (("g", g), ("x", x), ("stats", stats)):
         _chk(t, n)
-    nsplit = max(1, min(max(1, 1024 // ngroups), rows_per_group // 32))
+    if nsplit is None:
+        nsplit = max(1, min(max(1, 1024 // ngroups), rows_per_group // 32))
     slab = torch.empty(nsplit, ngroups, 2, Cc, device=g.device, dtype=torch.float32)
     _call("ws_chan_sums", _p(g), _p(x), _p(stats), st_div, rows_per_group, ngroups, nsplit, Cc, _p(slab))
     out = torch.empty(ngroups, 2, Cc, device=g.device, dtype=torch.float32)
     reduce_slabs(slab, nsplit, ngroups * 2 * Cc, ngroups * 2 * Cc, out)
-    return out
+    return (out, slab) if with_slab else out
 
 
 def norm_ab(sums, gamma, ngroups: int, Cc: int, n_per_group: int, ab):
@@ -1355,16 +1361,18 @@ def ola_bwd(dest, R: int, Tp: int, Lk: int, hop: int, Tout: int, dframes):
     _call("ws_ola_bwd", _p(dest), R, Tp, Lk, hop, Tout, _p(dframes))
 
 
-def total_sum(x):
-    """sum of all elements as a [1] tensor (deterministic two-stage reduction)"""
+def total_sum(x, nslab=None, with_slab=False):
+    """sum of all elements as a [1] tensor (deterministic two-stage reduction); nslab = None: one slab entry per 4096 floats,
+    at most 1024; with_slab: (sum, slab)"""
     _chk(x, "x")
     n = x.numel()
-    nslab = max(1, min(1024, n // 4096))
+    if nslab is None:
+        nslab = max(1, min(1024, n // 4096))
     slab = torch.empty(nslab, device=x.device, dtype=torch.float32)
     _call("ws_sum_partial", _p(x), n, _p(slab), nslab)
     out = torch.empty(1, device=x.device, dtype=torch.float32)
     reduce_slabs(slab, nslab, 1, 1, out)
-    return out
+    return (out, slab) if with_slab else out
 
 
 # ---- SpEx+ speaker encoder pieces -------------------------------------------------------------------
@@ -1375,14 +1383,17 @@ def _bn_splits(M: int):
     return max(1, min(512, M // 256))
 
 
-def bn_stats(x, M: int, Cc: int, running_mean, running_var, stats, eps=BN_EPS, momentum=BN_MOMENTUM):
+def bn_stats(x, M: int, Cc: int, running_mean, running_var, stats, eps=BN_EPS, momentum=BN_MOMENTUM, nsplit=None,
+             with_slab=False):
+    """nsplit = None: _bn_splits(M); with_slab: returns the scratch [nsplit, C] (the second pass's partial sums)"""
     if M <= 1:      # torch.nn.BatchNorm*: "Expected more than 1 value per channel when training"
         raise ValueError(f"BatchNorm in training mode needs more than 1 value per channel (got {M} row)")
     for n, t in (("x", x), ("running_mean", running_mean), ("running_var", running_var), ("stats", stats)):
         _chk(t, n)
-    ns = _bn_splits(M)
+    ns = _bn_splits(M) if nsplit is None else nsplit
     scratch = torch.empty(ns, Cc, device=x.device, dtype=torch.float32)
     _call("ws_bn_stats", _p(x), M, Cc, eps, momentum, _p(running_mean), _p(running_var), ns, _p(scratch), _p(stats))
+    return scratch if with_slab else None
 
 
 def bn_prelu_fwd(x, stats, gamma, beta, res, a, M: int, Cc: int, u, y):
@@ -1392,15 +1403,15 @@ def bn_prelu_fwd(x, stats, gamma, beta, res, a, M: int, Cc: int, u, y):
     _call("ws_bn_prelu_fwd", _p(x), _p(stats), _p(gamma), _p(beta), _p(res), _p(a), M, Cc, _p(u), _p(y))
 
 
-def bn_bwd(x, du, stats, gamma, M: int, Cc: int, dx):
-    """returns sums [2, C] = (dbeta, dgamma)"""
+def bn_bwd(x, du, stats, gamma, M: int, Cc: int, dx, nsplit=None, with_slab=False):
+    """returns sums [2, C] = (dbeta, dgamma); nsplit = None: _bn_splits(M); with_slab: (sums, slab [nsplit, 2, C])"""
     for n, t in (("x", x), ("du", du), ("stats", stats), ("gamma", gamma), ("dx", dx)):
         _chk(t, n)
-    ns = _bn_splits(M)
+    ns = _bn_splits(M) if nsplit is None else nsplit
     slab = torch.empty(ns, 2, Cc, device=x.device, dtype=torch.float32)
     sums = torch.empty(2, Cc, device=x.device, dtype=torch.float32)
     _call("ws_bn_bwd", _p(x), _p(du), _p(stats), _p(gamma), M, Cc, ns, _p(slab), _p(sums), _p(dx))
-    return sums
+    return (sums, slab) if with_slab else sums
 
 
 def bn_bwd_any(x, du, stats, gamma, M: int, Cc: int, dx, training: bool):
