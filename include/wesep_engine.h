@@ -529,8 +529,9 @@ void ws_engine_live_pool_close(ws_live_pool* p);
  * No launch mixes rows: with the row composition of the forwards held fixed, a slot's bits do not depend on the other slots'
  * sample values -- as far as the architecture's rectangular plan keeps its rows apart.  With one row per forward
  * (max_rows = 1) every window is bit for bit ws_engine_separate on that window alone.
- * NOT built: a sample rate per slot; a different K per slot; backlog handling beyond one window (a caller that falls behind
- * has to tick, or drop audio itself).
+ * A sample rate per slot: the rate tail pool below (ws_engine_rate_tail_pool_*).
+ * NOT built: a different K per slot; backlog handling beyond one window (a caller that falls behind has to tick, or drop audio
+ * itself).
  * WS_ERR_INVALID with a message and nothing launched: a slot of a push, tick or flush that is free, flushed, named twice or
  * part of a failed call; n[i] < 1; est_cap below the emission, checked for every entry before any launch; a NULL pointer; the
  * push overflow above; a full pool; the bounds of open. */
@@ -545,6 +546,83 @@ int ws_engine_tail_pool_tick(ws_tail_pool* p, int n_active, const int* slots, fl
 int ws_engine_tail_pool_flush(ws_tail_pool* p, int slot, float* est, int est_cap, int* n_out);
 int ws_engine_tail_pool_detach(ws_tail_pool* p, int slot);
 void ws_engine_tail_pool_close(ws_tail_pool* p);
+
+/* ---- rate tail pool (runtime/rate_tail_pool.cc; DESIGN sections 7 "Rate tail pool" and 11b) -- new symbols,
+ * WS_ENGINE_ABI_VERSION 2 unchanged.  The tail pool above with a SAMPLE RATE PER SLOT: a telephony call at 8 kHz and a WebRTC
+ * call at 48 kHz get the low-latency path to pBSRNN, DPCCN and (non-causal) Conv-TasNet containers in the same ticks.  A slot
+ * carries and returns audio at its caller's rate r; the separator runs at the container's rate r0.
+ * THE RULE, per slot.  A is the r -> r0 filter (U_A, D_A, w_A, K_A), B the r0 -> r filter (ws_resample_geom).  Window S, fade C and
+ * warm are samples at the CONTAINER's rate, exactly as in the tail pool.  N_c: caller-rate samples pushed.
+ *   N      the container-rate samples the recording HAS: the streaming emission count of wesep_hip.h,
+ *          U_A max(0, floor((N_c - w_A) / D_A)), known on the host before anything runs.
+ *   push   appends caller-rate samples on the host: NO launch, NO synchronisation.  Refused ("tick first") when
+ *          ceil(U_A (N_c + n) / D_A) - E > S, before anything of the call is appended: what a flush right after the push would
+ *          have to emit must fit one window.
+ *   tick   the tail pool's rule on N, unchanged: firing condition, window [max(0, N - S), N), emission [E, N - C), hold, blend,
+ *          ramp, F.  The window's samples are kept NOWHERE at the container's rate: the gather (ws_window_resample_rows_fwd)
+ *          computes them from the caller-rate span that their taps cover, so the pool carries no input-resampler state and a
+ *          window's bits are those of ws_resample_fwd on the whole recording.  The emitted samples of every (slot, target) are
+ *          a stream: they go through B as a streaming resampler whose history is held per slot and target in the pool's state,
+ *          double-buffered.  The tick returns B's emission, at the caller's rate; n_out[i] is known before anything runs.
+ *   flush  N becomes ceil(U_A N_c / D_A); the last window runs with A's final rule (taps behind the end are skipped); the tail
+ *          flush rule emits [E, N); B takes them and ends its stream in the same launch (final = 1 on `history | new`: the bits
+ *          of B's step followed by B's flush).  The total is cropped so that a slot returns exactly N_c samples a target over
+ *          its life (B's uncropped total is never below N_c).
+ *   a slot at the container's rate runs the identity table (U = D = K = 1, tap 1.0) through both filters: its samples are the
+ *          plain tail pool's.
+ * PARITY, per slot: bit for bit what the existing public pieces give when chained -- a streaming resampler r -> r0 fed the same
+ * packets; a tail pool at the container's rate fed its emissions and ticked at the same moments (its flush after the
+ * resampler's); one streaming resampler r0 -> r per target fed the pool's emissions and flushed, cropped to N_c -- with
+ * max_rows = 1, and whenever the two pools form the same forwards (the same slots attached in the same order and firing on the
+ * same ticks).
+ *   ws_engine_rate_tail_pool_open(e, slots, K, window, fade, warm, max_rows, rates, n_rates, &pool)  the checks of
+ *     ws_engine_tail_pool_open under this name; every listed rate validated in both directions and every tap table uploaded, as
+ *     ws_engine_rate_pool_open does (the container's own rate is always accepted).  A TF-GridNet container is refused by name:
+ *     its per-window standard deviation is taken on the host from container-rate samples, which this pool never has there.
+ *     Makes ONE device allocation, ws_engine_info "rate_tail_pool_state_bytes", that no later call grows, a function of
+ *     (slots, K, S, C, max_rows) and the worst listed geometry only: the tail pool's parts (the spans at the caller's rate, the
+ *     three tables), B's two buffers [K_B - 1 + S] per slot and target, B's compact output block, the ramp, the tables.
+ *   ws_engine_rate_tail_pool_attach(pool, enroll, enroll_kind, enroll_len, enroll_lengths, enroll_rate, sample_rate, &slot)  as
+ *     ws_engine_tail_pool_attach; sample_rate must be a listed rate (the message lists the accepted ones); a WS_ENROLL_WAVE
+ *     enrollment at enroll_rate != 0 is resampled first, every row over its own length (other kinds: enroll_rate 0).
+ *     A rate whose slots could never fire is refused: before the first firing a push is taken while ceil(U_A N_c / D_A) <= S, and
+ *     the filter's look-ahead keeps N below that; warm must not exceed U_A floor((floor(D_A S / U_A) - w_A) / D_A).
+ *   ws_engine_rate_tail_pool_push(pool, n_active, slots, chunks, n)  chunks[i]: n[i] >= 1 samples at slots[i]'s rate.
+ *     ws_engine_rate_tail_pool_room(pool, slot): the largest n the slot takes now (0: tick first; -1: not an attached, unflushed
+ *     slot) -- what a caller cuts a packet to.
+ *   ws_engine_rate_tail_pool_tick(pool, n_active, slots, est, est_cap, n_out)  est[i] is [K][est_cap[i]], n_out[i] samples a
+ *     target at the slot's rate; ws_engine_rate_tail_pool_cap(pool, slot) always suffices; est_cap is checked for every entry
+ *     before any launch.  If no named slot fires: NO launch, NO synchronisation.  Otherwise, in order: one upload of the staging
+ *     block (spans, embedding rows, tables), ONE ws_window_resample_rows_fwd, the forwards grouped exactly as the tail pool
+ *     groups them, ONE ws_tail_emit_rows_fwd writing straight behind B's histories, ONE ws_resample_stream_rows_fwd for B over
+ *     all (slot, target) rows, one copy to the host, ONE synchronisation.  ws_engine_info "n_launches" after a tick:
+ *         the forwards' rectangular counts + WS_RATE_TAIL_TICK_LAUNCHES + 1
+ *     whatever the number of firing slots and of distinct rates among them (one less in the one case that nothing reaches B: only
+ *     first firings with warm == fade).  "rate_tail_pool_forwards" and "rate_tail_pool_rows" report the last tick or flush.
+ *   ws_engine_rate_tail_pool_flush(pool, slot, est, est_cap, &n_out)  a tick of this one slot with the final rule: the same
+ *     count.  Only a slot at the container's rate can have N == F: ws_rows_copy_fwd of the hold behind B's history in place of
+ *     the gather, the forwards and the emission (nothing at all when the fade is 0).
+ *   ws_engine_rate_tail_pool_detach(pool, slot)    ws_engine_rate_tail_pool_close(pool)  before ws_engine_destroy.
+ * Dry-run engines take every call and return the right counts.  All pointers are HOST pointers; callers serialise.
+ * FAILURE: the slots named by a tick or flush that failed half way are refused by name until they are detached.
+ * No launch mixes rows: with the row composition of the forwards held fixed, a slot's bits do not depend on the other slots'
+ * sample values, NaN and inf included.
+ * NOT built: TF-GridNet containers; a different K per slot; backlog handling beyond one window.
+ * WS_ERR_INVALID with a message and nothing launched: the refusals of ws_engine_tail_pool_* and ws_engine_rate_pool_* under this
+ * family's names; an unlisted rate; the push overflow above. */
+typedef struct ws_rate_tail_pool ws_rate_tail_pool;
+#define WS_RATE_TAIL_TICK_LAUNCHES 3     /* ws_window_resample_rows_fwd + ws_tail_emit_rows_fwd + ws_resample_stream_rows_fwd */
+int ws_engine_rate_tail_pool_open(ws_engine* e, int slots, int K, int window, int fade, int warm, int max_rows, const int* rates,
+                                  int n_rates, ws_rate_tail_pool** out);
+int ws_engine_rate_tail_pool_attach(ws_rate_tail_pool* p, const void* enroll, int enroll_kind, int enroll_len, const int* enroll_lengths,
+                                    int enroll_rate, int sample_rate, int* slot);
+int ws_engine_rate_tail_pool_cap(const ws_rate_tail_pool* p, int slot);
+int ws_engine_rate_tail_pool_room(const ws_rate_tail_pool* p, int slot);
+int ws_engine_rate_tail_pool_push(ws_rate_tail_pool* p, int n_active, const int* slots, const float* const* chunks, const int* n);
+int ws_engine_rate_tail_pool_tick(ws_rate_tail_pool* p, int n_active, const int* slots, float* const* est, const int* est_cap, int* n_out);
+int ws_engine_rate_tail_pool_flush(ws_rate_tail_pool* p, int slot, float* est, int est_cap, int* n_out);
+int ws_engine_rate_tail_pool_detach(ws_rate_tail_pool* p, int slot);
+void ws_engine_rate_tail_pool_close(ws_rate_tail_pool* p);
 
 /* The reference runtime's call: one mixture, two enrollment utterances (int16 PCM), two estimates.
  * mix [n] int16; spk1 / spk2 [n_enroll] int16; out [2][n] float in [-1, 1] like the reference (it scales the mixture by

@@ -1490,7 +1490,29 @@ int ws_resample_stream_fwd(const float* buf, long long ldb, int R, int rate_in, 
  *   ws_rows_copy_fwd  row i: dst[dst_off + j] = src[src_off + j], j < len, then `fill` zeros behind them.  Pure data
  *                   movement (a gather of per-slot samples into a rectangle, or the scatter back); the same two-table
  *                   convention.  WS_ERR_INVALID before any launch, with the row index: len or fill negative or both 0, a range
- *                   that leaves its arena, a dst range that overlaps any other range of the call. */
+ *                   that leaves its arena, a dst range that overlaps any other range of the call.
+ *   ws_window_resample_rows_fwd  (a new symbol, ABI 20 unchanged) the gather of a rate tail pool (runtime/rate_tail_pool.cc): row
+ *                   i is L consecutive outputs of the whole-signal filter that start at ANY phase, computed from the span of
+ *                   the input that their taps cover.  Its descriptor names
+ *                     buf + in_off    the span, n_valid valid samples, numbered as a stream's buffer is: group g of the buffer
+ *                                     reads buf[in_off + g D - lead + k], k < K; lead in [0, w] is the number of taps of group
+ *                                     0 that lie before the span, which starts at sample 0 of the signal when lead > 0
+ *                     taps + taps_off its table [U][K] (or the identity U = D = K = 1), U, D, K explicit, w = (K - D) / 2
+ *                     g_first, p_first  the first output: phase p_first in [0, U) of the buffer's group g_first
+ *                     y + out_off     the L outputs, then `fill` zeros
+ *                     final           0: every tap of every output must fall on a valid sample; 1: the signal ends at
+ *                                     n_valid and taps behind it are skipped
+ *                   Output j is resample_one -- the device function of every call above -- on output g_first U + p_first + j of
+ *                   the buffer's numbering: with the buffer's group 0 the signal's group G0, the BITS ws_resample_fwd gives
+ *                   for output (G0 + g_first) U + p_first + j of the whole signal (final = 1: of the signal that ends with
+ *                   the span).  Nothing behind n_valid is read (NaN there reaches nothing), nothing behind L + fill is
+ *                   written.  Rows may share a span.  Grid (max_i ceil((L_i + fill_i) / 256), A); the tables as above (U K <=
+ *                   2048 floats: staged in LDS; larger: global memory); 64-bit offsets, no atomics, plain C++; the two-table
+ *                   convention.  WS_ERR_INVALID before any launch, each with the row index: U, D, K, lead, g_first as for
+ *                   ws_resample_stream_rows_fwd; p_first outside [0, U); n_valid < 1, L or fill negative or both 0; with
+ *                   final = 0 an output whose taps fall behind n_valid, with final = 1 outputs past ceil(U (n_valid + lead -
+ *                   w) / D); offsets reaching 2^31; a range that leaves its arena; a y range that meets any other range of
+ *                   the call; A outside [1, 65535]; a NULL pointer. */
 typedef struct ws_resample_row {
   long long in_off, taps_off, out_off, hist_off;
   int U, D, K;
@@ -1500,11 +1522,18 @@ typedef struct ws_rows_copy_row {
   long long src_off, dst_off;
   int len, fill;
 } ws_rows_copy_row;
+typedef struct ws_window_resample_row {
+  long long in_off, taps_off, out_off;
+  int U, D, K;
+  int lead, n_valid, final, g_first, p_first, L, fill;
+} ws_window_resample_row;
 int ws_resample_stream_rows_fwd(const ws_resample_row* rows, const ws_resample_row* d_rows, int A, const float* buf,
                                 long long n_buf, const float* taps, long long n_taps, float* y, long long n_y, float* hist,
                                 long long n_hist, void* stream);
 int ws_rows_copy_fwd(const ws_rows_copy_row* rows, const ws_rows_copy_row* d_rows, int A, const float* src, long long n_src,
                      float* dst, long long n_dst, void* stream);
+int ws_window_resample_rows_fwd(const ws_window_resample_row* rows, const ws_window_resample_row* d_rows, int A, const float* buf,
+                                long long n_buf, const float* taps, long long n_taps, float* y, long long n_y, void* stream);
 
 #ifdef __cplusplus
 }

@@ -368,6 +368,10 @@ WS_ENGINE_API long long ws_engine_info(const ws_engine* e, const char* key) {
   if (k == "tail_pool_state_bytes") return e->tail_pool_state_bytes;
   if (k == "tail_pool_forwards") return e->tail_pool_forwards;
   if (k == "tail_pool_rows") return e->tail_pool_rows;
+  // the same three of the rate tail pool
+  if (k == "rate_tail_pool_state_bytes") return e->rate_tail_pool_state_bytes;
+  if (k == "rate_tail_pool_forwards") return e->rate_tail_pool_forwards;
+  if (k == "rate_tail_pool_rows") return e->rate_tail_pool_rows;
   auto it = e->meta.find(k);
   return it == e->meta.end() ? -1 : it->second;
 }

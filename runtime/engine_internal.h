@@ -12,6 +12,7 @@
 //   live.cc          ws_engine_live_*: the windows of ws_engine_separate_long run as their samples arrive, any architecture
 //   live_pool.cc     ws_engine_live_pool_*: many live recordings, the windows one push completes in the same forwards
 //   tail_pool.cc     ws_engine_tail_pool_*: many live recordings on their trailing windows, fired by the caller's tick
+//   rate_tail_pool.cc  ws_engine_rate_tail_pool_*: the tail pool with a sample rate per slot
 //   stream.cc        what every streaming front end shares -- the launch chain of a group of frames (stream_chain), the state
 //                    block (StreamCore) and the speaker stage of a stream (stream_enroll) -- and ws_engine_stream_*: causal
 //                    cLN Conv-TasNet fed audio as it arrives, state carried on the device
@@ -316,6 +317,8 @@ struct ws_engine {
   long long live_pool_rounds = 0, live_pool_forwards = 0;   // rounds and forwards of the last live-pool push or flush
   long long tail_pool_state_bytes = 0;             // device state of the tail pool opened last (ws_engine_tail_pool_open)
   long long tail_pool_forwards = 0, tail_pool_rows = 0;     // forwards and separator rows of the last tail-pool tick or flush
+  long long rate_tail_pool_state_bytes = 0;        // device state of the rate tail pool opened last (ws_engine_rate_tail_pool_open)
+  long long rate_tail_pool_forwards = 0, rate_tail_pool_rows = 0;     // forwards and separator rows of its last tick or flush
   long long stream_state_bytes = 0;                // device state of the stream opened last (ws_engine_stream_open)
   long long cluster_fallbacks = 0;   // forwards in which a cluster recurrence timed out and the streaming kernels took over
   unsigned* cl_status = nullptr;     // sticky device word set by ws_lstm_fwd_cluster on a timeout

@@ -6,6 +6,7 @@
 //                 [--stream_ms 10 [--stream_pool 4 | --rate_pool 4] [--stream_block]] [--resample]
 //                 [--live_ms 100 --chunk_seconds 4 [--live_pool 4 [--live_hold_ms 3000]]]
 //                 [--tail_ms 100 --chunk_seconds 4 [--tail_fade_ms 10] [--tail_warm_seconds 4] [--tail_pool 4]]
+//                 [--tail_ms 40 --chunk_seconds 4 --tail_rate_pool 4 [--tail_fade_ms 10] [--tail_warm_seconds 3]]
 //   separate_main --wav_path mix.wav --spk1_emb e1.wav --spk2_emb e2.wav --model model.wsw --output_dir out
 //
 // wav_scp lines: "<key> <mixture.wav> <enroll_spk1.wav> <enroll_spk2.wav>".  For every line the mixture and the two
@@ -53,6 +54,12 @@
 // is new comes out M ms plus the fade after it went in; a line that ends is flushed and its slot re-attached.  The samples
 // follow the tail rule (include/wesep_engine.h), NOT the --chunk_seconds run.  A packet is cut where more than one window of
 // samples would be waiting.  Works with --jobs, --dry_run and --resample; refused together with every other mode.
+// --tail_ms M --tail_rate_pool N (with --chunk_seconds S; any model but TF-GridNet): the same rounds on one rate tail pool
+// (ws_engine_rate_tail_pool_*, K = 2): every line is fed at its own file's sample rate, in packets of M ms at that rate cut to
+// what ws_engine_rate_tail_pool_room still takes, and returned at that rate -- nothing is resampled around the pool, so
+// --resample is refused with it, and so is --tail_pool.  --tail_warm_seconds defaults to 3/4 S here (the filters' look-ahead
+// keeps a resampled line below a whole window before its first firing).  Outputs have the mixture's rate and length; a
+// --dry_run with an --output_dir writes the (all-zero) files.
 // --stream_ms M (causal cLN Conv-TasNet / SpEx+ models, ws_engine_info "streaming"): every line is fed to a stream
 // (ws_engine_stream_open / push / flush) in chunks of M milliseconds, as a live source would deliver it; the speaker encoder
 // runs once per line, at open.  Same files as the plain run: the streamed samples, then zeros where the plain run has its
@@ -196,11 +203,13 @@ int main(int argc, char** argv) {
   const int tail_fade = static_cast<int>(atof(args.get("tail_fade_ms", "10").c_str()) * sample_rate / 1000.0 + 0.5);
   const int tail_warm = args.has("tail_warm_seconds") ? static_cast<int>(atof(args.get("tail_warm_seconds", "0").c_str()) * sample_rate + 0.5) : window;
   const int tail_pool_n = atoi(args.get("tail_pool", "1").c_str());
+  const bool tail_rate = args.has("tail_rate_pool");
+  const int tail_rate_n = atoi(args.get("tail_rate_pool", "0").c_str());
   const bool rate_pooled = args.has("rate_pool");
   const int rate_pool_n = atoi(args.get("rate_pool", "0").c_str());
   // a dry run writes nothing -- except with --resample and an --output_dir: the (all-zero) files then show the rate and the
   // length an output will have
-  const bool write_out = !dry || ((resample || rate_pooled) && !out_dir.empty());
+  const bool write_out = !dry || ((resample || rate_pooled || tail_rate) && !out_dir.empty());
   if (args.has("help")) {
     printf("usage: separate_main --wav_scp scp --model model.wsw --output_dir out [--sample_rate 16000] [--devices 0,1]\n"
            "                     [--jobs J] [--batch N] [--sort_by_length] [--raw_out] [--dry_run]\n"
@@ -208,6 +217,7 @@ int main(int argc, char** argv) {
            "                     [--stream_ms M [--stream_pool N | --rate_pool N] [--stream_block]] [--resample]\n"
            "                     [--live_ms M --chunk_seconds S [--live_pool N [--live_hold_ms W]]]\n"
            "                     [--tail_ms M --chunk_seconds S [--tail_fade_ms F] [--tail_warm_seconds W] [--tail_pool N]]\n"
+           "                     [--tail_ms M --chunk_seconds S --tail_rate_pool N [--tail_fade_ms F] [--tail_warm_seconds W]]\n"
            "  --batch N          N scp lines per forward (pBSRNN and TF-GridNet models), every row at its own length\n"
            "  --sort_by_length   with --batch N: order the lines by mixture length (longest first, stable) before grouping;\n"
            "                     outputs keep their names, the log follows the processing order.  Without --batch the flag\n"
@@ -232,6 +242,9 @@ int main(int argc, char** argv) {
            "  --tail_warm_seconds W  the audio a line needs before its first window (default S)\n"
            "  --tail_pool N      N lines in flight at once on one tail pool (default 1); every line with new audio fires on the\n"
            "                     same tick and shares the forwards; a lane takes the next line when its own ends\n"
+           "  --tail_rate_pool N with --tail_ms M: N lines in flight at once on one rate tail pool, every line at its own file's\n"
+           "                     sample rate (packets of M ms at that rate, no --resample); --tail_warm_seconds defaults to 3/4 S;\n"
+           "                     outputs have the mixture's rate and length.  Not a TF-GridNet model, not with --tail_pool\n"
            "  --stream_ms M      causal cLN Conv-TasNet / SpEx+ models: feed every line to a stream in chunks of M ms; same\n"
            "                     files as the plain run.  Not together with --batch N > 1 or --chunk_seconds\n"
            "  --stream_pool N    with --stream_ms M: N consecutive lines at a time through one stream pool, one push per round\n"
@@ -246,6 +259,12 @@ int main(int argc, char** argv) {
   }
   if ((args.has("tail_fade_ms") || args.has("tail_warm_seconds") || args.has("tail_pool")) && !tail)
     return die("--tail_fade_ms, --tail_warm_seconds and --tail_pool need --tail_ms M: the tail pool is fed packets of M milliseconds");
+  if (tail_rate && !tail) return die("--tail_rate_pool needs --tail_ms M: the rate tail pool is fed packets of M milliseconds at every line's own rate");
+  if (tail_rate && args.has("tail_pool")) return die("--tail_rate_pool conflicts with --tail_pool: one pool per run; --tail_rate_pool takes lines at any rate");
+  if (tail_rate && resample)
+    return die("--tail_rate_pool conflicts with --resample: the rate tail pool takes every line at its own file's rate, nothing is resampled "
+               "around it");
+  if (tail_rate && tail_rate_n < 1) return die("--tail_rate_pool needs a positive number of lines");
   if (tail && !chunked) return die("--tail_ms needs --chunk_seconds S: a tail pool runs the trailing window of S seconds at every tick");
   if (tail && (batch > 1 || streamed || live || live_pooled || pooled || rate_pooled))
     return die("--tail_ms conflicts with --batch N > 1, --stream_ms, --live_ms, --live_pool, --stream_pool and --rate_pool: one mode per "
@@ -378,6 +397,175 @@ int main(int argc, char** argv) {
       for (int r = 0; r < R; ++r) memcpy(out + size_t(r) * n, back.data() + size_t(r) * m, size_t(std::min(n, m)) * 4);
       return true;
     };
+    // --tail_ms M --tail_rate_pool N: up to N lines in flight on one rate tail pool (ws_engine_rate_tail_pool_*, K = 2), every line at
+    // its own file's rate: a round pushes every lane its next packet of M ms at that rate -- cut to what the slot still takes -- and
+    // ticks all of them; the accepted rates are those of the scp's mixtures, read before the pool is opened; outputs have the
+    // mixture's rate and length.  An enrollment pair at one rate goes to the attach at that rate, another pair through
+    // ws_engine_resample first.
+    if (tail_rate) {
+      struct Lane {
+        bool live = false;
+        size_t line = 0;
+        std::vector<float> mix, out, got;      // at the file's rate: the mixture [n], the estimates [2][n]; a call's [2][cap]
+        int n = 0, pos = 0, done = 0, slot = -1, rate = 0, packet = 0, cap = 0;
+        long long pushes = 0;
+        std::chrono::steady_clock::time_point t0;
+      };
+      std::vector<int> rates;
+      for (const auto& w : waves) {
+        wesep_rt::Wav hdr;
+        std::string err;
+        if (!wesep_rt::read_wav(w[1], &hdr, &err)) {
+          fail(err);
+          ws_engine_destroy(engine);
+          return;
+        }
+        if (std::find(rates.begin(), rates.end(), hdr.sample_rate) == rates.end()) rates.push_back(hdr.sample_rate);
+      }
+      const int warm = args.has("tail_warm_seconds") ? tail_warm : 3 * window / 4;
+      ws_rate_tail_pool* rt = nullptr;
+      if (ws_engine_rate_tail_pool_open(engine, tail_rate_n, 2, window, tail_fade, warm, chunk_rows, rates.data(), static_cast<int>(rates.size()),
+                                        &rt) != 0) {
+        fail(std::string("--tail_rate_pool: ") + ws_engine_last_error());
+        ws_engine_destroy(engine);
+        return;
+      }
+      std::vector<Lane> lanes(tail_rate_n);
+      bool ok = true;
+      long long rounds = 0, launches = 0, forwards = 0, rows = 0;
+      double audio_ms = 0.0;
+      const auto pool_t0 = std::chrono::steady_clock::now();
+      auto start = [&](Lane& ln) {                // the next line of the scp into this lane: read it, attach its two enrollments
+        const size_t i = next++;
+        if (i >= waves.size() || failed) return;
+        const auto& w = waves[i];
+        wesep_rt::Wav mix, s1, s2;
+        std::string err;
+        if (!wesep_rt::read_wav(w[1], &mix, &err) || !wesep_rt::read_wav(w[2], &s1, &err) || !wesep_rt::read_wav(w[3], &s2, &err)) {
+          fail(err);
+          ok = false;
+          return;
+        }
+        std::vector<float> e[2];
+        int enroll_rate = 0;
+        if (s1.sample_rate == s2.sample_rate) {   // the attach resamples the pair
+          enroll_rate = s1.sample_rate;
+          for (int k = 0; k < 2; ++k)
+            for (int16_t v : (k ? s2 : s1).samples) e[k].push_back(static_cast<float>(v) / 32768.0f);
+        } else if (!to_model(s1.samples, s1.sample_rate, &e[0]) || !to_model(s2.samples, s2.sample_rate, &e[1])) {
+          fail(w[0] + ": " + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        const int n_enroll = static_cast<int>(std::min(e[0].size(), e[1].size()));
+        std::vector<float> enr(size_t(2) * n_enroll);
+        memcpy(enr.data(), e[0].data(), size_t(n_enroll) * 4);
+        memcpy(enr.data() + n_enroll, e[1].data(), size_t(n_enroll) * 4);
+        ln.line = i, ln.n = static_cast<int>(mix.samples.size()), ln.pos = ln.done = 0, ln.pushes = 0, ln.rate = mix.sample_rate;
+        ln.packet = std::max(1, static_cast<int>(tail_ms * ln.rate / 1000.0 + 0.5));
+        ln.mix.resize(ln.n);
+        for (int j = 0; j < ln.n; ++j) ln.mix[j] = static_cast<float>(mix.samples[j]) / 32768.0f;
+        ln.out.assign(size_t(2) * ln.n, 0.f);
+        ln.t0 = std::chrono::steady_clock::now();
+        if (ws_engine_rate_tail_pool_attach(rt, enr.data(), WS_ENROLL_WAVE, n_enroll, nullptr, enroll_rate, ln.rate, &ln.slot) != 0) {
+          fail(w[0] + ": " + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        ln.cap = ws_engine_rate_tail_pool_cap(rt, ln.slot);
+        ln.got.assign(size_t(2) * ln.cap, 0.f);
+        ln.live = true;
+      };
+      auto take = [&](Lane& ln, int m) {          // got [2][cap], m samples each, behind what came before
+        for (int k = 0; k < 2; ++k) memcpy(ln.out.data() + size_t(k) * ln.n + ln.done, ln.got.data() + size_t(k) * ln.cap, size_t(m) * 4);
+        ln.done += m;
+      };
+      auto finish = [&](Lane& ln) {               // flush the slot, free it, write the line's files at the mixture's rate
+        const auto& w = waves[ln.line];
+        int m = 0;
+        if (ws_engine_rate_tail_pool_flush(rt, ln.slot, ln.got.data(), ln.cap, &m) != 0 || ws_engine_rate_tail_pool_detach(rt, ln.slot) != 0) {
+          fail(w[0] + ": " + ws_engine_last_error());
+          ok = false;
+          return;
+        }
+        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, "rate_tail_pool_forwards");
+        take(ln, m);
+        ln.live = false;
+        std::string err;
+        if (ln.done != ln.n) {
+          fail(w[0] + ": the rate tail pool returned " + std::to_string(ln.done) + " samples for " + std::to_string(ln.n));
+          ok = false;
+          return;
+        }
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ln.t0).count();
+        if (write_out && (!wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk1.wav", ln.out.data(), ln.n, ln.rate, &err) ||
+                          !wesep_rt::write_wav(out_dir + "/" + w[0] + "-spk2.wav", ln.out.data() + ln.n, ln.n, ln.rate, &err))) {
+          fail(err);
+          ok = false;
+          return;
+        }
+        if (!dry && raw_out) {
+          for (int k = 0; k < 2; ++k) {
+            FILE* f = fopen((out_dir + "/" + w[0] + "-spk" + std::to_string(k + 1) + ".f32").c_str(), "wb");
+            if (!f || fwrite(ln.out.data() + size_t(k) * ln.n, 4, ln.n, f) != size_t(ln.n)) fail("cannot write raw output");
+            if (f) fclose(f);
+          }
+        }
+        std::lock_guard<std::mutex> l(io_mu);
+        printf("process: %s RTF: %.4f (rate tail pool of %d lines: %d Hz, %lld ticks, packets of %d samples, fade %d, %lld bytes of rate tail "
+               "pool state)%s\n", w[0].c_str(), ms / (1000.0 * ln.n / ln.rate), tail_rate_n, ln.rate, ln.pushes, ln.packet, tail_fade,
+               ws_engine_info(engine, "rate_tail_pool_state_bytes"), dry ? " [dry run]" : "");
+        audio_ms += 1000.0 * ln.n / ln.rate;
+      };
+      for (int a = 0; a < tail_rate_n; ++a)
+        if (ok) start(lanes[a]);
+      while (ok && !failed) {
+        std::vector<int> slots, ns, caps, n_out, who;
+        std::vector<const float*> chunks;
+        std::vector<float*> ests;
+        for (int a = 0; a < tail_rate_n && ok; ++a) {
+          Lane& ln = lanes[a];
+          if (!ln.live) continue;
+          const int room = ws_engine_rate_tail_pool_room(rt, ln.slot);
+          if (room < 1) {                         // the last tick did not fire the line and it takes no more
+            fail(waves[ln.line][0] + ": a window of audio is waiting and the line does not fire: lower --tail_warm_seconds");
+            ok = false;
+            break;
+          }
+          slots.push_back(ln.slot), ns.push_back(std::min({ln.packet, ln.n - ln.pos, room})), caps.push_back(ln.cap), who.push_back(a);
+          chunks.push_back(ln.mix.data() + ln.pos), ests.push_back(ln.got.data());
+        }
+        if (slots.empty() || !ok) break;
+        n_out.assign(slots.size(), 0);
+        const int A = static_cast<int>(slots.size());
+        if (ws_engine_rate_tail_pool_push(rt, A, slots.data(), chunks.data(), ns.data()) != 0 ||
+            ws_engine_rate_tail_pool_tick(rt, A, slots.data(), ests.data(), caps.data(), n_out.data()) != 0) {
+          fail(std::string("--tail_rate_pool: ") + ws_engine_last_error());
+          ok = false;
+          break;
+        }
+        launches += ws_engine_info(engine, "n_launches"), forwards += ws_engine_info(engine, "rate_tail_pool_forwards");
+        rows += ws_engine_info(engine, "rate_tail_pool_rows"), ++rounds;
+        for (size_t r = 0; r < who.size() && ok; ++r) {
+          Lane& ln = lanes[who[r]];
+          take(ln, n_out[r]);
+          ln.pos += ns[r], ++ln.pushes;
+          if (ln.pos >= ln.n) {
+            finish(ln);
+            if (ok) start(ln);
+          }
+        }
+      }
+      ws_engine_rate_tail_pool_close(rt);
+      if (ok) {
+        std::lock_guard<std::mutex> l(io_mu);
+        printf("rate tail pool: %lld ticks, %lld rows, %lld forwards, %lld launches\n", rounds, rows, forwards, launches);
+        total_audio_ms += audio_ms;
+        total_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pool_t0).count();
+      }
+      ws_engine_destroy(engine);
+      return;
+    }
     // --live_pool N: up to N lines in flight on one live pool of N slots (K = 2), each fed its next packet of live_n samples at the
     // model's rate in one push per round; a lane takes the next line when its own ends.  With --resample a line's files are
     // brought to the model's rate before and its estimates back after, as for --live_ms.

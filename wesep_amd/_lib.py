@@ -341,6 +341,8 @@ _SIGS = {
     # rows forms: (host table, device table, A), then the arenas with their lengths in floats
     "ws_resample_stream_rows_fwd": (_i, [_p, _p, _i, _p, _ll, _p, _ll, _p, _ll, _p, _ll, _p]),
     "ws_rows_copy_fwd": (_i, [_p, _p, _i, _p, _ll, _p, _ll, _p]),
+    # rate tail pool: windows of the whole-signal filter from any phase -- (host table, device table, A), buf, taps, y with lengths
+    "ws_window_resample_rows_fwd": (_i, [_p, _p, _i, _p, _ll, _p, _ll, _p, _ll, _p]),
     # live pool (longform.hip): the rows forms of the window gather and of the ring cross-fade
     "ws_window_slots_fwd": (_i, [_p, _p, _i, _p, _ll, _p, _ll, _p]),
     "ws_xfade_stream_rows_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _ll, _p, _ll, _p, _ll, _p]),
@@ -353,6 +355,10 @@ RESAMPLE_ROW = np.dtype([("in_off", "<i8"), ("taps_off", "<i8"), ("out_off", "<i
                          ("K", "<i4"), ("lead", "<i4"), ("n_valid", "<i4"), ("final", "<i4"), ("g_first", "<i4"), ("n_out", "<i4"),
                          ("hist_from", "<i4"), ("hist_len", "<i4")])
 ROWS_COPY_ROW = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("fill", "<i4")])
+# ws_window_resample_row
+WINDOW_RESAMPLE_ROW = np.dtype([("in_off", "<i8"), ("taps_off", "<i8"), ("out_off", "<i8"), ("U", "<i4"), ("D", "<i4"), ("K", "<i4"),
+                                ("lead", "<i4"), ("n_valid", "<i4"), ("final", "<i4"), ("g_first", "<i4"), ("p_first", "<i4"),
+                                ("L", "<i4"), ("fill", "<i4")])
 # ws_window_slot_row, ws_xfade_stream_row (the latter ends in four bytes of padding)
 WINDOW_SLOT_ROW = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("scale", "<f4")])
 XFADE_STREAM_ROW = np.dtype([("ring_off", "<i8"), ("scale_off", "<i8"), ("out_off", "<i8"), ("i0", "<i8"), ("count", "<i8"),

@@ -64,7 +64,7 @@ ENGINE_OUT = os.path.join(RUNTIME, "libwesep_engine.so")
 MAIN_OUT = os.path.join(RUNTIME, "separate_main")
 # libwesep_engine.so: one translation unit per part (runtime/engine_internal.h); it exports the C ABI only
 ENGINE_SRCS = ["engine.cc", "speaker.cc", "bsrnn_plan.cc", "tasnet_plan.cc", "dpccn_plan.cc", "gridnet_plan.cc",
-               "longform.cc", "live.cc", "live_pool.cc", "tail_pool.cc", "stream.cc", "stream_pool.cc", "rate.cc", "rate_pool.cc"]
+               "longform.cc", "live.cc", "live_pool.cc", "tail_pool.cc", "rate_tail_pool.cc", "stream.cc", "stream_pool.cc", "rate.cc", "rate_pool.cc"]
 
 
 def build_runtime(force=False, verbose=True):

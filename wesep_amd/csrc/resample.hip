@@ -19,6 +19,9 @@
 //
 // Rows forms (below the solo launch): ws_resample_stream_rows_fwd runs A rows, each with its own geometry, table, buffer,
 // position and destinations, through the same resample_one in one launch; ws_rows_copy_fwd is table-driven data movement.
+// ws_window_resample_rows_fwd is the gather of a rate tail pool: row i is L consecutive outputs of the whole-signal filter that
+// start at ANY phase of a group (a trailing window does not start on a group boundary), computed from the input span that
+// their taps cover and written to a destination of its own, `fill` zeros behind them.
 #include <algorithm>
 #include <cstdint>
 #include <vector>
@@ -146,6 +149,38 @@ __global__ __launch_bounds__(256) void resample_rows_kernel(const ws_resample_ro
     y[r.out_off + i] = resample_one(row, tg + p * r.K, r.D, r.K, r.lead, r.n_valid, grp);
 }
 
+// grid (max_i blocks of L_i + fill_i, A): workgroup (b, i) owns 256 consecutive floats of row i's destination -- outputs first,
+// zeros behind them -- and leaves before any barrier when b is beyond the row's count.  A workgroup that lies wholly in the
+// zeros stages no table.  Everything that decides these is blockIdx and the descriptor: workgroup-uniform.
+__global__ __launch_bounds__(256) void window_resample_rows_kernel(const ws_window_resample_row* __restrict__ rows,
+                                                                   const float* __restrict__ buf, const float* __restrict__ taps,
+                                                                   float* __restrict__ y) {
+  extern __shared__ float s_taps[];
+  const ws_window_resample_row r = rows[blockIdx.y];
+  const int n = r.L + r.fill;
+  const int i0 = (int)blockIdx.x * 256;
+  if (i0 >= n) return;
+  const float* tg = taps + r.taps_off;
+  const bool lds = r.U * r.K <= RS_LDS_TAPS;
+  if (lds && i0 < r.L) {
+    for (int i = threadIdx.x; i < r.U * r.K; i += 256) s_taps[i] = tg[i];
+    __syncthreads();
+  }
+  const int i = i0 + (int)threadIdx.x;
+  if (i >= n) return;
+  if (i >= r.L) {
+    y[r.out_off + i] = 0.f;
+    return;
+  }
+  const int q = r.g_first * r.U + r.p_first + i;
+  const int grp = q / r.U, p = q - grp * r.U;
+  const float* row = buf + r.in_off;
+  if (lds)
+    y[r.out_off + i] = resample_one(row, s_taps + p * r.K, r.D, r.K, r.lead, r.n_valid, grp);
+  else
+    y[r.out_off + i] = resample_one(row, tg + p * r.K, r.D, r.K, r.lead, r.n_valid, grp);
+}
+
 // grid (max_i nb_i, A): row i copies len floats and writes fill zeros behind them
 __global__ __launch_bounds__(256) void rows_copy_kernel(const ws_rows_copy_row* __restrict__ rows, const float* __restrict__ src,
                                                         float* __restrict__ dst) {
@@ -246,6 +281,71 @@ extern "C" int ws_resample_stream_rows_fwd(const ws_resample_row* rows, const ws
   if (rc != WS_OK) return rc;
   hipLaunchKernelGGL(resample_rows_kernel, dim3((unsigned)nb_max, (unsigned)A), dim3(256), any_lds ? RS_LDS_TAPS * sizeof(float) : 0,
                      (hipStream_t)stream, d_rows, buf, taps, y, hist);
+  return ws_check_launch(who);
+}
+
+extern "C" int ws_window_resample_rows_fwd(const ws_window_resample_row* rows, const ws_window_resample_row* d_rows, int A,
+                                           const float* buf, long long n_buf, const float* taps, long long n_taps, float* y,
+                                           long long n_y, void* stream) {
+  const char* who = "ws_window_resample_rows_fwd";
+  WS_REQUIRE(rows && d_rows && buf && taps && y, "%s: rows, d_rows, buf, taps or y is NULL", who);
+  WS_REQUIRE(A > 0 && A <= 65535, "%s: A=%d is outside [1, 65535]", who, A);
+  WS_REQUIRE(n_buf >= 0 && n_taps >= 0 && n_y >= 0, "%s: an arena length is negative (buf %lld, taps %lld, y %lld)", who, n_buf, n_taps, n_y);
+  std::vector<RsSpan> spans;
+  spans.reserve((size_t)A * 3);
+  long long nb_max = 0;
+  bool any_lds = false;
+  for (int i = 0; i < A; ++i) {
+    const ws_window_resample_row& r = rows[i];
+    WS_REQUIRE(r.U >= 1 && r.D >= 1 && r.U <= RS_MAX_UD && r.D <= RS_MAX_UD, "%s: row %d: U=%d, D=%d; U and D lie in [1, %d]", who, i, r.U, r.D,
+               RS_MAX_UD);
+    WS_REQUIRE(r.K >= 1 && r.K <= RS_MAX_K, "%s: row %d: K=%d taps per output sample; K lies in [1, %d]", who, i, r.K, RS_MAX_K);
+    WS_REQUIRE(r.K >= r.D, "%s: row %d: K=%d is below D=%d", who, i, r.K, r.D);
+    WS_REQUIRE((r.K - r.D) % 2 == 0, "%s: row %d: K - D = %d is odd (K = 2 w + D)", who, i, r.K - r.D);
+    const int w = (r.K - r.D) / 2;
+    WS_REQUIRE(r.n_valid > 0 && r.L >= 0 && r.fill >= 0 && r.L + (long long)r.fill > 0,
+               "%s: row %d: bad sizes (n_valid=%d >= 1, L=%d, fill=%d, one of them positive)", who, i, r.n_valid, r.L, r.fill);
+    WS_REQUIRE(r.lead >= 0 && r.lead <= w && r.g_first >= 0, "%s: row %d: lead=%d outside [0, w=%d] or g_first=%d negative", who, i, r.lead, w,
+               r.g_first);
+    WS_REQUIRE(r.p_first >= 0 && r.p_first < r.U, "%s: row %d: p_first=%d is outside [0, U=%d)", who, i, r.p_first, r.U);
+    WS_REQUIRE(r.in_off >= 0 && r.in_off <= n_buf - r.n_valid, "%s: row %d: buf [%lld, %lld + %d) leaves the arena of %lld floats", who, i,
+               r.in_off, r.in_off, r.n_valid, n_buf);
+    WS_REQUIRE(r.taps_off >= 0 && r.taps_off <= n_taps - (long long)r.U * r.K, "%s: row %d: taps [%lld, %lld + %d * %d) leaves the arena of %lld floats",
+               who, i, r.taps_off, r.taps_off, r.U, r.K, n_taps);
+    const long long n_dst = (long long)r.L + r.fill;
+    WS_REQUIRE(r.out_off >= 0 && r.out_off <= n_y - n_dst, "%s: row %d: y [%lld, %lld + %d + %d) leaves the arena of %lld floats", who, i, r.out_off,
+               r.out_off, r.L, r.fill, n_y);
+    const long long q_end = (long long)r.g_first * r.U + r.p_first + r.L;
+    WS_REQUIRE(q_end + r.U + 256 < (1LL << 31) && (q_end / r.U + 2) * r.D + r.K < (1LL << 31) && (long long)r.n_valid + r.K + 256 < (1LL << 31) &&
+                   n_dst + 256 < (1LL << 31),
+               "%s: row %d: offsets reach 2^31 (g_first=%d, p_first=%d, L=%d, fill=%d, n_valid=%d)", who, i, r.g_first, r.p_first, r.L, r.fill,
+               r.n_valid);
+    if (r.L > 0) {
+      if (r.final) {
+        const long long span = (long long)r.n_valid + r.lead - w;
+        const long long allowed = span > 0 ? ((long long)r.U * span + r.D - 1) / r.D : 0;
+        WS_REQUIRE(q_end <= allowed, "%s: row %d: outputs up to %lld asked, the %d valid samples end the signal at output %lld", who, i, q_end,
+                   r.n_valid, allowed);
+      } else {
+        const long long last_grp = (q_end - 1) / r.U;
+        WS_REQUIRE(last_grp * r.D - r.lead + r.K <= r.n_valid,
+                   "%s: row %d: outputs up to %lld need %lld valid samples, %d are given and the end is not final", who, i, q_end,
+                   last_grp * r.D - r.lead + r.K, r.n_valid);
+      }
+    }
+    const auto span = [i](const float* p, long long off, long long n, bool wr, const char* name) {
+      return RsSpan{reinterpret_cast<uintptr_t>(p + off), reinterpret_cast<uintptr_t>(p + off + n), i, wr, name};
+    };
+    spans.push_back(span(buf, r.in_off, r.n_valid, false, "buf"));
+    spans.push_back(span(taps, r.taps_off, (long long)r.U * r.K, false, "taps"));
+    spans.push_back(span(y, r.out_off, n_dst, true, "y"));
+    nb_max = std::max(nb_max, (n_dst + 255) / 256);
+    any_lds = any_lds || r.U * r.K <= RS_LDS_TAPS;
+  }
+  const int rc = rs_spans_disjoint(who, spans);
+  if (rc != WS_OK) return rc;
+  hipLaunchKernelGGL(window_resample_rows_kernel, dim3((unsigned)nb_max, (unsigned)A), dim3(256), any_lds ? RS_LDS_TAPS * sizeof(float) : 0,
+                     (hipStream_t)stream, d_rows, buf, taps, y);
   return ws_check_launch(who);
 }
 

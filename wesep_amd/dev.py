@@ -2444,6 +2444,26 @@ def rows_copy_fwd(rows, src, dst):
     return d_tab
 
 
+def window_resample_rows_table(rows) -> np.ndarray:
+    """ws_window_resample_row [A] from dicts with the fields in_off, taps_off, out_off, U, D, K, lead, n_valid, final, g_first,
+    p_first, L, fill."""
+    return _rows_table(rows, L.WINDOW_RESAMPLE_ROW, "ws_window_resample_rows_fwd")
+
+
+def window_resample_rows(rows, buf, taps, y):
+    """ws_window_resample_rows_fwd: row i writes the L outputs of the whole-signal filter from phase p_first of group g_first on,
+    computed from its span buf[in_off : in_off + n_valid], to y[out_off :] and `fill` zeros behind them; buf, taps and y are
+    arenas (1-D float32 on one device).  Returns the device table (alive until the launch has run)."""
+    who = "ws_window_resample_rows_fwd"
+    tab = window_resample_rows_table(rows)
+    n_buf, n_taps, n_y = _arena(buf, who, "buf"), _arena(taps, who, "taps"), _arena(y, who, "y")
+    if buf is None or taps is None or y is None:
+        raise L.WesepHipError(f"{who}: buf, taps and y must be given")
+    d_tab = L.upload_struct_array(tab, buf.device)
+    _call(who, C.c_void_p(tab.ctypes.data), C.c_void_p(d_tab.data_ptr()), len(tab), _p(buf), n_buf, _p(taps), n_taps, _p(y), n_y)
+    return d_tab
+
+
 def window_slots_table(rows) -> np.ndarray:
     """ws_window_slot_row [A] from dicts with the fields src_off, dst_off, len, scale (left out: 1)."""
     return _rows_table([dict({"scale": 1.0}, **r) for r in rows] if not isinstance(rows, np.ndarray) else rows, L.WINDOW_SLOT_ROW,

@@ -28,7 +28,10 @@ SYMBOLS = ("ws_engine_abi_version", "ws_engine_last_error", "ws_engine_create", 
            "ws_engine_live_pool_detach", "ws_engine_live_pool_close",
            "ws_engine_live_pool_store", "ws_engine_live_pool_run", "ws_engine_live_pool_due",
            "ws_engine_tail_pool_open", "ws_engine_tail_pool_attach", "ws_engine_tail_pool_push", "ws_engine_tail_pool_tick",
-           "ws_engine_tail_pool_flush", "ws_engine_tail_pool_detach", "ws_engine_tail_pool_close")
+           "ws_engine_tail_pool_flush", "ws_engine_tail_pool_detach", "ws_engine_tail_pool_close",
+           "ws_engine_rate_tail_pool_open", "ws_engine_rate_tail_pool_attach", "ws_engine_rate_tail_pool_cap", "ws_engine_rate_tail_pool_room",
+           "ws_engine_rate_tail_pool_push", "ws_engine_rate_tail_pool_tick", "ws_engine_rate_tail_pool_flush",
+           "ws_engine_rate_tail_pool_detach", "ws_engine_rate_tail_pool_close")
 STREAM_FLUSH_CAP = 160  # WS_STREAM_FLUSH_CAP
 STREAM_BLOCK_KERNEL = 1  # WS_STREAM_BLOCK_KERNEL: every block of a stream / pool group as one entry-point call
 _lib = None
@@ -168,6 +171,25 @@ def lib():
         l.ws_engine_tail_pool_detach.argtypes = [C.c_void_p, C.c_int]
         l.ws_engine_tail_pool_close.restype = None
         l.ws_engine_tail_pool_close.argtypes = [C.c_void_p]
+        l.ws_engine_rate_tail_pool_open.restype = C.c_int
+        l.ws_engine_rate_tail_pool_open.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                    C.POINTER(C.c_void_p)]
+        l.ws_engine_rate_tail_pool_attach.restype = C.c_int
+        l.ws_engine_rate_tail_pool_attach.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_rate_tail_pool_cap.restype = C.c_int
+        l.ws_engine_rate_tail_pool_cap.argtypes = [C.c_void_p, C.c_int]
+        l.ws_engine_rate_tail_pool_room.restype = C.c_int
+        l.ws_engine_rate_tail_pool_room.argtypes = [C.c_void_p, C.c_int]
+        l.ws_engine_rate_tail_pool_push.restype = C.c_int
+        l.ws_engine_rate_tail_pool_push.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.ws_engine_rate_tail_pool_tick.restype = C.c_int
+        l.ws_engine_rate_tail_pool_tick.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.ws_engine_rate_tail_pool_flush.restype = C.c_int
+        l.ws_engine_rate_tail_pool_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.ws_engine_rate_tail_pool_detach.restype = C.c_int
+        l.ws_engine_rate_tail_pool_detach.argtypes = [C.c_void_p, C.c_int]
+        l.ws_engine_rate_tail_pool_close.restype = None
+        l.ws_engine_rate_tail_pool_close.argtypes = [C.c_void_p]
         if l.ws_engine_abi_version() != ENGINE_ABI_VERSION:
             raise WesepHipError("libwesep_engine.so ABI version mismatch; rebuild")
         _lib = l
@@ -357,6 +379,19 @@ class Engine:
         """A one-slot tail pool for one recording: push(chunk) appends and ticks, and returns [K, m] (m = 0 while the slot does not
         fire); flush() returns the rest.  enrolls as in separate_long() (K of them)."""
         return EngineTail(self, enrolls, kind, window, fade, warm, max_rows)
+
+    def rate_tail_pool(self, slots, K, window, fade, rates, warm=None, max_rows=8):
+        """tail_pool() whose slots carry and return audio at their own sample rates (`rates`: the rates it will accept; the
+        container's own always is).  window, fade and warm stay samples at the container's rate (warm None: 3/4 of the window -- the
+        filters' look-ahead keeps a resampled slot below a whole window before its first firing).  A tick is the tail pool's plus
+        three launches, whatever the number of firing slots and of distinct rates.  TF-GridNet containers are refused.  Close
+        the pool before the engine."""
+        return RateTailPool(self, slots, K, window, fade, rates, warm, max_rows)
+
+    def rate_tail(self, enrolls, kind, window, fade, sample_rate, enroll_rate=0, warm=None, max_rows=8):
+        """A one-slot rate tail pool for one recording at sample_rate: push(chunk) appends and ticks, and returns [K, m] at
+        sample_rate; flush() returns the rest.  Over its life it returns exactly the samples pushed."""
+        return EngineRateTail(self, enrolls, kind, window, fade, sample_rate, enroll_rate, warm, max_rows)
 
     def stream(self, rows, enroll, kind, max_chunk_frames=64, block_kernel=False):
         """A stream of `rows` rows on a causal cLN Conv-TasNet / SpEx+ container (info("streaming") == 1): enroll as in
@@ -820,6 +855,137 @@ class EngineTail:
             if got is not None:
                 parts.append(got)
                 self._waiting -= got.shape[1]
+        return np.concatenate(parts, axis=1)
+
+    def flush(self):
+        return self.pool.flush(self.slot)
+
+    def close(self):
+        self.pool.close()
+
+
+RATE_TAIL_TICK_LAUNCHES = 3         # WS_RATE_TAIL_TICK_LAUNCHES: the gather, the emission and resampler B of a tick
+
+
+def rate_tail_launches(forward_plans):
+    """"n_launches" after a rate-tail-pool tick (or a flush that runs a window): forward_plans is its forwards' rectangular
+    counts."""
+    return sum(forward_plans) + RATE_TAIL_TICK_LAUNCHES + 1
+
+
+class RateTailPool:
+    """ws_engine_rate_tail_pool_* (include/wesep_engine.h): a TailPool whose slots carry and return audio at their own sample
+    rates.  Per slot the concatenation of what its ticks and its flush return has exactly as many samples as were pushed; the
+    rule is restated in tests/emu_rate_tail.py."""
+
+    def __init__(self, engine, slots, K, window, fade, rates, warm=None, max_rows=8):
+        self._h, self._engine = C.c_void_p(), engine      # (the engine must outlive the pool)
+        self.slots, self.K, self.window, self.fade, self.max_rows = int(slots), int(K), int(window), int(fade), int(max_rows)
+        self.warm = 3 * self.window // 4 if warm is None else int(warm)    # (a resampled slot never has a whole window before it fires)
+        self._live = set()                                # attached and not flushed: what tick(None) names
+        rates = np.ascontiguousarray(list(rates), dtype=np.int32)
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_tail_pool_open(engine._h, self.slots, self.K, self.window, self.fade, self.warm, self.max_rows,
+                                                   rates.ctypes.data, len(rates), C.byref(self._h)), "ws_engine_rate_tail_pool_open")
+
+    def attach(self, enrolls, kind, sample_rate, enroll_rate=0):
+        """K enrollments as in Engine.separate_long(), the slot's sample rate -> the slot they took.  A waveform enrollment is at
+        enroll_rate (0: the container's).  The speaker stage runs here, once."""
+        enroll, pitch, lengths = _enroll_rows(enrolls, kind, None)
+        if enroll.shape[0] != self.K:
+            raise ValueError(f"RateTailPool.attach: {enroll.shape[0]} enrollments, the pool was opened for K = {self.K}")
+        slot = C.c_int(-1)
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_tail_pool_attach(self._h, enroll.ctypes.data, kind, pitch,
+                                                     None if lengths is None else lengths.ctypes.data, int(enroll_rate), int(sample_rate),
+                                                     C.byref(slot)), "ws_engine_rate_tail_pool_attach")
+        self._live.add(slot.value)
+        return slot.value
+
+    def cap(self, slot):
+        """Samples a target that a tick or the flush of `slot` returns at most (ws_engine_rate_tail_pool_cap)."""
+        return int(lib().ws_engine_rate_tail_pool_cap(self._h, int(slot)))
+
+    def room(self, slot):
+        """The largest push `slot` takes now, in samples at its rate (0: tick first; ws_engine_rate_tail_pool_room)."""
+        return int(lib().ws_engine_rate_tail_pool_room(self._h, int(slot)))
+
+    def push(self, chunks):
+        """{slot: chunk [n_slot >= 1] at the slot's rate}: the samples wait on the host for the next tick.  No launch."""
+        ids = list(chunks)
+        data = [np.ascontiguousarray(chunks[i], dtype=np.float32).reshape(-1) for i in ids]
+        n = np.array([x.shape[0] for x in data], dtype=np.int32)
+        A = len(ids)
+        slots = np.array(ids, dtype=np.int32)
+        cp = (C.c_void_p * max(A, 1))(*[x.ctypes.data for x in data])
+        _check(lib().ws_engine_rate_tail_pool_push(self._h, A, slots.ctypes.data, C.cast(cp, C.c_void_p), n.ctypes.data),
+               "ws_engine_rate_tail_pool_push")
+
+    def tick(self, slots=None, est_cap=None):
+        """-> {slot: float32 [K, m_slot] at the slot's rate} for the slots that returned samples.  slots: the slots to name
+        (None: every attached, unflushed one).  est_cap: {slot: samples a target the buffer holds} (default: cap(slot))."""
+        ids = sorted(self._live) if slots is None else [int(s) for s in slots]
+        if not ids:
+            return {}
+        A = len(ids)
+        caps = np.array([max(self.cap(i), 0) if est_cap is None else int(est_cap[i]) for i in ids], dtype=np.int32)
+        bufs = [np.zeros((self.K, max(int(c), 1)), dtype=np.float32) for c in caps]
+        arr, m = np.array(ids, dtype=np.int32), np.zeros(A, dtype=np.int32)
+        ep = (C.c_void_p * A)(*[b.ctypes.data for b in bufs])
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_tail_pool_tick(self._h, A, arr.ctypes.data, C.cast(ep, C.c_void_p), caps.ctypes.data, m.ctypes.data),
+               "ws_engine_rate_tail_pool_tick")
+        return {i: b[:, :int(k)].copy() for i, b, k in zip(ids, bufs, m) if int(k) > 0}
+
+    def flush(self, slot, est_cap=None):
+        """The end of one slot's recording: the last window, resampler B's rest, cropped to the samples pushed."""
+        cap = max(self.cap(slot), 0) if est_cap is None else int(est_cap)
+        buf, m = np.zeros((self.K, max(cap, 1)), dtype=np.float32), C.c_int(0)
+        _quiesce_torch()
+        _check(lib().ws_engine_rate_tail_pool_flush(self._h, int(slot), buf.ctypes.data, cap, C.byref(m)), "ws_engine_rate_tail_pool_flush")
+        self._live.discard(int(slot))
+        return buf[:, :m.value].copy()
+
+    def detach(self, slot):
+        """Frees the slot for the next attach."""
+        _check(lib().ws_engine_rate_tail_pool_detach(self._h, int(slot)), "ws_engine_rate_tail_pool_detach")
+        self._live.discard(int(slot))
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None and getattr(self._engine, "_h", None):
+            _lib.ws_engine_rate_tail_pool_close(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+class EngineRateTail:
+    """Engine.rate_tail(): one recording on a one-slot RateTailPool.  push() appends and ticks; a chunk that would leave more
+    than one window of audio that has not come out is fed in pieces with a tick between them."""
+
+    def __init__(self, engine, enrolls, kind, window, fade, sample_rate, enroll_rate=0, warm=None, max_rows=8):
+        enroll, _, _ = _enroll_rows(enrolls, kind, None)
+        self.pool = RateTailPool(engine, 1, enroll.shape[0], window, fade, [int(sample_rate)], warm, max_rows)
+        self.K, self.window, self.sample_rate = self.pool.K, self.pool.window, int(sample_rate)
+        self.slot = self.pool.attach(enrolls, kind, sample_rate, enroll_rate)
+
+    def push(self, chunk):
+        """chunk [n] at sample_rate, n >= 1 -> [K, m] float32 at sample_rate, possibly empty."""
+        chunk = np.ascontiguousarray(chunk, dtype=np.float32).reshape(-1)
+        parts, at = [np.zeros((self.K, 0), np.float32)], 0
+        while at < chunk.shape[0]:
+            take = min(chunk.shape[0] - at, self.pool.room(self.slot))
+            if take < 1:
+                raise WesepHipError("EngineRateTail.push: a window of audio is waiting and the slot does not fire")
+            self.pool.push({self.slot: chunk[at:at + take]})
+            at += take
+            got = self.pool.tick([self.slot]).get(self.slot)
+            if got is not None:
+                parts.append(got)
         return np.concatenate(parts, axis=1)
 
     def flush(self):
