@@ -710,7 +710,11 @@ int ws_mask_istft_bwd(const float* dwav, const float* xbs, const float* mask3, i
  * out[p][n] = z[p][n] * (a0 + a[r][n]) + b[r][n],  r = p / rows_per_r; a or b may be NULL. */
 int ws_affine_fwd(const float* z, const float* a, const float* b, float a0, long long rows,
                   int rows_per_r, int N, float* out, void* stream);
-/* dz_in = dz*(a0+a) (dz_in may be NULL); da_slab[split][r][n] = sum dz*z_in; db_slab likewise sum dz            */
+/* dz_in = dz*(a0+a) (dz_in may be NULL); da_slab[split][r][n] = sum dz*z_in; db_slab likewise sum dz.
+ * Split s of row r owns the rows j in [s * chunk, min(rows_per_r, (s + 1) * chunk)) of that r, chunk = ceil(rows_per_r /
+ * nsplit); every slab element [nsplit][R][N] is written, a split that owns no row (nsplit above rows_per_r) leaves exact
+ * zeros.  da_slab NULL (then z_in may be NULL) / db_slab NULL: that slab is not written.  N <= 128; N % 4 != 0 takes the
+ * scalar kernel (same sums, row lanes in a different order).                                                       */
 int ws_affine_bwd(const float* dz, const float* z_in, const float* a, float a0, long long rows,
                   int rows_per_r, int N, int nsplit, float* dz_in, float* da_slab, float* db_slab,
                   float* da, float* db, unsigned* counter, void* stream);
@@ -736,7 +740,9 @@ typedef struct ws_tensor_ref {
 } ws_tensor_ref;
 /* guard (optional device words; ABI v17: FOUR words, see ws_guard_commit): guard[0] is set to 1 when any tensor's norm is
  * NaN / Inf.  The caller zeroes guard[0] before the first launch of a step (the skip word of that step's
- * ws_clip_adam_step launches).                                                                                       */
+ * ws_clip_adam_step launches).  The launch only ever writes 1: a guard[0] that is non-zero at launch stays non-zero (no
+ * launch resets it; it is untouched when every norm is finite), one that is 0 stays 0 when every norm is finite.  An entry
+ * whose grad is NULL is not read: its norm is exactly 0 (and ws_clip_adam_step leaves its tensors untouched).          */
 int ws_grad_norms(const ws_tensor_ref* tab, int ntensors, float* norms, unsigned* guard, void* stream);
 /* ABI v17: closes an optimizer step's book-keeping ON THE DEVICE, after the step's last ws_clip_adam_step launch.  With
  * skipped := guard[0] != 0 || (skip1 && *skip1 != 0):  skipped -> ++guard[1] (steps skipped so far: exact, monotonic),
@@ -1131,7 +1137,9 @@ int ws_rowln_bwd(const float* x, const float* dy, const float* stats, const floa
  * stats[h][b*T + t][2] = (mean, rstd).  ws_heads_bwd: dx (layout of x, row stride lddx) from x, dy (layout of y), the
  * statistics; slab[nwg][2*W + 8], W = Q*nh*ch: per-workgroup partial sums of d(gamma) (elements [0, W) in the order
  * (q, h, e)), d(beta) ([W, 2W)) and d(slope) ([2W, 2W + nh)) for ws_reduce_slabs; nwg = the launch grid (any > 0: the
- * sums are reproducible for a given nwg).  ch % 4 == 0, nh <= 8, W <= 9216. */
+ * sums are reproducible for a given nwg).  Workgroup i owns the rows b*T + t = i, i + nwg, ...; every slab row is
+ * written whole (the 8 - nh pad words as zeros), and a workgroup that owns no row (nwg above B*T) writes a row of exact
+ * zeros.  The columns of dx outside the nh*ch written stay untouched.  ch % 4 == 0, nh <= 8, W <= 9216. */
 typedef struct ws_heads_args {
   const float* x;
   const float* dy;

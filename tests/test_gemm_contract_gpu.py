@@ -144,6 +144,23 @@ def test_reduce_slabs_contract(case):
     _run(case)
 
 
+def test_conv_wgrad_above_64_kb_of_lds_on_two_devices():
+    """k = 3, C = 80 takes 122 880 bytes of dynamic LDS: the function's limit has to be raised on EVERY device that launches
+    it, not once per process.  The same case on device 0 and then on device 1, both held to the reference."""
+    _cuda()
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    dims = dict(Nn=16, ldg="Nn", split="one", bias=1, k=3, stride=(1, 1), dil=1, p="k/2", C=80, ldp="0", img="3x5")
+    case = gc.Case("conv_wgrad", "two-devices-k3-C80-Nn16", dims, (gc.WG_INST[0],), 4242)
+    b = gc.build(case)
+    ref = gc.reference(b)
+    for i in (0, 1):
+        d = torch.device(f"cuda:{i}")
+        with torch.cuda.device(d):
+            outs, _, _ = _launch(case, b, d)
+        assert _check_all(case, b, ref, outs, f"{case.name} on device {i}") <= 1.0
+
+
 def test_zz_write_worst_ratios():
     """Last in the file: the worst err / bound and the case count per instantiation -> $WESEP_TEST_OUT/gemm_contract.json."""
     _cuda()

@@ -13,13 +13,15 @@
 // (3 MFMAs, fp32 accumulate) like every GEMM of the library; the next tile's loads fly under the current tile's MFMAs.
 // Splits write slabs; the caller reduces them (deterministic, no atomics).
 #include "common.h"
+#include <mutex>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 #define CW_LD 40       // bf16 per LDS row (32 pixels + 8: 80 B, conflict-free 16-byte fragment reads)
 #define CW_MAXK 768    // patch columns per workgroup
-#define CW_ITEMS 3     // (pixel quad, tap, channel quad) items per thread and tile: 8 * CW_MAXK / 4 / 512
+#define CW_MAX_DEVICES 64
+#define CW_ITEMS 3    // (pixel quad, tap, channel quad) items per thread and tile: 8 * CW_MAXK / 4 / 512
 
 struct CwMeta {
   long long off;  // element offset of tap (0, 0) of the pixel's window (may lie before the image)
@@ -249,12 +251,26 @@ extern "C" int ws_conv_wgrad(const ws_conv_wgrad_args* a, void* stream) {
              "ws_conv_wgrad: one image below 2^31 elements");
   const int kchunk = Kk < CW_MAXK ? Kk : CW_MAXK, nchunks = (Kk + CW_MAXK - 1) / CW_MAXK;
   const size_t lds_bytes = (size_t)2 * (32 + 32 * ((kchunk + 31) / 32)) * CW_LD * sizeof(__bf16);
-  static bool attr_set = false;
-  if (!attr_set) {
-    // (a failure here -- no device -- shows up as the launch error below, not as an argument error)
-    attr_set = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (32 + CW_MAXK) * CW_LD * 2) == hipSuccess;
-    (void)hipGetLastError();
+  // a launch above 64 KB (k * k * C >= 353) needs the function's limit raised first, to the largest geometry the checks
+  // above admit.  The attribute is PER DEVICE (conv3x3.hip, tasnet.hip): one flag per device of the node, under a lock; a
+  // refusal -- or no device -- is an error of the entry point, not a silent launch
+  if (lds_bytes > 65536) {
+    static std::mutex mu;
+    static bool raised[CW_MAX_DEVICES] = {};
+    std::lock_guard<std::mutex> lk(mu);
+    int dev = -1;
+    hipError_t e = hipGetDevice(&dev);
+    if (!(e == hipSuccess && dev >= 0 && dev < CW_MAX_DEVICES && raised[dev])) {
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (32 + CW_MAXK) * CW_LD * 2);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ws_set_error("ws_conv_wgrad: %zu bytes of dynamic LDS refused (%s)", lds_bytes, hipGetErrorString(e));
+        return WS_ERR_LAUNCH;
+      }
+      if (dev >= 0 && dev < CW_MAX_DEVICES) raised[dev] = true;
+    }
   }
   hipStream_t s = (hipStream_t)stream;
   ws_prof_begin(WS_PROF_GEMM_TN, s);

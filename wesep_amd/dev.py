@@ -2298,16 +2298,17 @@ def heads_fwd(x, x_ld: int, x_off: int, slope, gamma, beta, B: int, T: int, Tp: 
 
 
 def heads_bwd(x, x_ld: int, x_off: int, dy, slope, gamma, stats, B: int, T: int, Tp: int, Q: int, nh: int, ch: int,
-              dx, dx_ld: int, dx_off: int):
-    """dx into columns [dx_off, dx_off + nh*ch) of [B*T*Q, dx_ld]; returns (dgamma [nh, Q*ch], dbeta [nh, Q*ch], dslope [nh])."""
+              dx, dx_ld: int, dx_off: int, nwg: Optional[int] = None, with_slab: bool = False):
+    """dx into columns [dx_off, dx_off + nh*ch) of [B*T*Q, dx_ld]; returns (dgamma [nh, Q*ch], dbeta [nh, Q*ch], dslope [nh]).
+    nwg: the launch grid (default min(B*T, 512)); with_slab: the slab [nwg, 2*W + 8] as a fourth value."""
     for nm, t in (("x", x), ("dy", dy), ("slope", slope), ("gamma", gamma), ("stats", stats), ("dx", dx)):
         _chk(t, nm)
     _cols_ok(x, B * T * Q, x_ld, x_off, nh * ch, "heads_bwd x")
     _cols_ok(dx, B * T * Q, dx_ld, dx_off, nh * ch, "heads_bwd dx")
     W = Q * nh * ch
-    nwg = min(B * T, 512)
+    nwg = min(B * T, 512) if nwg is None else nwg
     stride = 2 * W + HEADS_SLAB_PAD
-    slab = torch.empty(nwg, stride, device=x.device, dtype=torch.float32)
+    slab = torch.empty(max(nwg, 0), stride, device=x.device, dtype=torch.float32)
     a = _heads_args(x, x_ld, x_off, slope, gamma, None, B, T, Tp, Q, nh, ch, stats)
     a.dy, a.dx, a.lddx, a.slab, a.nwg = _p(dy), _p(dx, dx_off), dx_ld, _p(slab), nwg
     L.check(L.lib().ws_heads_bwd(C.byref(a), L.stream_ptr()), "ws_heads_bwd")
@@ -2315,7 +2316,8 @@ def heads_bwd(x, x_ld: int, x_off: int, dy, slope, gamma, stats, B: int, T: int,
     reduce_slabs(slab, nwg, stride, stride, tot)
     dg = tot[:W].view(Q, nh, ch).permute(1, 0, 2).reshape(nh, Q * ch).contiguous()
     db = tot[W:2 * W].view(Q, nh, ch).permute(1, 0, 2).reshape(nh, Q * ch).contiguous()
-    return dg, db, tot[2 * W:2 * W + nh].contiguous()
+    ds = tot[2 * W:2 * W + nh].contiguous()
+    return (dg, db, ds, slab) if with_slab else (dg, db, ds)
 
 
 def softmax_rows_bwd(y, dy, rows: int, n: int, scale: float, dx):
