@@ -909,13 +909,15 @@ int ws_lstm_fwd_fused(const ws_lstm_fused_args* a, void* stream);
 int ws_im2col(const float* x, int R, int H, int W, int C, int k, int s, int p, long long ldp, float* patches,
               void* stream);
 int ws_col2im(const float* dpatches, int R, int H, int W, int C, int k, int s, int p, float* dx, void* stream);
-/* TSTP pooling: x [R][F][T][C] -> stats [R][2][C*F] = (mean over T, sqrt(unbiased var + eps)), feature c*F + f */
+/* TSTP pooling: x [R][F][T][C] -> stats [R][2][C*F] = (mean over T, sqrt(unbiased var + eps)), feature c*F + f; two
+ * passes, var = sum (x - mean)^2 / (T - 1); T = 1: var = 0, std = sqrt(eps)                                        */
 int ws_tstp_fwd(const float* x, int R, int F, int T, int C, float eps, float* stats, void* stream);
 int ws_tstp_bwd(const float* x, const float* stats, const float* dstats, int R, int F, int T, int C, float* dx,
                 void* stream);
 /* ASTP (attentive statistics pooling, wespeaker ECAPA-TDNN; wesep/models/bsrnn.py:217,352-356 via bsrnn.yaml:66-71) on
  * channels-last x, logits [R][T][C]: alpha = softmax_T(logits), out [R][2C] = sum alpha x || sqrt(max(sum alpha x^2 -
- * mean^2, floor)), aux [R][4][C] = (max logit, sum exp, mean, sum alpha x^2) saved for ws_astp_bwd.               */
+ * mean^2, floor)), aux [R][4][C] = (max logit, sum exp, mean, sum alpha x^2) saved for ws_astp_bwd (aux[3] is E[x^2],
+ * not the variance).  ws_astp_bwd takes the gradient through std where aux[3] - aux[2]^2 > floor (strict), 0 otherwise. */
 int ws_astp_fwd(const float* x, const float* logits, int R, int T, int C, float floor_, float* out, float* aux,
                 void* stream);
 int ws_astp_bwd(const float* x, const float* logits, const float* out, const float* aux, const float* dout, int R, int T,
@@ -927,11 +929,15 @@ int ws_astp_bwd(const float* x, const float* logits, const float* out, const flo
  * pack = Q*H blocks of ws_mhastp_sizes(..., block_floats) floats, block (q, h) at (q*H + h): W1 with columns in the
  * order f*(C/H) + c, b1, then (layers 2) W2, b2 as they are; ws_mhastp_pack writes one block.
  * fwd: out [R][Q][H][2][dm] = (mean, sqrt(max(var, 1e-7))) per head in upstream order; aux [R][Q][H][4][dm] = (max logit,
- * sum exp, mean, var), features in the kernel order f*(C/H) + c, for ws_mhastp_bwd.  One launch for any T.
+ * sum exp, mean, var), features in the kernel order f*(C/H) + c, for ws_mhastp_bwd (aux[3] is the raw, unclamped
+ * variance sum alpha x^2 - mean^2, where ASTP's is E[x^2]).  One launch for any T.  ws_mhastp_bwd takes the gradient
+ * through std where aux[3] >= 1e-7 (not strict), 0 otherwise.
  * bwd: dx [R][F][T][C] (written, not accumulated).  dpack NULL: no weight gradients (one launch).  Otherwise work =
  * ws_mhastp_sizes(..., work_floats) floats, slab = nsplit * Q*H*block floats (unused when nsplit == 1) and
  * dpack gets the weight gradients in the pack layout but with W1's columns in the upstream order c*F + f, i.e.
- * every block is (dW1, db1, dW2, db2) as the parameters are shaped (two more launches, deterministic: no atomics). */
+ * every block is (dW1, db1, dW2, db2) as the parameters are shaped (two more launches, deterministic: no atomics).
+ * Split s of the weight gradients sums the rows m = r*T + t in [s*ceil(R*T/nsplit), ...); a split that owns no row is
+ * legal and leaves exact zeros in its slab. */
 /* block_floats: one (query, head) block of the pack; work_floats: the backward's workspace (either pointer may be NULL) */
 int ws_mhastp_sizes(int R, int T, int Q, int H, int layers, int ds, int d_model, long long* block_floats,
                     long long* work_floats);
@@ -947,7 +953,9 @@ int ws_mhastp_bwd(const float* x, const float* pack, const float* aux, const flo
  * (row, head) pairs, and part_floats = tsplit*R*Q*H*4*d_model, the forward's workspace.  fwd_split: workgroup (r*H + h, s)
  * keeps the online-softmax state of frames [s*ceil(T/tsplit), ...) in part, then one merge launch combines the splits in
  * ascending order and writes out and aux exactly as ws_mhastp_fwd lays them out (two launches, no atomics).
- * bwd_split: ws_mhastp_bwd with its dx launch on the (R*H, tsplit) grid; the weight gradients are unchanged.        */
+ * bwd_split: ws_mhastp_bwd with its dx launch on the (R*H, tsplit) grid; the weight gradients are unchanged.
+ * 1 <= tsplit <= T.  A T split that owns no frame (ceil(T/tsplit)*s >= T) is legal: it leaves the state
+ * (-inf, 0, 0, 0) in part, the merge skips it, and the backward writes nothing for it.                              */
 int ws_mhastp_split_sizes(int R, int F, int T, int C, int Q, int H, int cus, int* tsplit, long long* part_floats);
 int ws_mhastp_fwd_split(const float* x, const float* pack, int R, int F, int T, int C, int Q, int H, int layers, int ds,
                         int tsplit, float* part, float* out, float* aux, void* stream);
@@ -971,7 +979,8 @@ int ws_seg_scale(const float* x, const float* m, int R, int T, int C, int seg_le
 
 /* ---- in-model enrollment front-end (bsrnn.py:231-242,343-350) -------------------
  * out[r][j] = y[reflect(j - pad)], y = pre-emphasis of x (speaker.py:10-23), row stride ldo >= T + 2*pad:
- * the centred, reflect-padded signal whose hop-strided row views are the STFT frames.                     */
+ * the centred, reflect-padded signal whose hop-strided row views are the STFT frames.  y[0] = x[0] - coef*x[1]
+ * (a reflect pad of 1), so T > 1 and T > pad; columns [T + 2*pad, ldo) are not written.                    */
 int ws_preemph_pad(const float* x, int R, int T, int pad, int ldo, float coef, float* out, void* stream);
 /* p[m][f] = re^2 + im^2 of interleaved spectra [M][lds] (nf bins); columns nf..ldp-1 zeroed               */
 int ws_power_spec(const float* spec, long long M, int nf, int lds, int ldp, float* p, void* stream);
@@ -1162,6 +1171,8 @@ int ws_heads_bwd(const ws_heads_args* a, void* stream);
  * width there -- a convolution at w < W_r' then reads what it reads on the row alone.  Length tables are device int[R];
  * every kernel clamps the entries it reads so that none moves an access out of its row; a NULL table is WS_ERR_INVALID.
  * Zeros are selected, not multiplied: NaN / Inf behind a row's end never reach a valid output.
+ * The clamp ranges: tlen[r] to [1, T] in ws_tstp_fwd_len, ws_astp_fwd_len, ws_time_mean_len and ws_cmn_len, to [0, T] in
+ * ws_tail_select_len; wlen[r] to [0, W] in ws_bn_prelu_fwd_len; lengths[r] to [max(pad + 1, 2), T] in ws_preemph_pad_len.
  *   ws_bn_prelu_fwd_len  ws_bn_prelu_fwd on rows [M][C]; row m belongs to r = m / rows_per_r and sits at w = m % W
  *                        (W divides rows_per_r, rows_per_r divides M): u and y are zeros where w >= wlen[r], and bit for
  *                        bit what ws_bn_prelu_fwd writes elsewhere; x and res are not read behind wlen[r]
@@ -1170,8 +1181,9 @@ int ws_heads_bwd(const ws_heads_args* a, void* stream);
  *   ws_time_mean_len     mean [R][C] over t < tlen[r] of x [R][T][C] (the SE squeeze)
  *   ws_cmn_len           y[r][t][:] = t < tlen[r] ? x[r][t][:] - mean_r[:] : 0, mean_r over t < tlen[r]; y may be x
  *   ws_tail_select_len   y[r][t][:] = t < tlen[r] ? x[r][t][:] : 0 on [R][T][C], C % 4 == 0; y may be x
- *   ws_preemph_pad_len   ws_preemph_pad whose reflect padding turns at lengths[r] (clamped to (pad, T]); zeros from
- *                        lengths[r] + 2 pad on; nothing behind lengths[r] is read */
+ *   ws_preemph_pad_len   ws_preemph_pad whose reflect padding turns at lengths[r] (clamped to [max(pad + 1, 2), T]:
+ *                        pre-emphasis with its reflect pad of 1 needs two samples); zeros from lengths[r] + 2 pad on up
+ *                        to T + 2 pad; nothing behind the clamped lengths[r] is read */
 int ws_bn_prelu_fwd_len(const float* x, const float* stats, const float* gamma, const float* beta, const float* res,
                         const float* a, long long M, int C, int rows_per_r, int W, const int* wlen, float* u, float* y,
                         void* stream);

@@ -5,7 +5,7 @@ ws_rowbias_act_fwd and ws_act_bwd.  Same shape as tests/norm_contract.py and tes
 guards and the pairwise generator with its registries come from tests/gemm_contract.py, Partial / check_partial / sum32 from
 tests/norm_contract.py.  No GPU code here: test_map_contract_host_cpu.py checks this module, test_map_contract_gpu.py runs
 every case through wesep_amd.dev.  Out of scope: TSTP, ASTP, seg_sums / seg_scale, pre-emphasis, power spectrum and log of
-the same file (fp64 row tests in test_ragged_speaker_gpu.py) and the modes of ws_chan_sums dev.inorm_fwd / bwd do not use:
+the same file (under contract in tests/pool_contract.py) and the modes of ws_chan_sums dev.inorm_fwd / bwd do not use:
 all three modes of ws_chan_sums, with every split count, are under contract in tests/tasnet_contract.py.
 
 1. REFERENCE.  compute(entry, spec, tensors, dtype) restates include/wesep_hip.h as explicit index arithmetic (gathers over

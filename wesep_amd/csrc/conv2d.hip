@@ -423,7 +423,9 @@ __global__ void log_eps_kernel(float* x, long long n, float eps) {
 }
 
 extern "C" int ws_preemph_pad(const float* x, int R, int T, int pad, int ldo, float coef, float* out, void* stream) {
-  WS_REQUIRE(x && out && R > 0 && T > pad && pad >= 0 && ldo >= T + 2 * pad, "ws_preemph_pad: bad args (T > pad)");
+  // T > 1: y[0] = x[0] - coef * x[1] (the reflect pad of 1) reads a second sample
+  WS_REQUIRE(x && out && R > 0 && T > 1 && T > pad && pad >= 0 && ldo >= T + 2 * pad,
+             "ws_preemph_pad: bad args (T > 1, T > pad)");
   hipLaunchKernelGGL(preemph_pad_kernel, dim3(cv_blocks((long long)R * (T + 2 * pad))), dim3(256), 0,
                      (hipStream_t)stream, x, R, T, pad, ldo, coef, out);
   return ws_check_launch("ws_preemph_pad");

@@ -155,7 +155,7 @@ __global__ void tail_select_len_kernel(const float* x, int R, int T, int C, cons
 }
 
 // ---- ws_preemph_pad whose reflect padding turns at the row's own end; nothing behind lengths[r] is read ---------------
-// out[r][j] = y[reflect(j - pad)] for j < L + 2 pad, 0 behind, L = lengths[r] clamped to (pad, T]
+// out[r][j] = y[reflect(j - pad)] for j < L + 2 pad, 0 behind, L = lengths[r] clamped to [max(pad + 1, 2), T]
 __global__ void preemph_pad_len_kernel(const float* __restrict__ x, int R, int T, int pad, int ldo, float coef,
                                        const int* __restrict__ lengths, float* __restrict__ out) {
   const int Tp = T + 2 * pad;
@@ -163,7 +163,7 @@ __global__ void preemph_pad_len_kernel(const float* __restrict__ x, int R, int T
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
     const int r = (int)(i / Tp), j = (int)(i - (long long)r * Tp);
-    const int L = rg_clamp(lengths[r], pad + 1, T);
+    const int L = rg_clamp(lengths[r], max(pad + 1, 2), T);      // two samples at least: y[0] reads x[1]
     float v = 0.f;
     if (j < L + 2 * pad) {
       int k = j - pad;

@@ -1565,19 +1565,37 @@ def mhastp_nsplit(R: int, T: int) -> int:
 
 
 def mhastp_bwd(x, pack, aux, dout, R: int, F: int, T: int, Cc: int, Q: int, H: int, layers: int, ds: int, dx,
-               dpack=None):
-    """dx (and, with dpack, the weight gradients in the pack layout): one launch, or three with dpack."""
+               dpack=None, nsplit=None, work=None, slab=None, with_slab=False):
+    """dx (and, with dpack, the weight gradients in the pack layout): one launch, or three with dpack.  nsplit / work /
+    slab None: the rule of mhastp_nsplit and buffers of the wrapper's own; with_slab: the slab (None at one split) is
+    handed back."""
     for n, t in (("x", x), ("pack", pack), ("aux", aux), ("dout", dout), ("dx", dx)):
         _chk(t, n)
-    work = slab = None
-    nsplit = 0
-    if dpack is not None:
-        nsplit = mhastp_nsplit(R, T)
-        work = torch.empty(mhastp_sizes(R, T, Q, H, layers, ds, Cc // H * F)[1], device=x.device, dtype=torch.float32)
-        if nsplit > 1:
-            slab = torch.empty(nsplit * dpack.numel(), device=x.device, dtype=torch.float32)
+    nsplit, work, slab = _mhastp_wgrad_bufs(x, dpack, R, F, T, Cc, Q, H, layers, ds, nsplit, work, slab)
     _call("ws_mhastp_bwd", _p(x), _p(pack), _p(aux), _p(dout), R, F, T, Cc, Q, H, layers, ds, _p(dx), _p(work),
           _p(slab), nsplit, _p(dpack))
+    if with_slab:
+        return slab
+
+
+def _mhastp_wgrad_bufs(x, dpack, R, F, T, Cc, Q, H, layers, ds, nsplit, work, slab):
+    """(nsplit, work, slab) of the MHASTP weight gradients: what the caller gave, else the wrapper's own."""
+    if dpack is None:
+        return 0, None, None
+    if nsplit is None:
+        nsplit = mhastp_nsplit(R, T)
+    need = mhastp_sizes(R, T, Q, H, layers, ds, Cc // H * F)[1]
+    if work is None:
+        work = torch.empty(need, device=x.device, dtype=torch.float32)
+    if slab is None and nsplit > 1:
+        slab = torch.empty(nsplit * dpack.numel(), device=x.device, dtype=torch.float32)
+    _chk(work, "work")
+    _chk(slab, "slab")
+    if work.numel() < need:
+        raise L.WesepHipError(f"mhastp_bwd: work has {work.numel()} floats, the weight gradients need {need}")
+    if nsplit > 1 and slab.numel() < nsplit * dpack.numel():
+        raise L.WesepHipError(f"mhastp_bwd: slab has {slab.numel()} floats, {nsplit} splits need {nsplit * dpack.numel()}")
+    return nsplit, work, (slab if nsplit > 1 else None)
 
 
 def mhastp_split_sizes(R: int, F: int, T: int, Cc: int, Q: int, H: int, cus: int):
@@ -1589,35 +1607,34 @@ def mhastp_split_sizes(R: int, F: int, T: int, Cc: int, Q: int, H: int, cus: int
 
 
 def mhastp_fwd_split(x, pack, R: int, F: int, T: int, Cc: int, Q: int, H: int, layers: int, ds: int, out, aux,
-                     tsplit=None):
-    """MHASTP forward on the (R*H, tsplit) grid plus the merge; tsplit None: sized for this device's CUs."""
-    for n, t in (("x", x), ("pack", pack), ("out", out), ("aux", aux)):
+                     tsplit=None, part=None):
+    """MHASTP forward on the (R*H, tsplit) grid plus the merge; tsplit None: sized for this device's CUs; part None: a
+    workspace of the wrapper's own (tsplit * R*Q*H*4*d_model floats)."""
+    for n, t in (("x", x), ("pack", pack), ("out", out), ("aux", aux), ("part", part)):
         _chk(t, n)
-    n, part = mhastp_split_sizes(R, F, T, Cc, Q, H, cu_count(x.device))
+    n, floats = mhastp_split_sizes(R, F, T, Cc, Q, H, cu_count(x.device))
     if tsplit is not None:
-        n, part = tsplit, part // n * tsplit
-    work = torch.empty(part, device=x.device, dtype=torch.float32)
-    _call("ws_mhastp_fwd_split", _p(x), _p(pack), R, F, T, Cc, Q, H, layers, ds, n, _p(work), _p(out), _p(aux))
+        n, floats = tsplit, floats // n * tsplit
+    if part is None:
+        part = torch.empty(floats, device=x.device, dtype=torch.float32)
+    elif part.numel() < floats:
+        raise L.WesepHipError(f"mhastp_fwd_split: part has {part.numel()} floats, {n} splits need {floats}")
+    _call("ws_mhastp_fwd_split", _p(x), _p(pack), R, F, T, Cc, Q, H, layers, ds, n, _p(part), _p(out), _p(aux))
     return n
 
 
 def mhastp_bwd_split(x, pack, aux, dout, R: int, F: int, T: int, Cc: int, Q: int, H: int, layers: int, ds: int, dx,
-                     dpack=None, tsplit=None):
-    """mhastp_bwd with the dx launch split over T (tsplit None: sized for this device's CUs)."""
+                     dpack=None, tsplit=None, nsplit=None, work=None, slab=None, with_slab=False):
+    """mhastp_bwd with the dx launch split over T (tsplit None: sized for this device's CUs); nsplit / work / slab /
+    with_slab as in mhastp_bwd (with_slab: (tsplit, slab) comes back)."""
     for n, t in (("x", x), ("pack", pack), ("aux", aux), ("dout", dout), ("dx", dx)):
         _chk(t, n)
     if tsplit is None:
         tsplit = mhastp_split_sizes(R, F, T, Cc, Q, H, cu_count(x.device))[0]
-    work = slab = None
-    nsplit = 0
-    if dpack is not None:
-        nsplit = mhastp_nsplit(R, T)
-        work = torch.empty(mhastp_sizes(R, T, Q, H, layers, ds, Cc // H * F)[1], device=x.device, dtype=torch.float32)
-        if nsplit > 1:
-            slab = torch.empty(nsplit * dpack.numel(), device=x.device, dtype=torch.float32)
+    nsplit, work, slab = _mhastp_wgrad_bufs(x, dpack, R, F, T, Cc, Q, H, layers, ds, nsplit, work, slab)
     _call("ws_mhastp_bwd_split", _p(x), _p(pack), _p(aux), _p(dout), R, F, T, Cc, Q, H, layers, ds, tsplit, _p(dx),
           _p(work), _p(slab), nsplit, _p(dpack))
-    return tsplit
+    return (tsplit, slab) if with_slab else tsplit
 
 
 ASTP_FLOOR = 1e-7
